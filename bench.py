@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RTFx (audio-seconds per wall-second) of the streaming forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B --right-context R --dtype bf16]
+    python bench.py --gpus N --steps K --warmup W [--batch B --right-context R --dtype bf16] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch: every stream of the batch is pushed 1280*(1+R) new PCM samples
 (80 ms * (1+R) of audio), which runs PCM->log-mel, one cached encoder chunk (24 layers) and the RNN-T greedy decode for
@@ -10,8 +10,9 @@ stream, 80 ms lookahead (R = 0), full-size seeded synthetic weights and PCM (no 
 PCM is resident in HBM before the timed region starts (NASR_FLAG_PCM_DEVICE); the hand-over of host buffers (H2D inside
 the timed region) is reported beside it as `host_pcm`, never as `value`.
 
-Timing: W untimed warm-up steps, then 5 regions of EXACTLY K steps each, every region bracketed by a barrier + device
-synchronisation on both sides, max over ranks per region; `value` is the median region.  The engine runs consecutive steps
+Timing: W untimed warm-up steps, then --regions regions of EXACTLY K steps each (one region by default, five with --full),
+every region bracketed by a barrier + device synchronisation on both sides, max over ranks per region; `value` is the
+median region.  The engine runs consecutive steps
 side by side (`pipeline` = 4: a call returns the tokens of the step four calls back), so a region that starts on an idle
 device first fills that pipeline and a device synchronise at its end drains it -- a fixed cost per REGION that made the
 per-step figure depend on --steps (round 2: 0.49 ms at 20 steps, 0.43 at 200).  The timed interval therefore starts after
@@ -24,7 +25,11 @@ random encoder with trained-network-like residual scaling, a joint fitted to the
 on which the reduced-precision engines are token-exact against the F32 oracle (`token_agreement`); `--checkpoint random`
 selects the near-tie stress checkpoint of rounds 1-2 (same shapes, same kernels, same step time).
 
-Also in the line (rank 0):
+A plain run (no --full) does only what the headline needs: set up, warm up, time the K steps, write the outputs
+(--dump-outputs DIR: what the last timed step handed its caller, as float .npy files) and print the line.  Everything
+below is measured only with --full.
+
+Also in the line with --full (rank 0):
   * `configs`: the other single-GPU configurations BASELINE.json names -- configs[2] (Q8_0 tensors, 64 streams, 1.12 s
     lookahead; with --gpus N this is configs[3]: 64 streams per GPU) and configs[4] (the same + the diarization
     side-car), each with its own roofline;
@@ -38,8 +43,8 @@ their status.  Streams are independent units: rank r owns its own streams on GPU
 scaling, no data-path collective; torch.distributed (RCCL) only lines the ranks up (barrier) and takes
 the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0 (~4 KB: headline, `configs`, `roofline`, `cpu_baseline`, `f32_engine`, `token_agreement`
-first); per-kernel tables, every region's time and the notes go to gpurun_out/bench_details.json.
+Prints ONE JSON line on rank 0 (with --full ~4 KB: headline, `configs`, `roofline`, `cpu_baseline`, `f32_engine`,
+`token_agreement` first; per-kernel tables, every region's time and the notes go to the --details file).
 """
 from __future__ import annotations
 
@@ -133,7 +138,15 @@ def parse(argv=None):
                     help="engine option pipeline = E: the encoder in E pieces of L / E layers, piece k of step s beside piece k + 1 of step "
                          "s - 1 ..., the decode of step s - E beside them (1: only the decode beside the next encoder; the engine runs at most as many "
                          "pieces as it finds HIP streams that truly overlap: 4 with the runtime's 4 hardware queues, the decode graphs then run behind the fourth piece)")
-    ap.add_argument("--regions", type=int, default=REPEATS, help="timed regions of K steps (the median is reported)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help=f"timed regions of K steps (the median is reported; default 1, with --full {REPEATS})")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (cold / host-PCM / grouped / synchronous figures, the profile pass, "
+                         "buffered audio, CPU baseline and token agreement, the f32 engine, the other BASELINE configurations) and write --details")
+    ap.add_argument("--details", default="bench_out/bench_details.json",
+                    help="--full: file for per-kernel tables, every region's time and the notes (relative: to the repository root)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--checkpoint", default="speech", choices=["speech", "random"],
                     help="speech: joint fitted to the phone inventory of the synthetic speech audio (wide top-2 margins, token-exact "
                          "at reduced precision); random: the near-tie stress checkpoint (N(0, s^2) logits)")
@@ -300,6 +313,29 @@ class Run:
         for s in self.streams:
             s.destroy()
         self.eng.close()
+
+
+DUMP_STREAMS = 64       # streams whose encoder output --dump-outputs writes (a fixed, seeded sample of larger batches)
+
+
+def dump_outputs(d: Path, run, capi):
+    """--dump-outputs: what the last timed step handed its caller, as float arrays -- the token ids each stream's call returned
+    (tokens.npy, B x max count, -1 past a stream's count; token_counts.npy) and the encoder output of the chunk that step pushed
+    (encoder_out.npy, streams x frames x 1024, float32; encoder_out_streams.npy: which streams, all of them up to DUMP_STREAMS).
+    Called after the timed region; the encoder-out tap completes the steps still in flight."""
+    d.mkdir(parents=True, exist_ok=True)
+    counts = np.array([run.ntok[b] for b in range(run.B)], np.float64)
+    toks = np.full((run.B, max(1, int(counts.max()))), -1.0)
+    for b in range(run.B):
+        toks[b, :run.ntok[b]] = run.tok_bufs[b][:run.ntok[b]]
+    frames = run.n_step // 1280                                    # encoder frames (80 ms) per push
+    n_pick = max(1, min(run.B, DUMP_STREAMS, (48 << 20) // (frames * 1024 * 4)))      # the whole dump stays far below 64 MB
+    pick = np.arange(run.B) if n_pick == run.B else np.sort(np.random.default_rng(0).choice(run.B, n_pick, replace=False))
+    enc = np.stack([run.streams[b].tap(capi.TAP_ENCODER_OUT).reshape(-1, 1024) for b in pick]).astype(np.float32)
+    np.save(d / "tokens.npy", toks)
+    np.save(d / "token_counts.npy", counts)
+    np.save(d / "encoder_out.npy", enc)
+    np.save(d / "encoder_out_streams.npy", pick.astype(np.float64))
 
 
 PRIME = 8      # untimed steps after a region's opening barrier: refill the (at most 5-deep) step pipeline, replay every graph once
@@ -491,6 +527,9 @@ def cpu_baseline_sample(ob, om, synth, p, R, n_step, cpu_seconds, passes=3):
 
 def main():
     args = parse()
+    audio_regions = REPEATS if args.regions is None else args.regions      # the PCM budget below: the same in plain and full runs
+    if args.regions is None:
+        args.regions = REPEATS if args.full else 1
     ENGINE_OPTIONS[:] = args.engine_option
     # the CPU baseline's threads: one per core, neighbours close (before torch / the oracle load an OpenMP runtime, which reads these once)
     os.environ.setdefault("OMP_PROC_BIND", "close")
@@ -553,7 +592,7 @@ def main():
             sharding.barrier(dist, None)
         for _ in range(args.warmup):
             run.step()
-        regions = timed_regions(run, args.steps, barrier, max_over_ranks, repeats=REPEATS, prime=0)
+        regions = timed_regions(run, args.steps, barrier, max_over_ranks, repeats=args.regions, prime=0)
         if rank == 0:
             s = summarize(regions, args.steps, run.audio_per_step, world)
             print(json.dumps({"metric": "RTFx (audio-sec/sec), nemotron-0.6B streaming forward path", "value": s["value"], "unit": "audio-s/s",
@@ -601,8 +640,12 @@ def main():
     depth = 0 if args.sync_steps else args.pipeline_depth
     prime = PRIME if depth else 0
     prof_steps = 0 if args.no_profile_pass else min(args.steps, 50)
-    need_s = (args.warmup + (args.regions + 3) * (args.steps + prime) * 2 + prof_steps + 4) * synth.shift_samples(R) * args.chunks_per_step / synth.SAMPLE_RATE
+    # PCM per stream as a --full run with the same arguments budgets it (the stream's audio depends on its length): a plain run
+    # feeds the headline the same audio
+    need_s = (args.warmup + (audio_regions + 3) * (args.steps + prime) * 2 + prof_steps + 4) * synth.shift_samples(R) * args.chunks_per_step / synth.SAMPLE_RATE
     audio_s = min(max(need_s, args.cpu_seconds + 2.0), 120.0)
+    if not args.full:
+        prof_steps = 0
     run_ids = [args.stream_offset + i for i in sharding.stream_ids(rank, world, B)]
     run = Run(capi, synth, engW, args.layers, dtype, B, R, local_rank, run_ids, args.chunks_per_step,
               pipeline=depth, audio_s=audio_s, speech=speech)
@@ -623,6 +666,8 @@ def main():
     run.drain()                                # pipelined steps: the last warm-up step's tokens are not the timed region's
     run.tokens = 0
     regions = timed_regions(run, args.steps, barrier, max_over_ranks, repeats=args.regions, prime=prime)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), run, capi)
     run.drain()
     tokens_timed, chunks_timed = run.tokens, run.streams[0].progress().chunks
     per_rank = None
@@ -638,12 +683,12 @@ def main():
         dist.all_gather_object(gathered, mine)
         per_rank = gathered
     head = summarize(regions, args.steps, run.audio_per_step, world)
-    cold = head                                # synchronous steps: a region is idle-to-idle already
-    if prime:
+    cold = head if args.full else None         # synchronous steps: a region is idle-to-idle already
+    if prime and args.full:
         cold = summarize(timed_regions(run, args.steps, barrier, max_over_ranks, repeats=min(3, args.regions), prime=0), args.steps, run.audio_per_step, world)
         run.drain()
     host_pcm = None
-    if not args.no_host_pcm:
+    if args.full and not args.no_host_pcm:
         host_regions = timed_regions(run, args.steps, barrier, max_over_ranks, host=True, repeats=min(3, args.regions), prime=prime)
         run.drain()
         host_pcm = summarize(host_regions, args.steps, run.audio_per_step, world)
@@ -651,7 +696,7 @@ def main():
 
     # the grouped pipeline (option pipeline = 8: 8 steps in flight, four steps per launch) on the same run, for the record
     grouped_ms = None
-    if depth == 4 and B * T * args.chunks_per_step <= 2 and args.dtype == "bf16" and args.layers % 8 == 0 and not args.no_grouped:
+    if args.full and depth == 4 and B * T * args.chunks_per_step <= 2 and args.dtype == "bf16" and args.layers % 8 == 0 and not args.no_grouped:
         run.eng.set_option("pipeline", 8)
         for _ in range(12):
             run.step()
@@ -671,7 +716,7 @@ def main():
     # ---- the same stream fed buffered audio (file transcription): 256 chunks per push share one launch sequence ----
     buffered = None
     tok_log_keep, frames_keep = list(run.tok_log[0]), (run.streams[0].token_frames() if rank == 0 else [])
-    if rank == 0 and world == 1 and (B, args.chunks_per_step) == (1, 1) and not args.no_buffered:
+    if args.full and rank == 0 and world == 1 and (B, args.chunks_per_step) == (1, 1) and not args.no_buffered:
         eng, L = run.eng, run.L
         G, n_push = 256, 8
         nb = synth.shift_samples(R) * G
@@ -827,7 +872,7 @@ def main():
     # ---- CPU baseline: the oracle (a port of the reference's algorithm), bounded sample; token agreement -------------
     cpu, agreement, cpu_ref, f32_entry, random_ckpt = None, None, None, None, None
     headline_is_default = (B, R, args.dtype, args.layers, args.chunks_per_step, args.weights) == (1, 0, "bf16", 24, 1, "f32")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import binding as ob
         om = ob.OracleModel(Wcpu, args.layers)
         n_step = run.n_step
@@ -918,7 +963,7 @@ def main():
 
     # ---- the other configurations BASELINE.json names ------------------------------------------------------------------
     configs = {}
-    if headline_is_default and not args.no_extra_configs:
+    if args.full and headline_is_default and not args.no_extra_configs:
         if run is not None:
             run.close()
             run = None
@@ -1009,7 +1054,7 @@ def main():
                     configs[bkey] = dict(error=str(ex)[:300])
             del q8W
 
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world > 1 and not args.no_cpu_baseline:
         # N > 1: the same baseline, after the last timed region (the other ranks are already in the closing barrier), on this rank's share
         # of the host: threads = cores / world (set before the oracle library loads), so that a SCALE line is self-contained
         os.environ.setdefault("NASR_ORACLE_THREADS", str(max(1, min(16, host_info()["affinity"] // world))))
@@ -1051,7 +1096,7 @@ def main():
             "cpu_baseline": cpu,
             "f32_engine": f32_entry,
             "token_agreement": agreement,
-            "cold_ms_per_step": cold["ms_per_step"],
+            "cold_ms_per_step": cold["ms_per_step"] if cold else None,
             "random_checkpoint": random_ckpt,
             "synchronous_ms_per_step": round(1e3 * sync_step_s, 4) if sync_step_s else None,
             "host_pcm_ms_per_step": host_pcm["ms_per_step"] if host_pcm else None,
@@ -1061,18 +1106,20 @@ def main():
             "buffered_audio": buffered,
             "diarization": diar,
             "cpu_baseline_reference_cli": cpu_ref,
-            "timing": f"median of {args.regions} regions of {args.steps} steps; region = barrier+sync, {prime} priming steps, K timed calls; max over ranks",
-            "details": "gpurun_out/bench_details.json",
+            "timing": f"median of {args.regions} region(s) of {args.steps} steps; region = barrier+sync, {prime} priming steps, K timed calls; max over ranks",
+            "details": args.details if args.full else None,
         }
-        out = {k: v for k, v in out.items() if v is not None or k in ("vs_baseline", "roofline", "cpu_baseline")}
-        details.update(runs_ms_per_step=head["runs_ms_per_step"], cold_runs_ms_per_step=cold["runs_ms_per_step"],
-                       host_pcm=host_pcm, roofline=roofline, step_roofline=sr, chunks=chunks_timed, setup_s={"weights": round(t_weights, 1)},
-                       kernels=[dict(name=k["name"], launches=k["launches"], ms=round(k["total_ms"], 3)) for k in kernels], line=out)
-        try:
-            (ROOT / "gpurun_out").mkdir(exist_ok=True)
-            (ROOT / "gpurun_out" / "bench_details.json").write_text(json.dumps(details, indent=1))
-        except OSError:
-            out["details"] = None
+        out = {k: v for k, v in out.items() if v is not None or k == "vs_baseline" or (args.full and k in ("roofline", "cpu_baseline"))}
+        if args.full:
+            details.update(runs_ms_per_step=head["runs_ms_per_step"], cold_runs_ms_per_step=cold["runs_ms_per_step"],
+                           host_pcm=host_pcm, roofline=roofline, step_roofline=sr, chunks=chunks_timed, setup_s={"weights": round(t_weights, 1)},
+                           kernels=[dict(name=k["name"], launches=k["launches"], ms=round(k["total_ms"], 3)) for k in kernels], line=out)
+            try:
+                dpath = ROOT / args.details                  # an absolute --details stays as it is
+                dpath.parent.mkdir(parents=True, exist_ok=True)
+                dpath.write_text(json.dumps(details, indent=1))
+            except OSError:
+                out["details"] = None
         print(json.dumps(out), flush=True)
     if run is not None:
         run.close()

@@ -1,6 +1,6 @@
-"""Debug driver: the mixed-lookahead server scenario of tests/test_gpu_server_load.py with a short client timeout; if the server is still
-alive afterwards, all its thread stacks are dumped with rocgdb."""
-import subprocess, sys, time
+"""Debug driver: the mixed-lookahead server scenario of tests/test_gpu_server_load.py with a short client timeout; afterwards the
+server is stopped and what it wrote is printed (whether it was still alive says whether it hung)."""
+import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
@@ -20,9 +20,7 @@ try:
         print(st.R, st.delay, st.pcm.size, len(st.send_times), repr(st.text[:50]), st.ended is not None)
 except Exception as ex:
     print("client exception", repr(ex))
-if proc.poll() is None:
-    out = subprocess.run(["/opt/rocm/bin/rocgdb", "-p", str(proc.pid), "-batch", "-ex", "thread apply all bt 12"], capture_output=True, text=True, timeout=120)
-    print(out.stdout[-6000:])
+print("server still alive after the clients:", proc.poll() is None)
 srv, err = sl.stop_server(proc)
 print(srv)
 print(err[-3000:])

@@ -15,12 +15,14 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import re
 import signal
 import socket
 import struct
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 from pathlib import Path
@@ -225,6 +227,13 @@ def run_load(sock_path, n_streams, seconds, R, mode, n_conns=8, timeout=300.0, c
                 aggregate_rtfx=round(audio_s / wall, 1), transcripts_correct=correct, tokens=int(lat.size), errors=errors[:5],
                 token_latency_ms=dict(p50=round(1e3 * float(np.percentile(lat, 50)), 1), p99=round(1e3 * float(np.percentile(lat, 99)), 1),
                                       max=round(1e3 * float(lat.max()), 1)))
+
+
+def short_socket_dir() -> Path:
+    """A fresh private directory for a Unix socket.  A socket's path must fit sun_path (108 bytes with its NUL), which a deep
+    pytest tmp_path can exceed, so the directory goes under /tmp (the system temp directory where /tmp is not writable).
+    The caller removes it."""
+    return Path(tempfile.mkdtemp(prefix="nasr-", dir="/tmp" if os.access("/tmp", os.W_OK) else None))
 
 
 def start_server(model, sock_path, max_streams, pipeline, extra=()):

@@ -5,6 +5,7 @@ tests/test_speech_checkpoint.py), three of them are checked against the F32 orac
 RTFx, token latency and the histogram of streams per engine call."""
 import json
 import os
+import shutil
 from pathlib import Path
 
 import pytest
@@ -16,11 +17,19 @@ from tests import server_load as sl
 pytestmark = pytest.mark.gpu
 
 
-def test_server_under_load_16_streams(tmp_path):
+@pytest.fixture
+def sock_dir():
+    """where the server's Unix socket goes: tmp_path can be too deep for a socket path"""
+    d = sl.short_socket_dir()
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def test_server_under_load_16_streams(tmp_path, sock_dir):
     model = sl.write_model(tmp_path / "speech-q8_0.gguf", 24, "q8_0")
     reports = {}
     for mode, seconds, R in (("realtime", 8.0, 0), ("burst", 12.0, 13)):
-        sock = str(tmp_path / f"asr-{mode}.sock")
+        sock = str(sock_dir / f"asr-{mode}.sock")
         proc = sl.start_server(model, sock, 16, 4, extra=("--prewarm", str(R)))
         try:
             rep = sl.run_load(sock, 16, seconds, R, mode, n_conns=4, client="native" if mode == "burst" else "python", workdir=str(tmp_path))
@@ -55,13 +64,13 @@ def test_server_under_load_16_streams(tmp_path):
         assert text == sl.expected_text(ev)[0]
 
 
-def test_server_with_mixed_lookaheads_and_sessions_that_come_and_go(tmp_path):
+def test_server_with_mixed_lookaheads_and_sessions_that_come_and_go(tmp_path, sock_dir):
     """The batch former under what a real population does: 12 live streams with lookahead 0, 1 and 13 mixed on 3 connections, starting 0 ... 2.2 s
     apart and 3 ... 7 s long, so that sessions join and leave while others are mid-stream and every call groups whoever holds a whole chunk
     of its lookahead.  Only the default lookahead is prewarmed (the other shapes are captured on the way).  Every transcript == the phone
     sequence of its audio; nothing runs eagerly but stream ends."""
     model = sl.write_model(tmp_path / "speech-q8_0.gguf", 24, "q8_0")
-    sock = str(tmp_path / "asr-mixed.sock")
+    sock = str(sock_dir / "asr-mixed.sock")
     streams = [sl.StreamState(40 + i, (0, 13, 1, 0, 13, 0)[i % 6], 3.0 + (i * 0.37) % 4.0, delay=0.2 * i) for i in range(12)]
     proc = sl.start_server(model, sock, 16, 4)
     try:
@@ -74,12 +83,12 @@ def test_server_with_mixed_lookaheads_and_sessions_that_come_and_go(tmp_path):
     assert rep["token_latency_ms"]["p99"] < 400.0, rep          # shapes are captured on the way: a first call of a new batch size costs ~20 ms
 
 
-def test_server_with_four_engines_spreads_the_streams(tmp_path):
+def test_server_with_four_engines_spreads_the_streams(tmp_path, sock_dir):
     """`--devices` = one engine + FIFO + worker thread per entry, stream s on entry s mod count (src/nemo-server.cpp has one model and one worker; the
     N-GPU form of this server is what an 8-GPU node runs).  On the one GPU of a test box: `--devices 0,0,0,0`, 32 live streams (round 4 tested two
     entries with a handful of streams): every transcript correct, every engine serves calls, and no engine is handed more than its share."""
     model = sl.write_model(tmp_path / "speech-q8_0.gguf", 24, "q8_0")
-    sock = str(tmp_path / "asr-4dev.sock")
+    sock = str(sock_dir / "asr-4dev.sock")
     proc = sl.start_server(model, sock, 8, 4, extra=("--prewarm", "0", "--devices", "0,0,0,0"))
     try:
         rep = sl.run_load(sock, 32, 5.0, 0, "realtime", n_conns=4, client="native", workdir=str(tmp_path))

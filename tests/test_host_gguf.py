@@ -1,6 +1,7 @@
 """Host side above the C ABI: the ggml-free GGUF v3 reader and the CLI.
 CPU tests cover the file format; the GPU test runs the CLI end to end."""
 import json
+import shutil
 import struct
 import subprocess
 from pathlib import Path
@@ -12,6 +13,15 @@ from nemotron_asr_amd import gguf_io, synth
 
 ROOT = Path(__file__).resolve().parent.parent
 BIN = ROOT / "nemotron-asr.cpp_amd" / "bin"
+
+
+@pytest.fixture
+def sock_dir():
+    """where the server's Unix socket goes: tmp_path can be too deep for a socket path"""
+    from tests import server_load as sl
+    d = sl.short_socket_dir()
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 def _fnv(data: bytes) -> str:
@@ -210,7 +220,7 @@ def test_cli_runs_the_reference_invocations_unchanged(tmp_path):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype_flag,pipeline", [("--f32", 0), (None, 0), ("--f32", 3)])
-def test_server_batches_streams(tmp_path, dtype_flag, pipeline):
+def test_server_batches_streams(tmp_path, sock_dir, dtype_flag, pipeline):
     """Wire protocol of the reference server (src/server-protocol.h:24-41) served by the batch-forming worker:
     3 streams on 2 connections (two right_context groups), text == oracle tokens -> text, errors are framed.
     pipeline = 2: the worker's engine calls overlap on the GPU (text arrives calls later or when the FIFO runs empty):
@@ -225,7 +235,7 @@ def test_server_batches_streams(tmp_path, dtype_flag, pipeline):
     gguf_io.write_gguf(model, W, gguf_io.default_hparams(n_layers=n_layers), vocab)
     srv = BIN / "nemo-server-amd"
     assert srv.exists(), "run __graft_entry__.build()"
-    path = str(tmp_path / "asr.sock")
+    path = str(sock_dir / "asr.sock")
     # two lanes (engine + FIFO + worker each) on the one GPU of the test box: stream s is served by lane s mod 2
     proc = subprocess.Popen([str(srv), str(model), "--unix", path] + ([dtype_flag] if dtype_flag else []) + ["--max-streams", "8", "--devices", "0,0", "--cuda"]      # --cuda / --cpu: the reference's backend flags (src/nemo-server.cpp:405-406), accepted and ignored
                             + (["--pipeline", str(pipeline)] if pipeline else []), stderr=subprocess.PIPE, text=True)
@@ -312,7 +322,7 @@ def test_server_batches_streams(tmp_path, dtype_flag, pipeline):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("pipeline", [0, 4])
-def test_server_language_switch_mid_stream_on_a_multilingual_model(tmp_path, pipeline):
+def test_server_language_switch_mid_stream_on_a_multilingual_model(tmp_path, sock_dir, pipeline):
     """SET_LANG through the socket (reference src/nemo-server.cpp: the audio queued before the switch uses the old language).  A multilingual GGUF
     (4 prompts), f32 engine, two streams started with different languages; stream 0 switches twice mid-stream at sample positions that fall INSIDE a
     chunk (the batch former hands over the sub-chunk remainder before the switch), stream 1 never.  Text == the oracle driven the same way
@@ -326,7 +336,7 @@ def test_server_language_switch_mid_stream_on_a_multilingual_model(tmp_path, pip
     langs = {"en": 0, "de": 1, "fr": 2, "auto": 3}
     model = tmp_path / "multi.gguf"
     gguf_io.write_gguf(model, W, gguf_io.default_hparams(n_layers=n_layers, num_prompts=P), vocab, prompt_dict=langs)
-    path = str(tmp_path / "asr.sock")
+    path = str(sock_dir / "asr.sock")
     proc = subprocess.Popen([str(BIN / "nemo-server-amd"), str(model), "--unix", path, "--f32", "--max-streams", "4", "--right-context", str(R)]
                             + (["--pipeline", str(pipeline)] if pipeline else []), stderr=subprocess.PIPE, text=True)
     try:
