@@ -267,6 +267,33 @@ int nasr_device_free(nasr_engine *e, void *p);
 int nasr_device_upload(nasr_engine *e, void *dst_device, const void *src_host, int64_t bytes);
 int nasr_engine_synchronize(nasr_engine *e);
 
+/* ---- offline full-context transcription: replaces nemo_transcribe_audio / nemo_encode (src/nemo-ggml.cpp:1600-1737, declared
+ * src/nemo-ggml.h:359-375; the `transcribe` binary, src/transcribe.cpp) for B whole utterances at once.  mel[b]: n_frames[b] log-mel
+ * frames [n][128] f32 (host memory) = the preprocessor run once over the whole utterance, no zero prefix.  Encoder frames
+ * T = s(s(s(n_frames))), s(n) = n / 2 + 1 (ConvSubsampling without drop-2); every query attends to every key of its own utterance;
+ * the depthwise conv starts from a zero history; prompt fusion uses prompt_index[b] (NULL = -1 for all); greedy decode with the
+ * reference's rules, frames numbered from 0 within the utterance.  n_tokens[b] = tokens emitted for utterance b; the first
+ * min(n_tokens[b], tokens_cap[b]) are written to tokens_out[b], their encoder-frame indices to frames_out[b] if frames_out != NULL.
+ * An utterance with T > NASR_OFFLINE_MAX_FRAMES fails the call (the engine stays usable); n_frames[b] = 0 gives 0 tokens.  The call
+ * first completes pipelined steps in flight and touches no stream state (K/V rings, conv caches, decoder states, mel buffers,
+ * token rings, graph caches); it runs eagerly.  NASR_FLAG_NO_SYNC is rejected.  Utterances are packed densely and cut into
+ * sub-batches of at most "offline_rows" encoder rows (engine option, default 16 384): results are bit-identical to one
+ * utterance per call. */
+#define NASR_OFFLINE_MAX_FRAMES 2048   /* encoder frames per utterance = the reference's max_pos_len (src/nemo-ggml.cpp:229-233) */
+int nasr_engine_transcribe_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames,
+                               const int32_t *prompt_index, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                               int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags);
+/* the same from s16 PCM: pcm[b] holds n_samples[b] samples of a whole utterance (host memory, or device memory with
+ * NASR_FLAG_PCM_DEVICE).  The log-mel is the reference preprocessor run once over the whole utterance (src/preprocessor.cpp,
+ * no 9-frame zero prefix): 1 + (256 + n - 512) / 160 frames, none below 256 samples (such an utterance gives 0 tokens). */
+int nasr_engine_transcribe(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples,
+                           const int32_t *prompt_index, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                           int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags);
+/* after an offline call (either entry) made with nasr_engine_set_debug(e, 1): NASR_TAP_MEL [n][128] / NASR_TAP_SUBSAMPLED
+ * [T][1024] / NASR_TAP_LAYER_OUT (index = layer) / NASR_TAP_ENCODER_OUT of utterance u of that call.  Every offline call forgets
+ * the taps of the one before.  Returns the number of floats written (<= cap), with out == NULL the number available, or < 0. */
+int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, float *out, int64_t cap);
+
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =
  * the tensors of diarize.gguf ("vad.*" and/or "spk.*", F32, layouts of scripts/convert_diarize_to_gguf.py:129-158),

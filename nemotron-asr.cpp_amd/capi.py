@@ -30,7 +30,9 @@ EXPORTS = [
     "nasr_engine_profile_read", "nasr_engine_hip_stream", "nasr_engine_lend_stream", "nasr_device_alloc", "nasr_device_free",
     "nasr_device_upload", "nasr_engine_synchronize", "nasr_engine_get_counter", "nasr_stream_debug_fill_kv",
     "nasr_diar_create", "nasr_diar_destroy", "nasr_diar_set_stream", "nasr_diar_vad", "nasr_diar_embed", "nasr_diar_logmel", "nasr_diar_last_gpu_ms",
+    "nasr_engine_transcribe_mel", "nasr_engine_transcribe", "nasr_engine_offline_tap",
 ]
+OFFLINE_MAX_FRAMES = 2048
 
 
 class HParams(C.Structure):
@@ -107,6 +109,10 @@ def lib():
         L.nasr_device_upload.argtypes = [vp, vp, vp, C.c_int64]
         L.nasr_engine_synchronize.argtypes = [vp]
         L.nasr_engine_get_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+        L.nasr_engine_transcribe_mel.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, ip, C.POINTER(vp), C.c_uint32]
+        L.nasr_engine_transcribe.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, ip, C.POINTER(vp), C.c_uint32]
+        L.nasr_engine_offline_tap.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64]
+        L.nasr_engine_offline_tap.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -406,6 +412,52 @@ class Engine:
         bufs, tptrs, caps, n = self._tok_bufs(B, cap)
         _chk(lib().nasr_engine_collect(self.h, self._handles(streams), B, tptrs, caps, n))
         return self._gather(streams, bufs, tptrs, caps, n, cap)
+
+    # ---- offline full-context transcription of whole utterances --------------------------------
+    def _offline(self, fn, ptrs, ns, frames_per_unit, prompts, tok_cap, flags):
+        B = len(ns)
+        pr = (C.c_int32 * B)(*[int(p) for p in prompts]) if prompts is not None else None
+        caps_l = [tok_cap or (int(n) // frames_per_unit + 4) * 10 + 16 for n in ns]
+        tb = [np.zeros(c, np.int32) for c in caps_l]
+        fb = [np.zeros(c, np.int32) for c in caps_l]
+        tp = (C.c_void_p * B)(*[t.ctypes.data for t in tb])
+        fp = (C.c_void_p * B)(*[f.ctypes.data for f in fb])
+        caps = (C.c_int32 * B)(*caps_l)
+        n = (C.c_int32 * B)()
+        _chk(fn(self.h, B, ptrs, (C.c_int32 * B)(*[int(v) for v in ns]), pr, tp, caps, n, fp, flags))
+        k = [min(n[b], caps_l[b]) for b in range(B)]
+        return [tb[b][:k[b]].tolist() for b in range(B)], [fb[b][:k[b]].tolist() for b in range(B)]
+
+    def transcribe_mel(self, mels, prompts=None, tok_cap=None):
+        """mels: list of [n][128] float32 log-mel arrays (the preprocessor over each whole utterance).  Returns (tokens, frames):
+        one list per utterance, frames = encoder-frame index of every token."""
+        if len(mels) == 0:
+            return [], []
+        arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._offline(lib().nasr_engine_transcribe_mel, ptrs, [a.shape[0] for a in arrs], 8, prompts, tok_cap, 0)
+
+    def transcribe(self, pcms, prompts=None, tok_cap=None, flags=0):
+        """pcms: list of int16 arrays, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE).  Returns (tokens, frames)."""
+        if len(pcms) == 0:
+            return [], []
+        if flags & FLAG_PCM_DEVICE:
+            ptrs = (C.c_void_p * len(pcms))(*[p for p, _ in pcms])
+            ns = [n for _, n in pcms]
+        else:
+            arrs = [np.ascontiguousarray(p, np.int16) for p in pcms]
+            ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+            ns = [a.size for a in arrs]
+        return self._offline(lib().nasr_engine_transcribe, ptrs, ns, 1280, prompts, tok_cap, flags)
+
+    def offline_tap(self, which, u, index=0):
+        """after an offline call made with set_debug(True): tap `which` (TAP_MEL / TAP_SUBSAMPLED / TAP_LAYER_OUT / TAP_ENCODER_OUT) of utterance u"""
+        width = 128 if which == TAP_MEL else 1024
+        L = lib()
+        cap = _chk(L.nasr_engine_offline_tap(self.h, which, u, index, None, 0))
+        out = np.zeros(max(cap, 1), np.float32)
+        n = _chk(L.nasr_engine_offline_tap(self.h, which, u, index, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
+        return out[:n].reshape(-1, width).copy()
 
     # ---- measurement ------------------------------------------------------------------
     def profile(self, on=True):

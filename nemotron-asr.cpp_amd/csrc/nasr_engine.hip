@@ -623,6 +623,7 @@ void engine_destroy_impl(nasr_engine *e) {
     if (getenv("NASR_STATS") && e->gp_steps)
         fprintf(stderr, "nasr: grouped pipeline: %lld steps, chain launches %lld through graphs, %lld eager\n", (long long)e->gp_steps,
                 (long long)e->gp_graph_chains, (long long)e->gp_eager_chains);
+    offline_destroy(e);
     for (auto *s : e->slots) delete s;
     for (void *p : e->allocs) hipFree(p);
     for (auto &kv : e->graphs) hipGraphExecDestroy(kv.second);

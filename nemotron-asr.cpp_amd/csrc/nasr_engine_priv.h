@@ -59,8 +59,10 @@ constexpr int STAMP_PER_SLOT = 8 * 24, STAMP_SLOTS = 5;
 
 // ---------------------------------------------------------------------------------------
 struct nasr_engine;
+struct OfflineState;                 // nasr_offline.hip: buffers of the offline path, allocated on its first call
 namespace nasr_eng {
 void prof_flush(nasr_engine *e);
+void offline_destroy(nasr_engine *e);
 }
 struct LayerW {
     float *ln_ff1_w, *ln_ff1_b, *ln_att_w, *ln_att_b, *ln_conv_w, *ln_conv_b, *ln_ff2_w, *ln_ff2_b, *ln_out_w, *ln_out_b;
@@ -236,6 +238,8 @@ struct nasr_engine {
     std::vector<nasr_stream *> slots;
     std::vector<void *> allocs;
     Prof prof;
+    OfflineState *off = nullptr;     // offline path (nasr_engine_transcribe_mel): nullptr until its first call
+    int opt_offline_rows = 16384;    // option "offline_rows": encoder rows per offline sub-batch
 };
 
 constexpr int COLLECT_STRIDE = 256;

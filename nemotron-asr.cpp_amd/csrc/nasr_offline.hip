@@ -1,0 +1,608 @@
+// nasr_offline.hip -- offline full-context transcription of whole utterances, batched (nasr_engine_transcribe_mel).
+// Replaces nemo_transcribe_audio / nemo_encode (reference src/nemo-ggml.cpp:1600-1737): the preprocessor output of a whole
+// utterance -> ConvSubsampling without drop-2 -> 24 conformer layers whose attention sees every frame of the utterance
+// (build_rel_pos_mha :668-755, no mask, no cache; the depthwise conv starts from a zero history) -> prompt fusion -> greedy
+// RNN-T decode (:1231-).  The utterances of a call are packed densely (M = sum T_b rows, no padding) and cut into sub-batches
+// of at most "offline_rows" rows (nasr_offline_plan.h); every kernel's result for a row depends on its own utterance only, so
+// a sub-batch gives the bits the utterance gives alone.  Nothing of the streaming state is touched: the path has its own
+// buffers (allocated on the first call), its own decoder slots and token rings, and never captures a graph.
+#include "nasr_engine_priv.h"
+#include "nasr_offline.h"
+
+struct OfflineState {
+    std::vector<void *> bufs;                    // everything below, freed with the engine (or when a buffer grows)
+    int rows_cap = 0;
+    size_t part_cap = 0, sub_a_cap = 0, sub_b_cap = 0, mel_cap = 0;
+    float *x = nullptr, *part = nullptr, *glu = nullptr, *hfuse = nullptr, *encproj = nullptr, *zero_bias = nullptr;
+    void *a = nullptr, *hbuf = nullptr, *qkv = nullptr, *ctx = nullptr, *cbuf = nullptr;
+    int *tpos = nullptr; int4 *items = nullptr; RowDesc *prow = nullptr;
+    void *sub_a = nullptr, *sub_b = nullptr;     // front-end images (f32 sized)
+    float *mel = nullptr;
+    // PCM entry: the streaming front end's buffers for a group of utterances (one preprocessor state each) and the log-mel it produces
+    float *abuf = nullptr, *last_sample = nullptr, *mel_ring = nullptr, *pmel = nullptr; int16_t *pcm = nullptr; PcmDesc *pdesc = nullptr;
+    size_t pmel_cap = 0, pcm_cap = 0;
+    OffSubDesc *sdesc = nullptr;
+    std::vector<void *> pos;                     // per layer [4095][1024] act dtype
+    // decode: one slot per utterance of a sub-batch
+    DecCtrl *ctrl = nullptr; float *h = nullptr, *c = nullptr, *predg = nullptr, *win = nullptr;
+    unsigned long long *key = nullptr; int *n_active = nullptr, *dlist = nullptr, *tok_ring = nullptr, *tok_frame = nullptr;
+    unsigned *rowmap = nullptr; RowDesc *drows = nullptr; int4 *dwin = nullptr;
+    float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
+    // debug taps of the last call, by utterance
+    std::vector<std::vector<float>> tap_mel, tap_sub, tap_enc;
+    std::vector<std::vector<std::vector<float>>> tap_lay;
+};
+
+namespace nasr_eng {
+
+static int off_alloc(OfflineState *o, void **p, size_t bytes) {
+    HIPCHK(hipMalloc(p, std::max<size_t>(bytes, 16)));
+    o->bufs.push_back(*p);
+    return 0;
+}
+static void off_free(OfflineState *o, void *p) {
+    if (!p) return;
+    for (auto &b : o->bufs) if (b == p) { hipFree(p); b = nullptr; }
+}
+
+void offline_destroy(nasr_engine *e) {
+    if (!e->off) return;
+    for (void *p : e->off->bufs) if (p) hipFree(p);
+    delete e->off;
+    e->off = nullptr;
+}
+
+// linear_pos of the sinusoid rows of relative positions 2047 .. -2047, once per engine (the reference slices the T-centred
+// 2T - 1 rows of the same table, src/nemo-ggml.cpp:17-32, :229-233, :700-705)
+static int ensure_offline_pos(nasr_engine *e, OfflineState *o) {
+    if (!o->pos.empty()) return 0;
+    const size_t n = (size_t)OFFLINE_NREL * D;
+    std::vector<float> emb(n);
+    for (int r = 0; r < OFFLINE_NREL; r++) host_pos_emb((OFFLINE_MAX_T - 1) - r, &emb[(size_t)r * D]);
+    float *demb = nullptr, *dout = nullptr;
+    HIPCHK(hipMalloc((void **)&demb, n * 4));
+    HIPCHK(hipMalloc((void **)&dout, n * 4));
+    HIPCHK(hipMemcpy(demb, emb.data(), n * 4, hipMemcpyHostToDevice));
+    for (auto &L : e->L) {
+        GemmParams g;
+        memset(&g, 0, sizeof(g));
+        g.A = demb; g.W = L.wpos_f32; g.M = OFFLINE_NREL; g.N = D; g.K = D; g.lda = D;
+        g.epi = EPI_PART_F32; g.out_f32 = dout; g.ldo = D; g.splits = 1;
+        g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        launch_gemm_f32(g, e->st);
+        void *pp;
+        if (off_alloc(o, &pp, n * e->esz)) return -1;
+        if (e->bf16) launch_f32_to_bf16(dout, (bf16_t *)pp, (int64_t)n, e->st);
+        else HIPCHK(hipMemcpyAsync(pp, dout, n * 4, hipMemcpyDeviceToDevice, e->st));
+        o->pos.push_back(pp);
+    }
+    HIPCHK(hipStreamSynchronize(e->st));
+    hipFree(demb);
+    hipFree(dout);
+    return 0;
+}
+
+// row buffers for `rows` packed rows (grown, never shrunk) and the decode slots
+static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
+    if (rows <= o->rows_cap) return 0;
+    HIPCHK(hipStreamSynchronize(e->st));
+    void **row_bufs[] = {(void **)&o->x, (void **)&o->glu, (void **)&o->hfuse, (void **)&o->encproj, &o->a, &o->hbuf, &o->qkv, &o->ctx,
+                         &o->cbuf, (void **)&o->tpos, (void **)&o->items, (void **)&o->prow};
+    for (void **p : row_bufs) { off_free(o, *p); *p = nullptr; }
+    const size_t M = (size_t)std::max(rows, 64), es = e->esz;
+    int rc = 0;
+    rc |= off_alloc(o, (void **)&o->x, M * D * 4);
+    rc |= off_alloc(o, (void **)&o->glu, M * D * 4);
+    rc |= off_alloc(o, (void **)&o->hfuse, e->hp.num_prompts > 0 ? M * 2048 * 4 : 16);
+    rc |= off_alloc(o, (void **)&o->encproj, M * JNT * 4);
+    rc |= off_alloc(o, &o->a, M * D * es);
+    rc |= off_alloc(o, &o->hbuf, M * FF * es);
+    rc |= off_alloc(o, &o->qkv, M * 3 * D * es);
+    rc |= off_alloc(o, &o->ctx, M * D * es);
+    rc |= off_alloc(o, &o->cbuf, M * D * es);
+    rc |= off_alloc(o, (void **)&o->tpos, M * 4);
+    rc |= off_alloc(o, (void **)&o->items, M * sizeof(int4));        // at most one attention work item per row
+    rc |= off_alloc(o, (void **)&o->prow, M * sizeof(RowDesc));
+    if (rc) return -1;
+    o->rows_cap = (int)M;
+    if (!o->zero_bias) {
+        if (off_alloc(o, (void **)&o->zero_bias, 3 * D * 4)) return -1;
+        HIPCHK(hipMemset(o->zero_bias, 0, 3 * D * 4));
+    }
+    if (!o->ctrl) {
+        const size_t U = nasr_plan::OFFLINE_MAX_UTTS, W = OFF_DEC_WIN;
+        rc |= off_alloc(o, (void **)&o->ctrl, U * sizeof(DecCtrl));
+        rc |= off_alloc(o, (void **)&o->h, U * 4 * HID * 4);
+        rc |= off_alloc(o, (void **)&o->c, U * 4 * HID * 4);
+        rc |= off_alloc(o, (void **)&o->predg, U * JNT * 4);
+        rc |= off_alloc(o, (void **)&o->win, U * W * JNT * 4);
+        rc |= off_alloc(o, (void **)&o->key, U * W * 8);
+        rc |= off_alloc(o, (void **)&o->n_active, 16);
+        rc |= off_alloc(o, (void **)&o->dlist, U * 4);
+        rc |= off_alloc(o, (void **)&o->rowmap, U * W * 4);
+        rc |= off_alloc(o, (void **)&o->tok_ring, U * TOK_CAP * 4);
+        rc |= off_alloc(o, (void **)&o->tok_frame, U * TOK_CAP * 4);
+        rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
+        rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
+        rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
+        if (rc) return -1;
+        HIPCHK(hipMemset(o->n_active, 0, 16));
+    }
+    return 0;
+}
+
+static int grow(nasr_engine *e, OfflineState *o, void **p, size_t &cap, size_t bytes) {
+    if (bytes <= cap) return 0;
+    HIPCHK(hipStreamSynchronize(e->st));
+    off_free(o, *p);
+    *p = nullptr;
+    if (off_alloc(o, p, bytes)) return -1;
+    cap = bytes;
+    return 0;
+}
+
+// one sub-batch: utterances [first, first + n) of the call; tokens / frames appended to toks[b] / frs[b]
+static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const *mel, const int32_t *n_mel, const int32_t *prompt_index,
+                             const std::vector<int> &Tall, int first, int n, std::vector<std::vector<int32_t>> &toks,
+                             std::vector<std::vector<int32_t>> &frs) {
+    hipStream_t st = e->st;
+    const int act = e->bf16 ? 1 : 0, nL = e->hp.n_layers, ks = e->hp.kernel_size;
+    // ---- plan of the sub-batch: packed rows, front-end images, attention work items -----------------------------
+    std::vector<int> off(n), T(n);
+    std::vector<OffSubDesc> sd(n);
+    int M = 0, mel_rows = 0, h2_rows = 0, h3_rows = 0, max_h2 = 0, maxT = 0;
+    for (int k = 0; k < n; k++) {
+        const int b = first + k;
+        T[k] = Tall[b]; off[k] = M; M += T[k]; maxT = std::max(maxT, T[k]);
+        sd[k].mel_off = mel_rows; sd[k].n_mel = n_mel[b]; sd[k].out_row = h2_rows; sd[k].pad = 0;
+        mel_rows += n_mel[b];
+        h2_rows += nasr_plan::sub_h2(n_mel[b]);
+        h3_rows += T[k];
+        max_h2 = std::max(max_h2, nasr_plan::sub_h2(n_mel[b]));
+    }
+    if (M == 0) return 0;                                    // every utterance too short for one mel frame: nothing runs
+    if (ensure_rows(e, o, M)) return -1;
+    const int qb = off_attn_qb(act);
+    std::vector<int4> items;
+    std::vector<int> tpos(M);
+    std::vector<RowDesc> prow(M);
+    for (int k = 0; k < n; k++) {
+        for (int q0 = 0; q0 < T[k]; q0 += qb) items.push_back(make_int4(off[k], T[k], q0, 0));
+        for (int t = 0; t < T[k]; t++) {
+            tpos[off[k] + t] = t;
+            RowDesc &rd = prow[off[k] + t];
+            memset(&rd, 0, sizeof(rd));
+            rd.prompt = prompt_index ? prompt_index[first + k] : -1;
+        }
+    }
+    HIPCHK(hipMemcpy(o->items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->tpos, tpos.data(), (size_t)M * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->prow, prow.data(), (size_t)M * sizeof(RowDesc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->sdesc, sd.data(), (size_t)n * sizeof(OffSubDesc), hipMemcpyHostToDevice));
+    // Every GEMM of the path runs on at least OFF_MIN_ROWS rows (the rows past M are scratch whose results nobody reads) and without
+    // split-K: the GEMM form -- and with it the summation order of every output row -- is then the same whatever the rows of the other
+    // utterances, which is what makes a batch bit-identical to its utterances alone (the skinny kernel below 33 rows and split-K sum
+    // differently; the large-M variants give the same bits, tests/micro/gemm_variant_identity.py).
+    auto gm = [](int rows) { return std::max(rows, OFF_MIN_ROWS); };
+    const int Mg = gm(M);
+    if (grow(e, o, (void **)&o->part, o->part_cap, (size_t)Mg * D * 4)) return -1;
+    // front-end images: conv0+dw output [H2][33][256] act, pw3 output f32, dw output [H3][17][256] act, pw6 output act
+    const size_t img = std::max({(size_t)gm(h2_rows * 33), (size_t)gm(h3_rows * 17), (size_t)Mg * 17}) * SUBC * 4;
+    if (grow(e, o, &o->sub_a, o->sub_a_cap, img) || grow(e, o, &o->sub_b, o->sub_b_cap, img)) return -1;
+    if (grow(e, o, (void **)&o->mel, o->mel_cap, (size_t)std::max(mel_rows, 1) * NMEL * 4)) return -1;
+    for (int k = 0; k < n; k++)
+        if (n_mel[first + k] > 0)
+            HIPCHK(hipMemcpyAsync(o->mel + (size_t)sd[k].mel_off * NMEL, mel[first + k], (size_t)n_mel[first + k] * NMEL * 4, hipMemcpyDefault, st));   // host (mel entry) or device (PCM entry)
+    // debug taps of this sub-batch
+    if (e->debug) {
+        off_free(o, o->t_sub); off_free(o, o->t_lay); off_free(o, o->t_enc);
+        if (off_alloc(o, (void **)&o->t_sub, (size_t)M * D * 4) || off_alloc(o, (void **)&o->t_lay, (size_t)nL * M * D * 4) ||
+            off_alloc(o, (void **)&o->t_enc, (size_t)M * D * 4)) return -1;
+    }
+    GemmParams g;
+    // ---- subsampling over every whole utterance (no drop-2) ------------------------------------------------------
+    {
+        ProfScope ps(e, "k_off_conv0_dw", (double)mel_rows * NMEL * 4 + (double)h2_rows * 33 * SUBC * e->esz, 2.0 * h2_rows * 33 * SUBC * 90);
+        launch_off_conv0_dw(o->sdesc, n, max_h2, o->mel, e->w0t, e->b0, e->w2t, e->b2, o->sub_b, act, st);
+    }
+    memset(&g, 0, sizeof(g));
+    g.A = o->sub_b; g.W = e->w3; g.M = gm(h2_rows * 33); g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
+    g.epi = EPI_BIAS_RELU_F32; g.out_f32 = (float *)o->sub_a; g.ldo = SUBC; g.bias = e->b3;
+    run_gemm(e, g, false, "sub_pw3");
+    {
+        ProfScope ps(e, "k_sub_dw", (double)h2_rows * 33 * SUBC * 4, 2.0 * h3_rows * 17 * SUBC * 9);
+        int r3 = 0;
+        for (int k = 0; k < n; k++) {
+            const int h2 = nasr_plan::sub_h2(n_mel[first + k]);
+            if (h2 == 0) continue;
+            launch_sub_dw((const float *)o->sub_a + (size_t)sd[k].out_row * 33 * SUBC, 1, h2, 33, e->w5t, e->b5,
+                          (char *)o->sub_b + (size_t)r3 * 17 * SUBC * e->esz, act, st);
+            r3 += T[k];
+        }
+    }
+    memset(&g, 0, sizeof(g));
+    g.A = o->sub_b; g.W = e->w6; g.M = gm(h3_rows * 17); g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
+    g.epi = EPI_BIAS_RELU_ACT; g.out_act = o->sub_a; g.ldo_act = SUBC; g.bias = e->b6;
+    run_gemm(e, g, false, "sub_pw6");
+    memset(&g, 0, sizeof(g));
+    g.A = o->sub_a; g.W = e->sub_out_w; g.M = Mg; g.N = D; g.K = SUBFLAT; g.lda = SUBFLAT; g.splits = 1;
+    g.epi = EPI_BIAS_F32; g.out_f32 = o->x; g.ldo = D; g.bias = e->sub_out_b;
+    run_gemm(e, g, false, "sub_out");
+    if (e->debug) HIPCHK(hipMemcpyAsync(o->t_sub, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+
+    // ---- conformer layers over all M rows ------------------------------------------------------------------------
+    auto post = [&](const PostParams &q, double bytes) {
+        ProfScope ps(e, "k_post", bytes);
+        launch_post(q, st);
+    };
+    auto resid_gemm = [&](const void *A, int lda, void *w, int K, float scale, const char *tag) -> int {
+        GemmParams a;
+        memset(&a, 0, sizeof(a));
+        a.A = A; a.W = w; a.M = Mg; a.N = D; a.K = K; a.lda = lda; a.splits = 1;
+        const bool fold = e->bf16 && gemm_resid_foldable(Mg, D, K, 1, e->opt_t64_tiles + 1);
+        if (fold) { a.epi = EPI_RESID_F32; a.out_f32 = o->x; a.resid = o->x; a.resid_scale = scale; a.ldo = D; }
+        else { a.epi = EPI_PART_F32; a.out_f32 = o->part; a.ldo = D; }
+        run_gemm(e, a, false, tag);
+        return fold ? 0 : a.splits;
+    };
+    {
+        PostParams pp;
+        memset(&pp, 0, sizeof(pp));
+        pp.x = o->x; pp.M = M; pp.ln2_w = e->L[0].ln_ff1_w; pp.ln2_b = e->L[0].ln_ff1_b; pp.a_out = o->a; pp.act_bf16 = act;
+        post(pp, (double)M * D * (4 + e->esz));
+    }
+    for (int l = 0; l < nL; l++) {
+        LayerW &L = e->L[l];
+        auto ffn = [&](void *w1, void *w2, const float *nln_w, const float *nln_b, bool last) {
+            GemmParams a;
+            memset(&a, 0, sizeof(a));
+            a.A = o->a; a.W = w1; a.M = Mg; a.N = FF; a.K = D; a.lda = D; a.splits = 1;
+            a.epi = EPI_SILU_ACT; a.out_act = o->hbuf; a.ldo_act = FF;
+            run_gemm(e, a, false, "ffn_w1");
+            const int sp = resid_gemm(o->hbuf, FF, w2, FF, 0.5f, "ffn_w2");
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 0.5f;
+            q.a_out = o->a; q.act_bf16 = act;
+            if (last) { q.ln_out = 1; q.ln1_w = L.ln_out_w; q.ln1_b = L.ln_out_b; }
+            q.ln2_w = nln_w; q.ln2_b = nln_b;
+            post(q, (double)M * D * (8 + 4 * sp + e->esz));
+        };
+        ffn(L.ff1_w1, L.ff1_w2, L.ln_att_w, L.ln_att_b, false);
+        // q | k | v of every row (no ring: the offline layer has no cache)
+        memset(&g, 0, sizeof(g));
+        g.A = o->a; g.W = L.wqkv; g.M = Mg; g.N = 3 * D; g.K = D; g.lda = D; g.splits = 1;
+        g.epi = EPI_BIAS_ACT; g.out_act = o->qkv; g.ldo_act = 3 * D; g.bias = o->zero_bias;
+        run_gemm(e, g, false, "qkv");
+        {
+            OffAttnParams ap;
+            ap.qkv = o->qkv; ap.pos = o->pos[l]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.items = o->items; ap.ctx = o->ctx;
+            double sq = 0;
+            for (int k = 0; k < n; k++) sq += (double)T[k] * T[k];
+            ProfScope ps(e, "k_off_attention", (double)M * 4 * D * e->esz, sq * NH * DH * 6.0);
+            launch_off_attention(ap, (int)items.size(), act, st);
+        }
+        int sp = resid_gemm(o->ctx, D, L.wo, D, 1.0f, "attn_out");
+        {
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 1.0f;
+            q.ln2_w = L.ln_conv_w; q.ln2_b = L.ln_conv_b; q.a_out = o->a; q.act_bf16 = act;
+            post(q, (double)M * D * (8 + 4 * sp + e->esz));
+        }
+        memset(&g, 0, sizeof(g));
+        g.A = o->a; g.W = L.pw1; g.M = Mg; g.N = 2 * D; g.K = D; g.lda = D; g.splits = 1;
+        g.epi = EPI_GLU; g.out_f32 = o->glu; g.ldo = D;
+        run_gemm(e, g, false, "pw1");
+        {
+            ProfScope ps(e, "k_off_dwconv", (double)M * D * (4 + e->esz), 2.0 * M * D * ks);
+            launch_off_dwconv(o->glu, o->tpos, M, L.dw, ks, L.cln_w, L.cln_b, o->cbuf, act, st);
+        }
+        sp = resid_gemm(o->cbuf, D, L.pw2, D, 1.0f, "pw2");
+        {
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 1.0f;
+            q.ln2_w = L.ln_ff2_w; q.ln2_b = L.ln_ff2_b; q.a_out = o->a; q.act_bf16 = act;
+            post(q, (double)M * D * (8 + 4 * sp + e->esz));
+        }
+        const bool has_next = l + 1 < nL;
+        ffn(L.ff2_w1, L.ff2_w2, has_next ? e->L[l + 1].ln_ff1_w : nullptr, has_next ? e->L[l + 1].ln_ff1_b : nullptr, true);
+        if (e->debug) HIPCHK(hipMemcpyAsync(o->t_lay + (size_t)l * M * D, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+    }
+    // ---- prompt fusion (multilingual, src/nemo-ggml.cpp:1087-1105): one prompt per row ------------------------------
+    if (e->hp.num_prompts > 0) {
+        memset(&g, 0, sizeof(g));
+        g.A = o->x; g.W = e->pk1a; g.M = Mg; g.N = 2048; g.K = D; g.lda = D; g.splits = 1;
+        g.epi = EPI_BIAS_F32; g.out_f32 = o->hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, 2048, D, 4), 2.0 * M * 2048 * D); launch_gemm_f32(g, st); }
+        launch_prompt_add_relu(o->hfuse, e->pk1p, o->prow, M, 1, e->hp.num_prompts, st);
+        memset(&g, 0, sizeof(g));
+        g.A = o->hfuse; g.W = e->pk2_w; g.M = Mg; g.N = D; g.K = 2048; g.lda = 2048; g.splits = 1;
+        g.epi = EPI_BIAS_F32; g.out_f32 = o->x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, D, 2048, 4), 2.0 * M * D * 2048); launch_gemm_f32(g, st); }
+    }
+    if (e->debug) HIPCHK(hipMemcpyAsync(o->t_enc, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+    {
+        ProfScope ps(e, "k_encproj", (double)JNT * D * 4 + (double)M * (D + JNT) * 4, 2.0 * M * JNT * D);
+        launch_encproj(o->x, e->jenc_w, e->jenc_b, o->encproj, M, D, JNT, st);
+    }
+    // ---- greedy decode in windows of 256 frames per utterance (token ring: 4096 > 256 x 10 symbols) -----------------
+    launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
+    std::vector<int> tok_read(n, 0);
+    std::vector<DecCtrl> hctrl(n);
+    std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
+    for (int w0 = 0; w0 < maxT; w0 += OFF_DEC_WIN) {
+        std::vector<RowDesc> rd(n);
+        std::vector<int4> wd(n);
+        int max_dec = 0;
+        for (int k = 0; k < n; k++) {
+            const int nd = std::min(std::max(T[k] - w0, 0), OFF_DEC_WIN);
+            memset(&rd[k], 0, sizeof(RowDesc));
+            rd[k].slot = k; rd[k].n_dec = nd; rd[k].prompt = -1;
+            wd[k] = make_int4(off[k] + w0, nd, 0, 0);
+            max_dec = std::max(max_dec, nd);
+        }
+        HIPCHK(hipMemcpyAsync(o->drows, rd.data(), (size_t)n * sizeof(RowDesc), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(o->dwin, wd.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
+        launch_off_window(o->encproj, o->dwin, n, OFF_DEC_WIN, o->win, st);
+        DecParams dp;
+        memset(&dp, 0, sizeof(dp));
+        dp.rows = o->drows; dp.B = n; dp.T = OFF_DEC_WIN; dp.ctrl = o->ctrl; dp.h = o->h; dp.c = o->c; dp.encproj = o->win;
+        dp.embed = e->embed;
+        for (int i = 0; i < 2; i++) { dp.w_ih[i] = e->w_ih[i]; dp.w_hh[i] = e->w_hh[i]; dp.b_ih[i] = e->b_ih[i]; dp.b_hh[i] = e->b_hh[i]; }
+        dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
+        dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
+        dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
+        launch_decode_begin(dp, st);
+        int it = 0, budget = decode_blind_iterations(max_dec), h_active = 0;
+        while (max_dec > 0) {
+            enqueue_decode_iters(e, dp, n, budget, it);
+            HIPCHK(hipMemcpyAsync(&h_active, o->n_active, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (h_active == 0) break;
+            if (it > max_dec * MAX_SYMBOLS + 64) return fail("offline decode did not terminate");
+            budget = std::min(2 * budget, 32);
+        }
+        // tokens of this window: at most 256 x 10 < TOK_CAP per slot, so the ring holds all of them
+        HIPCHK(hipMemcpyAsync(hctrl.data(), o->ctrl, (size_t)n * sizeof(DecCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ringf.data(), o->tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int k = 0; k < n; k++) {
+            const int n_new = hctrl[k].n_tok - tok_read[k];
+            if (n_new < 0 || n_new > TOK_CAP) return fail("offline token ring overrun on utterance %d", first + k);
+            for (int i = 0; i < n_new; i++) {
+                const int pos = (tok_read[k] + i) & (TOK_CAP - 1);
+                toks[first + k].push_back(ring[(size_t)k * TOK_CAP + pos]);
+                frs[first + k].push_back(ringf[(size_t)k * TOK_CAP + pos]);
+            }
+            tok_read[k] = hctrl[k].n_tok;
+        }
+    }
+    if (e->debug) {
+        HIPCHK(hipStreamSynchronize(st));
+        for (int k = 0; k < n; k++) {
+            const int b = first + k;
+            const size_t rows = (size_t)T[k] * D, o0 = (size_t)off[k] * D;
+            o->tap_sub[b].resize(rows); o->tap_enc[b].resize(rows);
+            HIPCHK(hipMemcpy(o->tap_sub[b].data(), o->t_sub + o0, rows * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(o->tap_enc[b].data(), o->t_enc + o0, rows * 4, hipMemcpyDeviceToHost));
+            o->tap_lay[b].assign(nL, std::vector<float>(rows));
+            for (int l = 0; l < nL; l++)
+                HIPCHK(hipMemcpy(o->tap_lay[b][l].data(), o->t_lay + (size_t)l * M * D + o0, rows * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+}  // namespace nasr_eng
+
+namespace nasr_eng {
+// the call once the log-mel of every utterance exists: mel[b] in host memory (mel entry) or device memory (PCM entry)
+static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, bool mel_device, const int32_t *prompt_index,
+                           int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, int32_t *const *frames_out) {
+    OfflineState *o = e->off;
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> batches;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_frames, B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, batches, &bad)) {
+        if (bad >= 0 && n_frames[bad] >= 0)
+            return fail("utterance %d: %d mel frames give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len); "
+                        "transcribe longer audio with the streaming path (nemotron-asr-amd)", bad, n_frames[bad], nasr_plan::enc_frames(n_frames[bad]),
+                        NASR_OFFLINE_MAX_FRAMES);
+        return fail("offline plan rejected the call");
+    }
+    if (ensure_offline_pos(e, o)) return -1;
+    if (e->debug) {
+        o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {});
+        for (int b = 0; b < B; b++) {
+            o->tap_mel[b].resize((size_t)n_frames[b] * NMEL);
+            if (n_frames[b] > 0) HIPCHK(hipMemcpy(o->tap_mel[b].data(), mel[b], (size_t)n_frames[b] * NMEL * 4, mel_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+        }
+    }
+    std::vector<std::vector<int32_t>> toks(B), frs(B);
+    for (const auto &bt : batches)
+        if (run_offline_batch(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, toks, frs)) return -1;
+    for (int b = 0; b < B; b++) {
+        n_tokens[b] = (int32_t)toks[b].size();
+        const int cap = tokens_cap ? std::max(tokens_cap[b], 0) : 0;
+        const int n_copy = std::min((int)toks[b].size(), cap);
+        if (tokens_out && tokens_out[b]) for (int i = 0; i < n_copy; i++) tokens_out[b][i] = toks[b][i];
+        if (frames_out && frames_out[b]) for (int i = 0; i < n_copy; i++) frames_out[b][i] = frs[b][i];
+    }
+    return 0;
+}
+
+// checks shared by both entries; prepares the offline state and forgets the taps of the previous call
+static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const int32_t *n_tokens, uint32_t flags, const char *who) {
+    if (!n_tokens) return fail("%s: null n_tokens", who);
+    if (flags & NASR_FLAG_NO_SYNC) return fail("%s: NASR_FLAG_NO_SYNC is not supported by the offline path", who);
+    if (prompt_index && e->hp.num_prompts > 0)
+        for (int b = 0; b < B; b++)
+            if (prompt_index[b] < -1 || prompt_index[b] >= e->hp.num_prompts) return fail("prompt_index[%d] = %d out of range", b, prompt_index[b]);
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;                 // complete pipelined steps in flight, as every entry point does
+    if (!e->off) e->off = new OfflineState();
+    OfflineState *o = e->off;
+    o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
+    return 0;
+}
+
+// whole-utterance log-mel on the device: the streaming front end (k_preemph / k_melframes / k_abuf_shift, the reference preprocessor with
+// its 256-sample zero start, src/preprocessor.cpp:330-395) run over each utterance from a fresh state, in sub-pushes of MAX_PUSH samples --
+// its result does not depend on how the samples are cut (tests/test_oracle_golden.py::test_mel_piece_size_independent), so this is the
+// preprocessor run once over the whole utterance.  Frames land in o->pmel, utterance b at mel_off[b].
+constexpr int PCM_GROUP = 32;                     // utterances whose preprocessor states exist at once
+static int offline_mel(nasr_engine *e, OfflineState *o, int B, const int16_t *const *pcm, const int32_t *n_samples, bool pcm_device,
+                       std::vector<int32_t> &n_mel, std::vector<const float *> &mel_ptr) {
+    hipStream_t st = e->st;
+    n_mel.assign(B, 0);
+    std::vector<size_t> mel_off(B, 0);
+    size_t total = 0;
+    for (int b = 0; b < B; b++) {
+        n_mel[b] = nasr_plan::mel_frames(n_samples[b]);
+        mel_off[b] = total;
+        total += (size_t)n_mel[b];
+    }
+    if (!o->abuf) {
+        if (off_alloc(o, (void **)&o->abuf, (size_t)PCM_GROUP * 2 * ABUF_CAP * 4) || off_alloc(o, (void **)&o->last_sample, PCM_GROUP * 4) ||
+            off_alloc(o, (void **)&o->mel_ring, (size_t)PCM_GROUP * MEL_RING * NMEL * 4) || off_alloc(o, (void **)&o->pdesc, PCM_GROUP * sizeof(PcmDesc)))
+            return -1;
+    }
+    if (grow(e, o, (void **)&o->pmel, o->pmel_cap, std::max<size_t>(total, 1) * NMEL * 4)) return -1;
+    for (int g0 = 0; g0 < B; g0 += PCM_GROUP) {
+        const int G = std::min(PCM_GROUP, B - g0);
+        std::vector<const int16_t *> src(G, nullptr);
+        if (pcm_device) {
+            for (int k = 0; k < G; k++) src[k] = pcm[g0 + k];
+        } else {
+            size_t n = 0;
+            for (int k = 0; k < G; k++) n += (size_t)n_samples[g0 + k];
+            if (grow(e, o, (void **)&o->pcm, o->pcm_cap, std::max<size_t>(n, 1) * 2)) return -1;
+            size_t at = 0;
+            for (int k = 0; k < G; k++) {
+                src[k] = o->pcm + at;
+                if (n_samples[g0 + k] > 0) HIPCHK(hipMemcpyAsync(o->pcm + at, pcm[g0 + k], (size_t)n_samples[g0 + k] * 2, hipMemcpyHostToDevice, st));
+                at += (size_t)n_samples[g0 + k];
+            }
+        }
+        // fresh preprocessor state: 256 zero samples at parity 0, last sample 0 (k_stream_reset's values)
+        for (int k = 0; k < G; k++) HIPCHK(hipMemsetAsync(o->abuf + (size_t)k * 2 * ABUF_CAP, 0, (NFFT / 2) * 4, st));
+        HIPCHK(hipMemsetAsync(o->last_sample, 0, PCM_GROUP * 4, st));
+        std::vector<int64_t> done(G, 0);
+        std::vector<int> cnt(G, NFFT / 2), par(G, 0), made(G, 0);
+        for (;;) {
+            std::vector<PcmDesc> pd;
+            std::vector<int> who;
+            int max_frames = 0, max_n = 0;
+            for (int k = 0; k < G; k++) {
+                const int64_t rem = n_samples[g0 + k] - done[k];
+                if (rem <= 0) continue;
+                PcmDesc d;
+                memset(&d, 0, sizeof(d));
+                d.pcm = src[k] + done[k]; d.slot = k; d.n = (int)std::min<int64_t>(rem, MAX_PUSH);
+                d.cnt = cnt[k]; d.par = par[k];
+                const int avail = d.cnt + d.n;
+                d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
+                d.mel_wpos = 0;                                  // every sub-push writes from ring row 0; the frames are copied out below
+                d.consumed = d.n_frames * HOP;
+                pd.push_back(d); who.push_back(k);
+                max_frames = std::max(max_frames, d.n_frames); max_n = std::max(max_n, d.n);
+            }
+            if (pd.empty()) break;
+            HIPCHK(hipMemcpyAsync(o->pdesc, pd.data(), pd.size() * sizeof(PcmDesc), hipMemcpyHostToDevice, st));
+            MelParams mp;
+            memset(&mp, 0, sizeof(mp));
+            mp.desc = o->pdesc; mp.B = (int)pd.size(); mp.max_frames = max_frames; mp.abuf = o->abuf; mp.last_sample = o->last_sample;
+            mp.mel_ring = o->mel_ring; mp.window = e->window; mp.fbT = e->fbT; mp.fb_band = e->fb_band; mp.cos_t = e->cos_t; mp.sin_t = e->sin_t;
+            {
+                ProfScope ps(e, "k_mel", 0, 0);
+                launch_mel(mp, max_n, st);
+            }
+            for (size_t i = 0; i < pd.size(); i++) {
+                const int k = who[i], b = g0 + k;
+                if (pd[i].n_frames > 0) {
+                    if (made[k] + pd[i].n_frames > n_mel[b]) return fail("internal: mel frame count of utterance %d", b);
+                    HIPCHK(hipMemcpyAsync(o->pmel + (mel_off[b] + made[k]) * NMEL, o->mel_ring + (size_t)k * MEL_RING * NMEL,
+                                          (size_t)pd[i].n_frames * NMEL * 4, hipMemcpyDeviceToDevice, st));
+                    par[k] ^= 1;
+                }
+                made[k] += pd[i].n_frames;
+                done[k] += pd[i].n;
+                cnt[k] = pd[i].cnt + pd[i].n - pd[i].consumed;
+            }
+            // the descriptor block is rewritten by the next sub-push: the launches reading it must have run
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        for (int k = 0; k < G; k++)
+            if (made[k] != n_mel[g0 + k]) return fail("internal: utterance %d gave %d mel frames, planned %d", g0 + k, made[k], n_mel[g0 + k]);
+    }
+    mel_ptr.assign(B, nullptr);
+    for (int b = 0; b < B; b++) mel_ptr[b] = o->pmel + mel_off[b] * NMEL;
+    return 0;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_transcribe_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames,
+                                          const int32_t *prompt_index, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                                          int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    if (B == 0) return 0;
+    if (!mel || !n_frames) return fail("null mel / n_frames");
+    for (int b = 0; b < B; b++)
+        if (n_frames[b] < 0 || (n_frames[b] > 0 && !mel[b])) return fail("bad mel input for utterance %d", b);
+    if (begin_call(e, B, prompt_index, n_tokens, flags, "nasr_engine_transcribe_mel")) return -1;
+    return transcribe_core(e, B, mel, n_frames, false, prompt_index, tokens_out, tokens_cap, n_tokens, frames_out);
+}
+
+extern "C" int nasr_engine_transcribe(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples,
+                                      const int32_t *prompt_index, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                                      int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    if (B == 0) return 0;
+    if (!pcm || !n_samples) return fail("null pcm / n_samples");
+    std::vector<int32_t> n_mel(B);
+    for (int b = 0; b < B; b++) {
+        if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail("bad pcm input for utterance %d", b);
+        n_mel[b] = nasr_plan::mel_frames(n_samples[b]);
+    }
+    // the limit is checked before any work (the plan rejects the same call again below, with the same message)
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> bt;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_mel.data(), B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, bt, &bad))
+        return fail("utterance %d: %d samples give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len, %.1f s); "
+                    "transcribe longer audio with the streaming path (nemotron-asr-amd)", bad, bad >= 0 ? n_samples[bad] : -1,
+                    bad >= 0 ? nasr_plan::enc_frames(n_mel[bad]) : -1, NASR_OFFLINE_MAX_FRAMES, nasr_plan::max_samples() / 16000.0);
+    if (begin_call(e, B, prompt_index, n_tokens, flags, "nasr_engine_transcribe")) return -1;
+    std::vector<const float *> mel;
+    if (offline_mel(e, e->off, B, pcm, n_samples, (flags & NASR_FLAG_PCM_DEVICE) != 0, n_mel, mel)) return -1;
+    return transcribe_core(e, B, mel.data(), n_mel.data(), true, prompt_index, tokens_out, tokens_cap, n_tokens, frames_out);
+}
+
+extern "C" int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, float *out, int64_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    OfflineState *o = e->off;
+    if (!o || u < 0 || u >= (int)o->tap_mel.size()) return fail("no offline tap of utterance %d (the last offline call must run with nasr_engine_set_debug(e, 1))", u);
+    const std::vector<float> *src = nullptr;
+    if (which == NASR_TAP_MEL) src = &o->tap_mel[u];
+    else if (which == NASR_TAP_SUBSAMPLED) src = &o->tap_sub[u];
+    else if (which == NASR_TAP_ENCODER_OUT) src = &o->tap_enc[u];
+    else if (which == NASR_TAP_LAYER_OUT) {
+        if (index < 0 || index >= (int)o->tap_lay[u].size()) {
+            if (o->tap_lay[u].empty() && index >= 0 && index < e->hp.n_layers) src = nullptr;      // an utterance with no encoder frames
+            else return fail("layer %d out of range", index);
+        } else src = &o->tap_lay[u][index];
+    } else return fail("offline tap %d not available", which);
+    if (!src) { static const std::vector<float> none; src = &none; }
+    if (!out) return (int64_t)src->size();                  // size query
+    const int64_t n = std::min<int64_t>((int64_t)src->size(), cap);
+    memcpy(out, src->data(), (size_t)n * 4);
+    return n;
+}
