@@ -6,6 +6,7 @@
 #include "nasr_wave.h"
 #include "nasr_post.h"
 #include "nasr_offline.h"
+#include "nasr_conv0_dw.h"
 
 namespace nasr {
 
@@ -263,17 +264,16 @@ void launch_off_dwconv(const float *glu, const int *tpos, int M, const float *dw
     if (M > 0) hipLaunchKernelGGL(k_off_dwconv, dim3(M), dim3(256), 0, st, glu, tpos, dw, ks, ln_w, ln_b, out, act_bf16);
 }
 
-// ---- conv0 (3x3 stride 2, + ReLU) fused into the first depthwise 3x3 stride-2 conv, on a whole utterance --------------
-// k_sub_conv0_dw's body with the mel read from the packed utterance buffer instead of a stream's ring: same operations in
-// the same order (this file is compiled without FMA contraction; the bf16 engine's explicit fmaf as there).  Grid = (H2 max,
-// utterances); out rows of utterance b start at desc.out_row (rows of [W2][256]).
+// ---- conv0 + the first depthwise conv (nasr_conv0_dw.h) on a whole utterance --------------------------------------------
+// The mel is read from the packed utterance buffer instead of a stream's ring.  Grid = (H2 max, utterances); out rows of
+// utterance b start at desc.out_row (rows of [W2][256]).
 template <bool OUT_BF16>
 __global__ __launch_bounds__(256) void k_off_conv0_dw(const OffSubDesc *desc, const float *mel_all, const float *w0t, const float *b0,
                                                       const float *w2t, const float *b2, void *out) {
     constexpr int W1 = 65, W2 = 33;
     __shared__ __attribute__((aligned(16))) float sm[7][144];
     const OffSubDesc dd = desc[blockIdx.y];
-    const int c = threadIdx.x, t2 = blockIdx.x, n_mel = dd.n_mel;
+    const int t2 = blockIdx.x, n_mel = dd.n_mel;
     const int H1 = n_mel / 2 + 1, H2 = H1 / 2 + 1;
     if (n_mel <= 0 || t2 >= H2) return;                           // whole workgroup (no barrier is skipped by part of it); no mel: no rows
     const float *mel = mel_all + (size_t)dd.mel_off * NMEL;
@@ -281,52 +281,7 @@ __global__ __launch_bounds__(256) void k_off_conv0_dw(const OffSubDesc *desc, co
         const int rr = i / 144, iw = i - rr * 144 - 6, ih = 4 * t2 - 6 + rr;
         sm[rr][i - rr * 144] = (ih >= 0 && ih < n_mel && iw >= 0 && iw < NMEL) ? mel[(size_t)ih * NMEL + iw] : 0.0f;
     }
-    float w0[9], w2[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) { w0[k] = w0t[k * SUBC + c]; w2[k] = w2t[k * SUBC + c]; }
-    const float bias0 = b0[c], bias2 = b2[c];
-    __syncthreads();
-    float carry[3] = {0.0f, 0.0f, 0.0f};
-    for (int f2 = 0; f2 < W2; f2++) {
-        float pch[7][8];
-#pragma unroll
-        for (int rr = 0; rr < 7; rr++) {
-            const float4 lo = *(const float4 *)&sm[rr][4 * f2], hi = *(const float4 *)&sm[rr][4 * f2 + 4];
-            pch[rr][0] = lo.x; pch[rr][1] = lo.y; pch[rr][2] = lo.z; pch[rr][3] = lo.w;
-            pch[rr][4] = hi.x; pch[rr][5] = hi.y; pch[rr][6] = hi.z; pch[rr][7] = hi.w;
-        }
-        float acc2 = 0.0f;
-#pragma unroll
-        for (int kh2 = 0; kh2 < 3; kh2++) {
-            const int t = 2 * t2 + kh2 - 2;
-            if (t < 0 || t >= H1) continue;
-#pragma unroll
-            for (int kw2 = 0; kw2 < 3; kw2++) {
-                const int f = 2 * f2 + kw2 - 2;
-                if (f < 0 || f >= W1) continue;
-                float a0;
-                if (kw2 == 0 && f2 > 0) a0 = carry[kh2];
-                else {
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int kh = 0; kh < 3; kh++)
-#pragma unroll
-                        for (int kw = 0; kw < 3; kw++) {
-                            if (OUT_BF16) acc = __builtin_fmaf(w0[kh * 3 + kw], pch[2 * kh2 + kh][2 * kw2 + kw], acc);
-                            else acc += w0[kh * 3 + kw] * pch[2 * kh2 + kh][2 * kw2 + kw];
-                        }
-                    a0 = fmaxf(acc + bias0, 0.0f);
-                }
-                if (kw2 == 2) carry[kh2] = a0;
-                if (OUT_BF16) acc2 = __builtin_fmaf(w2[kh2 * 3 + kw2], a0, acc2);
-                else acc2 += w2[kh2 * 3 + kw2] * a0;
-            }
-        }
-        acc2 += bias2;
-        const size_t o = (((size_t)dd.out_row + t2) * W2 + f2) * SUBC + c;
-        if (OUT_BF16) ((bf16_t *)out)[o] = f32_to_bf16(acc2);
-        else ((float *)out)[o] = acc2;
-    }
+    conv0_dw_row<OUT_BF16>(sm, t2, H1, W1, W2, 0, W2, w0t, b0, w2t, b2, out, (size_t)dd.out_row + t2);
 }
 void launch_off_conv0_dw(const OffSubDesc *desc, int B, int max_h2, const float *mel_all, const float *w0t, const float *b0,
                          const float *w2t, const float *b2, void *out, int out_bf16, hipStream_t st) {

@@ -1,5 +1,6 @@
 // nasr_encoder.hip -- the chunk step: launch sequences of the encoder (subsampling, 24 cached conformer layers in their small-M and
 // large-M forms, prompt fusion, joint.enc) and of the decode, token collection (reference src/nemo-stream.cpp:336-690, :840-930).
+// The offline call (nasr_offline.hip) runs the same subsampling GEMMs, large-M layers, encoder tail and decoder weights.
 #include "nasr_engine_priv.h"
 
 // ---- the chunk step: encoder + decode for the rows that have a full chunk buffered ----------------
@@ -212,7 +213,6 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
     };
     const int l0 = bound(seg), l1 = bound(seg + 1);
     const bool front = part == 0 ? seg == 0 : part == 1, tail = part == 0 ? seg == nseg - 1 : part == 2;
-    GemmParams g;
 
     // debug taps are indexed by slot: [slot][TMAX][1024] (+ layers)
     auto tap_copy = [&](float *tap_base, size_t per_slot, size_t layer_off) -> int {
@@ -228,24 +228,14 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
         ProfScope ps(e, "k_sub_conv0_dw", (double)Bs * (chunk_mel * NMEL * 4 + H2 * W2 * SUBC * (act ? 2 : 4)), 2.0 * Bs * H2 * W2 * SUBC * 90);
         launch_sub_conv0_dw(vrows, Bs, chunk_mel, e->mel_ring, e->w0t, e->b0, e->w2t, e->b2, e->sub_b, act, H1, W1, st);
     }
-    memset(&g, 0, sizeof(g));
-    g.A = e->sub_b; g.W = e->w3; g.M = Bs * H2 * W2; g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
-    g.epi = EPI_BIAS_RELU_F32; g.out_f32 = e->sub_a; g.ldo = SUBC; g.bias = e->b3;
-    run_gemm(e, g, false, "sub_pw3");
+    run_sub_pw3(e, e->sub_b, e->sub_a, Bs * H2 * W2);
     {
         ProfScope ps(e, "k_sub_dw", (double)B * H2 * W2 * SUBC * 4, 2.0 * B * H3 * W3 * SUBC * 9);
         launch_sub_dw(e->sub_a, Bs, H2, W2, e->w5t, e->b5, e->sub_b, act, st);
     }
-    memset(&g, 0, sizeof(g));
-    g.A = e->sub_b; g.W = e->w6; g.M = Bs * H3 * W3; g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
-    g.epi = EPI_BIAS_RELU_ACT; g.out_act = e->sub_a; g.ldo_act = SUBC; g.bias = e->b6;
-    run_gemm(e, g, false, "sub_pw6");
+    run_sub_pw6(e, e->sub_b, e->sub_a, Bs * H3 * W3);
     // out projection on the last T of the T+2 frames (drop 2: src/nemo-stream.cpp:154-162,:303)
-    memset(&g, 0, sizeof(g));
-    g.A = e->sub_a; g.W = e->sub_out_w; g.M = M; g.N = D; g.K = SUBFLAT; g.lda = SUBFLAT; g.splits = 1;
-    g.rows_per_batch = T; g.batch_stride = H3 * SUBFLAT; g.row_offset = DROP_EXTRA;
-    g.epi = EPI_BIAS_F32; g.out_f32 = e->x; g.ldo = D; g.bias = e->sub_out_b;
-    run_gemm(e, g, false, "sub_out");
+    run_sub_out(e, e->sub_a, e->x, M, T, H3 * SUBFLAT, DROP_EXTRA);
     if (e->debug && tap_copy(e->tap_sub, (size_t)TMAX * D, 0)) return -1;
     }   // front
 
@@ -289,159 +279,205 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
         if (run_layers_fused(e, rows, B, T, G, snap8(seg, bound8(seg)), snap8(seg + 1, bound8(seg + 1)))) return -1;
     } else {
     // ---- 24 cached conformer layers -----------------------------------------------------------
-        // Round 5, chained launches: a k_post that is due is held back (`pend`) and rides as the HEAD PHASE of the GEMM that reads its rows
-        // (GemmParams::chain; W1, QKV, pw1 -- same arithmetic, same bits, one launch and one dependent boundary fewer); if the next launch is
-        // not such a GEMM, or the piece ends, it is launched on its own as before.
-        const bool chain = e->bf16 && !e->debug && !e->prof.on && e->opt_chain && (e->opt_chain == 2 || e->gemm_coresident) && M >= 769 && M < 1344;
-        PostParams pend;
-        bool has_pend = false;
-        double pend_bytes = 0;
-        auto flush_post = [&]() {
-            if (!has_pend) return;
-            has_pend = false;
-            if (e->opt_ablate & 1) return;
-            ProfScope ps(e, "k_post", pend_bytes);
-            launch_post(pend, st);
-        };
-        auto post = [&](const PostParams &q, double bytes) {
-            pend = q; pend_bytes = bytes; has_pend = true;
-            if (!chain) flush_post();
-        };
-        auto gemm_a = [&](GemmParams &gp, const char *tag) {          // a GEMM whose A operand is e->a, the rows of the k_post before it
-            if (has_pend && !(e->opt_ablate & 1) && gemm_chain_ok(gp.M, gp.N, gp.K, gp.splits)) {
-                gp.chain.post = pend;
-                gp.chain.head_rows = 4;
-                gp.chain.head_wgs = (((M + 3) / 4) + 7) & ~7;          // a multiple of 8: the tiles behind keep their XCDs
-                gp.chain.flags = e->chain_flags;
-                gp.chain.error = (unsigned *)(e->n_active + 3);
-                has_pend = false;
-            } else flush_post();
-            run_gemm(e, gp, false, tag);
-        };
-        if (front) {
-            PostParams pp;
-            memset(&pp, 0, sizeof(pp));
-            pp.x = e->x; pp.M = M; pp.ln2_w = e->L[0].ln_ff1_w; pp.ln2_b = e->L[0].ln_ff1_b; pp.a_out = e->a; pp.act_bf16 = act;
-            post(pp, (double)M * D * (4 + e->esz));
-        }
-
-        const int nL = e->hp.n_layers, ks = e->hp.kernel_size;
-        for (int l = l0; l < l1; l++) {
-            LayerW &L = e->L[l];
-            // a residual GEMM (N = 1024): x += scale * A.W^T.  Round 5: where one workgroup owns the complete K sum of a tile (no split-K, or the
-            // welded two-slice form k_gemm_t64w) the GEMM adds to x in its own epilogue and the k_post behind it is left with the LayerNorm
-            // (returns 0 splits for it); otherwise split-K partial slabs + k_post as in rounds 1-4.  Same bits either way.
-            auto resid_gemm = [&](const void *A, int lda, void *w, int K, float scale, const char *tag) -> int {
-                GemmParams a;
-                memset(&a, 0, sizeof(a));
-                a.A = A; a.W = w; a.M = M; a.N = D; a.K = K; a.lda = lda; a.splits = pick_splits(e, M, D, K);
-                // without split-K the fold costs nothing (same kernel, no slab): always; the welded two-slice kernel is two co-resident workgroups in one --
-                // what pipelined steps run anyway, 12 % slower than k_gemm_t64<4> on 224 CUs when the step is alone on the chip: pipelined steps only
-                const bool fold = e->bf16 && e->opt_resid_epilogue && (a.splits == 1 || e->opt_resid_epilogue == 2 || e->gemm_coresident) && gemm_resid_foldable(M, D, K, a.splits, e->opt_t64_tiles + 1);
-                if (fold) { a.epi = EPI_RESID_F32; a.out_f32 = e->x; a.resid = e->x; a.resid_scale = scale; a.ldo = D; }
-                else { a.epi = EPI_PART_F32; a.out_f32 = e->part; a.ldo = D; }
-                run_gemm(e, a, false, tag);
-                return fold ? 0 : a.splits;
-            };
-            auto ffn = [&](void *w1, void *w2, const float *nln_w, const float *nln_b, bool last) {
-                GemmParams a;
-                memset(&a, 0, sizeof(a));
-                a.A = e->a; a.W = w1; a.M = M; a.N = FF; a.K = D; a.lda = D; a.splits = 1;
-                a.epi = EPI_SILU_ACT; a.out_act = e->hbuf; a.ldo_act = FF;
-                gemm_a(a, "ffn_w1");
-                a.splits = resid_gemm(e->hbuf, FF, w2, FF, 0.5f, "ffn_w2");
-                PostParams q;
-                memset(&q, 0, sizeof(q));
-                q.x = e->x; q.M = M; q.part = e->part; q.splits = a.splits; q.scale = 0.5f;   // :633-634
-                q.a_out = e->a; q.act_bf16 = act;
-                if (last) { q.ln_out = 1; q.ln1_w = L.ln_out_w; q.ln1_b = L.ln_out_b; }       // :687
-                q.ln2_w = nln_w; q.ln2_b = nln_b;
-                post(q, (double)M * D * (8 + 4 * a.splits + e->esz));
-            };
-            // 1. FFN1 (:631-634) -> a = LN_att(x)
-            ffn(L.ff1_w1, L.ff1_w2, L.ln_att_w, L.ln_att_b, false);
-            // 2. attention (:637-643)
-            memset(&g, 0, sizeof(g));
-            g.A = e->a; g.W = L.wqkv; g.M = M; g.N = 3 * D; g.K = D; g.lda = D; g.splits = 1;
+        const int ks = e->hp.kernel_size;
+        LayerRun r;
+        r.x = e->x; r.part = e->part; r.glu = e->glu; r.a = e->a; r.hbuf = e->hbuf; r.ctx = e->ctx; r.cbuf = e->cbuf;
+        r.M = r.Mg = M;
+        r.split_k = true;
+        r.chain = e->bf16 && !e->debug && !e->prof.on && e->opt_chain && (e->opt_chain == 2 || e->gemm_coresident) && M >= 769 && M < 1344;
+        // attention (:637-643): q, and K / V straight into the layer's rings
+        r.qkv_out = [&](int l, GemmParams &g) {
             g.epi = EPI_QKV; g.q_out = e->q; g.kv_pool = e->kv_pool[l]; g.kv_slot_stride = (int64_t)2 * KVC * D;
             g.rows = rows; g.T = TS;
-            gemm_a(g, "qkv");
-            {
-                AttnParams ap;
-                memset(&ap, 0, sizeof(ap));
-                ap.q = e->q; ap.kv_pool = e->kv_pool[l]; ap.kv_slot_stride = (int64_t)2 * KVC * D; ap.act_bf16 = act;
-                ap.posproj = L.posproj[T]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.rows = rows; ap.B = B; ap.T = T; ap.TS = TS;
-                ap.ctx_out = e->ctx; ap.ablate = (e->opt_ablate >> 6) & 3;
-                const int KV = LCTX + T;
-                ProfScope ps(e, "k_attention", (double)B * (2.0 * KV + KV + T - 1) * D * e->esz, 2.0 * B * T * KV * D * 3);
-                if (!(e->opt_ablate & 2)) launch_attention(ap, st);
-            }
-            g.splits = resid_gemm(e->ctx, D, L.wo, D, 1.0f, "attn_out");
-            {
-                PostParams q;
-                memset(&q, 0, sizeof(q));
-                q.x = e->x; q.M = M; q.part = e->part; q.splits = g.splits; q.scale = 1.0f;
-                q.ln2_w = L.ln_conv_w; q.ln2_b = L.ln_conv_b; q.a_out = e->a; q.act_bf16 = act;
-                post(q, (double)M * D * (8 + 4 * g.splits + e->esz));
-            }
-            // 3. conv module (:646-679)
-            memset(&g, 0, sizeof(g));
-            g.A = e->a; g.W = L.pw1; g.M = M; g.N = 2 * D; g.K = D; g.lda = D; g.splits = 1;
-            g.epi = EPI_GLU; g.out_f32 = e->glu; g.ldo = D;
-            gemm_a(g, "pw1");
-            {
-                ConvParams cp;
-                memset(&cp, 0, sizeof(cp));
-                cp.glu = e->glu; cp.cc_pool = e->cc_pool[l]; cp.cc_slot_stride = (int64_t)2 * (ks - 1) * D;
-                cp.dw = L.dw; cp.ln_w = L.cln_w; cp.ln_b = L.cln_b; cp.rows = rows; cp.B = B; cp.T = TS; cp.ks = ks;
-                cp.c_out = e->cbuf; cp.act_bf16 = act; cp.stream_form = e->opt_dwconv_stream ? 1 : 0;
-                ProfScope ps(e, "k_dwconv", (double)M * D * (4 + e->esz) + (double)B * 2 * (ks - 1) * D * 4, 2.0 * M * D * ks);
-                if (!(e->opt_ablate & 4)) launch_dwconv(cp, st);
-            }
-            g.splits = resid_gemm(e->cbuf, D, L.pw2, D, 1.0f, "pw2");
-            {
-                PostParams q;
-                memset(&q, 0, sizeof(q));
-                q.x = e->x; q.M = M; q.part = e->part; q.splits = g.splits; q.scale = 1.0f;
-                q.ln2_w = L.ln_ff2_w; q.ln2_b = L.ln_ff2_b; q.a_out = e->a; q.act_bf16 = act;
-                post(q, (double)M * D * (8 + 4 * g.splits + e->esz));
-            }
-            // 4. FFN2 (:682-685) + norm_out (:687); then the next layer's first LayerNorm
-            const bool has_next = l + 1 < nL;
-            ffn(L.ff2_w1, L.ff2_w2, has_next ? e->L[l + 1].ln_ff1_w : nullptr, has_next ? e->L[l + 1].ln_ff1_b : nullptr, true);
-            if (e->debug) { flush_post(); if (tap_copy(e->tap_layers, (size_t)nL * TMAX * D, (size_t)l * TMAX * D)) return -1; }
-        }
-        flush_post();          // the piece ends: the last k_post has no GEMM of this piece behind it
+        };
+        r.attention = [&](int l) {
+            const LayerW &L = e->L[l];
+            AttnParams ap;
+            memset(&ap, 0, sizeof(ap));
+            ap.q = e->q; ap.kv_pool = e->kv_pool[l]; ap.kv_slot_stride = (int64_t)2 * KVC * D; ap.act_bf16 = act;
+            ap.posproj = L.posproj[T]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.rows = rows; ap.B = B; ap.T = T; ap.TS = TS;
+            ap.ctx_out = e->ctx; ap.ablate = (e->opt_ablate >> 6) & 3;
+            const int KV = LCTX + T;
+            ProfScope ps(e, "k_attention", (double)B * (2.0 * KV + KV + T - 1) * D * e->esz, 2.0 * B * T * KV * D * 3);
+            if (!(e->opt_ablate & 2)) launch_attention(ap, st);
+        };
+        // conv module (:646-679): the depthwise conv continues from the stream's conv cache
+        r.dwconv = [&](int l) {
+            const LayerW &L = e->L[l];
+            ConvParams cp;
+            memset(&cp, 0, sizeof(cp));
+            cp.glu = e->glu; cp.cc_pool = e->cc_pool[l]; cp.cc_slot_stride = (int64_t)2 * (ks - 1) * D;
+            cp.dw = L.dw; cp.ln_w = L.cln_w; cp.ln_b = L.cln_b; cp.rows = rows; cp.B = B; cp.T = TS; cp.ks = ks;
+            cp.c_out = e->cbuf; cp.act_bf16 = act; cp.stream_form = e->opt_dwconv_stream ? 1 : 0;
+            ProfScope ps(e, "k_dwconv", (double)M * D * (4 + e->esz) + (double)B * 2 * (ks - 1) * D * 4, 2.0 * M * D * ks);
+            if (!(e->opt_ablate & 4)) launch_dwconv(cp, st);
+        };
+        if (e->debug) r.tap = [&](int l) { return tap_copy(e->tap_layers, (size_t)nLayers * TMAX * D, (size_t)l * TMAX * D); };
+        if (enqueue_layers(e, r, l0, l1)) return -1;
     }
     if (!tail) return 0;
+    return enqueue_encoder_tail(e, e->x, e->hfuse, e->encproj, rows, M, M, G * T,
+                                [&]() { return e->debug ? tap_copy(e->tap_enc, (size_t)TMAX * D, 0) : 0; });
+}
+
+// ---- large-M form of the conformer layers (more than four rows; every offline call) ------------------------------------------
+// Round 5, chained launches: a k_post that is due is held back (`pend`) and rides as the HEAD PHASE of the GEMM that reads its rows
+// (GemmParams::chain; W1, QKV, pw1 -- same arithmetic, same bits, one launch and one dependent boundary fewer); if the next launch is
+// not such a GEMM, or the run ends, it is launched on its own as before.
+int enqueue_layers(nasr_engine *e, const LayerRun &r, int l0, int l1) {
+    hipStream_t st = e->st;
+    const int act = e->bf16 ? 1 : 0, nL = e->hp.n_layers, M = r.M;
+    PostParams pend;
+    bool has_pend = false;
+    double pend_bytes = 0;
+    auto flush_post = [&]() {
+        if (!has_pend) return;
+        has_pend = false;
+        if (e->opt_ablate & 1) return;
+        ProfScope ps(e, "k_post", pend_bytes);
+        launch_post(pend, st);
+    };
+    auto post = [&](const PostParams &q, double bytes) {
+        pend = q; pend_bytes = bytes; has_pend = true;
+        if (!r.chain) flush_post();
+    };
+    auto gemm_a = [&](GemmParams &gp, const char *tag) {          // a GEMM whose A operand is r.a, the rows of the k_post before it
+        if (has_pend && !(e->opt_ablate & 1) && gemm_chain_ok(gp.M, gp.N, gp.K, gp.splits)) {
+            gp.chain.post = pend;
+            gp.chain.head_rows = 4;
+            gp.chain.head_wgs = (((M + 3) / 4) + 7) & ~7;          // a multiple of 8: the tiles behind keep their XCDs
+            gp.chain.flags = e->chain_flags;
+            gp.chain.error = (unsigned *)(e->n_active + 3);
+            has_pend = false;
+        } else flush_post();
+        run_gemm(e, gp, false, tag);
+    };
+    // a residual GEMM (N = 1024): x += scale * A.W^T.  Round 5: where one workgroup owns the complete K sum of a tile (no split-K, or the
+    // welded two-slice form k_gemm_t64w) the GEMM adds to x in its own epilogue and the k_post behind it is left with the LayerNorm
+    // (returns 0 splits for it); otherwise split-K partial slabs + k_post as in rounds 1-4.  Same bits either way.
+    auto resid_gemm = [&](const void *A, int lda, void *w, int K, float scale, const char *tag) -> int {
+        GemmParams a = gemm_desc(A, lda, w, r.Mg, D, K);
+        if (r.split_k) a.splits = pick_splits(e, r.Mg, D, K);
+        // without split-K the fold costs nothing (same kernel, no slab): always; the welded two-slice kernel is two co-resident workgroups in one --
+        // what pipelined steps run anyway, 12 % slower than k_gemm_t64<4> on 224 CUs when the step is alone on the chip: pipelined steps only
+        const bool fold = e->bf16 && e->opt_resid_epilogue && (a.splits == 1 || e->opt_resid_epilogue == 2 || e->gemm_coresident) && gemm_resid_foldable(r.Mg, D, K, a.splits, e->opt_t64_tiles + 1);
+        if (fold) { a.epi = EPI_RESID_F32; a.out_f32 = r.x; a.resid = r.x; a.resid_scale = scale; a.ldo = D; }
+        else { a.epi = EPI_PART_F32; a.out_f32 = r.part; a.ldo = D; }
+        run_gemm(e, a, false, tag);
+        return fold ? 0 : a.splits;
+    };
+    if (l0 == 0) {
+        PostParams pp;
+        memset(&pp, 0, sizeof(pp));
+        pp.x = r.x; pp.M = M; pp.ln2_w = e->L[0].ln_ff1_w; pp.ln2_b = e->L[0].ln_ff1_b; pp.a_out = r.a; pp.act_bf16 = act;
+        post(pp, (double)M * D * (4 + e->esz));
+    }
+
+    for (int l = l0; l < l1; l++) {
+        LayerW &L = e->L[l];
+        auto ffn = [&](void *w1, void *w2, const float *nln_w, const float *nln_b, bool last) {
+            GemmParams a = gemm_desc(r.a, D, w1, r.Mg, FF, D);
+            a.epi = EPI_SILU_ACT; a.out_act = r.hbuf; a.ldo_act = FF;
+            gemm_a(a, "ffn_w1");
+            a.splits = resid_gemm(r.hbuf, FF, w2, FF, 0.5f, "ffn_w2");
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = r.x; q.M = M; q.part = r.part; q.splits = a.splits; q.scale = 0.5f;   // :633-634
+            q.a_out = r.a; q.act_bf16 = act;
+            if (last) { q.ln_out = 1; q.ln1_w = L.ln_out_w; q.ln1_b = L.ln_out_b; }       // :687
+            q.ln2_w = nln_w; q.ln2_b = nln_b;
+            post(q, (double)M * D * (8 + 4 * a.splits + e->esz));
+        };
+        // 1. FFN1 (:631-634) -> a = LN_att(x)
+        ffn(L.ff1_w1, L.ff1_w2, L.ln_att_w, L.ln_att_b, false);
+        // 2. attention (:637-643)
+        GemmParams g = gemm_desc(r.a, D, L.wqkv, r.Mg, 3 * D, D);
+        r.qkv_out(l, g);
+        gemm_a(g, "qkv");
+        r.attention(l);
+        g.splits = resid_gemm(r.ctx, D, L.wo, D, 1.0f, "attn_out");
+        {
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = r.x; q.M = M; q.part = r.part; q.splits = g.splits; q.scale = 1.0f;
+            q.ln2_w = L.ln_conv_w; q.ln2_b = L.ln_conv_b; q.a_out = r.a; q.act_bf16 = act;
+            post(q, (double)M * D * (8 + 4 * g.splits + e->esz));
+        }
+        // 3. conv module (:646-679)
+        g = gemm_desc(r.a, D, L.pw1, r.Mg, 2 * D, D);
+        g.epi = EPI_GLU; g.out_f32 = r.glu; g.ldo = D;
+        gemm_a(g, "pw1");
+        r.dwconv(l);
+        g.splits = resid_gemm(r.cbuf, D, L.pw2, D, 1.0f, "pw2");
+        {
+            PostParams q;
+            memset(&q, 0, sizeof(q));
+            q.x = r.x; q.M = M; q.part = r.part; q.splits = g.splits; q.scale = 1.0f;
+            q.ln2_w = L.ln_ff2_w; q.ln2_b = L.ln_ff2_b; q.a_out = r.a; q.act_bf16 = act;
+            post(q, (double)M * D * (8 + 4 * g.splits + e->esz));
+        }
+        // 4. FFN2 (:682-685) + norm_out (:687); then the next layer's first LayerNorm
+        const bool has_next = l + 1 < nL;
+        ffn(L.ff2_w1, L.ff2_w2, has_next ? e->L[l + 1].ln_ff1_w : nullptr, has_next ? e->L[l + 1].ln_ff1_b : nullptr, true);
+        if (r.tap) { flush_post(); if (r.tap(l)) return -1; }
+    }
+    flush_post();          // the run ends: the last k_post has no GEMM of this run behind it
+    return 0;
+}
+
+int enqueue_encoder_tail(nasr_engine *e, float *x, float *hfuse, float *encproj, const RowDesc *rows, int M, int Mg, int rows_per_prompt,
+                         const std::function<int()> &tap) {
+    hipStream_t st = e->st;
     // ---- a-11 prompt fusion (multilingual only, src/nemo-ggml.cpp:1087-1105) ---------------------
     if (e->hp.num_prompts > 0) {
-        memset(&g, 0, sizeof(g));
-        g.A = e->x; g.W = e->pk1a; g.M = M; g.N = 2048; g.K = D; g.lda = D; g.splits = 1;
-        g.epi = EPI_BIAS_F32; g.out_f32 = e->hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        GemmParams g = gemm_desc(x, D, e->pk1a, Mg, 2048, D);
+        g.epi = EPI_BIAS_F32; g.out_f32 = hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
         { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, 2048, D, 4), 2.0 * M * 2048 * D); launch_gemm_f32(g, st); }
-        launch_prompt_add_relu(e->hfuse, e->pk1p, rows, M, G * T, e->hp.num_prompts, st);
-        memset(&g, 0, sizeof(g));
-        g.A = e->hfuse; g.W = e->pk2_w; g.M = M; g.N = D; g.K = 2048; g.lda = 2048; g.splits = 1;
-        g.epi = EPI_BIAS_F32; g.out_f32 = e->x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        launch_prompt_add_relu(hfuse, e->pk1p, rows, M, rows_per_prompt, e->hp.num_prompts, st);
+        g = gemm_desc(hfuse, 2048, e->pk2_w, Mg, D, 2048);
+        g.epi = EPI_BIAS_F32; g.out_f32 = x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
         { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, D, 2048, 4), 2.0 * M * D * 2048); launch_gemm_f32(g, st); }
     }
-    if (e->debug && tap_copy(e->tap_enc, (size_t)TMAX * D, 0)) return -1;
+    if (tap && tap()) return -1;
 
     // ---- a-13 encoder projection of the joint, hoisted out of the symbol loop --------------------
     {
         ProfScope ps(e, "k_encproj", (double)JNT * D * 4 + (double)M * (D + JNT) * 4, 2.0 * M * JNT * D);
-        launch_encproj(e->x, e->jenc_w, e->jenc_b, e->encproj, M, D, JNT, st);
+        launch_encproj(x, e->jenc_w, e->jenc_b, encproj, M, D, JNT, st);
     }
     return 0;
+}
+
+// ---- a-2 subsampling GEMMs -------------------------------------------------------------------
+void run_sub_pw3(nasr_engine *e, const void *in, float *out, int M) {
+    GemmParams g = gemm_desc(in, SUBC, e->w3, M, SUBC, SUBC);
+    g.epi = EPI_BIAS_RELU_F32; g.out_f32 = out; g.ldo = SUBC; g.bias = e->b3;
+    run_gemm(e, g, false, "sub_pw3");
+}
+
+void run_sub_pw6(nasr_engine *e, const void *in, void *out, int M) {
+    GemmParams g = gemm_desc(in, SUBC, e->w6, M, SUBC, SUBC);
+    g.epi = EPI_BIAS_RELU_ACT; g.out_act = out; g.ldo_act = SUBC; g.bias = e->b6;
+    run_gemm(e, g, false, "sub_pw6");
+}
+
+void run_sub_out(nasr_engine *e, const void *in, float *x, int M, int rows_per_batch, int batch_stride, int row_offset) {
+    GemmParams g = gemm_desc(in, SUBFLAT, e->sub_out_w, M, D, SUBFLAT);
+    g.rows_per_batch = rows_per_batch; g.batch_stride = batch_stride; g.row_offset = row_offset;
+    g.epi = EPI_BIAS_F32; g.out_f32 = x; g.ldo = D; g.bias = e->sub_out_b;
+    run_gemm(e, g, false, "sub_out");
+}
+
+void bind_dec_weights(const nasr_engine *e, DecParams &dp) {
+    dp.embed = e->embed;
+    for (int i = 0; i < 2; i++) { dp.w_ih[i] = e->w_ih[i]; dp.w_hh[i] = e->w_hh[i]; dp.b_ih[i] = e->b_ih[i]; dp.b_hh[i] = e->b_hh[i]; }
+    dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
 }
 
 void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp) {
     memset(&dp, 0, sizeof(dp));
     dp.rows = rows; dp.B = B; dp.T = T; dp.ctrl = e->ctrl; dp.h = e->dec_h; dp.c = e->dec_c; dp.encproj = e->encproj;
-    dp.embed = e->embed;
-    for (int i = 0; i < 2; i++) { dp.w_ih[i] = e->w_ih[i]; dp.w_hh[i] = e->w_hh[i]; dp.b_ih[i] = e->b_ih[i]; dp.b_hh[i] = e->b_hh[i]; }
-    dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
+    bind_dec_weights(e, dp);
     dp.predg = e->predg; dp.key = e->key; dp.n_active = e->n_active; dp.n_dirty = e->n_active + 1; dp.n_rows = e->n_active + 2;
     dp.dlist = e->dlist; dp.rowmap = e->rowmap; dp.tok_ring = e->tok_ring; dp.tok_frame = e->tok_frame;
 }

@@ -286,11 +286,43 @@ void use_ws(nasr_engine *e, const nasr_engine::WS &w);
 void engine_destroy_impl(nasr_engine *e);
 int stream_zero_state(nasr_stream *s, bool keep_reference_state = false);
 double gemm_bytes(const nasr_engine *e, int M, int N, int K, int wesz);
+// out = A [M][K] (row stride lda) . W^T in one K slice, every other field zero: the caller sets the epilogue
+inline GemmParams gemm_desc(const void *A, int lda, const void *W, int M, int N, int K) {
+    GemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.W = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.splits = 1;
+    return g;
+}
 int run_gemm(nasr_engine *e, GemmParams &g, bool f32_weights, const char *tag);
 int pick_splits(const nasr_engine *e, int M, int N, int K);
+// the GEMMs of the subsampling (the chunk step and the offline call; each launches its own conv0 + dw and depthwise conv):
+// pointwise conv 3 (act -> f32, bias + ReLU) and 6 (act -> act, bias + ReLU) on M pixel rows, the out projection
+// [frames][17 x 256] act -> x f32 on M frame rows; rows_per_batch > 0: GemmParams' row map of its A operand
+void run_sub_pw3(nasr_engine *e, const void *in, float *out, int M);
+void run_sub_pw6(nasr_engine *e, const void *in, void *out, int M);
+void run_sub_out(nasr_engine *e, const void *in, float *x, int M, int rows_per_batch = 0, int batch_stride = 0, int row_offset = 0);
 int run_layers_fused(nasr_engine *e, const RowDesc *rows, int B, int T, int G, int k0, int k1, std::vector<FusedParams> *rec = nullptr);
+// The large-M conformer layers over packed rows: what the chunk step's unfused form and the offline call hand enqueue_layers.
+// Rows [0, M) hold data (k_post, the depthwise conv); the GEMMs run on Mg >= M rows (the rows past M are scratch nobody reads).
+struct LayerRun {
+    float *x, *part, *glu;               // residual stream (f32), split-K partial slabs, pw1's GLU output
+    void *a, *hbuf, *ctx, *cbuf;         // act dtype: LayerNorm output (the A operand of W1, QKV, pw1), FFN hidden, attention context, conv output
+    int M, Mg;
+    bool split_k;                        // the residual GEMMs may split K (pick_splits); false: one K slice
+    bool chain;                          // a due k_post may ride as the head phase of the next GEMM that reads its rows
+    std::function<void(int l, GemmParams &g)> qkv_out;   // layer l's QKV GEMM (A = a, its weights and shape set): where its output goes
+    std::function<void(int l)> attention;                 // layer l's attention: the QKV GEMM's output -> ctx
+    std::function<void(int l)> dwconv;                    // layer l's depthwise conv + LayerNorm + SiLU: glu -> cbuf
+    std::function<int(int l)> tap;                        // debug: x after layer l (empty: none)
+};
+int enqueue_layers(nasr_engine *e, const LayerRun &r, int l0, int l1);
+// prompt fusion (multilingual models) and the joint's encoder projection of rows [0, M) of x, the GEMMs on Mg >= M rows; row m
+// takes the prompt of rows[m / rows_per_prompt].  tap (debug, may be empty): x is the encoder output, before the projection
+int enqueue_encoder_tail(nasr_engine *e, float *x, float *hfuse, float *encproj, const RowDesc *rows, int M, int Mg, int rows_per_prompt,
+                         const std::function<int()> &tap);
 int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, const int *tap_slots, int B, int T, int R, int G = 1, int seg = 0,
                            int nseg = 1, int part = 0);
+void bind_dec_weights(const nasr_engine *e, DecParams &dp);     // the decoder's weights (prediction net, joint) into dp
 void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp);
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st = nullptr);
 void chunk_bookkeeping(nasr_stream *s, int row);

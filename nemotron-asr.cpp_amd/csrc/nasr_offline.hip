@@ -199,16 +199,12 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         if (off_alloc(o, (void **)&o->t_sub, (size_t)M * D * 4) || off_alloc(o, (void **)&o->t_lay, (size_t)nL * M * D * 4) ||
             off_alloc(o, (void **)&o->t_enc, (size_t)M * D * 4)) return -1;
     }
-    GemmParams g;
     // ---- subsampling over every whole utterance (no drop-2) ------------------------------------------------------
     {
         ProfScope ps(e, "k_off_conv0_dw", (double)mel_rows * NMEL * 4 + (double)h2_rows * 33 * SUBC * e->esz, 2.0 * h2_rows * 33 * SUBC * 90);
         launch_off_conv0_dw(o->sdesc, n, max_h2, o->mel, e->w0t, e->b0, e->w2t, e->b2, o->sub_b, act, st);
     }
-    memset(&g, 0, sizeof(g));
-    g.A = o->sub_b; g.W = e->w3; g.M = gm(h2_rows * 33); g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
-    g.epi = EPI_BIAS_RELU_F32; g.out_f32 = (float *)o->sub_a; g.ldo = SUBC; g.bias = e->b3;
-    run_gemm(e, g, false, "sub_pw3");
+    run_sub_pw3(e, o->sub_b, (float *)o->sub_a, gm(h2_rows * 33));
     {
         ProfScope ps(e, "k_sub_dw", (double)h2_rows * 33 * SUBC * 4, 2.0 * h3_rows * 17 * SUBC * 9);
         int r3 = 0;
@@ -220,113 +216,43 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
             r3 += T[k];
         }
     }
-    memset(&g, 0, sizeof(g));
-    g.A = o->sub_b; g.W = e->w6; g.M = gm(h3_rows * 17); g.N = SUBC; g.K = SUBC; g.lda = SUBC; g.splits = 1;
-    g.epi = EPI_BIAS_RELU_ACT; g.out_act = o->sub_a; g.ldo_act = SUBC; g.bias = e->b6;
-    run_gemm(e, g, false, "sub_pw6");
-    memset(&g, 0, sizeof(g));
-    g.A = o->sub_a; g.W = e->sub_out_w; g.M = Mg; g.N = D; g.K = SUBFLAT; g.lda = SUBFLAT; g.splits = 1;
-    g.epi = EPI_BIAS_F32; g.out_f32 = o->x; g.ldo = D; g.bias = e->sub_out_b;
-    run_gemm(e, g, false, "sub_out");
+    run_sub_pw6(e, o->sub_b, o->sub_a, gm(h3_rows * 17));
+    run_sub_out(e, o->sub_a, o->x, Mg);
     if (e->debug) HIPCHK(hipMemcpyAsync(o->t_sub, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
 
     // ---- conformer layers over all M rows ------------------------------------------------------------------------
-    auto post = [&](const PostParams &q, double bytes) {
-        ProfScope ps(e, "k_post", bytes);
-        launch_post(q, st);
+    LayerRun r;
+    r.x = o->x; r.part = o->part; r.glu = o->glu; r.a = o->a; r.hbuf = o->hbuf; r.ctx = o->ctx; r.cbuf = o->cbuf;
+    r.M = M; r.Mg = Mg;
+    r.split_k = false;
+    r.chain = false;
+    // q | k | v of every row (no ring: the offline layer has no cache)
+    r.qkv_out = [&](int, GemmParams &g) { g.epi = EPI_BIAS_ACT; g.out_act = o->qkv; g.ldo_act = 3 * D; g.bias = o->zero_bias; };
+    r.attention = [&](int l) {
+        const LayerW &L = e->L[l];
+        OffAttnParams ap;
+        ap.qkv = o->qkv; ap.pos = o->pos[l]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.items = o->items; ap.ctx = o->ctx;
+        double sq = 0;
+        for (int k = 0; k < n; k++) sq += (double)T[k] * T[k];
+        ProfScope ps(e, "k_off_attention", (double)M * 4 * D * e->esz, sq * NH * DH * 6.0);
+        launch_off_attention(ap, (int)items.size(), act, st);
     };
-    auto resid_gemm = [&](const void *A, int lda, void *w, int K, float scale, const char *tag) -> int {
-        GemmParams a;
-        memset(&a, 0, sizeof(a));
-        a.A = A; a.W = w; a.M = Mg; a.N = D; a.K = K; a.lda = lda; a.splits = 1;
-        const bool fold = e->bf16 && gemm_resid_foldable(Mg, D, K, 1, e->opt_t64_tiles + 1);
-        if (fold) { a.epi = EPI_RESID_F32; a.out_f32 = o->x; a.resid = o->x; a.resid_scale = scale; a.ldo = D; }
-        else { a.epi = EPI_PART_F32; a.out_f32 = o->part; a.ldo = D; }
-        run_gemm(e, a, false, tag);
-        return fold ? 0 : a.splits;
+    r.dwconv = [&](int l) {
+        const LayerW &L = e->L[l];
+        ProfScope ps(e, "k_off_dwconv", (double)M * D * (4 + e->esz), 2.0 * M * D * ks);
+        launch_off_dwconv(o->glu, o->tpos, M, L.dw, ks, L.cln_w, L.cln_b, o->cbuf, act, st);
     };
-    {
-        PostParams pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.x = o->x; pp.M = M; pp.ln2_w = e->L[0].ln_ff1_w; pp.ln2_b = e->L[0].ln_ff1_b; pp.a_out = o->a; pp.act_bf16 = act;
-        post(pp, (double)M * D * (4 + e->esz));
-    }
-    for (int l = 0; l < nL; l++) {
-        LayerW &L = e->L[l];
-        auto ffn = [&](void *w1, void *w2, const float *nln_w, const float *nln_b, bool last) {
-            GemmParams a;
-            memset(&a, 0, sizeof(a));
-            a.A = o->a; a.W = w1; a.M = Mg; a.N = FF; a.K = D; a.lda = D; a.splits = 1;
-            a.epi = EPI_SILU_ACT; a.out_act = o->hbuf; a.ldo_act = FF;
-            run_gemm(e, a, false, "ffn_w1");
-            const int sp = resid_gemm(o->hbuf, FF, w2, FF, 0.5f, "ffn_w2");
-            PostParams q;
-            memset(&q, 0, sizeof(q));
-            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 0.5f;
-            q.a_out = o->a; q.act_bf16 = act;
-            if (last) { q.ln_out = 1; q.ln1_w = L.ln_out_w; q.ln1_b = L.ln_out_b; }
-            q.ln2_w = nln_w; q.ln2_b = nln_b;
-            post(q, (double)M * D * (8 + 4 * sp + e->esz));
-        };
-        ffn(L.ff1_w1, L.ff1_w2, L.ln_att_w, L.ln_att_b, false);
-        // q | k | v of every row (no ring: the offline layer has no cache)
-        memset(&g, 0, sizeof(g));
-        g.A = o->a; g.W = L.wqkv; g.M = Mg; g.N = 3 * D; g.K = D; g.lda = D; g.splits = 1;
-        g.epi = EPI_BIAS_ACT; g.out_act = o->qkv; g.ldo_act = 3 * D; g.bias = o->zero_bias;
-        run_gemm(e, g, false, "qkv");
-        {
-            OffAttnParams ap;
-            ap.qkv = o->qkv; ap.pos = o->pos[l]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.items = o->items; ap.ctx = o->ctx;
-            double sq = 0;
-            for (int k = 0; k < n; k++) sq += (double)T[k] * T[k];
-            ProfScope ps(e, "k_off_attention", (double)M * 4 * D * e->esz, sq * NH * DH * 6.0);
-            launch_off_attention(ap, (int)items.size(), act, st);
-        }
-        int sp = resid_gemm(o->ctx, D, L.wo, D, 1.0f, "attn_out");
-        {
-            PostParams q;
-            memset(&q, 0, sizeof(q));
-            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 1.0f;
-            q.ln2_w = L.ln_conv_w; q.ln2_b = L.ln_conv_b; q.a_out = o->a; q.act_bf16 = act;
-            post(q, (double)M * D * (8 + 4 * sp + e->esz));
-        }
-        memset(&g, 0, sizeof(g));
-        g.A = o->a; g.W = L.pw1; g.M = Mg; g.N = 2 * D; g.K = D; g.lda = D; g.splits = 1;
-        g.epi = EPI_GLU; g.out_f32 = o->glu; g.ldo = D;
-        run_gemm(e, g, false, "pw1");
-        {
-            ProfScope ps(e, "k_off_dwconv", (double)M * D * (4 + e->esz), 2.0 * M * D * ks);
-            launch_off_dwconv(o->glu, o->tpos, M, L.dw, ks, L.cln_w, L.cln_b, o->cbuf, act, st);
-        }
-        sp = resid_gemm(o->cbuf, D, L.pw2, D, 1.0f, "pw2");
-        {
-            PostParams q;
-            memset(&q, 0, sizeof(q));
-            q.x = o->x; q.M = M; q.part = o->part; q.splits = sp; q.scale = 1.0f;
-            q.ln2_w = L.ln_ff2_w; q.ln2_b = L.ln_ff2_b; q.a_out = o->a; q.act_bf16 = act;
-            post(q, (double)M * D * (8 + 4 * sp + e->esz));
-        }
-        const bool has_next = l + 1 < nL;
-        ffn(L.ff2_w1, L.ff2_w2, has_next ? e->L[l + 1].ln_ff1_w : nullptr, has_next ? e->L[l + 1].ln_ff1_b : nullptr, true);
-        if (e->debug) HIPCHK(hipMemcpyAsync(o->t_lay + (size_t)l * M * D, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
-    }
-    // ---- prompt fusion (multilingual, src/nemo-ggml.cpp:1087-1105): one prompt per row ------------------------------
-    if (e->hp.num_prompts > 0) {
-        memset(&g, 0, sizeof(g));
-        g.A = o->x; g.W = e->pk1a; g.M = Mg; g.N = 2048; g.K = D; g.lda = D; g.splits = 1;
-        g.epi = EPI_BIAS_F32; g.out_f32 = o->hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
-        { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, 2048, D, 4), 2.0 * M * 2048 * D); launch_gemm_f32(g, st); }
-        launch_prompt_add_relu(o->hfuse, e->pk1p, o->prow, M, 1, e->hp.num_prompts, st);
-        memset(&g, 0, sizeof(g));
-        g.A = o->hfuse; g.W = e->pk2_w; g.M = Mg; g.N = D; g.K = 2048; g.lda = 2048; g.splits = 1;
-        g.epi = EPI_BIAS_F32; g.out_f32 = o->x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
-        { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, D, 2048, 4), 2.0 * M * D * 2048); launch_gemm_f32(g, st); }
-    }
-    if (e->debug) HIPCHK(hipMemcpyAsync(o->t_enc, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
-    {
-        ProfScope ps(e, "k_encproj", (double)JNT * D * 4 + (double)M * (D + JNT) * 4, 2.0 * M * JNT * D);
-        launch_encproj(o->x, e->jenc_w, e->jenc_b, o->encproj, M, D, JNT, st);
-    }
+    if (e->debug) r.tap = [&](int l) -> int {
+        HIPCHK(hipMemcpyAsync(o->t_lay + (size_t)l * M * D, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+        return 0;
+    };
+    if (enqueue_layers(e, r, 0, nL)) return -1;
+    // ---- prompt fusion (one prompt per row), the joint's encoder projection ------------------------------------------
+    if (enqueue_encoder_tail(e, o->x, o->hfuse, o->encproj, o->prow, M, Mg, 1, [&]() -> int {
+            if (e->debug) HIPCHK(hipMemcpyAsync(o->t_enc, o->x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+            return 0;
+        }))
+        return -1;
     // ---- greedy decode in windows of 256 frames per utterance (token ring: 4096 > 256 x 10 symbols) -----------------
     launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
     std::vector<int> tok_read(n, 0);
@@ -349,9 +275,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         DecParams dp;
         memset(&dp, 0, sizeof(dp));
         dp.rows = o->drows; dp.B = n; dp.T = OFF_DEC_WIN; dp.ctrl = o->ctrl; dp.h = o->h; dp.c = o->c; dp.encproj = o->win;
-        dp.embed = e->embed;
-        for (int i = 0; i < 2; i++) { dp.w_ih[i] = e->w_ih[i]; dp.w_hh[i] = e->w_hh[i]; dp.b_ih[i] = e->b_ih[i]; dp.b_hh[i] = e->b_hh[i]; }
-        dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
+        bind_dec_weights(e, dp);
         dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
         dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
         launch_decode_begin(dp, st);
