@@ -13,18 +13,19 @@
 //   * k_gemm_skinny (M <= 32): weight-streaming kernel, HBM-bound.  One 16-column tile x one
 //     64-row slab per workgroup, K split over the 4 waves (and over blockIdx.y for split-K);
 //     activations go straight to registers (requested before the weights); no LDS in the loop.
-//   * M > 32: LDS-tiled kernels, both operands by LDS-DMA into a ring, staged epilogue.  Deep rings, one workgroup per CU:
-//     k_gemm_roles<4> (128 x 128 tile, 8 loader + 8 consumer waves; >= 8 chunks per workgroup), k_gemm_tiled2<4> (the same
-//     tile, 8 waves that do both; short K), k_gemm_t64<4> (128 x 64 tile x 2 K-splits for the N = 1024 GEMMs).  Shallow rings,
-//     TWO workgroups per CU (pipelined steps above 768 rows, every step from 1 792 rows; GemmParams::coresident):
-//     k_gemm_tiled2_k32<4> (32-deep chunks, 4 x 16 KiB) and k_gemm_t64<3> (72 KiB).  All of them perform the same MFMAs in the
-//     same order per accumulator: which one runs never changes a bit of the result (tests/micro/gemm_variant_identity.py).
+//   * M > 32: LDS-tiled kernels, both operands by LDS-DMA into a ring, epilogue staged through LDS.  128 x 128 tiles: k_gemm_roles<4> and k_gemm_tiled2<4> (deep rings,
+//     one workgroup per CU), k_gemm_tiled3 and k_gemm_tiled2_k32<4> (32-deep chunks, two workgroups per CU; the latter carries a chained k_post head phase),
+//     k_gemm_persist<EPI> (one workgroup per CU walks its tiles).  128 x 64 tiles: k_gemm_t64<3|4> (split-K, N = 1024), k_gemm_t64w (both K halves in one workgroup,
+//     residual add in the epilogue).  224- / 256-row tiles from 1 344 / 1 792 rows: k_gemm_wide2<192|256, 7>, k_gemm_wide<256, 7|8>.  Which one runs, with which
+//     grid and LDS size, is gemm_plan_bf16() (nasr_gemm_plan.h: the rules and the measurements behind them; tests/test_gemm_plan.py).  All of them perform the same
+//     MFMAs in the same order per accumulator: which one runs never changes a bit of the result (tests/micro/gemm_variant_identity.py).
 // f32 path (parity mode): plain LDS-tiled FMA kernel, k ascending, deterministic.
 #include "nasr_internal.h"
 #include <type_traits>
 #include "nasr_epilogue.h"
 #include "nasr_wave.h"
 #include "nasr_post.h"
+#include "nasr_gemm_plan.h"
 
 namespace nasr {
 
@@ -106,7 +107,6 @@ __global__ __launch_bounds__(256) void k_gemm_skinny(GemmParams p) {
     }
 }
 
-constexpr int TM = 128;
 constexpr int TM_ROWS = 128;          // rows of a row chunk whose publication a chained launch counts (= TM)
 
 __device__ __forceinline__ int panel_off(int row, int chunk) {  // byte offset in a [128][64] bf16 panel
@@ -126,6 +126,14 @@ __device__ __forceinline__ int panel_off(int row, int chunk) {  // byte offset i
 //  * the DMA is issued from inline asm (M0 = wave-uniform LDS base), so hipcc does not see a pending
 //    LDS write and does not drain vmcnt(0) in front of every ds_read; completion is counted by hand
 //    (8 DMA instructions per wave per chunk).
+
+// Workgroup ids contiguous per XCD: the hardware deals blockIdx.x round-robin over the 8 XCDs; XCD x gets the ids [start(x), start(x) + its share) of nblk.
+__device__ __forceinline__ int xcd_contiguous_id(int id, int nblk) {
+    const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
+    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
+}
+// first 64-deep chunk of K slice `split` of `splits` (slice = [k_slice(split), k_slice(split + 1)); the 32-deep kernels double it: the same boundaries)
+__device__ __forceinline__ int k_slice(int kc_total, int split, int splits) { return (int)((long)kc_total * split / splits); }
 
 // Which tile a workgroup computes.  ids are contiguous per XCD (the remap at the top of every kernel); split-K slices outermost.
 // Rounds 1-3 ran the row chunk fastest: an XCD then sweeps ALL activation panels once per column group -- 14.7 MB at 7 168 rows x
@@ -148,7 +156,6 @@ __device__ __forceinline__ void tile_of(int id, int n_groups, int m_chunks, int 
 }
 
 // ------------------------------------------------------------------------------------
-constexpr int G2_SLOT = 32768;
 
 __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
     unsigned keep;
@@ -161,7 +168,6 @@ __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
 // 15.2 us with, 9.8 us without its stores).  The ring is free once the K loop is over: the accumulators are parked in it as
 // an f32 tile [128][132] and every thread then handles 4 consecutive columns of one row, so that a wave writes two whole
 // rows of the tile (2 x 512 B of f32 / 2 x 256 B of bf16) per instruction.  Same epi_quad, same values, other thread.
-constexpr int STG_LD = 132;      // floats per staged row (128 + 4: the 16 rows of a float4 store spread over the banks)
 __device__ __forceinline__ void stage_acc(float *stage, int m_local, int n_local, const f32x4 &a) {
     *(float4 *)(stage + m_local * STG_LD + n_local) = make_float4(a[0], a[1], a[2], a[3]);
 }
@@ -241,12 +247,7 @@ __global__ __launch_bounds__(512) void k_gemm_tiled2(GemmParams p, int n_groups,
     // 8 waves = 2 per SIMD: wave w owns n-tile pair (w & 3) x m-tiles [(w >> 2) * 4, +4).  One wave's
     // LDS-DMA issue (expensive: ~100+ cycles per 1 KiB instruction) overlaps its SIMD partner's MFMAs.
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split;
     tile_of(id, n_groups, m_chunks, p.tile_bands, mc, ng, split);
 
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(512) void k_gemm_tiled2(GemmParams p, int n_groups,
     const int q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5;
     const int kc_total = KT >> 1;
-    const int c0 = (int)((long)kc_total * split / p.splits), c1 = (int)((long)kc_total * (split + 1) / p.splits);
+    const int c0 = k_slice(kc_total, split, p.splits), c1 = k_slice(kc_total, split + 1, p.splits);
     const int nchunks = c1 - c0;
     const int m0 = mc * TM;
     const int ntile0 = (ng * 4 + ng4) * 2;
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(512) void k_gemm_tiled2_k32(GemmParams p, int n_gro
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int ng4 = wave & 3, mh = wave >> 2, q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5, kc_total = KT >> 1;
-    const int t0 = 2 * (int)((long)kc_total * split / p.splits), t1 = 2 * (int)((long)kc_total * (split + 1) / p.splits);
+    const int t0 = 2 * k_slice(kc_total, split, p.splits), t1 = 2 * k_slice(kc_total, split + 1, p.splits);
     const int nchunks = t1 - t0, m0 = mc * TM;
     // this wave DMAs weight tile ng * 8 + wave (one k-tile per chunk) and panel rows [wave * 16, +16)
     const uint4 *wpd = (const uint4 *)p.W + (size_t)(ng * 8 + wave) * KT * 64 + lane;
@@ -481,18 +482,13 @@ __global__ __launch_bounds__(512) void k_gemm_tiled3(GemmParams p, int n_groups,
     constexpr int NS = T3_NS;
     GSTAMP(0);
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split;
     tile_of(id, n_groups, m_chunks, p.tile_bands, mc, ng, split);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int ng4 = wave & 3, mh = wave >> 2, q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5, kc_total = KT >> 1;
-    const int t0 = 2 * (int)((long)kc_total * split / p.splits), t1 = 2 * (int)((long)kc_total * (split + 1) / p.splits);
+    const int t0 = 2 * k_slice(kc_total, split, p.splits), t1 = 2 * k_slice(kc_total, split + 1, p.splits);
     const int nchunks = t1 - t0, m0 = mc * TM;
     const char *wpd = (const char *)((const uint4 *)p.W + (size_t)(ng * 8 + wave) * KT * 64 + lane) + (size_t)t0 * 1024;
     const char *asrc;
@@ -585,24 +581,18 @@ __global__ __launch_bounds__(512) void k_gemm_tiled3(GemmParams p, int n_groups,
 // partial bytes on both sides of the seam.  8 waves = 2 n-tile pairs x 4 quarters of the rows (32 x 32 per wave); slot =
 // 16 KiB activation panel + 8 KiB weight tiles per 64-deep chunk, 3 DMA instructions per wave and chunk.
 // ------------------------------------------------------------------------------------
-constexpr int T64_SLOT = 24576, T64_STG_LD = 68;
 template <int NS>
 __global__ __launch_bounds__(512) void k_gemm_t64(GemmParams p, int n_groups, int m_chunks) {
     constexpr int P = NS - 1;
     extern __shared__ __attribute__((aligned(16))) char ring[];
     if (p.prio & 1) __builtin_amdgcn_s_setprio(3);
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split;
     tile_of(id, n_groups, m_chunks, p.tile_bands, mc, ng, split);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int ng2 = wave & 1, mq = wave >> 1, q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5, kc_total = KT >> 1;
-    const int c0 = (int)((long)kc_total * split / p.splits), c1 = (int)((long)kc_total * (split + 1) / p.splits);
+    const int c0 = k_slice(kc_total, split, p.splits), c1 = k_slice(kc_total, split + 1, p.splits);
     const int nchunks = c1 - c0, m0 = mc * TM, ntile0 = ng * 4;
     // this wave DMAs weight tile (ntile0 + (wave >> 1), k-tile wave & 1) and panel rows [wave * 16, +16)
     const uint4 *wpd = (const uint4 *)p.W + ((size_t)(ntile0 + (wave >> 1)) * KT + (wave & 1)) * 64 + lane;
@@ -684,16 +674,10 @@ __global__ __launch_bounds__(512) void k_gemm_t64(GemmParams p, int n_groups, in
 // CU, k_post is left with the LayerNorm.  Each half performs k_gemm_t64's MFMAs in k_gemm_t64's order (split = half of 2): p0 and p1 are
 // the slabs' values.  The residual tile (32 KiB) is requested at kernel entry, long before it is needed.
 // ------------------------------------------------------------------------------------
-constexpr int T64W_NS = 3, T64W_HALF = T64W_NS * T64_SLOT;          // 73 728 B per K-half
 __global__ __launch_bounds__(1024) void k_gemm_t64w(GemmParams p, int n_groups, int m_chunks) {
     constexpr int NS = T64W_NS, P = NS - 1;
     extern __shared__ __attribute__((aligned(16))) char ring_all[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split_unused;
     tile_of(id, n_groups, m_chunks, p.tile_bands, mc, ng, split_unused);
     const int wave16 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -701,7 +685,7 @@ __global__ __launch_bounds__(1024) void k_gemm_t64w(GemmParams p, int n_groups, 
     char *ring = ring_all + half * T64W_HALF;
     const int ng2 = wave & 1, mq = wave >> 1, q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5, kc_total = KT >> 1;
-    const int c0 = (int)((long)kc_total * half / 2), c1 = (int)((long)kc_total * (half + 1) / 2);     // k_gemm_t64's slice `half` of 2
+    const int c0 = k_slice(kc_total, half, 2), c1 = k_slice(kc_total, half + 1, 2);     // k_gemm_t64's slice `half` of 2
     const int nchunks = c1 - c0, m0 = mc * TM, ntile0 = ng * 4;
     // the residual tile: two float4 per thread (row e >> 4, columns 4 (e & 15) of the 128 x 64 tile, e = tid and tid + 1024)
     float4 xin[2];
@@ -799,12 +783,7 @@ template <int NS>
 __global__ __launch_bounds__(1024) void k_gemm_roles(GemmParams p, int n_groups, int m_chunks) {
     constexpr int P = NS - 1;
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split;
     tile_of(id, n_groups, m_chunks, p.tile_bands, mc, ng, split);
     const int wave16 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -812,7 +791,7 @@ __global__ __launch_bounds__(1024) void k_gemm_roles(GemmParams p, int n_groups,
     const int wave = wave16 & 7;
     const int ng4 = wave & 3, mh = wave >> 2, q = lane >> 4, r = lane & 15;
     const int KT = p.K >> 5, kc_total = KT >> 1;
-    const int c0 = (int)((long)kc_total * split / p.splits), c1 = (int)((long)kc_total * (split + 1) / p.splits);
+    const int c0 = k_slice(kc_total, split, p.splits), c1 = k_slice(kc_total, split + 1, p.splits);
     const int nchunks = c1 - c0, m0 = mc * TM, ntile0 = (ng * 4 + ng4) * 2;
     if (loader) {
         const uint4 *wpd = (const uint4 *)p.W + (size_t)(ntile0 + mh) * KT * 64 + lane;
@@ -925,7 +904,6 @@ __global__ __launch_bounds__(1024) void k_gemm_roles(GemmParams p, int n_groups,
 // with idle storers); and SiLU in the consumers stalled the MFMAs 1.3 us per tile.  Here the epilogue is a template parameter, the
 // per-tile pointers are computed once, the pack is branch-free and SiLU is the storers' work.
 // ------------------------------------------------------------------------------------
-constexpr int PS_NS = 3, PS_STAGE = PS_NS * G2_SLOT, PS_LDS = PS_STAGE + 65536;
 __device__ __forceinline__ unsigned ps_stage_off(int row, int cg) { return PS_STAGE + row * 512 + ((cg ^ (row & 31)) << 4); }
 __device__ __forceinline__ uint32_t bf16_rne_bits(float f) {          // f32_to_bf16 without a branch (same values, NaN kept NaN)
     const uint32_t u = __float_as_uint(f);
@@ -1115,31 +1093,12 @@ __global__ __launch_bounds__(1024) void k_gemm_persist(GemmParams p, int n_group
 // Same v_mfma_f32_16x16x32_bf16, k ascending from zero per accumulator: the bits of every other kernel of this file
 // (tests/micro/gemm_variant_identity.py, engine option "wide_tiles" = 0 / 1).
 // ------------------------------------------------------------------------------------
-constexpr int WD_NS = 4;
-// MT = 16-row m-tiles per wave: the tile has BM = 32 MT rows.  MT = 8 (256 rows) and MT = 7 (224 rows = 16 streams x R = 13: 7 168 rows
-// are 32 of them, so that N = 4096 gives 512 tiles = two FULL rounds of the chip where 256-row tiles give 1.75, and N = 2048 one
-// round of 256 smaller tiles instead of 224 larger ones) -- launch_gemm_bf16 takes the one whose rounds x rows is smaller.
-template <int BN, int MT> struct WideCfg {
-    static constexpr int BM = 32 * MT;
-    static constexpr int SLOT = (BM + BN) * 64;               // bytes per 32-deep chunk
-    static constexpr int NT = BN / 64;                        // weight fragments (16-row tiles) per wave and chunk
-    static constexpr int NP = BM / 16;                        // LDS-DMA pieces of the activation panel (16 rows x 64 B each)
-    static constexpr int PIECES = NP + BN / 16;               // + the weight tiles of 1 KiB
-    static constexpr int DMA = (PIECES + 7) / 8;              // LDS-DMA instructions per wave and chunk (a wave without a piece of its own repeats the last one)
-    static constexpr int STG_LD = BN + 4;                     // floats per staged row
-    static constexpr size_t LDS = (size_t)WD_NS * SLOT > (size_t)64 * (BN + 4) * 4 ? (size_t)WD_NS * SLOT : (size_t)64 * (BN + 4) * 4;
-};
 template <int BN, int MT>
 __global__ __launch_bounds__(512) void k_gemm_wide(GemmParams p, int n_groups, int m_chunks) {
     using C = WideCfg<BN, MT>;
     constexpr int P = WD_NS - 1, NT = C::NT, DMA = C::DMA, BM = C::BM;
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split_unused;
     tile_of(id, n_groups, m_chunks, p.tile_bands == 2 ? 2 : 1, mc, ng, split_unused);          // bands of column groups whatever the row count (tile_of() above)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1328,12 +1287,7 @@ __global__ __launch_bounds__(512) void k_gemm_wide2(GemmParams p, int n_groups, 
     GSTAMP(0);
     static_assert(MT >= DMA + 1, "one DMA instruction after each of the first DMA MFMA groups");
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    const int nblk = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     int mc, ng, split_unused;
     tile_of(id, n_groups, m_chunks, p.tile_bands == 2 ? 2 : 1, mc, ng, split_unused);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1448,222 +1402,33 @@ __global__ __launch_bounds__(512) void k_gemm_wide2(GemmParams p, int n_groups, 
     GSTAMP(3);
 }
 
-static size_t gemm_lds_bytes(int ns) {     // the ring, or the f32 tile the epilogue parks in it, whichever is larger
-    const size_t ring = (size_t)ns * G2_SLOT, stage = (size_t)TM * STG_LD * 4;
-    return ring > stage ? ring : stage;
-}
-
-static size_t gemm_k32_lds_bytes(int ns) {
-    const size_t ring = (size_t)ns * K32_SLOT, stage = (size_t)TM * STG_LD * 4;
-    return ring > stage ? ring : stage;
-}
-
 constexpr int F32M_KC = 32, F32M_NS = 3;
 template <int BM, int BN> __global__ void k_gemm_f32_mfma(GemmParams p, int n_groups, int m_chunks);      // the f32 engine's MFMA kernel, below
 
 static int g_num_cus = 256;      // MI355X; refreshed from the device below
+// The ring depths of round 5's loops stay beside the kernels whose counted waits are written for them; the plan's table states the four sizes they give as numbers.
+static_assert(GEMM_INST_LDS[GI_TILED3] == T3_NS * K32_SLOT && GEMM_INST_LDS[GI_TILED2_K32] == (4 * K32_SLOT > TM * STG_LD * 4 ? 4 * K32_SLOT : TM * STG_LD * 4) &&
+              GEMM_INST_LDS[GI_WIDE2_192_7] == wide2_lds<192, 7>() && GEMM_INST_LDS[GI_WIDE2_256_7] == wide2_lds<256, 7>(), "nasr_gemm_plan.h: LDS size of a kernel instance");
+// the kernels of NASR_GEMM_INSTANCES (nasr_gemm_plan.h), in its order; k_gemm_skinny takes the GemmParams alone
+#define X(id, k, lds) (const void *)k,
+static const void *const gemm_inst_kernel[GI_COUNT] = {NASR_GEMM_INSTANCES(X)};
+#undef X
 void init_gemm_kernel_attributes() {
-    hipFuncSetAttribute((const void *)k_gemm_tiled2<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(4));
-    hipFuncSetAttribute((const void *)k_gemm_roles<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(4));
-    hipFuncSetAttribute((const void *)k_gemm_t64<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * T64_SLOT);
-    hipFuncSetAttribute((const void *)k_gemm_t64<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * T64_SLOT);
-    hipFuncSetAttribute((const void *)k_gemm_t64w, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * T64W_HALF);
-    hipFuncSetAttribute((const void *)k_gemm_tiled2_k32<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_k32_lds_bytes(4));
-    hipFuncSetAttribute((const void *)k_gemm_tiled3, hipFuncAttributeMaxDynamicSharedMemorySize, T3_NS * K32_SLOT);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_PART_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_SILU_ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_GLU>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_BIAS_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_persist<EPI_BIAS_RELU_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS);
-    hipFuncSetAttribute((const void *)k_gemm_wide<256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideCfg<256, 8>::LDS);
-    hipFuncSetAttribute((const void *)k_gemm_wide<256, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideCfg<256, 7>::LDS);
-    hipFuncSetAttribute((const void *)k_gemm_wide2<256, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, wide2_lds<256, 7>());
-    hipFuncSetAttribute((const void *)k_gemm_wide2<192, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, wide2_lds<192, 7>());
+    for (int i = 0; i < GI_COUNT; i++)
+        if (GEMM_INST_LDS[i] > 0) hipFuncSetAttribute(gemm_inst_kernel[i], hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_INST_LDS[i]);
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_num_cus = cus;
     hipFuncSetAttribute((const void *)k_gemm_f32_mfma<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 256 * 128);
     hipFuncSetAttribute((const void *)k_gemm_f32_mfma<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 128 * 128);
 }
 
-// 128 x 64 tiles (k_gemm_t64): for the split-K GEMMs with N = 1024 when that halves the split factor, and for any other GEMM
-// whose 128 x 128 tiling gives at most 64 workgroups (a quarter of the CUs).  With pipelined steps "fill the chip" is the wrong
-// rule for the in-between sizes: CUs one launch leaves idle run another chain's kernels.  Measured with three lanes, half-width
-// tiles wherever the 128 x 128 tiling had <= 128 workgroups against the split-K form only: 16 streams x R = 13 (32-64 tiles)
-// 1.22 vs 1.32 ms per step, 32 streams (64-128 tiles) 1.82 vs 1.77, 64 streams (pw1: 112 tiles -> 224) 2.66 vs 2.65 -- although
-// alone the 112-tile launch takes 13.3 us and the vendor library's MT128x64 kernel 10.6 (tests/prof_gemm_shapes.sh).
-// Round 4: for the split-K GEMMs only up to 64 tiles of 128 x 128 (M <= 1 024).  Above that two K-halves of 128 x 128 tiles fill the chip by themselves
-// (72-120 tiles x 2 <= 256 workgroups) where the half-width form makes 288-480 workgroups of a shape that moves 1.5 x the operand bytes per flop: 112 streams
-// x R = 13 (104 tiles) synchronous 5.92 -> 5.30 ms, pipelined 3.82 -> 3.77; 128 streams (112 tiles) pipelined 4.21 -> 4.14, synchronous 5.52 -> 5.69
-// (profiles/r4_tile_order.md).  Engine option "t64_tiles" (the choice is made in two places that must agree: both read GemmParams::t64_tiles_p1).
-// t64_p1 = GemmParams::t64_tiles_p1 (the engine's option + 1; 0 = the default of 64): carried per GEMM so that several engines in one
-// process cannot change each other's choice between the two places that must agree (round-4 advisor: it was a process-wide global).
-bool gemm_use_t64(int M, int N, int epi, int t64_p1) {
-    if (M <= gemm_skinny_max_m()) return false;
-    const int tiles = (N / 128) * ((M + 127) / 128);
-    if (epi == EPI_PART_F32) return N == 1024 && tiles <= (t64_p1 > 0 ? t64_p1 - 1 : 64);
-    return tiles <= 64;
-}
-int gemm_tile_n(int M, int N, int epi, int t64_p1) { return gemm_use_t64(M, N, epi, t64_p1) ? 64 : 128; }
-// EPI_RESID_F32 needs the complete K sum in one workgroup: the welded two-slice 128 x 64 form where pick_splits chose two slices of
-// half-width tiles (256 < M <= 1 024 at the default "t64_tiles"), or any launch without split-K
-static bool gemm_welded(int M, int N, int K, int splits, int t64_p1) {
-    return splits == 2 && (K & 127) == 0 && gemm_use_t64(M, N, EPI_PART_F32, t64_p1);
-}
-// a GEMM whose A rows come out of a k_post can carry that k_post as its head phase (ChainParams) when it runs on the 128 x 128 tiles of
-// k_gemm_tiled2_k32: more than 32 rows, no split-K, N a multiple of 128, at most 64 row chunks (the counters)
-bool gemm_chain_ok(int M, int N, int K, int splits) {
-    return M > gemm_skinny_max_m() && splits == 1 && N % 128 == 0 && (K & 63) == 0 && (M + TM - 1) / TM <= 64;
-}
-bool gemm_resid_foldable(int M, int N, int K, int splits, int t64_p1) {
-    if (M <= gemm_skinny_max_m()) return false;
-    return splits == 1 || gemm_welded(M, N, K, splits, t64_p1);
-}
-
-// Largest M served by the weight-streaming ("skinny") kernel; above it the LDS-tiled kernels take over.  Round 1 had 128 (chosen
-// on synchronous steps).  Re-measured in round 2 (ms per step, <= 32 / <= 64 / <= 128 rows skinny):
-//   three lanes: 64 streams x R = 0 (M = 64) 1.15 / 1.33 / 1.33; 40 / 48 streams x R = 0 1.04 / 1.13 and 1.06 / 1.19 / -;
-//                64 x R = 1 (M = 128) 1.29 / 1.30 / 1.89; 8 x R = 13 and 16 x R = 6 (M = 112) 1.13 / 1.13 / 1.62;
-//                32 rows and fewer: skinny wins (32 streams x R = 0 0.94 against 1.00 tiled; 16 x R = 1 0.89 / 0.99)
-//   synchronous: M = 64 2.66 / - / 2.56, M = 48 2.56 / - / 2.41, M = 112 2.66 / - / 2.81, M = 128 2.95 / - / 3.17
-// -> 32 rows.  ONE threshold for both modes: which kernel a GEMM runs on must not depend on the mode, or pipelined steps would
-// stop being bit-identical to synchronous ones (the synchronous step pays <= 6 % for it between 33 and 64 rows and gains above).
-int gemm_skinny_max_m() {
-    return 32;
-}
-
-// Pipelined steps (GemmParams::coresident): four launch chains advance in lock-step rounds, so the GEMM launches of a round start
-// together and, with one 96-128 KiB workgroup per CU, run one after the other -- a round costs the SUM of its GEMMs.  With rings of
-// <= 72 KiB two of them share every CU: one workgroup's ring fill and barrier waits run under the other's MFMAs (64 streams x
-// R = 13: 2.64 -> 2.48 ms per step; alone on the chip the shallower rings cost 8 %, so synchronous steps keep the deep ones).
-// From seven 128-row tiles up (M > 768), where every GEMM of the step covers most of the chip: measured per step with four lanes,
-// 64 streams x R = 13 (M = 896) 2.61 -> 2.47 ms, 48 streams (M = 672) 2.05 -> 2.03, 40 streams (M = 560) 1.76 -> 1.81, 32 streams 1.51 -> 1.59.
-static bool gemm_coresident(const GemmParams &p) {
-    constexpr int min_m = 769;
-    if (p.coresident >= 2) return p.coresident == 2;          // engine option "gemm_cores" (A/B runs, the bit-identity test)
-    // more than one wave of tiles (M >= 1 792): workgroups of ONE launch start as earlier ones finish, so the two on a CU are out of
-    // phase by themselves -- synchronous steps gain as well (128 streams x R = 13: 6.51 -> 5.95 ms, 512 streams 19.9 -> 18.6 ms).
-    // Only with more tiles than CUs: a launch that puts at most one workgroup on a CU has nothing to pair and keeps the deep rings
-    // (cold operands, us per launch, deep / shallow: 1 792 rows pw1 224 tiles 12.6 / 16.7, W2 112 tiles 28.3 / 32.4; 3 584 rows W2 224 tiles
-    // 34.7 / 45.1, Wo 12.0 / 14.8 -- profiles/r4_tile_order.md)
-    if (p.coresident == 1 && p.M >= min_m) return true;
-    const long tiles = (long)(p.N / (gemm_use_t64(p.M, p.N, p.epi, p.t64_tiles_p1) ? 64 : 128)) * ((p.M + TM - 1) / TM) * (p.splits < 1 ? 1 : p.splits);
-    return p.M >= 1792 && tiles > g_num_cus;
-}
-
-// round 5's loops (k_gemm_wide2, k_gemm_tiled3) unless GemmParams::prio >> 2 == 5: rounds 1-4's (engine option "gemm_prio" = 20: A/B runs, gemm_variant_identity.py).
-// The probes this field also selected during the round (s_setprio around the MFMA cluster, "every fragment first", DMA between the MFMA groups on the old kernels) are
-// gone from the tree: profiles/r5_gemm_tile_stamps.md, r5_gemm_loops_probe_{7168,896}.txt.
-static bool gemm_new_loops(const GemmParams &p) { return (p.prio >> 2) == 0 || (p.prio >> 2) == 4; }
+// Which instance, grid and LDS size: gemm_plan_bf16() (nasr_gemm_plan.h).  This maps the plan to a launch.
 void launch_gemm_bf16(const GemmParams &p0, hipStream_t st) {
+    GemmPlan pl = gemm_plan_bf16(p0, g_num_cus);
     GemmParams p = p0;
-    if (p.splits < 1) p.splits = 1;
-    if (p.M <= gemm_skinny_max_m()) {
-        dim3 grid(p.N / 16, p.splits, (p.M + 63) / 64);
-        if (p.M <= 16) hipLaunchKernelGGL(k_gemm_skinny<1>, grid, dim3(256), 0, st, p);
-        else if (p.M <= 32) hipLaunchKernelGGL(k_gemm_skinny<2>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_gemm_skinny<4>, grid, dim3(256), 0, st, p);
-    } else {
-        int n_groups = p.N / 128, m_chunks = (p.M + TM - 1) / TM;
-        if (p.chain.head_wgs > 0) {                        // chained launch (the caller asked gemm_chain_ok()): k_gemm_tiled2_k32 is the kernel that carries a head phase
-            hipLaunchKernelGGL(k_gemm_tiled2_k32<4>, dim3(p.chain.head_wgs + n_groups * m_chunks * p.splits), dim3(512), gemm_k32_lds_bytes(4), st, p, n_groups, m_chunks);
-            return;
-        }
-        if (p.epi == EPI_RESID_F32 && p.splits == 2) {      // the caller asked gemm_resid_foldable(): both K slices in one 16-wave workgroup
-            GemmParams w = p;
-            w.splits = 1;                                  // tile_of(): one workgroup per tile
-            hipLaunchKernelGGL(k_gemm_t64w, dim3((p.N / 64) * m_chunks), dim3(1024), 2 * T64W_HALF, st, w, p.N / 64, m_chunks);
-            return;
-        }
-        if (gemm_use_t64(p.M, p.N, p.epi, p.t64_tiles_p1)) {       // half-width tiles: the caller chose splits for N / 64 column groups (gemm_tile_n)
-            n_groups = p.N / 64;
-            if (gemm_coresident(p))      // 3 slots = 72 KiB: two workgroups per CU
-                hipLaunchKernelGGL(k_gemm_t64<3>, dim3(n_groups * m_chunks * p.splits), dim3(512), 3 * T64_SLOT, st, p, n_groups, m_chunks);
-            else
-                hipLaunchKernelGGL(k_gemm_t64<4>, dim3(n_groups * m_chunks * p.splits), dim3(512), 4 * T64_SLOT, st, p, n_groups, m_chunks);
-            return;
-        }
-        // more than one wave of tiles: 256 x 256 tiles (half the operand bytes per flop) where their rounds fill the chip -- the last round at
-        // least 5 / 8 full, or three rounds and more (persist_probe, cold operands, us per launch against the per-tile pair: 7 168 rows W1 448
-        // tiles 78 / 83, pw1 224 tiles 38 / 45, QKV 336 tiles 69 / 70: a wash, left alone; 15 360 rows N = 1024 240 tiles 109 / 160).  The
-        // 256 x 128 form measured worse than the per-tile kernels with cold operands (W2 at 7 168 rows 92 / 77) and is not used.
-        // Synchronous steps only -- alone on the chip the QKV launch at 7 168 rows takes 52 us instead of 62, but a pipelined 512-stream step got SLOWER with it
-        // (13.65 against 13.50 ms, same box, three-way A/B): the half-empty round is where the other lanes' launches run.
-        // N = 3072 (QKV) on 224 x 192 tiles where 224 x 256 leaves a half-empty last round: 7 168 rows 384 tiles = 1.5 rounds -> 512 = two full rounds of
-        // 3 / 4-size tiles, 3 584 rows 192 tiles (0.75 of the chip) -> 256.  k_gemm_wide2 only (its wave-private epilogue takes 48-column blocks).
-        if (!p.no_wide && gemm_new_loops(p) && p.coresident != 1 && p.splits == 1 && p.M >= 1792 && (p.K & 63) == 0 && p.K >= 256 && p.N % 192 == 0 && p.N % 256 == 0) {
-            const long mw = (p.M + 223) / 224, t192 = (long)(p.N / 192) * mw, t256 = (long)(p.N / 256) * mw;
-            const long c192 = (t192 + g_num_cus - 1) / g_num_cus * 192, c256 = (t256 + g_num_cus - 1) / g_num_cus * 256;
-            if (c192 < c256 && t192 >= (long)g_num_cus * 7 / 8) {
-                hipLaunchKernelGGL((k_gemm_wide2<192, 7>), dim3((unsigned)t192), dim3(512), (wide2_lds<192, 7>()), st, p, p.N / 192, (int)mw);
-                return;
-            }
-        }
-        if (!p.no_wide && p.splits == 1 && p.M >= (p.coresident == 1 ? (p.wide_min_rows > 0 ? p.wide_min_rows : 1344) : 1792) && (p.K & 31) == 0 && p.N % 256 == 0) {
-            // 256- or 224-row tiles: whichever needs fewer rounds x rows (7 168 rows: N = 4096 two full rounds of 224-row tiles instead of
-            // 1.75 of 256-row ones, N = 2048 one round of 256 smaller tiles; 15 360 rows stay at 256).  Cold operands, us per launch, 256 / 224 rows:
-            // W1 at 7 168 rows 78.8 / 74.9, pw1 38.4 / 35.4, W1 at 3 584 rows 43.8 / 41.0; synchronous steps 512 streams 18.08 -> 17.82 ms, 256
-            // streams 9.56 -> 9.42; pipelined steps (three pieces) 384 streams 10.95 -> 10.82, 512 streams 14.32 = (profiles/r4_wide_tiles.md).
-            int best_mt = 0;
-            long best_cost = 0, best_tiles = 0;
-            for (int mt = 8; mt >= 7; mt--) {
-                const int bm = 32 * mt, mw = (p.M + bm - 1) / bm;
-                const long tiles = (long)(p.N / 256) * mw, last = tiles % g_num_cus;
-                if (!(tiles >= (long)g_num_cus * 7 / 8 && (last == 0 || last * 8 >= (long)g_num_cus * 5 || tiles >= (long)g_num_cus * 3))) continue;
-                const long cost = (tiles + g_num_cus - 1) / g_num_cus * bm;
-                if (!best_mt || cost < best_cost) { best_mt = mt; best_cost = cost; best_tiles = tiles; }
-            }
-            // Pipelined steps (other lanes' workgroups fill the CUs a launch leaves idle): 224-row tiles from 32 of them (round 4: 96; round 5, profiles/r5_gemm_tile_stamps.md section 3:
-            // what a pipelined step pays for a GEMM is its CU-time, and a 224 x 256 tile costs 40 % less of it than four 128 x 128 ones -- 256 streams 7.4 -> 7.2 ms), where the rule above finds
-            // too few to fill the chip.  What a pipelined step is short of is operand delivery -- at 64 streams the LDS fills of a step's
-            // 128 x 128 tiles add up to 23 GB = 9.5 TB/s, between what the Infinity Cache (8.6) and an XCD's L2 (17-19) deliver -- and a
-            // 224 x 256 tile moves 0.54 of the bytes per flop.  ms per step, four lanes, without / with: 96 streams 3.37 / 3.33, 128 streams
-            // 4.30 / 4.19, 192 streams 6.22 / 6.02; from 64 tiles: 4.21 (128 streams), 3.35 (96); at 64 streams (64 / 48 / 32 tiles) 2.42 -> 2.54, W1's 64 tiles alone 2.415 -> 2.449: not taken.
-            // With it: 256 streams 8.00 -> 7.93, 384 streams 11.75 -> 11.43, 512 streams (every GEMM of the layer on these tiles) 15.31 -> 14.49.
-            if (!best_mt && p.coresident == 1 && p.wide_rows != 2) {
-                const long tiles = (long)(p.N / 256) * ((p.M + 223) / 224);
-                if (tiles >= (p.wide_min_tiles > 0 ? p.wide_min_tiles : 32)) { best_mt = 7; best_tiles = tiles; }          // engine option "wide_min_tiles"
-            }
-            if (p.wide_rows == 256 && best_mt) { best_mt = 8; best_tiles = (long)(p.N / 256) * ((p.M + 255) / 256); }      // engine option "wide_tiles" = 256: round 4's first form only
-            if (best_mt == 8) {
-                hipLaunchKernelGGL((k_gemm_wide<256, 8>), dim3((unsigned)best_tiles), dim3(512), (WideCfg<256, 8>::LDS), st, p, p.N / 256, (p.M + 255) / 256);
-                return;
-            }
-            if (best_mt == 7) {
-                if (gemm_new_loops(p) && (p.K & 63) == 0 && p.K >= 256) hipLaunchKernelGGL((k_gemm_wide2<256, 7>), dim3((unsigned)best_tiles), dim3(512), (wide2_lds<256, 7>()), st, p, p.N / 256, (p.M + 223) / 224);
-                else hipLaunchKernelGGL((k_gemm_wide<256, 7>), dim3((unsigned)best_tiles), dim3(512), (WideCfg<256, 7>::LDS), st, p, p.N / 256, (p.M + 223) / 224);
-                return;
-            }
-        }
-        // several 128 x 128 tiles per CU: the persistent tile loop (one workgroup per CU; ring fills and epilogues off the critical path).
-        // From 1.75 tiles per CU: below that a workgroup has no second tile to hide anything under.
-        if (!p.no_persist && p.splits == 1 && p.K >= 1024 && (p.K & 63) == 0 && (long)n_groups * m_chunks * 4 >= (long)g_num_cus * 7) {
-            const dim3 pgrid(g_num_cus), pblock(1024);
-            switch (p.epi) {
-            case EPI_PART_F32: hipLaunchKernelGGL(k_gemm_persist<EPI_PART_F32>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            case EPI_SILU_ACT: hipLaunchKernelGGL(k_gemm_persist<EPI_SILU_ACT>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            case EPI_QKV: hipLaunchKernelGGL(k_gemm_persist<EPI_QKV>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            case EPI_GLU: hipLaunchKernelGGL(k_gemm_persist<EPI_GLU>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            case EPI_BIAS_F32: hipLaunchKernelGGL(k_gemm_persist<EPI_BIAS_F32>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            case EPI_BIAS_RELU_F32: hipLaunchKernelGGL(k_gemm_persist<EPI_BIAS_RELU_F32>, pgrid, pblock, PS_LDS, st, p, n_groups, m_chunks); return;
-            default: break;                        // the act-dtype bias epilogues (subsampling) stay on the per-tile kernels
-            }
-        }
-        dim3 grid(n_groups * m_chunks * p.splits);
-        if (gemm_coresident(p) && gemm_new_loops(p) && ((p.K >> 6) / p.splits) * 2 >= 6 && (p.K >> 6) % p.splits == 0) {
-            hipLaunchKernelGGL(k_gemm_tiled3, grid, dim3(512), T3_NS * K32_SLOT, st, p, n_groups, m_chunks);
-            return;
-        }
-        if (gemm_coresident(p)) {                  // 4 x 16 KiB ring (+ the staged tile: 66 KiB): two workgroups per CU
-            hipLaunchKernelGGL(k_gemm_tiled2_k32<4>, grid, dim3(512), gemm_k32_lds_bytes(4), st, p, n_groups, m_chunks);
-            return;
-        }
-        constexpr int roles_min_chunks = 8;
-        const bool roles = (p.K >> 6) / p.splits >= roles_min_chunks;
-        const size_t lds = gemm_lds_bytes(4);
-        if (roles) hipLaunchKernelGGL(k_gemm_roles<4>, grid, dim3(1024), lds, st, p, n_groups, m_chunks);
-        else hipLaunchKernelGGL(k_gemm_tiled2<4>, grid, dim3(512), lds, st, p, n_groups, m_chunks);
-    }
+    p.splits = pl.splits;
+    void *args[] = {&p, &pl.n_groups, &pl.m_chunks};
+    hipLaunchKernel(gemm_inst_kernel[pl.inst], dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(pl.block), args, (size_t)pl.lds, st);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1802,11 +1567,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmParams p, int n_group
     constexpr int ROWS = BM + BN, SLOT = ROWS * 128, DMA = ROWS / 32;      // DMA instructions per wave and chunk (8 rows each)
     constexpr int IM = BM / 64, IN = BN / 64;                              // 32 x 32 blocks per wave along m / n
     extern __shared__ __attribute__((aligned(16))) char ring[];
-    int id = blockIdx.x;
-    {
-        const int nblk = gridDim.x, qd = nblk >> 3, rm = nblk & 7, xcd = id & 7, loc = id >> 3;
-        id = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
     const int mc = id % m_chunks, ng = id / m_chunks;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, kh = lane >> 5;

@@ -2,6 +2,7 @@
 // large-M forms, prompt fusion, joint.enc) and of the decode, token collection (reference src/nemo-stream.cpp:336-690, :840-930).
 // The offline call (nasr_offline.hip) runs the same subsampling GEMMs, large-M layers, encoder tail and decoder weights.
 #include "nasr_engine_priv.h"
+#include "nasr_gemm_plan.h"
 
 // ---- the chunk step: encoder + decode for the rows that have a full chunk buffered ----------------
 namespace nasr_eng {
@@ -32,24 +33,7 @@ int run_gemm(nasr_engine *e, GemmParams &g, bool f32_weights, const char *tag) {
 }
 
 // residual GEMM: part = A.W^T (split-K), followed by k_post
-int pick_splits(const nasr_engine *e, int M, int N, int K) {
-    if (!e->bf16) return 1;
-    const bool skinny = M <= gemm_skinny_max_m();
-    int tasks = skinny ? (N / 16) * ((M + 63) / 64) : (N / gemm_tile_n(M, N, EPI_PART_F32, e->opt_t64_tiles + 1)) * ((M + 127) / 128);
-    // partial traffic grows with the split factor, and with pipelined steps the CUs a launch leaves idle run another chain's
-    // kernels: four splits only up to 40 tiles (three lanes, R = 13: 12 / 16 streams = 32 tiles 1.15 / 1.23 ms with 4 splits
-    // against 1.23 / 1.30 with 2; 24 streams = 48 tiles 1.53 vs 1.50; 32 streams = 64 tiles 1.82 vs 1.68; 64 streams = 112 tiles:
-    // 2 splits 2.76, 1 split 2.75, 4 splits 3.03)
-    // Round 5: one slice from 200 tiles of 128 x 128 (256 streams x R = 13: 224 tiles, 7.76 -> 7.48 ms per pipelined step): that many workgroups fill the chip
-    // by themselves, and a GEMM that owns its tiles' whole K sums adds to the residual stream in its own epilogue -- no partial slabs, k_post is the
-    // LayerNorm alone.  Counted in 128 x 128 tiles whatever the tile the launcher takes, so that every kernel variant sums in the same order.
-    if (!skinny && (N / 128) * ((M + 127) / 128) >= (e->opt_split_tasks > 0 ? e->opt_split_tasks : 200)) return 1;
-    if (!skinny) return tasks <= 40 ? 4 : (tasks < 256 ? 2 : 1);
-    constexpr int skinny_cap = 8;
-    int s = 1;
-    while (s < skinny_cap && tasks * s < 256 && (K / 32) / (s * 2) >= 4) s *= 2;
-    return s;
-}
+int pick_splits(const nasr_engine *e, int M, int N, int K) { return gemm_pick_splits(e->bf16, M, N, K, e->opt_t64_tiles + 1, e->opt_split_tasks); }
 
 // ---- small-M form of the 24 layers: 8 launches per layer (kernels_fused.hip) ------------------------
 // launches [k0, k1) of the 8 x n_layers launches of the fused layers: a piece boundary may sit inside a layer (every

@@ -141,7 +141,7 @@ struct GemmParams {
     const RowDesc *rows;  int T;  // row m -> stream m / T, frame m % T
     // pipelined steps: this launch shares the chip with other launch chains' GEMMs -- the large-M kernels then use the variants
     // whose LDS ring lets two workgroups share a CU (same arithmetic in the same order: bit-identical to the default kernels)
-    int coresident;       // 0: synchronous step, 1: pipelined step (the rule of kernels_gemm.hip decides), 2 / 3: always / never (engine option "gemm_cores")
+    int coresident;       // 0: synchronous step, 1: pipelined step (the rule of nasr_gemm_plan.h decides), 2 / 3: always / never (engine option "gemm_cores")
     // wave priority of the co-resident kernels (round-4 probe, tests/micro/cores_probe.hip): bit 0 = s_setprio 3 for the whole kernel,
     // bit 1 = back to 0 before the epilogue.  0 = leave the default (what ships unless the probe says otherwise).
     // prio >> 2 (round 5, engine option "gemm_prio"): 0 = round 5's loops (k_gemm_wide2, k_gemm_tiled3), 5 = rounds 1-4's (k_gemm_wide, k_gemm_tiled2_k32): A/B runs and the identity test
@@ -174,13 +174,7 @@ struct GemmParams {
 // ---- kernel launchers (defined in the .hip files) -----------------------------------
 void init_gemm_kernel_attributes();    // one-time hipFuncSetAttribute calls (never inside a stream capture)
 void init_fused_kernel_attributes();
-int gemm_skinny_max_m();     // largest M served by the weight-streaming kernel
-int gemm_tile_n(int M, int N, int epi, int t64_tiles_p1);      // output-tile width the large-M kernel will use (128, or 64 for the N = 1024 split-K GEMMs); t64_tiles_p1 as in GemmParams
-void launch_gemm_bf16(const GemmParams &p, hipStream_t st);
-// can a residual GEMM (N = 1024 ... D columns, `splits` K slices by pick_splits) add its product to the residual stream in its own epilogue
-// (EPI_RESID_F32)?  Yes where one workgroup owns the complete K sum of a tile: no split-K, or the two-slice 128 x 64 form (k_gemm_t64w)
-bool gemm_resid_foldable(int M, int N, int K, int splits, int t64_tiles_p1);
-bool gemm_chain_ok(int M, int N, int K, int splits);      // may this GEMM carry the k_post that produces its A rows as a head phase (GemmParams::chain)?
+void launch_gemm_bf16(const GemmParams &p, hipStream_t st);      // the kernel it takes and the rules its callers ask (gemm_chain_ok, gemm_resid_foldable, ...): nasr_gemm_plan.h
 void launch_gemm_f32(const GemmParams &p, hipStream_t st);
 void launch_pack_weight_bf16(const float *w_f32, bf16_t *packed, int N, int K, hipStream_t st);
 void launch_f32_to_bf16(const float *in, bf16_t *out, int64_t n, hipStream_t st);
