@@ -147,6 +147,11 @@ int nasr_stream_get_progress(const nasr_stream *s, nasr_stream_stats *out);
  * index of tokens [first, first + count) of this stream, counted from create/reset.  Only the most recent
  * 4096 tokens are kept on the device.  Returns the number written, < 0 on error. */
 int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t count, int32_t *frames_out);
+/* per-token confidence (the reference has no such output): ln P(token) of tokens [first, first + count) of this stream under the
+ * joint's softmax over all 1025 outputs, at the frame and decoder state where each was emitted; f32, in [-ln 1025, 0] because the
+ * token is the arg-max.  Same contract as nasr_stream_get_token_frames: completes steps in flight, tokens counted from create/reset,
+ * only the most recent 4096 kept, returns the number written, < 0 on error -- also when engine option "token_logprobs" is off. */
+int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out);
 
 /* ---- the step: replaces nemo_stream_process_incremental (src/nemo-stream.cpp:1145-1206)
  * for B streams at once = nemo_preprocessor_process (src/preprocessor.cpp:330-395) +
@@ -231,7 +236,12 @@ enum {
  * are invalid: bit mask of launches left out of a step: 1 residual + LayerNorm, 2 attention, 4 depthwise conv, 8 decode iterations, 16 front end, 32 encoder
  * GEMMs; what each costs a pipelined step: profiles/r5_ablation.md), "decode_lane" (0: the decode graphs run behind the last encoder
  * piece instead of on a stream of their own; read when the lanes are picked, so it is REJECTED after the first pipelined step or
- * nasr_engine_lend_stream). */
+ * nasr_engine_lend_stream).
+ * "token_logprobs" (0 default / 1): a capability, not a kernel A/B switch -- with 1 the device decode also keeps, for every emitted token,
+ * the natural-log softmax probability of that token over the 1025 joint outputs (blank included) at the frame and decoder state where it
+ * was emitted (nasr_stream_get_token_logprobs, nasr_engine_offline_token_logprobs).  Tokens, frames, iteration counts and decoder state
+ * are bit-identical to 0.  It selects the decode kernels that are captured into the step graphs and allocates a ring per stream, so it is
+ * REJECTED after the first step or offline call. */
 int nasr_engine_set_option(nasr_engine *e, const char *key, int value);
 /* diagnostics: "graph_execs" (hipGraphExec objects alive), "graph_shapes" (distinct cached step shapes), "graph_evictions",
  * "graph_replays" (calls served by a hipGraph, pipelined ones included), "eager_steps" (calls that were not graph-eligible: ragged
@@ -293,6 +303,10 @@ int nasr_engine_transcribe(nasr_engine *e, int B, const int16_t *const *pcm, con
  * [T][1024] / NASR_TAP_LAYER_OUT (index = layer) / NASR_TAP_ENCODER_OUT of utterance u of that call.  Every offline call forgets
  * the taps of the one before.  Returns the number of floats written (<= cap), with out == NULL the number available, or < 0. */
 int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, float *out, int64_t cap);
+/* ln P(token) of every token of utterance u of the LAST offline call (either entry; engine option "token_logprobs" = 1), in token order:
+ * out[i] belongs to tokens_out[u][i].  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
+ * call forgets the values of the one before. */
+int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
 
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =

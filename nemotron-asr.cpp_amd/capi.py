@@ -31,6 +31,7 @@ EXPORTS = [
     "nasr_device_upload", "nasr_engine_synchronize", "nasr_engine_get_counter", "nasr_stream_debug_fill_kv",
     "nasr_diar_create", "nasr_diar_destroy", "nasr_diar_set_stream", "nasr_diar_vad", "nasr_diar_embed", "nasr_diar_logmel", "nasr_diar_last_gpu_ms",
     "nasr_engine_transcribe_mel", "nasr_engine_transcribe", "nasr_engine_offline_tap",
+    "nasr_stream_get_token_logprobs", "nasr_engine_offline_token_logprobs",
 ]
 OFFLINE_MAX_FRAMES = 2048
 
@@ -113,6 +114,8 @@ def lib():
         L.nasr_engine_transcribe.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, ip, C.POINTER(vp), C.c_uint32]
         L.nasr_engine_offline_tap.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64]
         L.nasr_engine_offline_tap.restype = C.c_int64
+        L.nasr_stream_get_token_logprobs.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
+        L.nasr_engine_offline_token_logprobs.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
         _lib = L
     return _lib
 
@@ -184,6 +187,15 @@ class Stream:
         out = np.zeros(max(count, 1), np.int32)
         n = _chk(lib().nasr_stream_get_token_frames(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out[:n].tolist()
+
+    def token_logprobs(self, first=0, count=None) -> np.ndarray:
+        """ln P(token) under the joint's softmax (blank included) of tokens [first, first + count) since create/reset, f32;
+        needs engine option "token_logprobs" = 1 (set before the first step)"""
+        if count is None:
+            count = max(int(self.stats().tokens) - first, 0)
+        out = np.zeros(max(count, 1), np.float32)
+        n = _chk(lib().nasr_stream_get_token_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:n].copy()
 
     def tap(self, which, index=0, cap=None) -> np.ndarray:
         cap = cap or 1024 * 260          # up to MAXNEW = 256 encoder frames of one launch, or a 70-row cache
@@ -458,6 +470,14 @@ class Engine:
         out = np.zeros(max(cap, 1), np.float32)
         n = _chk(L.nasr_engine_offline_tap(self.h, which, u, index, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
         return out[:n].reshape(-1, width).copy()
+
+    def offline_token_logprobs(self, u) -> np.ndarray:
+        """ln P(token) of every token of utterance u of the last offline call (engine option "token_logprobs" = 1)"""
+        L = lib()
+        cap = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, None, 0))
+        out = np.zeros(max(cap, 1), np.float32)
+        n = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
+        return out[:n].copy()
 
     # ---- measurement ------------------------------------------------------------------
     def profile(self, on=True):

@@ -240,10 +240,16 @@ __global__ __launch_bounds__(256) void k_dec_pred(DecParams p) {
     }
 }
 
-__device__ __forceinline__ unsigned long long pack_key(float v, int idx) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                 // order-preserving
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (uint32_t)idx);
+using nasr_lp::pack_key;                                            // (order-preserving logit bits) << 32 | (0xffffffff - index), nasr_logprob.h
+static_assert(nasr_lp::LP_VOCAB == VOCAB && nasr_lp::SMALL_ROWS == 64, "nasr_logprob.h restates the joint kernels' shapes");
+// engine option "token_logprobs": the (max, sum of exp) part of a 16-entry vocab tile, lane (q, r) holding entries v0 .. v0 + 3 of row r's
+// logits; every lane of the row ends up with the same bits (merge is symmetric)
+__device__ __forceinline__ nasr_lp::Part lp_tile_part(float x0, float x1, float x2, float x3, int v0) {
+    nasr_lp::Part a = nasr_lp::lane4(x0, x1, x2, x3, nasr_lp::lane_valid(v0)), b;
+    b.m = __shfl_xor(a.m, 16); b.s = __shfl_xor(a.s, 16);
+    a = nasr_lp::merge(a, b);
+    b.m = __shfl_xor(a.m, 32); b.s = __shfl_xor(a.s, 32);
+    return nasr_lp::merge(a, b);
 }
 __device__ __forceinline__ unsigned long long kmax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
@@ -253,7 +259,7 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 
 // ---- joint, few rows (<= 64 rows in the step): logits = W_out . relu(encproj[row] + g) + b_out and
 // arg-max; grid = 65 (1040 padded vocab rows), 4 waves split K; first maximum wins (:899-906, :1220-1221)
-template <int MT>
+template <int MT, bool LP>
 __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, float (*red)[MT_MAX][64][4]) {
     const int nt = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
@@ -283,12 +289,14 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
     const int i = i0 + mt * 16 + r;
     if (mt < MT) {
         unsigned long long best = 0ull;
+        float lgs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int v = nt * 16 + q * 4 + j;
             if (v < VOCAB) {
                 const float lg = (((red[0][mt][lane][j] + red[1][mt][lane][j]) + red[2][mt][lane][j]) + red[3][mt][lane][j]) + p.out_b[v];
                 best = kmax(best, pack_key(lg, v));
+                if (LP) lgs[j] = lg;
             }
         }
         best = kmax(best, shfl_xor_u64(best, 16));
@@ -297,18 +305,24 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
             const unsigned rm = p.rowmap[i];
             atomicMax(&p.key[(size_t)(rm & 0xffffu) * p.T + (rm >> 16)], best);
         }
+        if (LP) {                                      // one part per 16-entry tile: part nt of the row, written by lane group 0
+            const nasr_lp::Part part = lp_tile_part(lgs[0], lgs[1], lgs[2], lgs[3], nt * 16 + q * 4);
+            const int row = nasr_lp::joint_store_row(i0, MT, wave, lane, nr);
+            if (row >= 0) p.lp_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), nt, nasr_lp::TILE_PARTS)] = part;
+        }
     }
 }
 
+template <bool LP>
 __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
     const int nr = *p.n_rows;
     if (nr == 0) return;
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nr; i0 += 16 * MT_MAX) {
-        const int left = nr - i0;
-        if (left <= 16) joint_pass<1>(p, i0, nr, red);
-        else if (left <= 32) joint_pass<2>(p, i0, nr, red);
-        else joint_pass<4>(p, i0, nr, red);
+        const int tiles = nasr_lp::joint_pass_tiles(nr - i0);      // 1, 2 or 4 m-tiles: 16, 32 or more rows left
+        if (tiles == 1) joint_pass<1, LP>(p, i0, nr, red);
+        else if (tiles == 2) joint_pass<2, LP>(p, i0, nr, red);
+        else joint_pass<4, LP>(p, i0, nr, red);
     }
 }
 
@@ -318,12 +332,14 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // workgroup and staged in LDS (double-buffered, 16-byte chunks XOR-swizzled with the row).  The
 // kernel is bound by the f32 MFMA (32 cycles per 16x16x4), 640 of them per wave.
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
+template <bool LP>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     const int nr = *p.n_rows;
     const int m0 = blockIdx.y * 64;
     if (m0 >= nr) return;
     __shared__ __attribute__((aligned(16))) float xs[2][64 * JT_KC];
     __shared__ unsigned long long bests[4][64];
+    __shared__ nasr_lp::Part lps[LP ? 4 : 1][64];      // token_logprobs: the four waves' tile parts of the 64 rows
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
     const int nt = blockIdx.x * 4 + wave;
     const bool has_tile = nt * 16 < VOCAB;
@@ -399,6 +415,14 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         best = kmax(best, shfl_xor_u64(best, 16));
         best = kmax(best, shfl_xor_u64(best, 32));
         if (q == 0) bests[wave][mt * 16 + r] = best;
+        if (LP) {
+            const int v0 = has_tile ? nt * 16 + q * 4 : VOCAB;          // no tile: the empty part
+            float lg[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) lg[j] = acc[mt][j] + p.out_b[v0 + j < VOCAB ? v0 + j : 0];
+            const nasr_lp::Part part = lp_tile_part(lg[0], lg[1], lg[2], lg[3], v0);
+            if (q == 0) lps[wave][mt * 16 + r] = part;
+        }
     }
     __syncthreads();
     if (threadIdx.x < 64 && m0 + threadIdx.x < nr) {
@@ -406,9 +430,17 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         const unsigned rm = p.rowmap[m0 + threadIdx.x];
         if (best) atomicMax(&p.key[(size_t)(rm & 0xffffu) * p.T + (rm >> 16)], best);
     }
+    if (LP) {                                      // one part per workgroup (64 entries): part blockIdx.x of the row, waves merged in order
+        const int row = nasr_lp::tiled_store_row(blockIdx.y, threadIdx.x, nr);
+        if (row >= 0) {
+            const nasr_lp::Part part = nasr_lp::wg64(lps[0][threadIdx.x], lps[1][threadIdx.x], lps[2][threadIdx.x], lps[3][threadIdx.x]);
+            p.lp_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), blockIdx.x, nasr_lp::WG_PARTS)] = part;
+        }
+    }
 }
 
 // ---- commit: walk each stream's evaluated frames up to its first non-blank -------------------------
+template <bool LP>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
@@ -421,8 +453,9 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
         if (!ct->active) continue;
         const int t0 = ct->t, nf = ct->n_frames;
         int f = t0, best = BLANK;
+        unsigned long long k = 0ull;
         for (; f < nf; f++) {
-            const unsigned long long k = p.key[(size_t)b * p.T + f];
+            k = p.key[(size_t)b * p.T + f];
             best = (int)(0xffffffffu - (uint32_t)(k & 0xffffffffull));
             if (best != BLANK) break;                  // blank: next frame, state untouched (src/nemo-stream.cpp:908-911)
         }
@@ -438,6 +471,11 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
             const int n = ct->n_tok;
             p.tok_ring[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = best;
             p.tok_frame[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = ct->frame0 + f;
+            if (LP) {                                  // the parts of frame f were written by this iteration's joint kernel (f is in rowmap)
+                const int np = nasr_lp::n_parts(p.B * p.T);
+                const nasr_lp::Part *parts = p.lp_part + nasr_lp::scratch_index(b * p.T + f, 0, np);
+                p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(nasr_lp::key_logit(k), parts, np);
+            }
             ct->n_tok = n + 1;
             ct->prev_token = best;
             ct->cur ^= 1;
@@ -507,9 +545,15 @@ void launch_decode_iter(const DecParams &p, int iter, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
     const int rows = p.B * p.T;
-    if (rows <= 64) hipLaunchKernelGGL(k_dec_joint, dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_dec_joint_tiled, dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(k_dec_commit, dim3(1), dim3(256), 0, st, p);
+    if (p.lp_part) {                            // engine option "token_logprobs": the variants that also leave the softmax parts / the token's log-probability
+        if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL(k_dec_joint<true>, dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(k_dec_joint_tiled<true>, dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(k_dec_commit<true>, dim3(1), dim3(256), 0, st, p);
+        return;
+    }
+    if (rows <= 64) hipLaunchKernelGGL(k_dec_joint<false>, dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_dec_joint_tiled<false>, dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(k_dec_commit<false>, dim3(1), dim3(256), 0, st, p);
 }
 // iterations enqueued before the host looks at n_active: (symbols of the busiest stream) + 1 are needed; a shortfall
 // costs one host round trip and a further round of iterations

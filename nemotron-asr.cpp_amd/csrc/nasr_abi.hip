@@ -20,6 +20,18 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         if (e->pipe_ready) return fail("decode_lane must be set before the first pipelined step (the lanes are already picked)");
         e->opt_decode_lane = value != 0;
     }
+    else if (!strcmp(key, "token_logprobs")) {
+        // selects the decode kernels that get captured into the step graphs and allocates their buffers: like "decode_lane", a later change would
+        // be a silent no-op for the graphs that exist (and the tokens already in the ring would have no value)
+        if (value != 0 && value != 1) return fail("token_logprobs must be 0 or 1");
+        if (e->dec_started || e->off) return fail("token_logprobs must be set before the first step or offline call (the decode kernels are already chosen)");
+        if (value && !e->lp_part) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP)) return -1;
+        }
+        e->opt_token_logprobs = value != 0;
+    }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
     else if (!strcmp(key, "wide_min_rows")) e->opt_wide_min_rows = value;
@@ -457,6 +469,26 @@ extern "C" int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first,
     std::vector<int> ring(TOK_CAP);
     HIPCHK(hipMemcpy(ring.data(), e->tok_frame + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(int), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) frames_out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
+    return count;
+}
+
+extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out) {
+    ApiGuard api_guard;
+    if (!s || (count > 0 && !out)) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative token range");
+    nasr_engine *e = s->e;
+    if (!e->opt_token_logprobs) return fail("no token log-probabilities: engine option \"token_logprobs\" is off (set it to 1 before the first step)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    HIPCHK(hipStreamSynchronize(e->st));
+    DecCtrl c;
+    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
+    if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
+    if (count <= 0) return 0;
+    std::vector<float> ring(TOK_CAP);
+    HIPCHK(hipMemcpy(ring.data(), e->tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
     return count;
 }
 

@@ -218,6 +218,11 @@ struct nasr_engine {
     unsigned long long *key;
     int *n_active;                   // [3] = n_active, n_dirty, n_rows
     int *dlist; unsigned *rowmap; int *tok_frame;
+    // option "token_logprobs": per-token log-probabilities from the decode kernels.  It picks the kernels that get captured into step graphs and
+    // allocates the two buffers, so it is taken only until the first decode has been enqueued (dec_started) or the first offline call has run
+    bool opt_token_logprobs = false, dec_started = false;
+    nasr_lp::Part *lp_part = nullptr;      // [max(64 x 65, w_rows x 17)] softmax parts of the rows of a decode iteration (nasr_logprob.h)
+    float *tok_logprob = nullptr;    // [slot][TOK_CAP] beside tok_ring / tok_frame
     int *collect_dev;                // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nasr_logprob.h"
 
 namespace nasr {
 
@@ -252,6 +253,9 @@ struct DecParams {
     unsigned *rowmap;            // [B * T] (frame << 16 | batch row) of every frame still to decode
     int *tok_ring;               // [slot][TOK_CAP]
     int *tok_frame;              // [slot][TOK_CAP] absolute encoder frame of each token
+    // engine option "token_logprobs" (both null when it is off: the launches are then the kernels without it)
+    nasr_lp::Part *lp_part;            // [B * T][n_parts] (max, sum of exp(x - max)) of every vocab slice of every evaluated row (nasr_logprob.h)
+    float *tok_logprob;          // [slot][TOK_CAP] natural-log softmax probability of each token where it was emitted
 };
 void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, int iter, hipStream_t st);

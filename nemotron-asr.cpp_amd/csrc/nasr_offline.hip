@@ -27,6 +27,8 @@ struct OfflineState {
     DecCtrl *ctrl = nullptr; float *h = nullptr, *c = nullptr, *predg = nullptr, *win = nullptr;
     unsigned long long *key = nullptr; int *n_active = nullptr, *dlist = nullptr, *tok_ring = nullptr, *tok_frame = nullptr;
     unsigned *rowmap = nullptr; RowDesc *drows = nullptr; int4 *dwin = nullptr;
+    nasr_lp::Part *lp_part = nullptr; float *tok_logprob = nullptr;      // engine option "token_logprobs" (allocated with the slots when it is on)
+    std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
     std::vector<std::vector<float>> tap_mel, tap_sub, tap_enc;
@@ -122,6 +124,10 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
         rc |= off_alloc(o, (void **)&o->rowmap, U * W * 4);
         rc |= off_alloc(o, (void **)&o->tok_ring, U * TOK_CAP * 4);
         rc |= off_alloc(o, (void **)&o->tok_frame, U * TOK_CAP * 4);
+        if (e->opt_token_logprobs) {
+            rc |= off_alloc(o, (void **)&o->lp_part, nasr_lp::scratch_parts((int)(U * W)) * sizeof(nasr_lp::Part));
+            rc |= off_alloc(o, (void **)&o->tok_logprob, U * TOK_CAP * 4);
+        }
         rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
         rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
         rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
@@ -258,6 +264,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
     std::vector<int> tok_read(n, 0);
     std::vector<DecCtrl> hctrl(n);
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
+    std::vector<float> ringl(o->tok_logprob ? (size_t)n * TOK_CAP : 0);
     for (int w0 = 0; w0 < maxT; w0 += OFF_DEC_WIN) {
         std::vector<RowDesc> rd(n);
         std::vector<int4> wd(n);
@@ -278,6 +285,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         bind_dec_weights(e, dp);
         dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
         dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
+        dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs"
         launch_decode_begin(dp, st);
         int it = 0, budget = decode_blind_iterations(max_dec), h_active = 0;
         while (max_dec > 0) {
@@ -292,6 +300,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         HIPCHK(hipMemcpyAsync(hctrl.data(), o->ctrl, (size_t)n * sizeof(DecCtrl), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ringf.data(), o->tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (int k = 0; k < n; k++) {
             const int n_new = hctrl[k].n_tok - tok_read[k];
@@ -300,6 +309,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
                 const int pos = (tok_read[k] + i) & (TOK_CAP - 1);
                 toks[first + k].push_back(ring[(size_t)k * TOK_CAP + pos]);
                 frs[first + k].push_back(ringf[(size_t)k * TOK_CAP + pos]);
+                if (!ringl.empty()) o->logprobs[first + k].push_back(ringl[(size_t)k * TOK_CAP + pos]);
             }
             tok_read[k] = hctrl[k].n_tok;
         }
@@ -338,6 +348,7 @@ static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const
         return fail("offline plan rejected the call");
     }
     if (ensure_offline_pos(e, o)) return -1;
+    o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
     if (e->debug) {
         o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {});
         for (int b = 0; b < B; b++) {
@@ -370,6 +381,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     if (!e->off) e->off = new OfflineState();
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
+    o->logprobs.clear();
     return 0;
 }
 
@@ -528,5 +540,18 @@ extern "C" int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int
     if (!out) return (int64_t)src->size();                  // size query
     const int64_t n = std::min<int64_t>((int64_t)src->size(), cap);
     memcpy(out, src->data(), (size_t)n * 4);
+    return n;
+}
+
+extern "C" int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->opt_token_logprobs) return fail("no token log-probabilities: engine option \"token_logprobs\" is off (set it to 1 before the first step or offline call)");
+    OfflineState *o = e->off;
+    if (!o || u < 0 || u >= (int)o->logprobs.size()) return fail("no offline token log-probabilities of utterance %d (they are those of the last offline call)", u);
+    const std::vector<float> &src = o->logprobs[u];
+    if (!out) return (int)src.size();                       // size query
+    const int n = std::min<int>((int)src.size(), std::max(cap, 0));
+    memcpy(out, src.data(), (size_t)n * 4);
     return n;
 }

@@ -2,6 +2,7 @@
 #include "nemo_amd.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -56,6 +57,19 @@ std::vector<timed_token> nemo_stream_get_timed_tokens(nemo_stream_context *sctx)
     if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
     for (size_t i = 0; i < first; i++) out.emplace_back(sctx->tokens[i], -1);
     for (int i = 0; i < got; i++) out.emplace_back(sctx->tokens[first + (size_t)i], frames[(size_t)i]);
+    return out;
+}
+
+std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx) {
+    std::vector<float> out;
+    if (!sctx) return out;
+    const size_t n = sctx->tokens.size();
+    std::vector<float> lp(n ? n : 1);
+    const size_t first = n > 4096 ? n - 4096 : 0;       // older values have left the device ring
+    const int got = nasr_stream_get_token_logprobs(sctx->stream, (int64_t)first, (int32_t)(n - first), lp.data());
+    if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
+    out.assign(first, NAN);
+    out.insert(out.end(), lp.begin(), lp.begin() + got);
     return out;
 }
 
@@ -135,6 +149,15 @@ nemo_context *nemo_init_with_rows(const char *model_path, int device, int dtype,
 }
 
 nemo_context *nemo_init(const char *model_path) { return nemo_init_with_device(model_path, 0, NASR_DTYPE_BF16, 64); }
+
+bool nemo_set_token_logprobs(nemo_context *ctx, bool on) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "token_logprobs", on ? 1 : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
 
 bool nemo_set_pipeline(nemo_context *ctx, int depth) {
     if (!ctx || !ctx->engine) return false;

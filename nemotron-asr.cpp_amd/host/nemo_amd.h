@@ -66,6 +66,8 @@ void nemo_free(nemo_context *ctx);
 bool nemo_set_language(nemo_context *ctx, const char *lang);  // default prompt for new streams
 // MI355X extension: pipelined steps (nasr_engine_set_option "pipeline"): the decode of one call runs beside the encoder of the
 // next; nemo_stream_process_incremental then returns each text delta one call later, nemo_stream_finalize returns the rest
+// MI355X extension: per-token log-probabilities (nasr_engine_set_option "token_logprobs"); before the first stream processes audio
+bool nemo_set_token_logprobs(nemo_context *ctx, bool on);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
@@ -102,5 +104,8 @@ struct timed_token {
 };
 // every token of the stream since init/reset with its frame (the engine keeps the frames of the last 4096 tokens)
 std::vector<timed_token> nemo_stream_get_timed_tokens(nemo_stream_context *sctx);
+// ln P(token) of every token of the stream since init/reset (needs nemo_set_token_logprobs; NaN for tokens that have left the
+// engine's 4096-token ring, as their frame is -1); word confidences from them: word_confidence.h
+std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx);
 // reference src/nemo-ggml.cpp:1556-1583: "{12.34}" in front of every word when timestamp_words is set
 std::string tokens_to_text(const std::vector<timed_token> &tokens, const std::vector<std::string> &vocab, bool timestamp_words);

@@ -13,15 +13,18 @@
 
 #include "diarize_pipeline_amd.h"
 #include "nemo_amd.h"
+#include "word_confidence.h"
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--pipeline [E]]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--pipeline [E]]\n"
             "  audio: raw s16le, 16 kHz, mono.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --read-chunks N: read N chunks of audio per call (default 1 = the reference's read size); a file is\n"
             "                   transcribed fastest with N = 256 and --pipeline 4: same transcript, the chunks of a read share one\n"
             "                   launch sequence and consecutive reads run side by side\n"
             "  --timestamps:    print the final transcript again with {seconds} in front of every word\n"
+            "  --confidence:    print the final transcript again with [0.93] behind every word: exp of the smallest log-probability among\n"
+            "                   the word's tokens under the joint's softmax (with --timestamps: one line, {seconds} in front and [p] behind)\n"
             "  --pipeline E:    consecutive reads overlap on the GPU, E = 0..4 (same transcript; each delta appears E reads later).\n"
             "                   1: decode of one read beside the encoder of the next; 2..4: the encoder in E pieces on E hardware queues\n"
             "                   (4 = the fastest way through a file).  --pipeline without a number = 1; --pipeline2 / --pipeline3 still work\n"
@@ -35,7 +38,7 @@ int main(int argc, char **argv) {
     const char *model_path = argv[1], *audio_path = argv[2];
     int chunk_ms = 80, right_context = 0, device = 0, dtype = 1, positional = 0;
     const char *lang = nullptr;
-    bool print_tokens = false, timestamps = false;
+    bool print_tokens = false, timestamps = false, confidence = false;
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
     float sub_shift_sec = 0.75f, vad_onset = -1.0f, vad_offset = -1.0f;
@@ -48,6 +51,7 @@ int main(int argc, char **argv) {
         else if (a == "--f32") dtype = 0;
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--timestamps") timestamps = true;
+        else if (a == "--confidence") confidence = true;
         else if (a == "--cpu" || a == "--cuda" || a == "--metal")      // reference src/transcribe_stream.cpp:86-88
             fprintf(stderr, "note: %s ignored -- this build runs on the MI355X HIP engine only\n", a.c_str());
         else if (a == "--pipeline") {
@@ -77,6 +81,7 @@ int main(int argc, char **argv) {
 
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
+    if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     nemo_cache_config cfg = nemo_cache_config::default_config();
@@ -136,7 +141,20 @@ int main(int argc, char **argv) {
     const double audio_s = (double)total / 16000.0;
     fprintf(stderr, "\nAudio duration:   %.2f s\nProcessing time:  %.3f s\nReal-time factor: %.4f (%.1fx real time)\nChunks: %d\n",
             audio_s, wall, audio_s > 0 ? wall / audio_s : 0.0, wall > 0 ? audio_s / wall : 0.0, sctx->total_chunks_processed);
-    if (timestamps) printf("%s\n", tokens_to_text(nemo_stream_get_timed_tokens(sctx), ctx->vocab, true).c_str());
+    if (timestamps && !confidence) printf("%s\n", tokens_to_text(nemo_stream_get_timed_tokens(sctx), ctx->vocab, true).c_str());
+    if (confidence) {
+        const std::vector<word_conf::Word> ws = word_conf::words(nemo_stream_get_tokens(sctx), nemo_stream_get_token_logprobs(sctx), ctx->vocab);
+        std::vector<std::string> stamps;
+        if (timestamps) {
+            const std::vector<timed_token> tt = nemo_stream_get_timed_tokens(sctx);
+            for (const word_conf::Word &w : ws) {
+                char stamp[32];
+                snprintf(stamp, sizeof(stamp), "{%.2f}", (size_t)w.first_token < tt.size() ? tt[(size_t)w.first_token].to_seconds() : -1.0f);
+                stamps.push_back(stamp);
+            }
+        }
+        printf("%s\n", word_conf::annotate(ws, timestamps ? &stamps : nullptr).c_str());
+    }
     if (print_tokens) {
         printf("TOKENS:");
         for (int t : nemo_stream_get_tokens(sctx)) printf(" %d", t);
