@@ -50,6 +50,7 @@ enum {
     NASR_FLAG_PCM_DEVICE = 1u << 0, /* pcm[] are device pointers (inputs already resident in HBM) */
     NASR_FLAG_NO_SYNC    = 1u << 1, /* do not copy tokens back / synchronise; poll with nasr_engine_collect() */
     NASR_FLAG_AUDIO_S16  = 1u << 2, /* nasr_diar_*: audio[] point at s16 PCM (sample / 32768), e.g. the ASR streams' own buffers */
+    NASR_FLAG_NO_BOOST   = 1u << 3, /* nasr_engine_transcribe / _transcribe_mel only: decode the utterances of this call without phrase boosting */
 };
 
 /* model hyper-parameters = the `nemo.*` GGUF keys read at src/nemo-ggml.cpp:108-142
@@ -149,9 +150,13 @@ int nasr_stream_get_progress(const nasr_stream *s, nasr_stream_stats *out);
 int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t count, int32_t *frames_out);
 /* per-token confidence (the reference has no such output): ln P(token) of tokens [first, first + count) of this stream under the
  * joint's softmax over all 1025 outputs, at the frame and decoder state where each was emitted; f32, in [-ln 1025, 0] because the
- * token is the arg-max.  Same contract as nasr_stream_get_token_frames: completes steps in flight, tokens counted from create/reset,
+ * token is the arg-max.  With phrase boosting (engine option "phrase_boost") the value stays the MODEL's probability, ln softmax of the raw
+ * logits at the chosen token: a boosted token need not be the raw arg-max, so the range is then (-inf, 0] (any finite value <= 0).  Same contract as nasr_stream_get_token_frames: completes steps in flight, tokens counted from create/reset,
  * only the most recent 4096 kept, returns the number written, < 0 on error -- also when engine option "token_logprobs" is off. */
 int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out);
+/* phrase boosting for this stream (engine option "phrase_boost"; default: enabled).  Completes steps in flight.  Every call, with either
+ * value, resets the stream's boost history (the emitted tokens a phrase can continue from), not its decoder state.  Fails when the option is off. */
+int nasr_stream_set_boost(nasr_stream *s, int enable);
 
 /* ---- the step: replaces nemo_stream_process_incremental (src/nemo-stream.cpp:1145-1206)
  * for B streams at once = nemo_preprocessor_process (src/preprocessor.cpp:330-395) +
@@ -241,12 +246,31 @@ enum {
  * the natural-log softmax probability of that token over the 1025 joint outputs (blank included) at the frame and decoder state where it
  * was emitted (nasr_stream_get_token_logprobs, nasr_engine_offline_token_logprobs).  Tokens, frames, iteration counts and decoder state
  * are bit-identical to 0.  It selects the decode kernels that are captured into the step graphs and allocates a ring per stream, so it is
- * REJECTED after the first step or offline call. */
+ * REJECTED after the first step or offline call.
+ * "phrase_boost" (0 default / N = 2 .. 4096): phrase boosting ("hotwords", "word boosting"; the reference has no such thing), a capability like
+ * "token_logprobs".  N is the capacity of the phrase automaton in states: 2 fixed ones plus one per distinct non-empty prefix of the phrases
+ * (about 100 phrases of 4 tokens: 400 states; 8 KB of tables per state, 34 MB at 4096).  With N > 0 the device decode takes
+ * arg-max_v (logit[v] + bonus(v)) instead of arg-max_v logit[v], first maximum wins as before, where for a stream whose emitted non-blank
+ * tokens since its last history reset are h, bonus(v) = the largest w_i over all phrases i and all k with p_i[0:k] a suffix of h and
+ * p_i[k] == v, 0 if there is none; blank never gets a bonus and never enters h.  So the first token of every phrase is always boosted, and
+ * token k only right after tokens 0 .. k-1 were emitted.  Every other rule of the decode is unchanged (10 symbols per frame, state commit on
+ * emission, frame numbering).  The history persists across steps, chunks and pipelined calls and is reset by nasr_stream_create, both
+ * reset modes, nasr_stream_set_boost and nasr_engine_set_boost_phrases; an offline utterance starts with an empty one.  With no phrases
+ * set (the state after this option) tokens, frames, iteration counts and decoder state are bit-identical to 0.  It selects the decode kernels
+ * that are captured into the step graphs and allocates the tables, so it is REJECTED after the first step or offline call; the phrases
+ * themselves can be replaced at any time. */
 int nasr_engine_set_option(nasr_engine *e, const char *key, int value);
+/* replaces the engine's boost set (engine option "phrase_boost" = N): phrase i = tokens[i][0 .. lens[i]), 1 .. 32 non-blank token ids
+ * (0 .. 1023), with bonus[i], finite, 0 < bonus <= 1e4, in natural-log units (added to the joint's logits).  n_phrases = 0 clears the set.
+ * Completes steps in flight, builds the automaton on the host, uploads it and resets EVERY stream's boost history; captured step graphs
+ * stay valid.  Fails -- leaving the engine usable and the previous set in force -- when the option is off, a token id is blank or out of
+ * range, a length is outside 1 .. 32, a bonus is not finite or not in (0, 1e4], or the set needs more than N states. */
+int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *const *tokens, const int32_t *lens, const float *bonus);
 /* diagnostics: "graph_execs" (hipGraphExec objects alive), "graph_shapes" (distinct cached step shapes), "graph_evictions",
  * "graph_replays" (calls served by a hipGraph, pipelined ones included), "eager_steps" (calls that were not graph-eligible: ragged
  * pushes, streams that complete different chunk counts), "pipelined_steps", "grouped_steps", "lanes" (HIP streams the engine found
- * to overlap; 0 before the first pipelined step).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
+ * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
+ * 2 with no phrases; 0 when engine option "phrase_boost" is off).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);
 /* enable recording of NASR_TAP_MEL / SUBSAMPLED / LAYER_OUT (costs extra copies) */
@@ -304,7 +328,8 @@ int nasr_engine_transcribe(nasr_engine *e, int B, const int16_t *const *pcm, con
  * the taps of the one before.  Returns the number of floats written (<= cap), with out == NULL the number available, or < 0. */
 int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, float *out, int64_t cap);
 /* ln P(token) of every token of utterance u of the LAST offline call (either entry; engine option "token_logprobs" = 1), in token order:
- * out[i] belongs to tokens_out[u][i].  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
+ * out[i] belongs to tokens_out[u][i]; in [-ln 1025, 0], or any finite value <= 0 with phrase boosting (the model's probability of a boosted
+ * token, see nasr_stream_get_token_logprobs).  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
  * call forgets the values of the one before. */
 int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
 

@@ -32,7 +32,10 @@ EXPORTS = [
     "nasr_diar_create", "nasr_diar_destroy", "nasr_diar_set_stream", "nasr_diar_vad", "nasr_diar_embed", "nasr_diar_logmel", "nasr_diar_last_gpu_ms",
     "nasr_engine_transcribe_mel", "nasr_engine_transcribe", "nasr_engine_offline_tap",
     "nasr_stream_get_token_logprobs", "nasr_engine_offline_token_logprobs",
+    "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
 ]
+FLAG_NO_BOOST = 1 << 3
+BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
 
 
@@ -116,6 +119,8 @@ def lib():
         L.nasr_engine_offline_tap.restype = C.c_int64
         L.nasr_stream_get_token_logprobs.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
         L.nasr_engine_offline_token_logprobs.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
+        L.nasr_engine_set_boost_phrases.argtypes = [vp, C.c_int, C.POINTER(ip), ip, C.POINTER(C.c_float)]
+        L.nasr_stream_set_boost.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -196,6 +201,10 @@ class Stream:
         out = np.zeros(max(count, 1), np.float32)
         n = _chk(lib().nasr_stream_get_token_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:n].copy()
+
+    def set_boost(self, enable=True):
+        """phrase boosting on / off for this stream (engine option "phrase_boost"); either way its boost history restarts"""
+        _chk(lib().nasr_stream_set_boost(self.h, int(bool(enable))))
 
     def tap(self, which, index=0, cap=None) -> np.ndarray:
         cap = cap or 1024 * 260          # up to MAXNEW = 256 encoder frames of one launch, or a 70-row cache
@@ -440,14 +449,14 @@ class Engine:
         k = [min(n[b], caps_l[b]) for b in range(B)]
         return [tb[b][:k[b]].tolist() for b in range(B)], [fb[b][:k[b]].tolist() for b in range(B)]
 
-    def transcribe_mel(self, mels, prompts=None, tok_cap=None):
+    def transcribe_mel(self, mels, prompts=None, tok_cap=None, flags=0):
         """mels: list of [n][128] float32 log-mel arrays (the preprocessor over each whole utterance).  Returns (tokens, frames):
         one list per utterance, frames = encoder-frame index of every token."""
         if len(mels) == 0:
             return [], []
         arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        return self._offline(lib().nasr_engine_transcribe_mel, ptrs, [a.shape[0] for a in arrs], 8, prompts, tok_cap, 0)
+        return self._offline(lib().nasr_engine_transcribe_mel, ptrs, [a.shape[0] for a in arrs], 8, prompts, tok_cap, flags)
 
     def transcribe(self, pcms, prompts=None, tok_cap=None, flags=0):
         """pcms: list of int16 arrays, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE).  Returns (tokens, frames)."""
@@ -470,6 +479,23 @@ class Engine:
         out = np.zeros(max(cap, 1), np.float32)
         n = _chk(L.nasr_engine_offline_tap(self.h, which, u, index, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
         return out[:n].reshape(-1, width).copy()
+
+    def set_boost_phrases(self, phrases, bonus=None):
+        """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token
+        ids, bonus = one float for all or one per phrase, 0 < bonus <= 1e4 in natural-log units; () clears the set.  Resets every
+        stream's boost history."""
+        phrases = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+        n = len(phrases)
+        if n == 0:
+            _chk(lib().nasr_engine_set_boost_phrases(self.h, 0, None, None, None))
+            return
+        w = np.asarray(bonus, np.float32)
+        w = np.ascontiguousarray(np.full(n, w, np.float32) if w.ndim == 0 else w)
+        if bonus is None or w.shape != (n,):
+            raise ValueError("bonus: one float, or one per phrase")
+        ptrs = (C.POINTER(C.c_int32) * n)(*[p.ctypes.data_as(C.POINTER(C.c_int32)) for p in phrases])
+        lens = np.asarray([p.size for p in phrases], np.int32)
+        _chk(lib().nasr_engine_set_boost_phrases(self.h, n, ptrs, lens.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))))
 
     def offline_token_logprobs(self, u) -> np.ndarray:
         """ln P(token) of every token of utterance u of the last offline call (engine option "token_logprobs" = 1)"""

@@ -242,6 +242,7 @@ __global__ __launch_bounds__(256) void k_dec_pred(DecParams p) {
 
 using nasr_lp::pack_key;                                            // (order-preserving logit bits) << 32 | (0xffffffff - index), nasr_logprob.h
 static_assert(nasr_lp::LP_VOCAB == VOCAB && nasr_lp::SMALL_ROWS == 64, "nasr_logprob.h restates the joint kernels' shapes");
+static_assert(nasr_lp::TILE_PARTS == 65 && nasr_lp::TILE_W == 16 && nasr_lp::WG_W == 64 && nasr_boost::VOCAB == VOCAB && nasr_boost::BLANK == BLANK && nasr_boost::COLS == 16 * ((VOCAB + 15) / 16), "nasr_boost.h restates the joint kernels' shapes");
 // engine option "token_logprobs": the (max, sum of exp) part of a 16-entry vocab tile, lane (q, r) holding entries v0 .. v0 + 3 of row r's
 // logits; every lane of the row ends up with the same bits (merge is symmetric)
 __device__ __forceinline__ nasr_lp::Part lp_tile_part(float x0, float x1, float x2, float x3, int v0) {
@@ -259,7 +260,10 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 
 // ---- joint, few rows (<= 64 rows in the step): logits = W_out . relu(encproj[row] + g) + b_out and
 // arg-max; grid = 65 (1040 padded vocab rows), 4 waves split K; first maximum wins (:899-906, :1220-1221)
-template <int MT, bool LP>
+// BOOST (engine option "phrase_boost", nasr_boost.h): the arg-max key is built from logit + bonus(automaton state of the row's slot, v) -- one
+// 16-byte load per lane and row -- while the softmax parts stay those of the raw logits; with LP the lane that owns the tile's winner also leaves
+// its raw logit in boost_raw [row][part] (one writer per element: a key names one vocabulary entry, and one lane holds it)
+template <int MT, bool LP, bool BOOST>
 __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, float (*red)[MT_MAX][64][4]) {
     const int nt = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
@@ -289,18 +293,28 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
     const int i = i0 + mt * 16 + r;
     if (mt < MT) {
         unsigned long long best = 0ull;
-        float lgs[4] = {0.f, 0.f, 0.f, 0.f};
+        float lgs[4] = {0.f, 0.f, 0.f, 0.f}, bon[4] = {0.f, 0.f, 0.f, 0.f};
+        if (BOOST) {
+            const int slot = p.rows[p.rowmap[i < nr ? i : i0] & 0xffffu].slot;
+            const nasr_boost::Bonus4 b4 = nasr_boost::bonus4_of(p.boost_bonus, p.boost_state[slot], nt * 16 + q * 4);
+            bon[0] = b4.x; bon[1] = b4.y; bon[2] = b4.z; bon[3] = b4.w;
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int v = nt * 16 + q * 4 + j;
             if (v < VOCAB) {
                 const float lg = (((red[0][mt][lane][j] + red[1][mt][lane][j]) + red[2][mt][lane][j]) + red[3][mt][lane][j]) + p.out_b[v];
-                best = kmax(best, pack_key(lg, v));
+                best = kmax(best, pack_key(BOOST ? lg + bon[j] : lg, v));
                 if (LP) lgs[j] = lg;
             }
         }
         best = kmax(best, shfl_xor_u64(best, 16));
         best = kmax(best, shfl_xor_u64(best, 32));
+        if (LP && BOOST) {
+            const int wv = nasr_lp::key_index_of(best) - (nt * 16 + q * 4);
+            if (best && i < nr && wv >= 0 && wv < 4)
+                p.boost_raw[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[i], p.T), nt, nasr_lp::TILE_PARTS)] = wv == 0 ? lgs[0] : wv == 1 ? lgs[1] : wv == 2 ? lgs[2] : lgs[3];
+        }
         if (q == 0 && i < nr && best) {
             const unsigned rm = p.rowmap[i];
             atomicMax(&p.key[(size_t)(rm & 0xffffu) * p.T + (rm >> 16)], best);
@@ -313,16 +327,16 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
     }
 }
 
-template <bool LP>
+template <bool LP, bool BOOST>
 __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
     const int nr = *p.n_rows;
     if (nr == 0) return;
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nr; i0 += 16 * MT_MAX) {
         const int tiles = nasr_lp::joint_pass_tiles(nr - i0);      // 1, 2 or 4 m-tiles: 16, 32 or more rows left
-        if (tiles == 1) joint_pass<1, LP>(p, i0, nr, red);
-        else if (tiles == 2) joint_pass<2, LP>(p, i0, nr, red);
-        else joint_pass<4, LP>(p, i0, nr, red);
+        if (tiles == 1) joint_pass<1, LP, BOOST>(p, i0, nr, red);
+        else if (tiles == 2) joint_pass<2, LP, BOOST>(p, i0, nr, red);
+        else joint_pass<4, LP, BOOST>(p, i0, nr, red);
     }
 }
 
@@ -332,7 +346,7 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // workgroup and staged in LDS (double-buffered, 16-byte chunks XOR-swizzled with the row).  The
 // kernel is bound by the f32 MFMA (32 cycles per 16x16x4), 640 of them per wave.
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
-template <bool LP>
+template <bool LP, bool BOOST>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     const int nr = *p.n_rows;
     const int m0 = blockIdx.y * 64;
@@ -340,6 +354,7 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     __shared__ __attribute__((aligned(16))) float xs[2][64 * JT_KC];
     __shared__ unsigned long long bests[4][64];
     __shared__ nasr_lp::Part lps[LP ? 4 : 1][64];      // token_logprobs: the four waves' tile parts of the 64 rows
+    __shared__ float raws[LP && BOOST ? 4 : 1][64];    // ... with phrase_boost: the raw logit of each wave's winner by boosted key
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
     const int nt = blockIdx.x * 4 + wave;
     const bool has_tile = nt * 16 < VOCAB;
@@ -364,6 +379,14 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
             *(float4 *)(&xs[buf][srow * JT_KC + (((sc0 + i) ^ (srow & 15)) << 2)]) = x;
         }
     };
+    int bstate[4] = {0, 0, 0, 0};                   // phrase_boost: automaton state of this lane's row of every m-tile (it moves only in k_dec_commit)
+    if (BOOST) {
+#pragma unroll
+        for (int mt = 0; mt < 4; mt++) {
+            const int row = m0 + mt * 16 + r;
+            bstate[mt] = p.boost_state[p.rows[p.rowmap[row < nr ? row : m0] & 0xffffu].slot];
+        }
+    }
     f32x4 acc[4];
 #pragma unroll
     for (int mt = 0; mt < 4; mt++) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -406,15 +429,27 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     for (int mt = 0; mt < 4; mt++) {
         unsigned long long best = 0ull;
         if (has_tile && mt < nmt) {
+            float bon[4] = {0.f, 0.f, 0.f, 0.f};
+            if (BOOST) {
+                const nasr_boost::Bonus4 b4 = nasr_boost::bonus4_of(p.boost_bonus, bstate[mt], nt * 16 + q * 4);
+                bon[0] = b4.x; bon[1] = b4.y; bon[2] = b4.z; bon[3] = b4.w;
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int v = nt * 16 + q * 4 + j;
-                if (v < VOCAB) best = kmax(best, pack_key(acc[mt][j] + p.out_b[v], v));
+                if (v < VOCAB) best = kmax(best, pack_key(BOOST ? (acc[mt][j] + p.out_b[v]) + bon[j] : acc[mt][j] + p.out_b[v], v));
             }
         }
         best = kmax(best, shfl_xor_u64(best, 16));
         best = kmax(best, shfl_xor_u64(best, 32));
         if (q == 0) bests[wave][mt * 16 + r] = best;
+        if (LP && BOOST) {                             // the lane that holds the wave's winner leaves its raw logit
+            const int wv = nasr_lp::key_index_of(best) - (nt * 16 + q * 4);
+            if (best && wv >= 0 && wv < 4) {
+                const float a = wv == 0 ? acc[mt][0] : wv == 1 ? acc[mt][1] : wv == 2 ? acc[mt][2] : acc[mt][3];
+                raws[wave][mt * 16 + r] = a + p.out_b[nt * 16 + q * 4 + wv];
+            }
+        }
         if (LP) {
             const int v0 = has_tile ? nt * 16 + q * 4 : VOCAB;          // no tile: the empty part
             float lg[4];
@@ -429,6 +464,13 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         const unsigned long long best = kmax(kmax(bests[0][threadIdx.x], bests[1][threadIdx.x]), kmax(bests[2][threadIdx.x], bests[3][threadIdx.x]));
         const unsigned rm = p.rowmap[m0 + threadIdx.x];
         if (best) atomicMax(&p.key[(size_t)(rm & 0xffffu) * p.T + (rm >> 16)], best);
+        if (LP && BOOST) {                             // the workgroup's winner is the winner of its wave: part blockIdx.x of the row
+            int w = 0;
+            unsigned long long kw = bests[0][threadIdx.x];
+#pragma unroll
+            for (int u = 1; u < 4; u++) if (bests[u][threadIdx.x] > kw) { kw = bests[u][threadIdx.x]; w = u; }
+            if (kw) p.boost_raw[nasr_lp::scratch_index(nasr_lp::key_index(rm, p.T), blockIdx.x, nasr_lp::WG_PARTS)] = raws[w][threadIdx.x];
+        }
     }
     if (LP) {                                      // one part per workgroup (64 entries): part blockIdx.x of the row, waves merged in order
         const int row = nasr_lp::tiled_store_row(blockIdx.y, threadIdx.x, nr);
@@ -440,7 +482,7 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 }
 
 // ---- commit: walk each stream's evaluated frames up to its first non-blank -------------------------
-template <bool LP>
+template <bool LP, bool BOOST>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
@@ -474,8 +516,11 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
             if (LP) {                                  // the parts of frame f were written by this iteration's joint kernel (f is in rowmap)
                 const int np = nasr_lp::n_parts(p.B * p.T);
                 const nasr_lp::Part *parts = p.lp_part + nasr_lp::scratch_index(b * p.T + f, 0, np);
-                p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(nasr_lp::key_logit(k), parts, np);
+                // phrase_boost: the key holds logit + bonus; the value stays the MODEL's probability of the token, from its raw logit
+                const float logit = BOOST ? p.boost_raw[nasr_lp::scratch_index(b * p.T + f, nasr_boost::raw_part_of(best, np), np)] : nasr_lp::key_logit(k);
+                p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(logit, parts, np);
             }
+            if (BOOST) p.boost_state[slot] = nasr_boost::next_of(p.boost_next, p.boost_state[slot], best);   // the history moves where the decoder state does
             ct->n_tok = n + 1;
             ct->prev_token = best;
             ct->cur ^= 1;
@@ -536,6 +581,13 @@ void launch_encproj(const float *x, const float *wpk, const float *bias, float *
 void launch_decode_begin(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_begin, dim3(1), dim3(256), 0, st, p);
 }
+template <bool LP, bool BOOST>
+static void launch_joint_commit(const DecParams &p, hipStream_t st) {
+    const int rows = p.B * p.T;
+    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k_dec_commit<LP, BOOST>), dim3(1), dim3(256), 0, st, p);
+}
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a
 // blindly enqueued (graph-captured) sequence cost only their launch slots.
@@ -544,16 +596,10 @@ void launch_decode_iter(const DecParams &p, int iter, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
-    const int rows = p.B * p.T;
-    if (p.lp_part) {                            // engine option "token_logprobs": the variants that also leave the softmax parts / the token's log-probability
-        if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL(k_dec_joint<true>, dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_dec_joint_tiled<true>, dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(k_dec_commit<true>, dim3(1), dim3(256), 0, st, p);
-        return;
-    }
-    if (rows <= 64) hipLaunchKernelGGL(k_dec_joint<false>, dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_dec_joint_tiled<false>, dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(k_dec_commit<false>, dim3(1), dim3(256), 0, st, p);
+    // engine options "token_logprobs" (lp_part) and "phrase_boost" (boost_bonus): the variants that also leave the softmax parts / the token's
+    // log-probability, and that add the phrase bonus to the arg-max key; with both off these are the kernels without either
+    if (p.lp_part) { if (p.boost_bonus) launch_joint_commit<true, true>(p, st); else launch_joint_commit<true, false>(p, st); }
+    else { if (p.boost_bonus) launch_joint_commit<false, true>(p, st); else launch_joint_commit<false, false>(p, st); }
 }
 // iterations enqueued before the host looks at n_active: (symbols of the busiest stream) + 1 are needed; a shortfall
 // costs one host round trip and a further round of iterations

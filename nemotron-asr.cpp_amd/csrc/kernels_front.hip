@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256) void k_stream_reset(StreamResetParams p) {
         c.dirty = 1;                                                       // no LSTM candidate computed yet
         c.frame0 = 0; c.frame_next = 0;
         p.ctrl[slot] = c;
+        if (p.boost_state) p.boost_state[slot] = p.boost_init;             // phrase_boost: an empty history
     }
 }
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st) {

@@ -2,6 +2,50 @@
 // include/nemotron_asr_amd.h that are not life cycle: options, step / finalize / collect, counters, taps, profiling, device helpers.
 #include "nasr_engine_priv.h"
 
+namespace nasr_eng {
+// builds the automaton on the host (nasr_boost.h) and, only if that succeeds, replaces the tables' content and puts every stream's history
+// back to the root; the caller has completed the steps in flight
+static int upload_boost_set(nasr_engine *e, int n_phrases, const int32_t *const *tokens, const int32_t *lens, const float *bonus) {
+    nasr_boost::Automaton a;
+    int bad = -1;
+    const int rc = nasr_boost::build(n_phrases, tokens, lens, bonus, e->boost_cap, a, &bad);
+    if (rc == nasr_boost::ERR_CAPACITY) return fail("boost phrases: %s of %d (engine option \"phrase_boost\"), at phrase %d", nasr_boost::status_text(rc), e->boost_cap, bad);
+    if (rc) return fail("boost phrases: %s (phrase %d)", nasr_boost::status_text(rc), bad);
+    HIPCHK(hipStreamSynchronize(e->st));
+    const size_t n = nasr_boost::table_elems(a.n_states);
+    HIPCHK(hipMemcpy(e->boost_bonus, a.bonus.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->boost_next, a.next.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::vector<int> st((size_t)e->max_streams, nasr_boost::STATE_ROOT);
+    for (int i = 0; i < e->max_streams; i++) if (e->slots[i] && !e->slots[i]->boost_enabled) st[(size_t)i] = nasr_boost::STATE_OFF;
+    HIPCHK(hipMemcpy(e->boost_state, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
+    e->boost_states = a.n_states;
+    return 0;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *const *tokens, const int32_t *lens, const float *bonus) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->opt_phrase_boost) return fail("no phrase boosting: engine option \"phrase_boost\" is off (set it to the state capacity before the first step or offline call)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    return upload_boost_set(e, n_phrases, tokens, lens, bonus);
+}
+
+extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
+    ApiGuard api_guard;
+    if (!s) return fail("null stream");
+    nasr_engine *e = s->e;
+    if (!e->opt_phrase_boost) return fail("no phrase boosting: engine option \"phrase_boost\" is off (set it to the state capacity before the first step or offline call)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    HIPCHK(hipStreamSynchronize(e->st));
+    const int state = enable ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF;      // either way an empty history
+    HIPCHK(hipMemcpy(e->boost_state + s->slot, &state, sizeof(int), hipMemcpyHostToDevice));
+    s->boost_enabled = enable != 0;
+    return 0;
+}
+
 extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value) {
     if (!e || !key) return fail("null argument");
     if (!strcmp(key, "fused")) e->opt_fused = value != 0;
@@ -31,6 +75,24 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
             if (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP)) return -1;
         }
         e->opt_token_logprobs = value != 0;
+    }
+    else if (!strcmp(key, "phrase_boost")) {
+        // like "token_logprobs": picks the decode kernels that get captured and allocates the automaton tables at a fixed capacity, so that
+        // nasr_engine_set_boost_phrases only ever rewrites their content and captured graphs stay valid
+        if (value != 0 && (value < nasr_boost::MIN_STATES || value > nasr_boost::MAX_STATES))
+            return fail("phrase_boost must be 0 or the automaton's state capacity, %d .. %d", nasr_boost::MIN_STATES, nasr_boost::MAX_STATES);
+        if (e->dec_started || e->off) return fail("phrase_boost must be set before the first step or offline call (the decode kernels are already chosen)");
+        if (value && e->boost_bonus && value != e->boost_cap) return fail("phrase_boost: the capacity is already %d states", e->boost_cap);
+        if (value && !e->boost_bonus) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (dalloc(e, &e->boost_bonus, nasr_boost::table_elems(value)) || dalloc(e, &e->boost_next, nasr_boost::table_elems(value)) ||
+                dalloc(e, &e->boost_state, (size_t)e->max_streams) || dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows))) return -1;
+            e->boost_cap = value;
+            e->opt_phrase_boost = value;
+            if (upload_boost_set(e, 0, nullptr, nullptr, nullptr)) { e->opt_phrase_boost = 0; return -1; }      // the empty set: the disabled state and the root
+        }
+        e->opt_phrase_boost = value;
     }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
@@ -274,6 +336,7 @@ extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int
                                 int32_t *n_tokens, uint32_t flags) {
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
     if (!pcm || !n_samples) return fail("null pcm / n_samples");
     HIPCHK(hipSetDevice(e->device));
     std::vector<const int16_t *> base(B, nullptr);
@@ -358,6 +421,7 @@ extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams,
                                     int32_t *n_tokens, uint32_t flags) {
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
     if (!mel || !n_frames) return fail("null mel / n_frames");
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
@@ -511,6 +575,7 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "eager_steps")) *value = e->eager_steps;
     else if (!strcmp(name, "pipelined_steps")) *value = e->pipe_steps;
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;
+    else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
     else if (!strcmp(name, "lanes")) *value = e->pipe_ready ? e->n_lanes : 0;      // HIP streams found to overlap (0: not picked yet)
     else return fail("unknown counter '%s'", name);
     return 0;

@@ -101,6 +101,7 @@ struct nasr_stream {
     int64_t samples_in;
     int last_T, last_row, last_ws;   // rows of the last chunk and the workspace set they are in (for taps)
     bool alive;
+    bool boost_enabled = true;       // nasr_stream_set_boost (engine option "phrase_boost")
     std::vector<int32_t> tok_queue;  // tokens gathered from the device, not yet handed to the caller
 };
 
@@ -223,6 +224,12 @@ struct nasr_engine {
     bool opt_token_logprobs = false, dec_started = false;
     nasr_lp::Part *lp_part = nullptr;      // [max(64 x 65, w_rows x 17)] softmax parts of the rows of a decode iteration (nasr_logprob.h)
     float *tok_logprob = nullptr;    // [slot][TOK_CAP] beside tok_ring / tok_frame
+    // option "phrase_boost" = the capacity of the automaton tables in states (0: off), nasr_boost.h.  Like "token_logprobs" it picks the kernels that
+    // get captured and allocates fixed-capacity tables whose pointers never change: replacing the set rewrites their content only
+    int opt_phrase_boost = 0, boost_cap = 0, boost_states = 0;      // capacity (0: off), capacity allocated; states of the current set (2 = the disabled state and the root: no phrase)
+    float *boost_bonus = nullptr; int32_t *boost_next = nullptr;   // [capacity][1040] each
+    int *boost_state = nullptr;      // [slot] automaton state of every stream's emitted history
+    float *boost_raw = nullptr;      // scratch beside lp_part: raw logit of every part's winner (read only when both options are on)
     int *collect_dev;                // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;

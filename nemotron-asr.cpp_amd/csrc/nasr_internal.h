@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nasr_logprob.h"
+#include "nasr_boost.h"
 
 namespace nasr {
 
@@ -203,6 +204,7 @@ struct StreamResetParams {      // one launch per stream start / reset (kernels_
     int keep_reference_state;   // NASR_RESET_REFERENCE: conv caches, audio-buffer carry and last_sample survive
     float *abuf, *last_sample, *mel_ring, *dec_h, *dec_c;
     DecCtrl *ctrl;
+    int *boost_state; int boost_init;   // engine option "phrase_boost" (null when off): the slot's automaton state goes back to the root (or 0 = disabled)
 };
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st);
 
@@ -256,6 +258,11 @@ struct DecParams {
     // engine option "token_logprobs" (both null when it is off: the launches are then the kernels without it)
     nasr_lp::Part *lp_part;            // [B * T][n_parts] (max, sum of exp(x - max)) of every vocab slice of every evaluated row (nasr_logprob.h)
     float *tok_logprob;          // [slot][TOK_CAP] natural-log softmax probability of each token where it was emitted
+    // engine option "phrase_boost" (all null when it is off), nasr_boost.h
+    const float *boost_bonus;    // [states][1040] bonus of every vocabulary entry in every automaton state
+    const int32_t *boost_next;   // [states][1040] state after emitting that entry
+    int *boost_state;            // [slot] automaton state of the slot's emitted history (0: boosting disabled for it, 1: root)
+    float *boost_raw;            // [B * T][n_parts] with "token_logprobs" too: raw logit of every part's winner by boosted key
 };
 void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, int iter, hipStream_t st);

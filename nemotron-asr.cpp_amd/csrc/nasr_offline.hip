@@ -28,6 +28,8 @@ struct OfflineState {
     unsigned long long *key = nullptr; int *n_active = nullptr, *dlist = nullptr, *tok_ring = nullptr, *tok_frame = nullptr;
     unsigned *rowmap = nullptr; RowDesc *drows = nullptr; int4 *dwin = nullptr;
     nasr_lp::Part *lp_part = nullptr; float *tok_logprob = nullptr;      // engine option "token_logprobs" (allocated with the slots when it is on)
+    int *boost_state = nullptr; float *boost_raw = nullptr;        // engine option "phrase_boost": the offline slots' automaton states (the tables are the engine's)
+    bool no_boost = false;                                         // NASR_FLAG_NO_BOOST of the call in progress
     std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
@@ -127,6 +129,10 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
         if (e->opt_token_logprobs) {
             rc |= off_alloc(o, (void **)&o->lp_part, nasr_lp::scratch_parts((int)(U * W)) * sizeof(nasr_lp::Part));
             rc |= off_alloc(o, (void **)&o->tok_logprob, U * TOK_CAP * 4);
+        }
+        if (e->opt_phrase_boost) {
+            rc |= off_alloc(o, (void **)&o->boost_state, U * 4);
+            rc |= off_alloc(o, (void **)&o->boost_raw, nasr_lp::scratch_parts((int)(U * W)) * 4);
         }
         rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
         rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
@@ -261,6 +267,8 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         return -1;
     // ---- greedy decode in windows of 256 frames per utterance (token ring: 4096 > 256 x 10 symbols) -----------------
     launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
+    if (o->boost_state)                                          // every utterance starts with an empty history (NASR_FLAG_NO_BOOST: in the disabled state)
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->boost_state, o->no_boost ? nasr_boost::STATE_OFF : nasr_boost::STATE_ROOT, (size_t)n, st));
     std::vector<int> tok_read(n, 0);
     std::vector<DecCtrl> hctrl(n);
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
@@ -286,6 +294,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
         dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
         dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs"
+        if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
         launch_decode_begin(dp, st);
         int it = 0, budget = decode_blind_iterations(max_dec), h_active = 0;
         while (max_dec > 0) {
@@ -382,6 +391,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
     o->logprobs.clear();
+    o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "boost_phrases.h"
 #include "gguf_reader.h"
 #include "nemotron_asr_amd.h"
 
@@ -153,6 +154,52 @@ nemo_context *nemo_init(const char *model_path) { return nemo_init_with_device(m
 bool nemo_set_token_logprobs(nemo_context *ctx, bool on) {
     if (!ctx || !ctx->engine) return false;
     if (nasr_engine_set_option(ctx->engine, "token_logprobs", on ? 1 : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool nemo_set_phrase_boost(nemo_context *ctx, int max_states) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "phrase_boost", max_states) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+static bool apply_boost_phrases(nemo_context *ctx, const boost_phrases::Result &r, const char *who) {
+    for (const std::string &p : r.problems) fprintf(stderr, "%s: skipped, %s\n", who, p.c_str());
+    std::vector<const int32_t *> tok;
+    std::vector<int32_t> len;
+    std::vector<float> bonus;
+    for (const boost_phrases::Phrase &p : r.phrases) { tok.push_back(p.tokens.data()); len.push_back((int32_t)p.tokens.size()); bonus.push_back(p.bonus); }
+    if (nasr_engine_set_boost_phrases(ctx->engine, (int)tok.size(), tok.data(), len.data(), bonus.data()) < 0) {
+        fprintf(stderr, "%s: %s\n", who, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool nemo_set_boost_phrases(nemo_context *ctx, const std::vector<std::string> &phrases, const std::vector<float> &bonus, float default_bonus) {
+    if (!ctx || !ctx->engine) return false;
+    return apply_boost_phrases(ctx, boost_phrases::from_list(phrases, bonus, ctx->vocab, default_bonus), __func__);
+}
+
+bool nemo_load_boost_file(nemo_context *ctx, const char *path, float default_bonus) {
+    if (!ctx || !ctx->engine || !path) return false;
+    boost_phrases::Result r;
+    if (!boost_phrases::parse_file(path, ctx->vocab, default_bonus, r)) {
+        fprintf(stderr, "%s: cannot read '%s'\n", __func__, path);
+        return false;
+    }
+    return apply_boost_phrases(ctx, r, __func__);
+}
+
+bool nemo_stream_set_boost(nemo_stream_context *sctx, bool enable) {
+    if (!sctx || !sctx->stream) return false;
+    if (nasr_stream_set_boost(sctx->stream, enable ? 1 : 0) < 0) {
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return false;
     }

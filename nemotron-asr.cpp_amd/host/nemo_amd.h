@@ -68,6 +68,15 @@ bool nemo_set_language(nemo_context *ctx, const char *lang);  // default prompt 
 // next; nemo_stream_process_incremental then returns each text delta one call later, nemo_stream_finalize returns the rest
 // MI355X extension: per-token log-probabilities (nasr_engine_set_option "token_logprobs"); before the first stream processes audio
 bool nemo_set_token_logprobs(nemo_context *ctx, bool on);
+// MI355X extension: phrase boosting ("hotwords"; nasr_engine_set_option "phrase_boost" + nasr_engine_set_boost_phrases).
+// nemo_set_phrase_boost: before the first stream processes audio; max_states = capacity of the phrase automaton, 2 .. 4096 (one state per
+// distinct phrase prefix + 2), 0 = off.  nemo_set_boost_phrases: any time afterwards; phrases as text (boost_phrases.h: each word segmented by
+// greedy longest match against the vocabulary, or `ids:12,55,9`), bonus[i] in natural-log units (a shorter list: default_bonus).  Phrases that
+// cannot be converted are reported on stderr and skipped; returns false if the engine refuses the set (the previous one then stays).  Every
+// stream's boost history restarts.  nemo_load_boost_file: the same from a file, one `phrase<TAB>bonus` per line (bonus optional).
+bool nemo_set_phrase_boost(nemo_context *ctx, int max_states);
+bool nemo_set_boost_phrases(nemo_context *ctx, const std::vector<std::string> &phrases, const std::vector<float> &bonus, float default_bonus = 4.0f);
+bool nemo_load_boost_file(nemo_context *ctx, const char *path, float default_bonus = 4.0f);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
@@ -78,6 +87,8 @@ std::string nemo_stream_finalize(nemo_stream_context *sctx);
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx);
 const std::vector<int> &nemo_stream_get_tokens(nemo_stream_context *sctx);
 void nemo_stream_reset(nemo_stream_context *sctx);
+// MI355X extension: phrase boosting on / off for this stream (default on; nasr_stream_set_boost); its boost history restarts either way
+bool nemo_stream_set_boost(nemo_stream_context *sctx, bool enable);
 void nemo_stream_free(nemo_stream_context *sctx);
 
 // MI355X extension: one launch sequence for B streams that share right_context.  out[b] receives the

@@ -484,7 +484,8 @@ void on_signal(int) { g_stop = true; if (g_listen_fd >= 0) ::shutdown(g_listen_f
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--cpu | --cuda]\n"
+        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--boost-file FILE] [--boost-bonus X] [--cpu | --cuda]\n"
+                        "  --boost-file: phrase boosting for every session: one `phrase<TAB>bonus` per line (bonus optional, default --boost-bonus or 4.0), loaded into every engine at start\n"
                         "  --prewarm: capture the step graphs of every batch size 1..max-streams for these right_context values before listening (~20 ms each);\n"
                         "             with --pipeline the default right_context is prewarmed unless --no-prewarm\n"
                         "  --tcp: default 127.0.0.1:8300 (the reference's port, src/nemo-server.cpp:411; the reference binds every interface when no host is given, this server binds loopback unless told otherwise: --tcp 0.0.0.0:8300)\n"
@@ -499,6 +500,8 @@ int main(int argc, char **argv) {
     int dtype = 1, max_streams = 64, backlog_chunks = 4;
     std::vector<int> prewarm_rc;
     bool no_prewarm = false;
+    const char *boost_file = nullptr;
+    float boost_bonus = 4.0f;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--tcp" && i + 1 < argc) tcp = argv[++i];
@@ -523,6 +526,8 @@ int main(int argc, char **argv) {
         }
         else if (a == "--pipeline" && i + 1 < argc) g_pipeline = atoi(argv[++i]);
         else if (a == "--no-prewarm") no_prewarm = true;
+        else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
+        else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
         else if (a == "--prewarm" && i + 1 < argc) {
             for (const char *p = argv[++i]; *p;) {
                 prewarm_rc.push_back(atoi(p));
@@ -539,6 +544,7 @@ int main(int argc, char **argv) {
         // that fell behind) are worked off in GEMMs of that many times the rows (64 streams x R = 13: 896 -> 3 584 rows)
         ln->model = nemo_init_with_rows(argv[1], dev, dtype, max_streams, max_streams * 14 * backlog_chunks);
         if (!ln->model) { fprintf(stderr, "Failed to load ASR model on device %d\n", dev); return 1; }
+        if (boost_file && !(nemo_set_phrase_boost(ln->model, 4096) && nemo_load_boost_file(ln->model, boost_file, boost_bonus))) return 1;
         if (g_pipeline > 0 && !nemo_set_pipeline(ln->model, g_pipeline)) return 1;
         // one step shape per batch size and right_context in use, and as many again for the multi-chunk shapes of a backlog (chunk counts are
         // powers of two): none is evicted in steady state

@@ -17,7 +17,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--pipeline [E]]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]]\n"
             "  audio: raw s16le, 16 kHz, mono.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --read-chunks N: read N chunks of audio per call (default 1 = the reference's read size); a file is\n"
             "                   transcribed fastest with N = 256 and --pipeline 4: same transcript, the chunks of a read share one\n"
@@ -25,6 +25,9 @@ static void usage(const char *prog) {
             "  --timestamps:    print the final transcript again with {seconds} in front of every word\n"
             "  --confidence:    print the final transcript again with [0.93] behind every word: exp of the smallest log-probability among\n"
             "                   the word's tokens under the joint's softmax (with --timestamps: one line, {seconds} in front and [p] behind)\n"
+            "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
+            "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
+            "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
             "  --pipeline E:    consecutive reads overlap on the GPU, E = 0..4 (same transcript; each delta appears E reads later).\n"
             "                   1: decode of one read beside the encoder of the next; 2..4: the encoder in E pieces on E hardware queues\n"
             "                   (4 = the fastest way through a file).  --pipeline without a number = 1; --pipeline2 / --pipeline3 still work\n"
@@ -39,6 +42,8 @@ int main(int argc, char **argv) {
     int chunk_ms = 80, right_context = 0, device = 0, dtype = 1, positional = 0;
     const char *lang = nullptr;
     bool print_tokens = false, timestamps = false, confidence = false;
+    const char *boost_file = nullptr;
+    float boost_bonus = 4.0f;
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
     float sub_shift_sec = 0.75f, vad_onset = -1.0f, vad_offset = -1.0f;
@@ -52,6 +57,8 @@ int main(int argc, char **argv) {
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--timestamps") timestamps = true;
         else if (a == "--confidence") confidence = true;
+        else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
+        else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
         else if (a == "--cpu" || a == "--cuda" || a == "--metal")      // reference src/transcribe_stream.cpp:86-88
             fprintf(stderr, "note: %s ignored -- this build runs on the MI355X HIP engine only\n", a.c_str());
         else if (a == "--pipeline") {
@@ -82,6 +89,7 @@ int main(int argc, char **argv) {
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
+    if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     nemo_cache_config cfg = nemo_cache_config::default_config();
