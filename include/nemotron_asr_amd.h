@@ -154,6 +154,15 @@ int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t co
  * logits at the chosen token: a boosted token need not be the raw arg-max, so the range is then (-inf, 0] (any finite value <= 0).  Same contract as nasr_stream_get_token_frames: completes steps in flight, tokens counted from create/reset,
  * only the most recent 4096 kept, returns the number written, < 0 on error -- also when engine option "token_logprobs" is off. */
 int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out);
+/* per-token alternatives (the reference has no such output; engine option "token_alternatives" = K): for tokens [first, first + count) of
+ * this stream the K largest of the 1025 joint outputs (blank included: a blank among them means the model nearly emitted nothing there) at
+ * the frame and decoder state where each token was emitted, as ids and ln P under the joint's softmax.  Descending logit, among equal logit
+ * bits the lower id first -- the arg-max's tie rule, so without phrase boosting entry 0 is the token and its value is the token's
+ * nasr_stream_get_token_logprobs value bit for bit; with boosting the ranking stays the MODEL's (raw logits) and the token need not be entry
+ * 0, nor among the K.
+ * [count][K] row-major; same contract as nasr_stream_get_token_logprobs: completes steps in flight, tokens counted from
+ * create/reset, only the most recent 4096 kept, returns the number of TOKENS written, < 0 on error (also when the option is off) */
+int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t first, int32_t count, int32_t *ids_out, float *logprobs_out);
 /* phrase boosting for this stream (engine option "phrase_boost"; default: enabled).  Completes steps in flight.  Every call, with either
  * value, resets the stream's boost history (the emitted tokens a phrase can continue from), not its decoder state.  Fails when the option is off. */
 int nasr_stream_set_boost(nasr_stream *s, int enable);
@@ -258,7 +267,14 @@ enum {
  * reset modes, nasr_stream_set_boost and nasr_engine_set_boost_phrases; an offline utterance starts with an empty one.  With no phrases
  * set (the state after this option) tokens, frames, iteration counts and decoder state are bit-identical to 0.  It selects the decode kernels
  * that are captured into the step graphs and allocates the tables, so it is REJECTED after the first step or offline call; the phrases
- * themselves can be replaced at any time. */
+ * themselves can be replaced at any time.
+ * "token_alternatives" (0 default / K = 1 .. 8): a capability like "token_logprobs" and independent of it -- with K > 0 the device decode also
+ * keeps, for every emitted token, the K largest of the 1025 joint outputs (blank included) at the frame and decoder state where it was
+ * emitted, as (id, ln P) pairs in descending order of the raw logit, the lower id first among equal logit bits
+ * (nasr_stream_get_token_alternatives, nasr_engine_offline_token_alternatives).  The ranking is the model's also under "phrase_boost": the
+ * emitted token then need not be entry 0; without phrases it is.  The results for K are the first K columns of those for any larger K.
+ * Tokens, frames, iteration counts and decoder state are bit-identical to 0.  It selects the decode kernels that are captured into the step
+ * graphs and allocates two rings per stream, so it is REJECTED after the first step or offline call. */
 int nasr_engine_set_option(nasr_engine *e, const char *key, int value);
 /* replaces the engine's boost set (engine option "phrase_boost" = N): phrase i = tokens[i][0 .. lens[i]), 1 .. 32 non-blank token ids
  * (0 .. 1023), with bonus[i], finite, 0 < bonus <= 1e4, in natural-log units (added to the joint's logits).  n_phrases = 0 clears the set.
@@ -332,6 +348,10 @@ int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, flo
  * token, see nasr_stream_get_token_logprobs).  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
  * call forgets the values of the one before. */
 int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
+/* the K alternatives (engine option "token_alternatives" = K) of every token of
+ * utterance u of the LAST offline call; cap in tokens; ids_out == NULL: the number available.  [tokens][K] row-major, row i belongs to
+ * tokens_out[u][i].  Returns the number of tokens written (<= cap) or < 0.  Every offline call forgets the values of the one before. */
+int nasr_engine_offline_token_alternatives(nasr_engine *e, int u, int32_t *ids_out, float *logprobs_out, int32_t cap);
 
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =

@@ -33,6 +33,7 @@ EXPORTS = [
     "nasr_engine_transcribe_mel", "nasr_engine_transcribe", "nasr_engine_offline_tap",
     "nasr_stream_get_token_logprobs", "nasr_engine_offline_token_logprobs",
     "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
+    "nasr_stream_get_token_alternatives", "nasr_engine_offline_token_alternatives",
 ]
 FLAG_NO_BOOST = 1 << 3
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
@@ -121,6 +122,8 @@ def lib():
         L.nasr_engine_offline_token_logprobs.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
         L.nasr_engine_set_boost_phrases.argtypes = [vp, C.c_int, C.POINTER(ip), ip, C.POINTER(C.c_float)]
         L.nasr_stream_set_boost.argtypes = [vp, C.c_int]
+        L.nasr_stream_get_token_alternatives.argtypes = [vp, C.c_int64, C.c_int32, ip, C.POINTER(C.c_float)]
+        L.nasr_engine_offline_token_alternatives.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_float), C.c_int32]
         _lib = L
     return _lib
 
@@ -201,6 +204,18 @@ class Stream:
         out = np.zeros(max(count, 1), np.float32)
         n = _chk(lib().nasr_stream_get_token_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:n].copy()
+
+    def token_alternatives(self, first=0, count=None):
+        """(ids [n][K] int32, lps [n][K] float32): the K most probable joint outputs (blank = 1024 included) where each of tokens
+        [first, first + count) since create/reset was emitted, descending, with ln P under the joint's softmax; needs engine option
+        "token_alternatives" = K (set before the first step)"""
+        if count is None:
+            count = max(int(self.stats().tokens) - first, 0)
+        K = self.engine.token_alternatives
+        ids = np.zeros((max(count, 1), max(K, 1)), np.int32)
+        lps = np.zeros((max(count, 1), max(K, 1)), np.float32)
+        n = _chk(lib().nasr_stream_get_token_alternatives(self.h, first, count, ids.ctypes.data_as(C.POINTER(C.c_int32)), lps.ctypes.data_as(C.POINTER(C.c_float))))
+        return ids[:n].copy(), lps[:n].copy()
 
     def set_boost(self, enable=True):
         """phrase boosting on / off for this stream (engine option "phrase_boost"); either way its boost history restarts"""
@@ -362,8 +377,12 @@ class Engine:
     def stream(self, right_context=0, prompt_index=-1) -> Stream:
         return Stream(self, right_context, prompt_index)
 
+    token_alternatives = 0          # K of option "token_alternatives": the width of the rows the two alternatives getters return
+
     def set_option(self, key: str, value: int):
         _chk(lib().nasr_engine_set_option(self.h, key.encode(), int(value)))
+        if key == "token_alternatives":
+            self.token_alternatives = int(value)
 
     def set_debug(self, on=True):
         _chk(lib().nasr_engine_set_debug(self.h, int(on)))
@@ -496,6 +515,16 @@ class Engine:
         ptrs = (C.POINTER(C.c_int32) * n)(*[p.ctypes.data_as(C.POINTER(C.c_int32)) for p in phrases])
         lens = np.asarray([p.size for p in phrases], np.int32)
         _chk(lib().nasr_engine_set_boost_phrases(self.h, n, ptrs, lens.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def offline_token_alternatives(self, u):
+        """(ids [n][K] int32, lps [n][K] float32) of every token of utterance u of the last offline call (engine option "token_alternatives" = K)"""
+        L = lib()
+        n = _chk(L.nasr_engine_offline_token_alternatives(self.h, u, None, None, 0))
+        K = max(self.token_alternatives, 1)
+        ids = np.zeros((max(n, 1), K), np.int32)
+        lps = np.zeros((max(n, 1), K), np.float32)
+        n = _chk(L.nasr_engine_offline_token_alternatives(self.h, u, ids.ctypes.data_as(C.POINTER(C.c_int32)), lps.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return ids[:n].copy(), lps[:n].copy()
 
     def offline_token_logprobs(self, u) -> np.ndarray:
         """ln P(token) of every token of utterance u of the last offline call (engine option "token_logprobs" = 1)"""

@@ -257,13 +257,28 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
     const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
     return ((unsigned long long)hi << 32) | lo;
 }
+// engine option "token_alternatives" (nasr_topk.h): the 8 largest RAW-logit keys of a 16-entry vocab tile, sorted, lane (q, r) holding entries
+// v0 .. v0 + 3 of row r's logits; every lane of the row ends up with the same list (keys are unique).  After the xor-16 step a list has at
+// most 8 entries, of which a lane contributes four: only those cross the lanes
+__device__ __forceinline__ void alt_tile_keys(float x0, float x1, float x2, float x3, int v0, unsigned long long *a) {
+    unsigned long long b[nasr_topk::KMAX];
+    nasr_topk::lane_keys(x0, x1, x2, x3, v0, a);
+#pragma unroll
+    for (int j = 0; j < nasr_topk::KMAX; j++) b[j] = j < 4 ? shfl_xor_u64(a[j], 16) : 0ull;
+    nasr_topk::merge8(a, b);
+#pragma unroll
+    for (int j = 0; j < nasr_topk::KMAX; j++) b[j] = shfl_xor_u64(a[j], 32);
+    nasr_topk::merge8(a, b);
+}
 
 // ---- joint, few rows (<= 64 rows in the step): logits = W_out . relu(encproj[row] + g) + b_out and
 // arg-max; grid = 65 (1040 padded vocab rows), 4 waves split K; first maximum wins (:899-906, :1220-1221)
 // BOOST (engine option "phrase_boost", nasr_boost.h): the arg-max key is built from logit + bonus(automaton state of the row's slot, v) -- one
 // 16-byte load per lane and row -- while the softmax parts stay those of the raw logits; with LP the lane that owns the tile's winner also leaves
 // its raw logit in boost_raw [row][part] (one writer per element: a key names one vocabulary entry, and one lane holds it)
-template <int MT, bool LP, bool BOOST>
+// ALT (engine option "token_alternatives", nasr_topk.h; always with LP): lane group 0 also leaves the tile's alt_k largest raw-logit keys in
+// alt_key [row][part][alt_k], beside the part
+template <int MT, bool LP, bool BOOST, bool ALT>
 __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, float (*red)[MT_MAX][64][4]) {
     const int nt = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
@@ -323,20 +338,29 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
             const nasr_lp::Part part = lp_tile_part(lgs[0], lgs[1], lgs[2], lgs[3], nt * 16 + q * 4);
             const int row = nasr_lp::joint_store_row(i0, MT, wave, lane, nr);
             if (row >= 0) p.lp_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), nt, nasr_lp::TILE_PARTS)] = part;
+            if (ALT) {
+                unsigned long long top[nasr_topk::KMAX];
+                alt_tile_keys(lgs[0], lgs[1], lgs[2], lgs[3], nt * 16 + q * 4, top);
+                if (row >= 0) {
+                    unsigned long long *dst = p.alt_key + nasr_topk::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), nt, nasr_lp::TILE_PARTS, p.alt_k);
+#pragma unroll
+                    for (int j = 0; j < nasr_topk::KMAX; j++) if (j < p.alt_k) dst[j] = top[j];
+                }
+            }
         }
     }
 }
 
-template <bool LP, bool BOOST>
+template <bool LP, bool BOOST, bool ALT>
 __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
     const int nr = *p.n_rows;
     if (nr == 0) return;
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nr; i0 += 16 * MT_MAX) {
         const int tiles = nasr_lp::joint_pass_tiles(nr - i0);      // 1, 2 or 4 m-tiles: 16, 32 or more rows left
-        if (tiles == 1) joint_pass<1, LP, BOOST>(p, i0, nr, red);
-        else if (tiles == 2) joint_pass<2, LP, BOOST>(p, i0, nr, red);
-        else joint_pass<4, LP, BOOST>(p, i0, nr, red);
+        if (tiles == 1) joint_pass<1, LP, BOOST, ALT>(p, i0, nr, red);
+        else if (tiles == 2) joint_pass<2, LP, BOOST, ALT>(p, i0, nr, red);
+        else joint_pass<4, LP, BOOST, ALT>(p, i0, nr, red);
     }
 }
 
@@ -346,7 +370,7 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // workgroup and staged in LDS (double-buffered, 16-byte chunks XOR-swizzled with the row).  The
 // kernel is bound by the f32 MFMA (32 cycles per 16x16x4), 640 of them per wave.
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
-template <bool LP, bool BOOST>
+template <bool LP, bool BOOST, bool ALT>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     const int nr = *p.n_rows;
     const int m0 = blockIdx.y * 64;
@@ -355,6 +379,10 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     __shared__ unsigned long long bests[4][64];
     __shared__ nasr_lp::Part lps[LP ? 4 : 1][64];      // token_logprobs: the four waves' tile parts of the 64 rows
     __shared__ float raws[LP && BOOST ? 4 : 1][64];    // ... with phrase_boost: the raw logit of each wave's winner by boosted key
+    // token_alternatives: the four waves' tile lists of the 64 rows, [wave][entry][row].  They take the place of the operand staging, which nobody
+    // reads after the K loop's last barrier
+    static_assert(sizeof(unsigned long long) * 4 * nasr_topk::KMAX * 64 <= sizeof(float) * 2 * 64 * JT_KC, "the lists fit the staging buffer");
+    unsigned long long (*alts)[nasr_topk::KMAX][64] = (unsigned long long (*)[nasr_topk::KMAX][64])&xs[0][0];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
     const int nt = blockIdx.x * 4 + wave;
     const bool has_tile = nt * 16 < VOCAB;
@@ -457,6 +485,14 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
             for (int j = 0; j < 4; j++) lg[j] = acc[mt][j] + p.out_b[v0 + j < VOCAB ? v0 + j : 0];
             const nasr_lp::Part part = lp_tile_part(lg[0], lg[1], lg[2], lg[3], v0);
             if (q == 0) lps[wave][mt * 16 + r] = part;
+            if (ALT) {                                 // no tile: v0 = VOCAB leaves the empty list
+                unsigned long long top[nasr_topk::KMAX];
+                alt_tile_keys(lg[0], lg[1], lg[2], lg[3], v0, top);
+                if (q == 0) {
+#pragma unroll
+                    for (int j = 0; j < nasr_topk::KMAX; j++) alts[wave][j][mt * 16 + r] = top[j];
+                }
+            }
         }
     }
     __syncthreads();
@@ -477,12 +513,26 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         if (row >= 0) {
             const nasr_lp::Part part = nasr_lp::wg64(lps[0][threadIdx.x], lps[1][threadIdx.x], lps[2][threadIdx.x], lps[3][threadIdx.x]);
             p.lp_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), blockIdx.x, nasr_lp::WG_PARTS)] = part;
+            if (ALT) {                                 // the workgroup's list: its four waves' lists merged in wave order
+                unsigned long long top[nasr_topk::KMAX], w[nasr_topk::KMAX];
+#pragma unroll
+                for (int j = 0; j < nasr_topk::KMAX; j++) top[j] = alts[0][j][threadIdx.x];
+#pragma unroll
+                for (int u = 1; u < 4; u++) {
+#pragma unroll
+                    for (int j = 0; j < nasr_topk::KMAX; j++) w[j] = alts[u][j][threadIdx.x];
+                    nasr_topk::merge8(top, w);
+                }
+                unsigned long long *dst = p.alt_key + nasr_topk::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), blockIdx.x, nasr_lp::WG_PARTS, p.alt_k);
+#pragma unroll
+                for (int j = 0; j < nasr_topk::KMAX; j++) if (j < p.alt_k) dst[j] = top[j];
+            }
         }
     }
 }
 
 // ---- commit: walk each stream's evaluated frames up to its first non-blank -------------------------
-template <bool LP, bool BOOST>
+template <bool LP, bool BOOST, bool ALT>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
@@ -518,7 +568,23 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
                 const nasr_lp::Part *parts = p.lp_part + nasr_lp::scratch_index(b * p.T + f, 0, np);
                 // phrase_boost: the key holds logit + bonus; the value stays the MODEL's probability of the token, from its raw logit
                 const float logit = BOOST ? p.boost_raw[nasr_lp::scratch_index(b * p.T + f, nasr_boost::raw_part_of(best, np), np)] : nasr_lp::key_logit(k);
-                p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(logit, parts, np);
+                if (!ALT) p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(logit, parts, np);
+                else {
+                    // token_alternatives: this thread merges the frame's slice lists itself -- the streams of a step are merged side by side, one
+                    // thread each; most slices end at their head, and the heads are loaded eight at a time (row_merge).  The token's own value comes from the same
+                    // (m, log s), so it equals the entry of the alternatives that names the token bit for bit
+                    float m, log_s;
+                    nasr_topk::row_softmax(parts, np, &m, &log_s);
+                    p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_topk::lp_of(logit, m, log_s);
+                    const int K = p.alt_k;
+                    nasr_topk::RowTop rt;
+                    nasr_topk::row_begin(rt);
+                    nasr_topk::row_merge(rt, K, p.alt_key + nasr_topk::scratch_index(b * p.T + f, 0, np, K), np);
+                    const size_t at = nasr_topk::ring_index(slot, n, TOK_CAP, K);
+#pragma unroll
+                    for (int j = 0; j < nasr_topk::KMAX; j++)
+                        if (j < K) { p.alt_id[at + j] = nasr_topk::alt_id(rt.top[j]); p.alt_lp[at + j] = nasr_topk::alt_lp(rt.top[j], m, log_s); }
+                }
             }
             if (BOOST) p.boost_state[slot] = nasr_boost::next_of(p.boost_next, p.boost_state[slot], best);   // the history moves where the decoder state does
             ct->n_tok = n + 1;
@@ -581,12 +647,13 @@ void launch_encproj(const float *x, const float *wpk, const float *bias, float *
 void launch_decode_begin(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_begin, dim3(1), dim3(256), 0, st, p);
 }
-template <bool LP, bool BOOST>
+template <bool LP, bool BOOST, bool ALT>
 static void launch_joint_commit(const DecParams &p, hipStream_t st) {
+    static_assert(LP || !ALT, "the alternatives take their probabilities from the softmax parts");
     const int rows = p.B * p.T;
-    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((k_dec_commit<LP, BOOST>), dim3(1), dim3(256), 0, st, p);
+    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT>), dim3(1), dim3(256), 0, st, p);
 }
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a
@@ -597,9 +664,11 @@ void launch_decode_iter(const DecParams &p, int iter, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
     // engine options "token_logprobs" (lp_part) and "phrase_boost" (boost_bonus): the variants that also leave the softmax parts / the token's
-    // log-probability, and that add the phrase bonus to the arg-max key; with both off these are the kernels without either
-    if (p.lp_part) { if (p.boost_bonus) launch_joint_commit<true, true>(p, st); else launch_joint_commit<true, false>(p, st); }
-    else { if (p.boost_bonus) launch_joint_commit<false, true>(p, st); else launch_joint_commit<false, false>(p, st); }
+    // log-probability, and that add the phrase bonus to the arg-max key; with both off these are the kernels without either.  "token_alternatives"
+    // (alt_key; lp_part comes with it) takes the variants that also leave every slice's largest keys / the token's K best outputs
+    if (p.alt_key) { if (p.boost_bonus) launch_joint_commit<true, true, true>(p, st); else launch_joint_commit<true, false, true>(p, st); }
+    else if (p.lp_part) { if (p.boost_bonus) launch_joint_commit<true, true, false>(p, st); else launch_joint_commit<true, false, false>(p, st); }
+    else { if (p.boost_bonus) launch_joint_commit<false, true, false>(p, st); else launch_joint_commit<false, false, false>(p, st); }
 }
 // iterations enqueued before the host looks at n_active: (symbols of the busiest stream) + 1 are needed; a shortfall
 // costs one host round trip and a further round of iterations

@@ -94,6 +94,22 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         }
         e->opt_phrase_boost = value;
     }
+    else if (!strcmp(key, "token_alternatives")) {
+        // like "token_logprobs": picks the decode kernels that get captured and allocates the scratch and the rings at K entries per token.  Its
+        // kernels always leave the softmax parts, so the buffers of "token_logprobs" come with it (that option's getters stay its own)
+        if (!nasr_topk::valid_k(value)) return fail("token_alternatives must be 0 .. %d", nasr_topk::KMAX);
+        if (e->dec_started || e->off) return fail("token_alternatives must be set before the first step or offline call (the decode kernels are already chosen)");
+        if (value && e->alt_key && value != e->alt_cap) return fail("token_alternatives: the rings already hold %d entries per token", e->alt_cap);
+        if (value && !e->alt_key) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (!e->lp_part && (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP))) return -1;
+            if (dalloc(e, &e->alt_key, nasr_topk::scratch_keys(e->w_rows, value)) || dalloc(e, &e->alt_id, (size_t)e->max_streams * TOK_CAP * value) ||
+                dalloc(e, &e->alt_lp, (size_t)e->max_streams * TOK_CAP * value)) return -1;
+            e->alt_cap = value;
+        }
+        e->opt_token_alt = value;
+    }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
     else if (!strcmp(key, "wide_min_rows")) e->opt_wide_min_rows = value;
@@ -553,6 +569,33 @@ extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t firs
     std::vector<float> ring(TOK_CAP);
     HIPCHK(hipMemcpy(ring.data(), e->tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
+    return count;
+}
+
+extern "C" int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t first, int32_t count, int32_t *ids_out, float *logprobs_out) {
+    ApiGuard api_guard;
+    if (!s || (count > 0 && (!ids_out || !logprobs_out))) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative token range");
+    nasr_engine *e = s->e;
+    const int K = e->opt_token_alt;
+    if (!K) return fail("no token alternatives: engine option \"token_alternatives\" is off (set it to K = 1 .. 8 before the first step)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    HIPCHK(hipStreamSynchronize(e->st));
+    DecCtrl c;
+    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
+    if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
+    if (count <= 0) return 0;
+    std::vector<int32_t> ids((size_t)TOK_CAP * K);
+    std::vector<float> lps((size_t)TOK_CAP * K);
+    HIPCHK(hipMemcpy(ids.data(), e->alt_id + (size_t)s->slot * TOK_CAP * K, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lps.data(), e->alt_lp + (size_t)s->slot * TOK_CAP * K, lps.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; i++) {
+        const size_t at = (size_t)((first + i) & (TOK_CAP - 1)) * K;
+        memcpy(ids_out + (size_t)i * K, ids.data() + at, (size_t)K * 4);
+        memcpy(logprobs_out + (size_t)i * K, lps.data() + at, (size_t)K * 4);
+    }
     return count;
 }
 

@@ -230,6 +230,11 @@ struct nasr_engine {
     float *boost_bonus = nullptr; int32_t *boost_next = nullptr;   // [capacity][1040] each
     int *boost_state = nullptr;      // [slot] automaton state of every stream's emitted history
     float *boost_raw = nullptr;      // scratch beside lp_part: raw logit of every part's winner (read only when both options are on)
+    // option "token_alternatives" = K (0: off, 1 .. 8), nasr_topk.h: the K largest joint outputs with their log-probabilities where every token was
+    // emitted.  Taken like "token_logprobs"; its kernels also leave the softmax parts, so lp_part / tok_logprob are allocated with it
+    int opt_token_alt = 0, alt_cap = 0;                            // K in use, K the buffers were allocated for
+    unsigned long long *alt_key = nullptr;                         // scratch beside lp_part: [row][slice][K] largest keys of every vocab slice
+    int32_t *alt_id = nullptr; float *alt_lp = nullptr;            // [slot][TOK_CAP][K] each, beside tok_ring / tok_frame / tok_logprob
     int *collect_dev;                // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;

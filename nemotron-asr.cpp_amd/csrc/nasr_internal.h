@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "nasr_logprob.h"
 #include "nasr_boost.h"
+#include "nasr_topk.h"
 
 namespace nasr {
 
@@ -263,6 +264,12 @@ struct DecParams {
     const int32_t *boost_next;   // [states][1040] state after emitting that entry
     int *boost_state;            // [slot] automaton state of the slot's emitted history (0: boosting disabled for it, 1: root)
     float *boost_raw;            // [B * T][n_parts] with "token_logprobs" too: raw logit of every part's winner by boosted key
+    // engine option "token_alternatives" = alt_k (all null / 0 when it is off), nasr_topk.h; these variants always leave the softmax parts too,
+    // so lp_part and tok_logprob are set with them
+    unsigned long long *alt_key; // [B * T][n_parts][alt_k] the alt_k largest raw-logit keys of every vocab slice of every evaluated row
+    int32_t *alt_id;             // [slot][TOK_CAP][alt_k] ids of the alt_k largest joint outputs where each token was emitted, descending
+    float *alt_lp;               // [slot][TOK_CAP][alt_k] their natural-log softmax probabilities
+    int alt_k;
 };
 void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, int iter, hipStream_t st);

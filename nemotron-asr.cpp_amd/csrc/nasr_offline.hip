@@ -30,6 +30,8 @@ struct OfflineState {
     nasr_lp::Part *lp_part = nullptr; float *tok_logprob = nullptr;      // engine option "token_logprobs" (allocated with the slots when it is on)
     int *boost_state = nullptr; float *boost_raw = nullptr;        // engine option "phrase_boost": the offline slots' automaton states (the tables are the engine's)
     bool no_boost = false;                                         // NASR_FLAG_NO_BOOST of the call in progress
+    unsigned long long *alt_key = nullptr; int32_t *alt_id = nullptr; float *alt_lp = nullptr;      // engine option "token_alternatives"
+    std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // ... of the last call, by utterance: [tokens][K] each
     std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
@@ -126,7 +128,12 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
         rc |= off_alloc(o, (void **)&o->rowmap, U * W * 4);
         rc |= off_alloc(o, (void **)&o->tok_ring, U * TOK_CAP * 4);
         rc |= off_alloc(o, (void **)&o->tok_frame, U * TOK_CAP * 4);
-        if (e->opt_token_logprobs) {
+        if (e->opt_token_alt) {
+            rc |= off_alloc(o, (void **)&o->alt_key, nasr_topk::scratch_keys((int)(U * W), e->opt_token_alt) * sizeof(unsigned long long));
+            rc |= off_alloc(o, (void **)&o->alt_id, U * TOK_CAP * e->opt_token_alt * 4);
+            rc |= off_alloc(o, (void **)&o->alt_lp, U * TOK_CAP * e->opt_token_alt * 4);
+        }
+        if (e->opt_token_logprobs || e->opt_token_alt) {
             rc |= off_alloc(o, (void **)&o->lp_part, nasr_lp::scratch_parts((int)(U * W)) * sizeof(nasr_lp::Part));
             rc |= off_alloc(o, (void **)&o->tok_logprob, U * TOK_CAP * 4);
         }
@@ -272,7 +279,10 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
     std::vector<int> tok_read(n, 0);
     std::vector<DecCtrl> hctrl(n);
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
-    std::vector<float> ringl(o->tok_logprob ? (size_t)n * TOK_CAP : 0);
+    std::vector<float> ringl(e->opt_token_logprobs ? (size_t)n * TOK_CAP : 0);
+    const int K = e->opt_token_alt;
+    std::vector<int32_t> ringai((size_t)n * TOK_CAP * K);
+    std::vector<float> ringal((size_t)n * TOK_CAP * K);
     for (int w0 = 0; w0 < maxT; w0 += OFF_DEC_WIN) {
         std::vector<RowDesc> rd(n);
         std::vector<int4> wd(n);
@@ -293,7 +303,8 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         bind_dec_weights(e, dp);
         dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
         dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
-        dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs"
+        dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs" or "token_alternatives"
+        if (K) { dp.alt_key = o->alt_key; dp.alt_id = o->alt_id; dp.alt_lp = o->alt_lp; dp.alt_k = K; }
         if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
         launch_decode_begin(dp, st);
         int it = 0, budget = decode_blind_iterations(max_dec), h_active = 0;
@@ -310,6 +321,10 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ringf.data(), o->tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
         if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
+        if (K) {
+            HIPCHK(hipMemcpyAsync(ringai.data(), o->alt_id, ringai.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ringal.data(), o->alt_lp, ringal.size() * 4, hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(hipStreamSynchronize(st));
         for (int k = 0; k < n; k++) {
             const int n_new = hctrl[k].n_tok - tok_read[k];
@@ -319,6 +334,11 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
                 toks[first + k].push_back(ring[(size_t)k * TOK_CAP + pos]);
                 frs[first + k].push_back(ringf[(size_t)k * TOK_CAP + pos]);
                 if (!ringl.empty()) o->logprobs[first + k].push_back(ringl[(size_t)k * TOK_CAP + pos]);
+                if (K) {
+                    const size_t at = ((size_t)k * TOK_CAP + pos) * K;
+                    o->alt_ids[first + k].insert(o->alt_ids[first + k].end(), ringai.begin() + at, ringai.begin() + at + K);
+                    o->alt_lps[first + k].insert(o->alt_lps[first + k].end(), ringal.begin() + at, ringal.begin() + at + K);
+                }
             }
             tok_read[k] = hctrl[k].n_tok;
         }
@@ -358,6 +378,7 @@ static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const
     }
     if (ensure_offline_pos(e, o)) return -1;
     o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
+    o->alt_ids.assign(e->opt_token_alt ? B : 0, {}); o->alt_lps.assign(e->opt_token_alt ? B : 0, {});
     if (e->debug) {
         o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {});
         for (int b = 0; b < B; b++) {
@@ -390,7 +411,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     if (!e->off) e->off = new OfflineState();
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
-    o->logprobs.clear();
+    o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
     return 0;
 }
@@ -563,5 +584,21 @@ extern "C" int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *
     if (!out) return (int)src.size();                       // size query
     const int n = std::min<int>((int)src.size(), std::max(cap, 0));
     memcpy(out, src.data(), (size_t)n * 4);
+    return n;
+}
+
+extern "C" int nasr_engine_offline_token_alternatives(nasr_engine *e, int u, int32_t *ids_out, float *logprobs_out, int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    const int K = e->opt_token_alt;
+    if (!K) return fail("no token alternatives: engine option \"token_alternatives\" is off (set it to K = 1 .. 8 before the first step or offline call)");
+    OfflineState *o = e->off;
+    if (!o || u < 0 || u >= (int)o->alt_ids.size()) return fail("no offline token alternatives of utterance %d (they are those of the last offline call)", u);
+    const int have = (int)(o->alt_ids[u].size() / (size_t)K);
+    if (!ids_out) return have;                              // size query, in tokens
+    if (!logprobs_out) return fail("null argument");
+    const int n = std::min<int>(have, std::max(cap, 0));
+    memcpy(ids_out, o->alt_ids[u].data(), (size_t)n * K * 4);
+    memcpy(logprobs_out, o->alt_lps[u].data(), (size_t)n * K * 4);
     return n;
 }

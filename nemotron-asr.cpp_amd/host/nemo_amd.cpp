@@ -74,6 +74,25 @@ std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx) {
     return out;
 }
 
+nemo_token_alternatives nemo_stream_get_token_alternatives(nemo_stream_context *sctx) {
+    nemo_token_alternatives out;
+    if (!sctx || !sctx->nctx || sctx->nctx->token_alternatives <= 0) return out;
+    const int k = sctx->nctx->token_alternatives;
+    const size_t n = sctx->tokens.size();
+    const size_t first = n > 4096 ? n - 4096 : 0;       // older values have left the device ring
+    std::vector<int32_t> ids((n - first) * k + 1);
+    std::vector<float> lp((n - first) * k + 1);
+    const int got = nasr_stream_get_token_alternatives(sctx->stream, (int64_t)first, (int32_t)(n - first), ids.data(), lp.data());
+    if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
+    out.k = k;
+    out.n_tokens = first + (size_t)got;
+    out.ids.assign(first * k, -1);
+    out.logprobs.assign(first * k, NAN);
+    out.ids.insert(out.ids.end(), ids.begin(), ids.begin() + (size_t)got * k);
+    out.logprobs.insert(out.logprobs.end(), lp.begin(), lp.begin() + (size_t)got * k);
+    return out;
+}
+
 nemo_context *nemo_init_with_device(const char *model_path, int device, int dtype, int max_streams) {
     return nemo_init_with_rows(model_path, device, dtype, max_streams, 0);
 }
@@ -203,6 +222,16 @@ bool nemo_stream_set_boost(nemo_stream_context *sctx, bool enable) {
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return false;
     }
+    return true;
+}
+
+bool nemo_set_token_alternatives(nemo_context *ctx, int k) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "token_alternatives", k) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    ctx->token_alternatives = k;
     return true;
 }
 

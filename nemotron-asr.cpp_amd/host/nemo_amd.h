@@ -26,6 +26,7 @@ struct nemo_context {               // reference: nemo_context / nemo_model (src
     int prompt_index = -1;          // default language prompt (101 = "auto") for multilingual models
     nasr_engine *engine = nullptr;
     int max_streams = 0;
+    int token_alternatives = 0;      // K of nemo_set_token_alternatives (0: off)
     int workspace_rows = 0;          // rows one engine call may carry (streams x chunks x (1 + right_context)); nasr_engine_create_ex
 };
 
@@ -68,6 +69,9 @@ bool nemo_set_language(nemo_context *ctx, const char *lang);  // default prompt 
 // next; nemo_stream_process_incremental then returns each text delta one call later, nemo_stream_finalize returns the rest
 // MI355X extension: per-token log-probabilities (nasr_engine_set_option "token_logprobs"); before the first stream processes audio
 bool nemo_set_token_logprobs(nemo_context *ctx, bool on);
+// MI355X extension: the K = 1 .. 8 most probable joint outputs at every emission (nasr_engine_set_option "token_alternatives"; 0 = off); before
+// the first stream processes audio
+bool nemo_set_token_alternatives(nemo_context *ctx, int k);
 // MI355X extension: phrase boosting ("hotwords"; nasr_engine_set_option "phrase_boost" + nasr_engine_set_boost_phrases).
 // nemo_set_phrase_boost: before the first stream processes audio; max_states = capacity of the phrase automaton, 2 .. 4096 (one state per
 // distinct phrase prefix + 2), 0 = off.  nemo_set_boost_phrases: any time afterwards; phrases as text (boost_phrases.h: each word segmented by
@@ -118,5 +122,15 @@ std::vector<timed_token> nemo_stream_get_timed_tokens(nemo_stream_context *sctx)
 // ln P(token) of every token of the stream since init/reset (needs nemo_set_token_logprobs; NaN for tokens that have left the
 // engine's 4096-token ring, as their frame is -1); word confidences from them: word_confidence.h
 std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx);
+// the K alternatives of every token of the stream since init/reset (needs nemo_set_token_alternatives): row i of ids / logprobs [n_tokens][k]
+// belongs to token i, descending probability, ids 0 .. 1024 (1024 = blank), logprobs = ln P; tokens that have left the engine's
+// 4096-token ring get ids -1 and NaN.  k = 0 and empty when the option is off
+struct nemo_token_alternatives {
+    int k = 0;
+    size_t n_tokens = 0;
+    std::vector<int32_t> ids;
+    std::vector<float> logprobs;
+};
+nemo_token_alternatives nemo_stream_get_token_alternatives(nemo_stream_context *sctx);
 // reference src/nemo-ggml.cpp:1556-1583: "{12.34}" in front of every word when timestamp_words is set
 std::string tokens_to_text(const std::vector<timed_token> &tokens, const std::vector<std::string> &vocab, bool timestamp_words);

@@ -11,13 +11,15 @@
 #include <string>
 #include <vector>
 
+#include <cmath>
+
 #include "diarize_pipeline_amd.h"
 #include "nemo_amd.h"
 #include "word_confidence.h"
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]]\n"
             "  audio: raw s16le, 16 kHz, mono.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --read-chunks N: read N chunks of audio per call (default 1 = the reference's read size); a file is\n"
             "                   transcribed fastest with N = 256 and --pipeline 4: same transcript, the chunks of a read share one\n"
@@ -25,6 +27,10 @@ static void usage(const char *prog) {
             "  --timestamps:    print the final transcript again with {seconds} in front of every word\n"
             "  --confidence:    print the final transcript again with [0.93] behind every word: exp of the smallest log-probability among\n"
             "                   the word's tokens under the joint's softmax (with --timestamps: one line, {seconds} in front and [p] behind)\n"
+            "  --alternatives K: after the transcript (and the --timestamps / --confidence line) one line per emitted token, `alt <i> <id>:<p> <id>:<p> ...`\n"
+            "                   with K = 1 .. 8 pairs: i = the token's index from 0, then the K most probable joint outputs at that emission (id 1024 =\n"
+            "                   blank: the model nearly emitted nothing) with p = their softmax probability as %%.4f, in descending order; without\n"
+            "                   --boost-file the first id is the token.  The first line and the --print-tokens line stay as they are\n"
             "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
             "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
             "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
@@ -43,6 +49,7 @@ int main(int argc, char **argv) {
     const char *lang = nullptr;
     bool print_tokens = false, timestamps = false, confidence = false;
     const char *boost_file = nullptr;
+    int alternatives = 0;
     float boost_bonus = 4.0f;
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
@@ -57,6 +64,7 @@ int main(int argc, char **argv) {
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--timestamps") timestamps = true;
         else if (a == "--confidence") confidence = true;
+        else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
         else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
         else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
         else if (a == "--cpu" || a == "--cuda" || a == "--metal")      // reference src/transcribe_stream.cpp:86-88
@@ -89,6 +97,7 @@ int main(int argc, char **argv) {
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
+    if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
     if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
@@ -162,6 +171,14 @@ int main(int argc, char **argv) {
             }
         }
         printf("%s\n", word_conf::annotate(ws, timestamps ? &stamps : nullptr).c_str());
+    }
+    if (alternatives) {
+        const nemo_token_alternatives alt = nemo_stream_get_token_alternatives(sctx);
+        for (size_t i = 0; i < alt.n_tokens; i++) {
+            printf("alt %zu", i);
+            for (int j = 0; j < alt.k; j++) printf(" %d:%.4f", alt.ids[i * alt.k + j], std::exp((double)alt.logprobs[i * alt.k + j]));
+            printf("\n");
+        }
     }
     if (print_tokens) {
         printf("TOKENS:");
