@@ -703,3 +703,102 @@ print("TOKENS", sum(len(t) for t in res[1]))
         assert 1 <= n_streams <= 3, lanes                                        # one queue fewer than the runtime offers
     else:
         assert n_streams >= 3, lanes
+
+
+# ---- kernel_size = 5: the generic tap loops of k_dwconv (debug mode below: the taps switch the fused layer off) and of the fused PRO_DWCONV prologue
+# (test_kernel_size_5_fused_layer_matches_unfused_and_oracle, no debug mode), and conv caches of 4 rows (T < ks - 1 at R = 0 and R = 1) ----
+@pytest.fixture(scope="module")
+def W5():
+    return synth.make_weights(n_layers=N_LAYERS, kernel_size=5)
+
+
+def _compare_streams_ks5(W5, dtype, R, B, n_chunks, tol_layer):
+    """B streams of an engine with kernel_size = 5 against one oracle stream each, chunk by chunk: chunk counts, layer taps, then the K / V / conv caches;
+    -> (engine tokens, oracle tokens) per stream"""
+    T = 1 + R
+    eng = capi.Engine(W5, n_layers=N_LAYERS, dtype=dtype, max_streams=B, kernel_size=5)
+    eng.set_debug(True)
+    om = ob.OracleModel(W5, N_LAYERS, kernel_size=5, emulate_bf16=dtype == capi.DTYPE_BF16)
+    sts = [eng.stream(R) for _ in range(B)]
+    osts = [ob.OracleStream(om, R) for _ in range(B)]
+    taps = [o.enable_taps() for o in osts]
+    mels = [_mel_stream(9 + 8 * T * n_chunks, seed=50 + b) for b in range(B)]
+    toks_g, toks_o = [[] for _ in range(B)], [[] for _ in range(B)]
+    worst = 0.0
+    for c in range(n_chunks):
+        pieces = [m[c * 8 * T:(c + 1) * 8 * T] for m in mels]
+        for b in range(B):
+            toks_o[b] += osts[b].push_mel(pieces[b])
+        for b, t in enumerate(eng.step_mel(sts, pieces)):
+            toks_g[b] += t
+        for b in range(B):
+            assert sts[b].stats().chunks == osts[b].total_chunks
+            if osts[b].total_chunks == 0:
+                continue
+            for l in range(N_LAYERS):
+                worst = _acc(worst, sts[b].tap(capi.TAP_LAYER_OUT, l).reshape(T, 1024) - taps[b][1][l])
+    assert osts[0].total_chunks >= n_chunks - 1
+    assert worst < tol_layer, worst
+    for b in range(B):
+        for l in range(N_LAYERS):
+            for which, tap in ((0, capi.TAP_K_CACHE), (1, capi.TAP_V_CACHE)):
+                got = sts[b].tap(tap, l, cap=70 * 1024).reshape(70, 1024)
+                assert np.abs(got - osts[b].get_cache(which, l)).max() < tol_layer * 4
+            got = sts[b].tap(capi.TAP_CONV_CACHE, l, cap=4 * 1024).reshape(4, 1024)
+            assert np.abs(got - osts[b].get_cache(2, l)).max() < tol_layer * 4
+    eng.close()
+    return toks_g, toks_o
+
+
+@pytest.mark.parametrize("R,n_chunks", [(0, 24), (13, 7)])
+def test_kernel_size_5_f32_engine_matches_f32_oracle(W5, R, n_chunks):
+    toks_g, toks_o = _compare_streams_ks5(W5, capi.DTYPE_F32, R, 1, n_chunks, 2e-3)
+    assert toks_g == toks_o
+
+
+@pytest.mark.parametrize("R,B,n_chunks", [(0, 1, 24), (0, 3, 24), (13, 1, 7), (13, 3, 7)])
+def test_kernel_size_5_bf16_engine_matches_bf16_oracle(W5, R, B, n_chunks):
+    """every layer's tap, which needs debug mode, and debug mode switches the fused layer off (nasr_encoder.hip: fused = bf16 && opt_fused && !debug && M <= 4):
+    all four shapes run the 14-launch layer with k_dwconv's generic tap loop, B = 3 at R = 0 included.  3e-2: this file's bf16 bound"""
+    _compare_streams_ks5(W5, capi.DTYPE_BF16, R, B, n_chunks, 3e-2)
+
+
+@pytest.mark.parametrize("R,B", [(0, 1), (0, 2), (1, 1), (0, 5)])
+def test_kernel_size_5_fused_layer_matches_unfused_and_oracle(W5, R, B):
+    """kernel_size = 5 without debug mode, so that M = B T <= 4 takes the fused layer: (0, 1) the one-row PRO_DWCONV prologue, (0, 2) and (1, 1) its two-row form
+    (two streams; one stream whose T = 2 < ks - 1 mixes old and new cache rows), inside the captured graph and on the engine's own conv-cache parity.  (0, 5) is
+    M = 5 > 4: the unfused layer whatever the option says.  Encoder output of every chunk and stream against the bf16 oracle and against the engine with
+    "fused" = 0, then the conv and K / V caches against both, all at this file's bf16 bound"""
+    T = 1 + R
+    eng = capi.Engine(W5, n_layers=N_LAYERS, dtype=capi.DTYPE_BF16, max_streams=2 * B, kernel_size=5)
+    n_chunks = 24 // T + 2
+    mels = [_mel_stream(8 * T * n_chunks, seed=70 + b) for b in range(B)]
+    outs = {}
+    for fused in (1, 0):
+        eng.set_option("fused", fused)
+        sts = [eng.stream(R) for _ in range(B)]
+        encs = []
+        for c in range(n_chunks):
+            eng.step_mel(sts, [m[c * 8 * T:(c + 1) * 8 * T] for m in mels])
+            encs.append(np.stack([s.tap(capi.TAP_ENCODER_OUT).reshape(T, 1024) for s in sts]))
+        caches = [[(s.tap(capi.TAP_CONV_CACHE, l, cap=4 * 1024).reshape(4, 1024), s.tap(capi.TAP_K_CACHE, l, cap=70 * 1024).reshape(70, 1024),
+                    s.tap(capi.TAP_V_CACHE, l, cap=70 * 1024).reshape(70, 1024)) for l in range(N_LAYERS)] for s in sts]
+        outs[fused] = (np.stack(encs), caches, [s.stats().chunks for s in sts])
+        for s in sts:
+            s.destroy()
+    assert _acc(0.0, outs[1][0] - outs[0][0]) < 3e-2
+    om = ob.OracleModel(W5, N_LAYERS, kernel_size=5, emulate_bf16=True)
+    for b in range(B):
+        ost = ob.OracleStream(om, R)
+        sub_tap, lay_tap = ost.enable_taps()
+        worst = 0.0
+        for c in range(n_chunks):
+            ost.push_mel(mels[b][c * 8 * T:(c + 1) * 8 * T])
+            if ost.total_chunks:
+                worst = _acc(worst, outs[1][0][c, b] - lay_tap[N_LAYERS - 1])
+        assert ost.total_chunks == outs[1][2][b] == outs[0][2][b] >= n_chunks - 1 and worst < 3e-2, worst
+        for l in range(N_LAYERS):
+            for which, ref in enumerate((ost.get_cache(2, l), ost.get_cache(0, l), ost.get_cache(1, l))):
+                assert _acc(0.0, outs[1][1][b][l][which] - outs[0][1][b][l][which]) < 3e-2, (b, l, which)
+                assert _acc(0.0, outs[1][1][b][l][which] - ref) < 3e-2 * 4, (b, l, which)
+    eng.close()
