@@ -353,6 +353,40 @@ int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_
  * tokens_out[u][i].  Returns the number of tokens written (<= cap) or < 0.  Every offline call forgets the values of the one before. */
 int nasr_engine_offline_token_alternatives(nasr_engine *e, int u, int32_t *ids_out, float *logprobs_out, int32_t cap);
 
+/* ---- forced alignment and transcript scoring (offline): given audio and a KNOWN transcript, when was each token spoken, and what is
+ * ln P(transcript | audio) under the model.  The encoder is exactly that of nasr_engine_transcribe(_mel): the same frame-count rule and
+ * NASR_OFFLINE_MAX_FRAMES failure, the same packing into sub-batches of "offline_rows", the same prompt fusion and the same contract (the call
+ * completes steps in flight, touches no stream state, rejects NASR_FLAG_NO_SYNC, runs eagerly).  tokens[b] holds U = n_tokens[b] ids in
+ * 0 .. 1023, 0 <= U <= NASR_ALIGN_MAX_TOKENS; a blank (1024), an id out of range or a longer transcript fails the whole call with a message
+ * that names the utterance, and the engine stays usable.
+ * Lattice of utterance b with T encoder frames: cell (t, u), 0 <= t < T, 0 <= u <= U, has the logits W_out . relu(encproj[t] + g[u]) + b_out --
+ * the joint the greedy decode evaluates -- with g[u] = joint.pred(h1_u) + b_pred, h_u the LSTM state after blank, y_0 .. y_{u-1} from the zero
+ * state (teacher forcing; u = 0 is the state a fresh decode starts in).  lb(t, u) = ln softmax at blank, ly(t, u) = ln softmax at y_u (u < U).
+ * Phrase boosting never applies: these are the model's probabilities.  The recursions are those of the standard RNN-T lattice, in double:
+ *   alpha(0, 0) = 0,  alpha(t, u) = logaddexp(alpha(t-1, u) + lb(t-1, u), alpha(t, u-1) + ly(t, u-1)),  loglik = alpha(T-1, U) + lb(T-1, U)
+ * and Viterbi the same with max, where the token move (t, u-1) -> (t, u) is taken only when its score is STRICTLY greater than the blank
+ * move's.  There is no cap of 10 symbols per frame here: that cap is a rule of the greedy loop, not of the model, so any number of tokens may
+ * fall on one frame (U > T is fine).  loglik_out[b] = ln P(y | audio); best_out[b] = the score of the best path, its final blank included
+ * (loglik >= best); frames_out[b][i] = the frame at which y_i is emitted on that path, non-decreasing, in 0 .. T-1;
+ * token_logprobs_out[b][i] = ly(frames_out[b][i], i).  Any of the four output pointers, or a per-utterance row pointer, may be NULL.
+ * T == 0 with U == 0: loglik = best = 0.  T == 0 with U > 0: loglik = best = -INFINITY, frames -1, log-probabilities -INFINITY, and the call
+ * succeeds.  U == 0: loglik = best = the sum of the blanks of column 0.
+ * Engine option "align_cells" (default 1 << 20, minimum 64): lattice cells one launch of the joint kernel covers; larger lattices and
+ * sub-batches take several launches.  The lattice of a sub-batch itself is held whole for the recursions (9 bytes per cell).  Results are
+ * bit-identical whatever its value and whatever else is in the batch. */
+#define NASR_ALIGN_MAX_TOKENS 1024
+int nasr_engine_align_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, const int32_t *prompt_index,
+                          const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                          int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags);
+/* the same from s16 PCM: pcm / n_samples and NASR_FLAG_PCM_DEVICE as for nasr_engine_transcribe */
+int nasr_engine_align(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples, const int32_t *prompt_index,
+                      const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                      int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags);
+/* after an align call made with nasr_engine_set_debug(e, 1): lb and ly of utterance u of that call, each [T][U + 1] row-major f32 (column U
+ * of lp_token reads -INFINITY); exp of them are the model's posteriors.  Returns the number of cells written (<= cap) to each non-NULL
+ * pointer, with both NULL the number available, or < 0.  Every align call or offline call forgets the lattice of the call before. */
+int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_blank_out, float *lp_token_out, int64_t cap);
+
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =
  * the tensors of diarize.gguf ("vad.*" and/or "spk.*", F32, layouts of scripts/convert_diarize_to_gguf.py:129-158),

@@ -34,7 +34,9 @@ EXPORTS = [
     "nasr_stream_get_token_logprobs", "nasr_engine_offline_token_logprobs",
     "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
     "nasr_stream_get_token_alternatives", "nasr_engine_offline_token_alternatives",
+    "nasr_engine_align_mel", "nasr_engine_align", "nasr_engine_align_lattice",
 ]
+ALIGN_MAX_TOKENS = 1024
 FLAG_NO_BOOST = 1 << 3
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
@@ -124,6 +126,11 @@ def lib():
         L.nasr_stream_set_boost.argtypes = [vp, C.c_int]
         L.nasr_stream_get_token_alternatives.argtypes = [vp, C.c_int64, C.c_int32, ip, C.POINTER(C.c_float)]
         L.nasr_engine_offline_token_alternatives.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_float), C.c_int32]
+        dp = C.POINTER(C.c_double)
+        L.nasr_engine_align_mel.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
+        L.nasr_engine_align.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
+        L.nasr_engine_align_lattice.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
+        L.nasr_engine_align_lattice.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -498,6 +505,69 @@ class Engine:
         out = np.zeros(max(cap, 1), np.float32)
         n = _chk(L.nasr_engine_offline_tap(self.h, which, u, index, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
         return out[:n].reshape(-1, width).copy()
+
+    # ---- forced alignment / transcript scoring ----------------------------------------------------
+    def _align(self, fn, ptrs, ns, tokens, prompts, flags):
+        B = len(ns)
+        if len(tokens) != B:
+            raise ValueError("one transcript per utterance")
+        pr = (C.c_int32 * B)(*[int(p) for p in prompts]) if prompts is not None else None
+        toks = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in tokens]
+        tp = (C.c_void_p * B)(*[t.ctypes.data if t.size else None for t in toks])
+        nt = (C.c_int32 * B)(*[t.size for t in toks])
+        ll, best = np.zeros(B, np.float64), np.zeros(B, np.float64)
+        fb = [np.zeros(max(t.size, 1), np.int32) for t in toks]
+        lb = [np.zeros(max(t.size, 1), np.float32) for t in toks]
+        fp = (C.c_void_p * B)(*[f.ctypes.data for f in fb])
+        lp = (C.c_void_p * B)(*[x.ctypes.data for x in lb])
+        dp = C.POINTER(C.c_double)
+        self._align_n_tokens = None                            # a failed call leaves no lattice
+        _chk(fn(self.h, B, ptrs, (C.c_int32 * B)(*[int(v) for v in ns]), pr, tp, nt, ll.ctypes.data_as(dp), best.ctypes.data_as(dp), fp, lp, flags))
+        self._align_n_tokens = [t.size for t in toks]          # the row width of align_lattice
+        return [(float(ll[b]), float(best[b]), fb[b][:toks[b].size].tolist(), lb[b][:toks[b].size].copy()) for b in range(B)]
+
+    def align_mel(self, mels, tokens, prompts=None, flags=0):
+        """forced alignment / scoring of known transcripts: mels as for transcribe_mel, tokens = one sequence of ids 0 .. 1023 per utterance.
+        Returns per utterance (loglik = ln P(tokens | audio), best = the best path's score, frames = the encoder frame at which each token
+        is emitted on that path, token_logprobs = ln P of each token there)."""
+        if len(mels) == 0:
+            return []
+        arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._align(lib().nasr_engine_align_mel, ptrs, [a.shape[0] for a in arrs], tokens, prompts, flags)
+
+    def align(self, pcms, tokens, prompts=None, flags=0):
+        """the same from int16 PCM, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE)"""
+        if len(pcms) == 0:
+            return []
+        if flags & FLAG_PCM_DEVICE:
+            ptrs = (C.c_void_p * len(pcms))(*[p for p, _ in pcms])
+            ns = [n for _, n in pcms]
+        else:
+            arrs = [np.ascontiguousarray(p, np.int16) for p in pcms]
+            ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+            ns = [a.size for a in arrs]
+        return self._align(lib().nasr_engine_align, ptrs, ns, tokens, prompts, flags)
+
+    _align_n_tokens = None
+
+    def align_lattice(self, u, n_tokens=None):
+        """after an align call made with set_debug(True): (lp_blank, lp_token) of utterance u, each [T][U + 1] float32.  U is the length
+        of the transcript that call was given for utterance u (remembered by this object; n_tokens, if given, must agree)"""
+        L = lib()
+        n = _chk(L.nasr_engine_align_lattice(self.h, u, None, None, 0))
+        known = self._align_n_tokens
+        if known is None or not 0 <= u < len(known):
+            raise NasrError(f"no lattice of utterance {u}: this object made no align call that holds it")
+        if n_tokens is not None and int(n_tokens) != known[u]:
+            raise ValueError(f"utterance {u} was aligned to {known[u]} tokens, not {n_tokens}")
+        U = known[u]
+        if n % (U + 1):
+            raise NasrError(f"lattice of utterance {u}: {n} cells are no multiple of U + 1 = {U + 1}")
+        b, t = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        fp = C.POINTER(C.c_float)
+        n = _chk(L.nasr_engine_align_lattice(self.h, u, b.ctypes.data_as(fp), t.ctypes.data_as(fp), n))
+        return b[:n].reshape(-1, U + 1).copy(), t[:n].reshape(-1, U + 1).copy()
 
     def set_boost_phrases(self, phrases, bonus=None):
         """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token

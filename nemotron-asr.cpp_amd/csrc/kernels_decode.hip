@@ -244,14 +244,8 @@ using nasr_lp::pack_key;                                            // (order-pr
 static_assert(nasr_lp::LP_VOCAB == VOCAB && nasr_lp::SMALL_ROWS == 64, "nasr_logprob.h restates the joint kernels' shapes");
 static_assert(nasr_lp::TILE_PARTS == 65 && nasr_lp::TILE_W == 16 && nasr_lp::WG_W == 64 && nasr_boost::VOCAB == VOCAB && nasr_boost::BLANK == BLANK && nasr_boost::COLS == 16 * ((VOCAB + 15) / 16), "nasr_boost.h restates the joint kernels' shapes");
 // engine option "token_logprobs": the (max, sum of exp) part of a 16-entry vocab tile, lane (q, r) holding entries v0 .. v0 + 3 of row r's
-// logits; every lane of the row ends up with the same bits (merge is symmetric)
-__device__ __forceinline__ nasr_lp::Part lp_tile_part(float x0, float x1, float x2, float x3, int v0) {
-    nasr_lp::Part a = nasr_lp::lane4(x0, x1, x2, x3, nasr_lp::lane_valid(v0)), b;
-    b.m = __shfl_xor(a.m, 16); b.s = __shfl_xor(a.s, 16);
-    a = nasr_lp::merge(a, b);
-    b.m = __shfl_xor(a.m, 32); b.s = __shfl_xor(a.s, 32);
-    return nasr_lp::merge(a, b);
-}
+// logits: nasr_lp::tile_part_wave (nasr_logprob.h, shared with kernels_align.hip)
+__device__ __forceinline__ nasr_lp::Part lp_tile_part(float x0, float x1, float x2, float x3, int v0) { return nasr_lp::tile_part_wave(x0, x1, x2, x3, v0); }
 __device__ __forceinline__ unsigned long long kmax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
     const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
@@ -654,6 +648,11 @@ static void launch_joint_commit(const DecParams &p, hipStream_t st) {
     if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
     hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT>), dim3(1), dim3(256), 0, st, p);
+}
+void launch_decode_candidates(const DecParams &p, hipStream_t st) {
+    hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
 }
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a

@@ -120,6 +120,7 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
     else if (!strcmp(key, "split_tasks")) e->opt_split_tasks = value;                // like "fused": set before the first step
     else if (!strcmp(key, "resid_epilogue")) { if (value < 0 || value > 2) return fail("resid_epilogue must be 0, 1 or 2"); e->opt_resid_epilogue = value; }      // like "fused": set before the first step
     else if (!strcmp(key, "offline_rows")) { if (value < 1) return fail("offline_rows must be >= 1"); e->opt_offline_rows = value; }
+    else if (!strcmp(key, "align_cells")) { if (value < nasr_align::MIN_CELLS) return fail("align_cells must be >= %d", nasr_align::MIN_CELLS); e->opt_align_cells = value; }
     else if (!strcmp(key, "ablate")) e->opt_ablate = value;          // measurement only (see the header); before the first step
     else if (!strcmp(key, "f32_mfma")) e->opt_f32_mfma = value != 0;      // 0: f32 GEMMs above four rows on the FMA tile kernel (round 3's path); like "fused", set before the first step
     else if (!strcmp(key, "pipeline")) {

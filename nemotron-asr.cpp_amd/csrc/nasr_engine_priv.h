@@ -257,6 +257,7 @@ struct nasr_engine {
     Prof prof;
     OfflineState *off = nullptr;     // offline path (nasr_engine_transcribe_mel): nullptr until its first call
     int opt_offline_rows = 16384;    // option "offline_rows": encoder rows per offline sub-batch
+    int opt_align_cells = nasr_align::DEFAULT_CELLS;   // option "align_cells": lattice cells per launch of k_align_lattice (nasr_engine_align*)
 };
 
 constexpr int COLLECT_STRIDE = 256;

@@ -5,6 +5,7 @@
 #include "nasr_logprob.h"
 #include "nasr_boost.h"
 #include "nasr_topk.h"
+#include "nasr_align.h"
 
 namespace nasr {
 
@@ -275,6 +276,36 @@ void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, int iter, hipStream_t st);
 int decode_blind_iterations(int frames);
 void launch_encproj(const float *x, const float *wpk, const float *bias, float *out, int M, int K, int N, hipStream_t st);
+// the LSTM candidate and g = joint.pred(h1') + b_pred of the rows in p.dlist (*p.n_dirty of them): the first three launches of launch_decode_iter
+void launch_decode_candidates(const DecParams &p, hipStream_t st);
+
+// ---- forced alignment / transcript scoring on the RNN-T lattice (kernels_align.hip, nasr_align.h) ------------------------------
+struct AlignPredParams {         // teacher forcing, step u: decoder slot k = utterance k of the sub-batch
+    const nasr_align::Utt *utt; int n; int u;
+    const int32_t *tok;          // the transcripts, utterance k at utt[k].tok0
+    DecCtrl *ctrl; int *dlist; int *n_dirty;
+    const float *predg;          // [slot][640] g of step u - 1
+    float *g;                    // [sum (U + 1)][640]
+};
+void launch_align_pred_step(const AlignPredParams &p, hipStream_t st);
+struct AlignParams {
+    const nasr_align::Utt *utt;
+    const nasr_align::Tile *tiles;   // the tiles of this launch, one workgroup each
+    const float *encproj;        // [M][640] packed rows of the sub-batch
+    const float *g;              // [sum (U + 1)][640]
+    const int32_t *tok;
+    const float *out_w, *out_b;  // the joint's output layer, packed as for the decode
+    float *lp_blank, *lp_token;  // [cells]
+};
+void launch_align_lattice(const AlignParams &p, int n_tiles, hipStream_t st);
+struct AlignRecParams {
+    const nasr_align::Utt *utt;
+    const float *lp_blank, *lp_token;
+    unsigned char *bp;           // [cells] 1 = the best path enters the cell by a token move
+    double *scores;              // [n][2] loglik, best
+    int32_t *frames; float *tok_lp;   // [sum U]
+};
+void launch_align_recursion(const AlignRecParams &p, int n, hipStream_t st);
 
 // ---- fused small-M kernels (M <= 16): prologue + weight-streaming GEMM + epilogue in one launch ----
 enum Pro { PRO_LN = 0, PRO_PLAIN = 1, PRO_ATTN = 2, PRO_DWCONV = 3 };

@@ -75,8 +75,23 @@ NASR_LP_HD Part merge(Part a, Part b) {
     return p;
 }
 NASR_LP_HD Part tile16(Part q0, Part q1, Part q2, Part q3) { return merge(merge(q0, q1), merge(q2, q3)); }
+#if defined(__HIPCC__)
+// tile16 on the device, for the joint kernels (kernels_decode.hip, kernels_align.hip): lane (q, r) of a wave holds entries v0 .. v0 + 3 of row r's
+// logits, the four lane groups meet over the xor-16 / xor-32 butterfly; every lane of the row ends up with the same bits (merge is symmetric)
+__device__ __forceinline__ Part tile_part_wave(float x0, float x1, float x2, float x3, int v0);
+#endif
 NASR_LP_HD Part wg64(Part w0, Part w1, Part w2, Part w3) { return merge(merge(merge(w0, w1), w2), w3); }
 NASR_LP_HD int lane_valid(int v0) { const int n = LP_VOCAB - v0; return n < 0 ? 0 : (n > 4 ? 4 : n); }     // of the lane's entries v0 .. v0 + 3
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ Part tile_part_wave(float x0, float x1, float x2, float x3, int v0) {
+    Part a = lane4(x0, x1, x2, x3, lane_valid(v0)), b;
+    b.m = __shfl_xor(a.m, 16); b.s = __shfl_xor(a.s, 16);
+    a = merge(a, b);
+    b.m = __shfl_xor(a.m, 32); b.s = __shfl_xor(a.s, 32);
+    return merge(a, b);
+}
+#endif
 
 // lp of the winning logit from a row's parts, merged in ascending part index.  logit - (m + log s) is evaluated as (logit - m) - log s: the
 // same value, but its rounding error does not grow with |m| (the winning logit IS m, so the first difference is exactly 0)

@@ -33,6 +33,15 @@ struct OfflineState {
     unsigned long long *alt_key = nullptr; int32_t *alt_id = nullptr; float *alt_lp = nullptr;      // engine option "token_alternatives"
     std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // ... of the last call, by utterance: [tokens][K] each
     std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
+    // forced alignment (nasr_engine_align*): the prediction-network rows g, the lattice of the sub-batch in flight (two values and one
+    // back-pointer byte per cell), its descriptors and its results
+    float *al_g = nullptr, *al_lpb = nullptr, *al_lpt = nullptr, *al_tlp = nullptr;
+    unsigned char *al_bp = nullptr;
+    nasr_align::Utt *al_utt = nullptr; nasr_align::Tile *al_tiles = nullptr;
+    int32_t *al_tok = nullptr, *al_frames = nullptr; double *al_scores = nullptr;
+    size_t al_g_cap = 0, al_lpb_cap = 0, al_lpt_cap = 0, al_tlp_cap = 0, al_bp_cap = 0, al_tiles_cap = 0, al_tok_cap = 0, al_frames_cap = 0;
+    bool lat_valid = false;                                        // the last call was an align call with debug on
+    std::vector<std::vector<float>> lat_b, lat_t;                  // ... its lattices by utterance: lp_blank, lp_token [T][U + 1]
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
     std::vector<std::vector<float>> tap_mel, tap_sub, tap_enc;
@@ -160,14 +169,19 @@ static int grow(nasr_engine *e, OfflineState *o, void **p, size_t &cap, size_t b
     return 0;
 }
 
-// one sub-batch: utterances [first, first + n) of the call; tokens / frames appended to toks[b] / frs[b]
-static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const *mel, const int32_t *n_mel, const int32_t *prompt_index,
-                             const std::vector<int> &Tall, int first, int n, std::vector<std::vector<int32_t>> &toks,
-                             std::vector<std::vector<int32_t>> &frs) {
+// a sub-batch whose encoder has been enqueued: utterances [first, first + n) of the call, utterance first + k in packed rows
+// [off[k], off[k] + T[k]) of o->encproj (and of the debug taps)
+struct OffBatch { int first = 0, n = 0, M = 0, maxT = 0; std::vector<int> off, T; };
+
+// the encoder of one sub-batch up to the joint's encoder projection: what transcription and alignment share
+static int run_offline_encoder(nasr_engine *e, OfflineState *o, const float *const *mel, const int32_t *n_mel, const int32_t *prompt_index,
+                               const std::vector<int> &Tall, int first, int n, OffBatch &ob) {
     hipStream_t st = e->st;
     const int act = e->bf16 ? 1 : 0, nL = e->hp.n_layers, ks = e->hp.kernel_size;
     // ---- plan of the sub-batch: packed rows, front-end images, attention work items -----------------------------
-    std::vector<int> off(n), T(n);
+    std::vector<int> &off = ob.off, &T = ob.T;
+    off.assign(n, 0); T.assign(n, 0);
+    ob.first = first; ob.n = n; ob.M = 0; ob.maxT = 0;
     std::vector<OffSubDesc> sd(n);
     int M = 0, mel_rows = 0, h2_rows = 0, h3_rows = 0, max_h2 = 0, maxT = 0;
     for (int k = 0; k < n; k++) {
@@ -179,6 +193,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         h3_rows += T[k];
         max_h2 = std::max(max_h2, nasr_plan::sub_h2(n_mel[b]));
     }
+    ob.M = M; ob.maxT = maxT;
     if (M == 0) return 0;                                    // every utterance too short for one mel frame: nothing runs
     if (ensure_rows(e, o, M)) return -1;
     const int qb = off_attn_qb(act);
@@ -272,6 +287,36 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
             return 0;
         }))
         return -1;
+    return 0;
+}
+
+// debug taps of a sub-batch, by utterance
+static int fetch_offline_taps(nasr_engine *e, OfflineState *o, const OffBatch &ob) {
+    const int nL = e->hp.n_layers, M = ob.M;
+    HIPCHK(hipStreamSynchronize(e->st));
+    for (int k = 0; k < ob.n; k++) {
+        const int b = ob.first + k;
+        const size_t rows = (size_t)ob.T[k] * D, o0 = (size_t)ob.off[k] * D;
+        o->tap_sub[b].resize(rows); o->tap_enc[b].resize(rows);
+        HIPCHK(hipMemcpy(o->tap_sub[b].data(), o->t_sub + o0, rows * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->tap_enc[b].data(), o->t_enc + o0, rows * 4, hipMemcpyDeviceToHost));
+        o->tap_lay[b].assign(nL, std::vector<float>(rows));
+        for (int l = 0; l < nL; l++)
+            HIPCHK(hipMemcpy(o->tap_lay[b][l].data(), o->t_lay + (size_t)l * M * D + o0, rows * 4, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// one sub-batch: utterances [first, first + n) of the call; tokens / frames appended to toks[b] / frs[b]
+static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const *mel, const int32_t *n_mel, const int32_t *prompt_index,
+                             const std::vector<int> &Tall, int first, int n, std::vector<std::vector<int32_t>> &toks,
+                             std::vector<std::vector<int32_t>> &frs) {
+    hipStream_t st = e->st;
+    OffBatch ob;
+    if (run_offline_encoder(e, o, mel, n_mel, prompt_index, Tall, first, n, ob)) return -1;
+    if (ob.M == 0) return 0;
+    const std::vector<int> &off = ob.off, &T = ob.T;
+    const int maxT = ob.maxT;
     // ---- greedy decode in windows of 256 frames per utterance (token ring: 4096 > 256 x 10 symbols) -----------------
     launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
     if (o->boost_state)                                          // every utterance starts with an empty history (NASR_FLAG_NO_BOOST: in the disabled state)
@@ -343,25 +388,24 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
             tok_read[k] = hctrl[k].n_tok;
         }
     }
-    if (e->debug) {
-        HIPCHK(hipStreamSynchronize(st));
-        for (int k = 0; k < n; k++) {
-            const int b = first + k;
-            const size_t rows = (size_t)T[k] * D, o0 = (size_t)off[k] * D;
-            o->tap_sub[b].resize(rows); o->tap_enc[b].resize(rows);
-            HIPCHK(hipMemcpy(o->tap_sub[b].data(), o->t_sub + o0, rows * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(o->tap_enc[b].data(), o->t_enc + o0, rows * 4, hipMemcpyDeviceToHost));
-            o->tap_lay[b].assign(nL, std::vector<float>(rows));
-            for (int l = 0; l < nL; l++)
-                HIPCHK(hipMemcpy(o->tap_lay[b][l].data(), o->t_lay + (size_t)l * M * D + o0, rows * 4, hipMemcpyDeviceToHost));
-        }
-    }
+    if (e->debug && fetch_offline_taps(e, o, ob)) return -1;
     return 0;
 }
 
 }  // namespace nasr_eng
 
 namespace nasr_eng {
+// debug: room for the taps of B utterances, the log-mel kept at once
+static int begin_taps(nasr_engine *e, OfflineState *o, int B, const float *const *mel, const int32_t *n_frames, bool mel_device) {
+    if (!e->debug) return 0;
+    o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {});
+    for (int b = 0; b < B; b++) {
+        o->tap_mel[b].resize((size_t)n_frames[b] * NMEL);
+        if (n_frames[b] > 0) HIPCHK(hipMemcpy(o->tap_mel[b].data(), mel[b], (size_t)n_frames[b] * NMEL * 4, mel_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    }
+    return 0;
+}
+
 // the call once the log-mel of every utterance exists: mel[b] in host memory (mel entry) or device memory (PCM entry)
 static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, bool mel_device, const int32_t *prompt_index,
                            int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, int32_t *const *frames_out) {
@@ -379,13 +423,7 @@ static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const
     if (ensure_offline_pos(e, o)) return -1;
     o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
     o->alt_ids.assign(e->opt_token_alt ? B : 0, {}); o->alt_lps.assign(e->opt_token_alt ? B : 0, {});
-    if (e->debug) {
-        o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {});
-        for (int b = 0; b < B; b++) {
-            o->tap_mel[b].resize((size_t)n_frames[b] * NMEL);
-            if (n_frames[b] > 0) HIPCHK(hipMemcpy(o->tap_mel[b].data(), mel[b], (size_t)n_frames[b] * NMEL * 4, mel_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        }
-    }
+    if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
     std::vector<std::vector<int32_t>> toks(B), frs(B);
     for (const auto &bt : batches)
         if (run_offline_batch(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, toks, frs)) return -1;
@@ -412,6 +450,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
     o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear();
+    o->lat_valid = false; o->lat_b.clear(); o->lat_t.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
     return 0;
 }
@@ -600,5 +639,217 @@ extern "C" int nasr_engine_offline_token_alternatives(nasr_engine *e, int u, int
     const int n = std::min<int>(have, std::max(cap, 0));
     memcpy(ids_out, o->alt_ids[u].data(), (size_t)n * K * 4);
     memcpy(logprobs_out, o->alt_lps[u].data(), (size_t)n * K * 4);
+    return n;
+}
+
+// ---- forced alignment and transcript scoring on the RNN-T lattice ---------------------------------------------------------------------
+namespace nasr_eng {
+struct AlignOut { std::vector<double> loglik, best; std::vector<std::vector<int32_t>> frames; std::vector<std::vector<float>> lps; };
+
+// the lattices of one sub-batch whose encoder projection is in o->encproj: teacher-forced prediction network, joint over every cell,
+// both recursions and the backtrace, all on the device
+static int align_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, const int32_t *const *tokens, const int32_t *n_tokens, AlignOut &out) {
+    hipStream_t st = e->st;
+    const double ninf = nasr_align::neg_inf_d();
+    std::vector<int> live;                                   // utterances with at least one encoder frame: decoder slot k = live[k]
+    std::vector<nasr_align::Utt> ud;
+    std::vector<int32_t> tok;
+    long long cells = 0;
+    int g_rows = 0, max_u = 0;
+    for (int k = 0; k < ob.n; k++) {
+        const int b = ob.first + k, U = n_tokens[b];
+        if (ob.T[k] == 0) {                                  // no frame: only the empty transcript has a path
+            out.loglik[b] = out.best[b] = U == 0 ? 0.0 : ninf;
+            out.frames[b].assign(U, -1);
+            out.lps[b].assign(U, nasr_lp::neg_inf());
+            continue;
+        }
+        nasr_align::Utt u;
+        u.enc_row = ob.off[k]; u.g_row = g_rows; u.T = ob.T[k]; u.U = U; u.cell0 = cells; u.tok0 = (int)tok.size(); u.pad = 0;
+        ud.push_back(u); live.push_back(k);
+        tok.insert(tok.end(), tokens[b], tokens[b] + U);
+        cells += nasr_align::n_cells(u.T, U);
+        g_rows += U + 1;
+        max_u = std::max(max_u, U);
+    }
+    const int n = (int)live.size();
+    if (n == 0) return 0;
+    if (!o->al_utt) {
+        if (off_alloc(o, (void **)&o->al_utt, nasr_plan::OFFLINE_MAX_UTTS * sizeof(nasr_align::Utt)) ||
+            off_alloc(o, (void **)&o->al_scores, nasr_plan::OFFLINE_MAX_UTTS * 2 * sizeof(double))) return -1;
+    }
+    std::vector<nasr_align::Tile> tiles;
+    std::vector<int> lfirst;
+    nasr_align::plan_launches(ud.data(), n, e->opt_align_cells, tiles, lfirst);
+    const size_t ntok = std::max<size_t>(tok.size(), 1);
+    if (grow(e, o, (void **)&o->al_g, o->al_g_cap, (size_t)g_rows * JNT * 4) || grow(e, o, (void **)&o->al_lpb, o->al_lpb_cap, (size_t)cells * 4) ||
+        grow(e, o, (void **)&o->al_lpt, o->al_lpt_cap, (size_t)cells * 4) || grow(e, o, (void **)&o->al_bp, o->al_bp_cap, (size_t)cells) ||
+        grow(e, o, (void **)&o->al_tiles, o->al_tiles_cap, tiles.size() * sizeof(nasr_align::Tile)) || grow(e, o, (void **)&o->al_tok, o->al_tok_cap, ntok * 4) ||
+        grow(e, o, (void **)&o->al_frames, o->al_frames_cap, ntok * 4) || grow(e, o, (void **)&o->al_tlp, o->al_tlp_cap, ntok * 4)) return -1;
+    std::vector<RowDesc> rd(n);
+    for (int k = 0; k < n; k++) { memset(&rd[k], 0, sizeof(RowDesc)); rd[k].slot = k; rd[k].prompt = -1; }
+    // (the host vectors live until the stream is synchronised below)
+    HIPCHK(hipMemcpyAsync(o->al_utt, ud.data(), (size_t)n * sizeof(nasr_align::Utt), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->al_tiles, tiles.data(), tiles.size() * sizeof(nasr_align::Tile), hipMemcpyHostToDevice, st));
+    if (!tok.empty()) HIPCHK(hipMemcpyAsync(o->al_tok, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->drows, rd.data(), (size_t)n * sizeof(RowDesc), hipMemcpyHostToDevice, st));
+    // ---- g[u] of every utterance: the decode's own LSTM / joint.pred launches over the utterances that still have a position u --------
+    launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
+    DecParams dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.rows = o->drows; dp.B = n; dp.T = 1; dp.ctrl = o->ctrl; dp.h = o->h; dp.c = o->c;
+    bind_dec_weights(e, dp);
+    dp.predg = o->predg; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2; dp.dlist = o->dlist;
+    AlignPredParams pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.utt = o->al_utt; pp.n = n; pp.tok = o->al_tok; pp.ctrl = o->ctrl; pp.dlist = o->dlist; pp.n_dirty = dp.n_dirty; pp.predg = o->predg; pp.g = o->al_g;
+    {
+        ProfScope ps(e, "k_align_pred", 0, 0);
+        for (int u = 0; u <= max_u + 1; u++) {
+            pp.u = u;
+            launch_align_pred_step(pp, st);
+            if (u <= max_u) launch_decode_candidates(dp, st);
+        }
+    }
+    // ---- the joint over every cell, "align_cells" cells per launch ---------------------------------------------------------------------
+    AlignParams ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.utt = o->al_utt; ap.encproj = o->encproj; ap.g = o->al_g; ap.tok = o->al_tok; ap.out_w = dp.out_w; ap.out_b = dp.out_b;
+    ap.lp_blank = o->al_lpb; ap.lp_token = o->al_lpt;
+    for (size_t i = 0; i + 1 < lfirst.size(); i++) {
+        const int cnt = lfirst[i + 1] - lfirst[i];
+        double c = 0;
+        for (int j = lfirst[i]; j < lfirst[i + 1]; j++) c += nasr_align::tile_cells(ud[tiles[j].utt].T, ud[tiles[j].utt].U, tiles[j].t0, tiles[j].u0);
+        ProfScope ps(e, "k_align_lattice", (double)cnt * 1040 * JNT * 4, c * 2.0 * JNT * VOCAB);
+        ap.tiles = o->al_tiles + lfirst[i];
+        launch_align_lattice(ap, cnt, st);
+    }
+    // ---- forward and Viterbi recursions, backtrace ------------------------------------------------------------------------------------
+    AlignRecParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.utt = o->al_utt; rp.lp_blank = o->al_lpb; rp.lp_token = o->al_lpt; rp.bp = o->al_bp; rp.scores = o->al_scores; rp.frames = o->al_frames; rp.tok_lp = o->al_tlp;
+    {
+        ProfScope ps(e, "k_align_recursion", (double)cells * 9, 0);
+        launch_align_recursion(rp, n, st);
+    }
+    std::vector<double> sc((size_t)n * 2);
+    std::vector<int32_t> fr(tok.size());
+    std::vector<float> lp(tok.size());
+    HIPCHK(hipMemcpyAsync(sc.data(), o->al_scores, sc.size() * 8, hipMemcpyDeviceToHost, st));
+    if (!tok.empty()) {
+        HIPCHK(hipMemcpyAsync(fr.data(), o->al_frames, fr.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(lp.data(), o->al_tlp, lp.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < n; k++) {
+        const int b = ob.first + live[k];
+        out.loglik[b] = sc[(size_t)2 * k]; out.best[b] = sc[(size_t)2 * k + 1];
+        out.frames[b].assign(fr.begin() + ud[k].tok0, fr.begin() + ud[k].tok0 + ud[k].U);
+        out.lps[b].assign(lp.begin() + ud[k].tok0, lp.begin() + ud[k].tok0 + ud[k].U);
+        if (e->debug) {
+            const size_t nc = (size_t)nasr_align::n_cells(ud[k].T, ud[k].U);
+            o->lat_b[b].resize(nc); o->lat_t[b].resize(nc);
+            HIPCHK(hipMemcpy(o->lat_b[b].data(), o->al_lpb + ud[k].cell0, nc * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(o->lat_t[b].data(), o->al_lpt + ud[k].cell0, nc * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+static int align_core(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, bool mel_device, const int32_t *prompt_index,
+                      const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out, int32_t *const *frames_out,
+                      float *const *token_logprobs_out) {
+    OfflineState *o = e->off;
+    for (int b = 0; b < B; b++) {
+        const int U = n_tokens[b];
+        if (U < 0 || U > NASR_ALIGN_MAX_TOKENS)
+            return fail("utterance %d: a transcript of %d tokens, outside 0 .. NASR_ALIGN_MAX_TOKENS = %d", b, U, NASR_ALIGN_MAX_TOKENS);
+        if (U > 0 && (!tokens || !tokens[b])) return fail("utterance %d: null transcript", b);
+        for (int i = 0; i < U; i++)
+            if (tokens[b][i] < 0 || tokens[b][i] >= BLANK)
+                return fail("utterance %d: token %d of its transcript is %d; only ids 0 .. %d can be aligned (%d is blank)", b, i, tokens[b][i], BLANK - 1, BLANK);
+    }
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> batches;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_frames, B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, batches, &bad)) {
+        if (bad >= 0 && n_frames[bad] >= 0)
+            return fail("utterance %d: %d mel frames give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len)",
+                        bad, n_frames[bad], nasr_plan::enc_frames(n_frames[bad]), NASR_OFFLINE_MAX_FRAMES);
+        return fail("offline plan rejected the call");
+    }
+    if (ensure_offline_pos(e, o)) return -1;
+    if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
+    if (e->debug) { o->lat_b.assign(B, {}); o->lat_t.assign(B, {}); }
+    AlignOut out;
+    out.loglik.assign(B, 0.0); out.best.assign(B, 0.0); out.frames.assign(B, {}); out.lps.assign(B, {});
+    for (const auto &bt : batches) {
+        OffBatch ob;
+        if (run_offline_encoder(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, ob)) return -1;
+        if (align_batch(e, o, ob, tokens, n_tokens, out)) return -1;
+        if (e->debug && ob.M > 0 && fetch_offline_taps(e, o, ob)) return -1;
+    }
+    o->lat_valid = e->debug;
+    for (int b = 0; b < B; b++) {
+        if (loglik_out) loglik_out[b] = out.loglik[b];
+        if (best_out) best_out[b] = out.best[b];
+        if (frames_out && frames_out[b]) memcpy(frames_out[b], out.frames[b].data(), out.frames[b].size() * 4);
+        if (token_logprobs_out && token_logprobs_out[b]) memcpy(token_logprobs_out[b], out.lps[b].data(), out.lps[b].size() * 4);
+    }
+    return 0;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_align_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, const int32_t *prompt_index,
+                                     const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                                     int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    if (B == 0) return 0;
+    if (!mel || !n_frames) return fail("null mel / n_frames");
+    for (int b = 0; b < B; b++)
+        if (n_frames[b] < 0 || (n_frames[b] > 0 && !mel[b])) return fail("bad mel input for utterance %d", b);
+    if (begin_call(e, B, prompt_index, n_tokens, flags, "nasr_engine_align_mel")) return -1;
+    return align_core(e, B, mel, n_frames, false, prompt_index, tokens, n_tokens, loglik_out, best_out, frames_out, token_logprobs_out);
+}
+
+extern "C" int nasr_engine_align(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples, const int32_t *prompt_index,
+                                 const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                                 int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    if (B == 0) return 0;
+    if (!pcm || !n_samples) return fail("null pcm / n_samples");
+    std::vector<int32_t> n_mel(B);
+    for (int b = 0; b < B; b++) {
+        if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail("bad pcm input for utterance %d", b);
+        n_mel[b] = nasr_plan::mel_frames(n_samples[b]);
+    }
+    if (begin_call(e, B, prompt_index, n_tokens, flags, "nasr_engine_align")) return -1;
+    // the limit is checked before any work, as in nasr_engine_transcribe
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> bt;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_mel.data(), B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, bt, &bad))
+        return fail("utterance %d: %d samples give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len, %.1f s)",
+                    bad, bad >= 0 ? n_samples[bad] : -1, bad >= 0 ? nasr_plan::enc_frames(n_mel[bad]) : -1, NASR_OFFLINE_MAX_FRAMES, nasr_plan::max_samples() / 16000.0);
+    std::vector<const float *> mel;
+    if (offline_mel(e, e->off, B, pcm, n_samples, (flags & NASR_FLAG_PCM_DEVICE) != 0, n_mel, mel)) return -1;
+    return align_core(e, B, mel.data(), n_mel.data(), true, prompt_index, tokens, n_tokens, loglik_out, best_out, frames_out, token_logprobs_out);
+}
+
+extern "C" int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_blank_out, float *lp_token_out, int64_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    OfflineState *o = e->off;
+    if (!o || !o->lat_valid || u < 0 || u >= (int)o->lat_b.size())
+        return fail("no lattice of utterance %d (the last offline call must be an align call made with nasr_engine_set_debug(e, 1))", u);
+    const int64_t have = (int64_t)o->lat_b[u].size();
+    if (!lp_blank_out && !lp_token_out) return have;         // size query
+    const int64_t n = std::min<int64_t>(have, std::max<int64_t>(cap, 0));
+    if (lp_blank_out) memcpy(lp_blank_out, o->lat_b[u].data(), (size_t)n * 4);
+    if (lp_token_out) memcpy(lp_token_out, o->lat_t[u].data(), (size_t)n * 4);
     return n;
 }

@@ -264,6 +264,24 @@ static bool lookup_lang(nemo_context *ctx, const char *lang, const char *who, in
     return true;
 }
 
+nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_samples, const std::vector<int32_t> &tokens) {
+    nemo_alignment out;
+    if (!ctx || !ctx->engine || n_samples < 0 || (n_samples > 0 && !audio)) return out;
+    out.frames.assign(tokens.size(), -1);
+    out.logprobs.assign(tokens.size(), NAN);
+    const int32_t n_tok = (int32_t)tokens.size(), prompt = ctx->prompt_index;
+    const int32_t *tp = tokens.data();
+    int32_t *fp = out.frames.data();
+    float *lp = out.logprobs.data();
+    if (nasr_engine_align(ctx->engine, 1, &audio, &n_samples, ctx->hparams.num_prompts > 0 ? &prompt : nullptr, &tp, &n_tok, &out.loglik, &out.best,
+                          &fp, &lp, 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return out;
+    }
+    out.ok = true;
+    return out;
+}
+
 bool nemo_set_language(nemo_context *ctx, const char *lang) {
     if (!ctx || !lang) return false;
     return lookup_lang(ctx, lang, __func__, ctx->prompt_index);

@@ -83,6 +83,18 @@ bool nemo_set_boost_phrases(nemo_context *ctx, const std::vector<std::string> &p
 bool nemo_load_boost_file(nemo_context *ctx, const char *path, float default_bonus = 4.0f);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
+// MI355X extension: forced alignment / transcript scoring of one whole utterance (nasr_engine_align): tokens = ids 0 .. 1023 of a KNOWN
+// transcript (at most 1024).  loglik = ln P(tokens | audio), best = the best path's score, frames[i] = the encoder frame (80 ms each) at which
+// token i is emitted on that path, logprobs[i] = ln P of token i there.  The context's language prompt applies.  ok = false on failure
+// (the reason on stderr)
+struct nemo_alignment {
+    bool ok = false;
+    double loglik = 0.0, best = 0.0;
+    std::vector<int32_t> frames;
+    std::vector<float> logprobs;
+};
+nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_samples, const std::vector<int32_t> &tokens);
+
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
 nemo_stream_context *nemo_stream_init(nemo_context *ctx, const nemo_cache_config *config = nullptr);
 bool nemo_stream_set_language(nemo_stream_context *sctx, const char *lang);
