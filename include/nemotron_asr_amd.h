@@ -180,6 +180,37 @@ int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int B,
                      int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens,
                      uint32_t flags);
 
+/* ---- audio input conversion on the device (the reference's answer to everything but s16le 16 kHz mono is "pipe it through ffmpeg
+ * -ar 16000 -ac 1 -f s16le"): a stream can be told what its audio looks like, and the engine turns it into the 16 kHz s16 samples
+ * nasr_engine_step takes, in one launch for all streams of a call, with streaming state: the samples do not depend on how the audio is
+ * cut into pushes.  Rates 8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000 Hz; s16, f32 (a non-finite value reads as 0), G.711
+ * mu-law and A-law; 1 .. 8 interleaved channels, of which `channel` >= 0 picks one and -1 takes the mean.  The resampler is a
+ * Kaiser-windowed sinc (32 zero crossings per side, beta 9, roll-off 0.94: +-0.1 dB up to 0.87 of the lower Nyquist, -80 dB from 1.03 of it)
+ * evaluated in f32 in a fixed order; csrc/nasr_resample.h states the arithmetic and is the host restatement the kernel is tested against
+ * bit for bit.  Latency 32 periods of the lower rate: 2 ms at 48 kHz, 4 ms at 8 kHz.  16 kHz is converted without a filter. */
+enum { NASR_AUDIO_S16 = 0, NASR_AUDIO_F32 = 1, NASR_AUDIO_MULAW = 2, NASR_AUDIO_ALAW = 3 };
+typedef struct nasr_audio_format { int32_t sample_rate, encoding, channels, channel; } nasr_audio_format;  /* default {16000, S16, 1, 0} */
+/* succeeds only on a stream that has taken no audio since create or reset; fails -- the previous format stays in force -- otherwise and
+ * for an unsupported rate, encoding, channel count or channel index.  The format survives both reset modes. */
+int nasr_stream_set_audio_format(nasr_stream *s, const nasr_audio_format *f);
+/* nasr_engine_step for audio in each stream's own format: audio[b] holds n_frames[b] input frames (sample times, all channels), host
+ * memory, or device memory with NASR_FLAG_PCM_DEVICE (then naturally aligned: 2 bytes for s16, 4 for f32; checked).  The converter writes the 16 kHz samples the frames complete (nasr_audio_out_ready)
+ * and the call goes on exactly as nasr_engine_step does with them; a stream with the default format is passed through and gives
+ * nasr_engine_step's bits.  A call that completes no sample for any stream is a nasr_engine_step of zero samples.  samples_in counts 16 kHz samples.
+ * nasr_engine_step itself refuses a stream whose format is not the default.  nasr_engine_finalize first hands the front end the
+ * converter's tail (nasr_audio_out_total - nasr_audio_out_ready samples, zeros as future input). */
+int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *streams, int B, const void *const *audio,
+                           const int32_t *n_frames, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                           int32_t *n_tokens, uint32_t flags);
+/* one-shot, stateless: the same kernel over a whole buffer from a zero history, flushed: nasr_audio_out_total(f, n_frames) samples into
+ * out (host memory; with NASR_FLAG_PCM_DEVICE audio AND out are device memory, naturally aligned).  Completes steps in flight, touches no stream.  Returns
+ * the number of samples written or < 0 (also when cap is too small).  Feed the result to nasr_engine_transcribe / nasr_engine_align. */
+int64_t nasr_engine_convert_audio(nasr_engine *e, const nasr_audio_format *f, const void *audio, int64_t n_frames,
+                                  int16_t *out, int64_t cap, uint32_t flags);
+/* host only, no GPU: 16 kHz samples available after n_frames_in input frames of a stream / in all once it has ended; < 0 for a bad format */
+int64_t nasr_audio_out_ready(const nasr_audio_format *f, int64_t n_frames_in);
+int64_t nasr_audio_out_total(const nasr_audio_format *f, int64_t n_frames_in);
+
 /* debug/parity tap: same as nasr_engine_step but takes log-mel frames [n_frames][128] f32
  * (host memory) and skips stage a-1, i.e. enters at the mel_buffer append of :1162. */
 int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams, int B,
@@ -207,6 +238,8 @@ enum {
     NASR_TAP_V_CACHE     = 5,
     NASR_TAP_CONV_CACHE  = 6, /*                                                 [ks-1][1024]  */
     NASR_TAP_DEC_STATE   = 7, /* h[2][640], c[2][640], then prev_token as float                */
+    NASR_TAP_PCM16       = 8, /* the 16 kHz samples the last step / step_audio / finalize call handed to the front end
+                                 for this stream, as floats holding the s16 values     [n]            */
 };
 /* engine options: "fused" (1: small-M fused layer kernels, default) / "graph" (1: hipGraph replay of the
  * steady-state step, default) / "multichunk" (1, default) are pure performance switches; results are unchanged.
@@ -251,6 +284,8 @@ enum {
  * GEMMs; what each costs a pipelined step: profiles/r5_ablation.md), "decode_lane" (0: the decode graphs run behind the last encoder
  * piece instead of on a stream of their own; read when the lanes are picked, so it is REJECTED after the first pipelined step or
  * nasr_engine_lend_stream).
+ * "audio_lds_table" (1 default / 0): nasr_engine_step_audio's kernel reads the coefficients of the 8 / 24 / 32 / 48 kHz tables from a copy in LDS
+ * (0: from global memory like the larger tables; same bits; A/B switch, profiles/audio_input.md).
  * "token_logprobs" (0 default / 1): a capability, not a kernel A/B switch -- with 1 the device decode also keeps, for every emitted token,
  * the natural-log softmax probability of that token over the 1025 joint outputs (blank included) at the frame and decoder state where it
  * was emitted (nasr_stream_get_token_logprobs, nasr_engine_offline_token_logprobs).  Tokens, frames, iteration counts and decoder state

@@ -21,6 +21,11 @@ DIAR_VAD_BF16 = 0x100       # OR into Diar's dtype: MarbleNet on the bf16 MFMA
 DIAR_VAD_F16 = 0x200        # ... on the f16 MFMA with IEEE-half activation planes
 RESET_FRESH, RESET_REFERENCE = 0, 1
 TAP_MEL, TAP_SUBSAMPLED, TAP_LAYER_OUT, TAP_ENCODER_OUT, TAP_K_CACHE, TAP_V_CACHE, TAP_CONV_CACHE, TAP_DEC_STATE = range(8)
+TAP_PCM16 = 8               # the 16 kHz samples the last step / step_audio / finalize call handed to the front end (debug)
+AUDIO_S16, AUDIO_F32, AUDIO_MULAW, AUDIO_ALAW = range(4)
+AUDIO_ENCODINGS = {"s16": AUDIO_S16, "f32": AUDIO_F32, "mulaw": AUDIO_MULAW, "alaw": AUDIO_ALAW}
+AUDIO_DTYPES = {AUDIO_S16: np.int16, AUDIO_F32: np.float32, AUDIO_MULAW: np.uint8, AUDIO_ALAW: np.uint8}
+AUDIO_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)
 
 EXPORTS = [
     "nasr_last_error", "nasr_abi_version", "nasr_tensor_to_f32", "nasr_engine_create", "nasr_engine_create_ex", "nasr_engine_destroy",
@@ -35,6 +40,7 @@ EXPORTS = [
     "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
     "nasr_stream_get_token_alternatives", "nasr_engine_offline_token_alternatives",
     "nasr_engine_align_mel", "nasr_engine_align", "nasr_engine_align_lattice",
+    "nasr_stream_set_audio_format", "nasr_engine_step_audio", "nasr_engine_convert_audio", "nasr_audio_out_ready", "nasr_audio_out_total",
 ]
 ALIGN_MAX_TOKENS = 1024
 FLAG_NO_BOOST = 1 << 3
@@ -57,6 +63,16 @@ class StreamStats(C.Structure):
     _fields_ = [("samples_in", C.c_int64), ("chunks", C.c_int32), ("decode_iterations", C.c_int32),
                 ("tokens", C.c_int32), ("cache_valid_len", C.c_int32), ("mel_frames_buffered", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class AudioFormat(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "encoding", "channels", "channel")]
+
+
+def audio_format(rate=16000, encoding="s16", channels=1, channel=0) -> AudioFormat:
+    """channel: an index, or -1 / "mix" for the mean of the channels"""
+    enc = AUDIO_ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+    return AudioFormat(int(rate), enc, int(channels), -1 if channel == "mix" else int(channel))
 
 
 class KernelStat(C.Structure):
@@ -131,8 +147,25 @@ def lib():
         L.nasr_engine_align.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
         L.nasr_engine_align_lattice.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
         L.nasr_engine_align_lattice.restype = C.c_int64
+        L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
+        L.nasr_engine_step_audio.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
+        L.nasr_engine_convert_audio.argtypes = [vp, C.POINTER(AudioFormat), vp, C.c_int64, vp, C.c_int64, C.c_uint32]
+        L.nasr_engine_convert_audio.restype = C.c_int64
+        for n in ("ready", "total"):
+            getattr(L, f"nasr_audio_out_{n}").argtypes = [C.POINTER(AudioFormat), C.c_int64]
+            getattr(L, f"nasr_audio_out_{n}").restype = C.c_int64
         _lib = L
     return _lib
+
+
+def audio_out_ready(fmt: AudioFormat, n_frames_in: int) -> int:
+    """16 kHz samples a stream of this format has completed after n_frames_in input frames (host arithmetic, no GPU)"""
+    return _chk(lib().nasr_audio_out_ready(C.byref(fmt), int(n_frames_in)))
+
+
+def audio_out_total(fmt: AudioFormat, n_frames_in: int) -> int:
+    """... and in all once the stream has ended (what finalize flushes is the difference)"""
+    return _chk(lib().nasr_audio_out_total(C.byref(fmt), int(n_frames_in)))
 
 
 def check_exports():
@@ -174,6 +207,14 @@ class Stream:
 
     def set_prompt(self, prompt_index: int):
         _chk(lib().nasr_stream_set_prompt(self.h, prompt_index))
+
+    fmt = None                      # AudioFormat once set_audio_format has succeeded (None: s16 16 kHz mono)
+
+    def set_audio_format(self, rate, encoding="s16", channels=1, channel=0):
+        """what this stream's audio looks like (before its first audio, or right after a reset); push it with Engine.step_audio"""
+        f = audio_format(rate, encoding, channels, channel)
+        _chk(lib().nasr_stream_set_audio_format(self.h, C.byref(f)))
+        self.fmt = f
 
     def debug_fill_kv(self, value: float):
         """test hook: every K/V ring row of this stream's slot := +-value (stale rows must never reach a result)"""
@@ -437,6 +478,39 @@ class Engine:
         bufs, tptrs, caps, n = self._tok_bufs(B, cap)
         _chk(lib().nasr_engine_step(self.h, self._handles(streams), B, ptrs, ns, tptrs, caps, n, flags))
         return self._gather(streams, bufs, tptrs, caps, n, cap) if not flags & FLAG_NO_SYNC else [[] for _ in range(B)]
+
+    def step_audio(self, streams, arrays, flags=0, tok_cap=None):
+        """arrays: per stream the interleaved input frames in the stream's own format (int16 / float32 / uint8 ndarrays, [frames] or
+        [frames][channels]), or (device_ptr, n_frames) with FLAG_PCM_DEVICE."""
+        B = len(streams)
+        if flags & FLAG_PCM_DEVICE:
+            ptrs = (C.c_void_p * B)(*[p for p, _ in arrays])
+            frames = [int(n) for _, n in arrays]
+        else:
+            arrs, frames = [], []
+            for s, a in zip(streams, arrays):
+                f = s.fmt or audio_format()
+                a = np.ascontiguousarray(a, AUDIO_DTYPES[f.encoding]).reshape(-1)
+                if a.size % f.channels:
+                    raise ValueError(f"{a.size} samples are not whole frames of {f.channels} channels")
+                arrs.append(a)
+                frames.append(a.size // f.channels)
+            ptrs = (C.c_void_p * B)(*[a.ctypes.data for a in arrs])
+        ns = (C.c_int32 * B)(*frames)
+        cap = tok_cap or (max(frames) // 640 + 16) * 10           # 8 kHz input: 640 frames per 80 ms
+        bufs, tptrs, caps, n = self._tok_bufs(B, cap)
+        _chk(lib().nasr_engine_step_audio(self.h, self._handles(streams), B, ptrs, ns, tptrs, caps, n, flags))
+        return self._gather(streams, bufs, tptrs, caps, n, cap) if not flags & FLAG_NO_SYNC else [[] for _ in range(B)]
+
+    def convert_audio(self, fmt: AudioFormat, array) -> np.ndarray:
+        """one-shot, stateless: a whole buffer in `fmt` -> its 16 kHz s16 samples (audio_out_total of them)"""
+        a = np.ascontiguousarray(array, AUDIO_DTYPES[fmt.encoding]).reshape(-1)
+        if a.size % fmt.channels:
+            raise ValueError(f"{a.size} samples are not whole frames of {fmt.channels} channels")
+        frames = a.size // fmt.channels
+        out = np.zeros(max(audio_out_total(fmt, frames), 1), np.int16)
+        n = _chk(lib().nasr_engine_convert_audio(self.h, C.byref(fmt), a.ctypes.data, frames, out.ctypes.data, out.size, 0))
+        return out[:n].copy()
 
     def step_mel(self, streams, mels, flags=0):
         B = len(streams)

@@ -151,6 +151,7 @@ __global__ __launch_bounds__(256) void k_stream_reset(StreamResetParams p) {
         ((float4 *)(p.dec_c + slot * 4 * HID))[i] = z4;
     }
     for (int i = threadIdx.x; i < PRE_CACHE * NMEL / 4; i += 256) ((float4 *)(p.mel_ring + slot * MEL_RING * NMEL))[i] = z4;   // mel_start = 0
+    if (p.aud_hist) for (int i = threadIdx.x; i < 2 * nasr_rs::HIST_MAX; i += 256) p.aud_hist[slot * 2 * nasr_rs::HIST_MAX + i] = 0.0f;   // audio converter: both parities, both modes
     if (!p.keep_reference_state) {
         for (int i = threadIdx.x; i < NFFT / 2 / 4; i += 256) ((float4 *)(p.abuf + slot * 2 * ABUF_CAP))[i] = z4;              // parity 0, src/preprocessor.cpp:220-221
         if (threadIdx.x == 0) p.last_sample[slot] = 0.0f;

@@ -121,6 +121,7 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
     else if (!strcmp(key, "resid_epilogue")) { if (value < 0 || value > 2) return fail("resid_epilogue must be 0, 1 or 2"); e->opt_resid_epilogue = value; }      // like "fused": set before the first step
     else if (!strcmp(key, "offline_rows")) { if (value < 1) return fail("offline_rows must be >= 1"); e->opt_offline_rows = value; }
     else if (!strcmp(key, "align_cells")) { if (value < nasr_align::MIN_CELLS) return fail("align_cells must be >= %d", nasr_align::MIN_CELLS); e->opt_align_cells = value; }
+    else if (!strcmp(key, "audio_lds_table")) e->opt_audio_lds_table = value != 0;      // A/B switch of k_audio_convert (same bits)
     else if (!strcmp(key, "ablate")) e->opt_ablate = value;          // measurement only (see the header); before the first step
     else if (!strcmp(key, "f32_mfma")) e->opt_f32_mfma = value != 0;      // 0: f32 GEMMs above four rows on the FMA tile kernel (round 3's path); like "fused", set before the first step
     else if (!strcmp(key, "pipeline")) {
@@ -347,15 +348,9 @@ int push_piece(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t
     return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens);
 }
 
-}  // namespace nasr_eng
-extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm,
-                                const int32_t *n_samples, int32_t *const *tokens_out, const int32_t *tokens_cap,
-                                int32_t *n_tokens, uint32_t flags) {
-    ApiGuard api_guard;
-    if (validate_batch(e, streams, B)) return -1;
-    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
-    if (!pcm || !n_samples) return fail("null pcm / n_samples");
-    HIPCHK(hipSetDevice(e->device));
+// s16 16 kHz mono in: host buffers are gathered into the device staging area (device buffers are read in place), then the step
+static int step_s16(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm, const int32_t *n_samples,
+                    int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, uint32_t flags) {
     std::vector<const int16_t *> base(B, nullptr);
     size_t total = 0;
     for (int b = 0; b < B; b++) {
@@ -398,7 +393,35 @@ extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int
     } else {
         for (int b = 0; b < B; b++) base[b] = pcm[b];
     }
+    return step_tail(e, streams, B, base.data(), n_samples, tokens_out, tokens_cap, n_tokens, flags);
+}
+
+// debug: keeps what this call hands the front end (NASR_TAP_PCM16); the tap of every stream that is not in the call is forgotten
+static int record_pcm_tap(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *base, const int32_t *n_samples) {
+    size_t total = 0;
+    for (int b = 0; b < B; b++) total += (size_t)n_samples[b];
+    if (total > e->tap_pcm_cap) {
+        HIPCHK(hipStreamSynchronize(e->st));
+        if (e->tap_pcm) hipFree(e->tap_pcm);
+        e->tap_pcm = nullptr;
+        e->tap_pcm_cap = total + 65536;
+        HIPCHK(hipMalloc((void **)&e->tap_pcm, e->tap_pcm_cap * 2));
+    }
+    std::fill(e->tap_pcm_n.begin(), e->tap_pcm_n.end(), 0);
+    size_t o = 0;
+    for (int b = 0; b < B; b++) {
+        e->tap_pcm_off[streams[b]->slot] = (int64_t)o;
+        e->tap_pcm_n[streams[b]->slot] = n_samples[b];
+        if (n_samples[b] > 0) HIPCHK(hipMemcpyAsync(e->tap_pcm + o, base[b], (size_t)n_samples[b] * 2, hipMemcpyDeviceToDevice, e->st));
+        o += (size_t)n_samples[b];
+    }
+    return 0;
+}
+
+int step_tail(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *base, const int32_t *n_samples,
+              int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, uint32_t flags) {
     if (e->debug) for (int b = 0; b < B; b++) { e->tap_mel_frames[streams[b]->slot] = 0; e->tap_mel_row[streams[b]->slot] = b; }
+    if (e->debug && record_pcm_tap(e, streams, B, base, n_samples)) return -1;
     for (int b = 0; b < B; b++) streams[b]->samples_in += n_samples[b];
     // A push longer than one launch sequence can take (MAXNEW encoder frames per stream, w_rows rows in all) is
     // cut into pieces of whole chunks; each piece is a multi-chunk step when the streams are aligned.
@@ -408,7 +431,7 @@ extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int
     const int64_t piece = (int64_t)gcap * 8 * T * HOP;
     bool multi = false;
     for (int b = 0; b < B; b++) multi = multi || n_samples[b] > piece;
-    if (!multi) return push_piece(e, streams, B, base.data(), n_samples, tokens_out, tokens_cap, n_tokens, flags);
+    if (!multi) return push_piece(e, streams, B, base, n_samples, tokens_out, tokens_cap, n_tokens, flags);
     std::vector<int64_t> off(B, 0);
     std::vector<int32_t> acc(B, 0), np(B), cap_left(B), got(B);
     std::vector<const int16_t *> ptr(B);
@@ -431,6 +454,263 @@ extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int
     }
     if (n_tokens) for (int b = 0; b < B; b++) n_tokens[b] = acc[b];
     return 0;
+}
+
+// ---- audio input conversion (nasr_resample.h, kernels_audio.hip) --------------------------------------------------------------------
+// the coefficient table of a rate: built in double on the host and uploaded the first time a stream or a one-shot conversion names the rate
+int ensure_audio_table(nasr_engine *e, const nasr_rs::Plan &p, const float **out) {
+    auto it = e->aud_tables.find(p.fin);
+    if (it == e->aud_tables.end()) {
+        for (long long n = 0; n < (long long)p.M * nasr_rs::BLOCK; n += nasr_rs::BLOCK)        // the spans repeat with period M blocks
+            if (nasr_rs::block_span(p, n) > nasr_rs::SPAN_CAP) return fail("internal: %d Hz needs %lld staged frames per workgroup", p.fin, nasr_rs::block_span(p, n));
+        if (p.hist > nasr_rs::HIST_MAX) return fail("internal: %d Hz needs a history of %d frames", p.fin, p.hist);
+        std::vector<float> c;
+        nasr_rs::build_table(p, c);
+        float *d = nullptr;
+        if (dalloc(e, &d, c.size())) return -1;
+        HIPCHK(hipMemcpy(d, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+        it = e->aud_tables.emplace(p.fin, d).first;
+    }
+    *out = it->second;
+    return 0;
+}
+
+static void fill_audio_desc(const nasr_engine *e, AudioDesc &d, const nasr_rs::Plan &p, const nasr_audio_format &f, const float *table) {
+    memset(&d, 0, sizeof(d));
+    d.lds_table = e->opt_audio_lds_table && 2 * p.half + 1 <= LDS_TABLE_MAX ? 1 : 0;
+    d.table = table; d.enc = f.encoding; d.channels = f.channels; d.channel = f.channel; d.L = p.L; d.M = p.M; d.half = p.half;
+}
+static double audio_flops(const nasr_rs::Plan &p, double n_out) { return n_out * 2.0 * (double)(2 * p.half / p.L + 1); }
+
+// descs[b].n_out samples of every stream b into e->pcm_stage, packed in order: ONE launch on the engine's stream.  pcm_stage is written here
+// where nasr_engine_step's H2D copy writes it, and under the same ordering: every reader of pcm_stage -- k_preemph, the first kernel of a
+// step -- is enqueued on e->st (eagerly, as the head of the synchronous step graph, in piece 0 of a pipelined step whose lane 0 IS e->st, in
+// chain 0 of the grouped pipeline, again lane 0), so stream order puts this launch behind the previous call's readers and in front of this call's
+static int run_audio_convert(nasr_engine *e, std::vector<AudioDesc> &descs, std::vector<const int16_t *> &base, double in_bytes, double flops) {
+    size_t total = 0;
+    long long max_out = 0;
+    for (auto &d : descs) { total += (size_t)d.n_out; max_out = std::max(max_out, d.n_out); }
+    if (total > e->pcm_stage_cap) {
+        HIPCHK(hipStreamSynchronize(e->st));
+        if (e->pcm_stage) hipFree(e->pcm_stage);
+        e->pcm_stage = nullptr;
+        e->pcm_stage_cap = total + 65536;
+        HIPCHK(hipMalloc((void **)&e->pcm_stage, e->pcm_stage_cap * 2));
+    }
+    size_t o = 0;
+    for (size_t b = 0; b < descs.size(); b++) {
+        descs[b].out = e->pcm_stage + o;
+        base[b] = e->pcm_stage + o;
+        o += (size_t)descs[b].n_out;
+    }
+    const AudioDesc *dd;
+    if (stage_desc(e, descs, &dd)) return -1;
+    ProfScope ps(e, "audio_convert", in_bytes + (double)total * 2, flops);
+    launch_audio_convert(dd, (int)descs.size(), max_out, e->st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// nasr_engine_finalize: the samples that waited for input which will not come, through the front end like any push (eager, tokens stay
+// on the device until the caller's collect)
+int audio_flush(nasr_engine *e, nasr_stream *const *streams, int B) {
+    if (e->debug) for (int b = 0; b < B; b++) e->tap_pcm_n[streams[b]->slot] = 0;      // NASR_TAP_PCM16: a finalize that flushes nothing hands over nothing
+    bool any = false;
+    for (int b = 0; b < B; b++) any = any || (!streams[b]->default_format() && nasr_rs::out_total(streams[b]->aud_plan, streams[b]->aud_in) > streams[b]->aud_out);
+    if (!any) return 0;
+    std::vector<AudioDesc> descs((size_t)B);
+    std::vector<const int16_t *> base((size_t)B, nullptr);
+    std::vector<int32_t> n16((size_t)B, 0);
+    double flops = 0;
+    for (int b = 0; b < B; b++) {
+        nasr_stream *s = streams[b];
+        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt, s->aud_table);
+        const long long n = s->default_format() ? 0 : nasr_rs::out_total(s->aud_plan, s->aud_in) - s->aud_out;
+        descs[b].hist = e->aud_hist + (size_t)s->slot * 2 * nasr_rs::HIST_MAX; descs[b].par = s->aud_par;
+        descs[b].n_before = s->aud_in; descs[b].n_push = 0; descs[b].out_first = s->aud_out; descs[b].n_out = n > 0 ? n : 0;
+        n16[b] = (int32_t)descs[b].n_out;
+        flops += audio_flops(s->aud_plan, (double)descs[b].n_out);
+    }
+    if (run_audio_convert(e, descs, base, 0, flops)) return -1;
+    for (int b = 0; b < B; b++) streams[b]->aud_out += n16[b];
+    return step_tail(e, streams, B, base.data(), n16.data(), nullptr, nullptr, nullptr, NASR_FLAG_NO_SYNC);
+}
+
+}  // namespace nasr_eng
+extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm,
+                                const int32_t *n_samples, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                                int32_t *n_tokens, uint32_t flags) {
+    ApiGuard api_guard;
+    if (validate_batch(e, streams, B)) return -1;
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (!pcm || !n_samples) return fail("null pcm / n_samples");
+    for (int b = 0; b < B; b++)
+        if (!streams[b]->default_format())
+            return fail("stream %d has an audio format of its own (%d Hz, encoding %d, %d channel(s)): push it with nasr_engine_step_audio", b,
+                        streams[b]->fmt.sample_rate, streams[b]->fmt.encoding, streams[b]->fmt.channels);
+    HIPCHK(hipSetDevice(e->device));
+    return step_s16(e, streams, B, pcm, n_samples, tokens_out, tokens_cap, n_tokens, flags);
+}
+
+static int check_audio_format(const nasr_audio_format *f) {
+    if (!f) return fail("null audio format");
+    nasr_rs::Plan p;
+    if (!nasr_rs::make_plan(f->sample_rate, &p)) return fail("unsupported sample rate %d (8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000)", f->sample_rate);
+    if (f->encoding < NASR_AUDIO_S16 || f->encoding > NASR_AUDIO_ALAW) return fail("unsupported audio encoding %d", f->encoding);
+    if (f->channels < 1 || f->channels > nasr_rs::MAX_CHANNELS) return fail("unsupported channel count %d (1 .. %d)", f->channels, nasr_rs::MAX_CHANNELS);
+    if (f->channel < -1 || f->channel >= f->channels) return fail("channel %d out of range (-1 = mean, 0 .. %d)", f->channel, f->channels - 1);
+    return 0;
+}
+
+extern "C" int64_t nasr_audio_out_ready(const nasr_audio_format *f, int64_t n_frames_in) {
+    if (check_audio_format(f)) return -1;
+    if (n_frames_in < 0) return fail("negative frame count");
+    nasr_rs::Plan p;
+    nasr_rs::make_plan(f->sample_rate, &p);
+    return nasr_rs::out_ready(p, n_frames_in);
+}
+extern "C" int64_t nasr_audio_out_total(const nasr_audio_format *f, int64_t n_frames_in) {
+    if (check_audio_format(f)) return -1;
+    if (n_frames_in < 0) return fail("negative frame count");
+    nasr_rs::Plan p;
+    nasr_rs::make_plan(f->sample_rate, &p);
+    return nasr_rs::out_total(p, n_frames_in);
+}
+
+extern "C" int nasr_stream_set_audio_format(nasr_stream *s, const nasr_audio_format *f) {
+    ApiGuard api_guard;
+    if (!s) return fail("null stream");
+    if (check_audio_format(f)) return -1;
+    if (s->samples_in != 0 || s->aud_in != 0) return fail("the audio format is set before a stream's first audio (or right after a reset): this one has taken %lld input frames",
+                                                          (long long)(s->aud_in ? s->aud_in : s->samples_in));
+    nasr_engine *e = s->e;
+    HIPCHK(hipSetDevice(e->device));
+    nasr_rs::Plan p;
+    nasr_rs::make_plan(f->sample_rate, &p);
+    const float *table = nullptr;
+    if (ensure_audio_table(e, p, &table)) return -1;
+    s->fmt = *f; s->aud_plan = p; s->aud_table = table;
+    return 0;
+}
+
+extern "C" int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *streams, int B, const void *const *audio,
+                                      const int32_t *n_frames, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                                      int32_t *n_tokens, uint32_t flags) {
+    ApiGuard api_guard;
+    if (validate_batch(e, streams, B)) return -1;
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (!audio || !n_frames) return fail("null audio / n_frames");
+    HIPCHK(hipSetDevice(e->device));
+    bool all_default = true;
+    for (int b = 0; b < B; b++) all_default = all_default && streams[b]->default_format();
+    if (all_default) return step_s16(e, streams, B, (const int16_t *const *)audio, n_frames, tokens_out, tokens_cap, n_tokens, flags);
+    std::vector<AudioDesc> descs((size_t)B);
+    std::vector<size_t> raw_off((size_t)B, 0), raw_bytes((size_t)B, 0);
+    size_t raw_total = 0;
+    double flops = 0;
+    for (int b = 0; b < B; b++) {
+        nasr_stream *s = streams[b];
+        if (n_frames[b] < 0) return fail("negative n_frames");
+        if (n_frames[b] > 0 && !audio[b]) return fail("null audio for stream %d", b);
+        if ((flags & NASR_FLAG_PCM_DEVICE) && ((uintptr_t)audio[b] % (size_t)nasr_rs::bytes_per_sample(s->fmt.encoding)))
+            return fail("stream %d: device audio must be naturally aligned (2 bytes for s16, 4 for f32)", b);
+        if (!s->aud_table && ensure_audio_table(e, s->aud_plan, &s->aud_table)) return -1;      // a default-format stream beside the others
+        const long long n_out = std::max<long long>(0, nasr_rs::out_ready(s->aud_plan, s->aud_in + n_frames[b]) - s->aud_out);
+        if (n_out > INT32_MAX) return fail("stream %d: the push completes more than 2^31 samples", b);
+        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt, s->aud_table);
+        descs[b].hist = e->aud_hist + (size_t)s->slot * 2 * nasr_rs::HIST_MAX; descs[b].par = s->aud_par;
+        descs[b].n_before = s->aud_in; descs[b].n_push = n_frames[b]; descs[b].out_first = s->aud_out; descs[b].n_out = n_out;
+        raw_bytes[b] = (size_t)n_frames[b] * s->fmt.channels * nasr_rs::bytes_per_sample(s->fmt.encoding);
+        raw_off[b] = raw_total;
+        raw_total += (raw_bytes[b] + 15) & ~(size_t)15;
+        flops += audio_flops(s->aud_plan, (double)n_out);
+    }
+    if (!(flags & NASR_FLAG_PCM_DEVICE)) {
+        // hand-over of host buffers as in nasr_engine_step: one gather into a rotating pinned block, one copy into the raw staging area
+        if (raw_total > e->raw_stage_cap) {
+            HIPCHK(hipStreamSynchronize(e->st));
+            if (e->raw_stage) hipFree(e->raw_stage);
+            e->raw_stage = nullptr;
+            e->raw_stage_cap = raw_total + 65536;
+            HIPCHK(hipMalloc((void **)&e->raw_stage, e->raw_stage_cap));
+        }
+        auto &pin = e->raw_pin[e->raw_pin_next++ & 3];
+        if (pin.pending) { HIPCHK(hipEventSynchronize(pin.copied)); pin.pending = false; }
+        if (raw_total > pin.cap) {
+            HIPCHK(hipStreamSynchronize(e->st));
+            if (pin.p) hipHostFree(pin.p);
+            pin.p = nullptr;
+            pin.cap = raw_total + 65536;
+            HIPCHK(hipHostMalloc((void **)&pin.p, pin.cap, hipHostMallocDefault));
+        }
+        for (int b = 0; b < B; b++) {
+            if (raw_bytes[b] > 0) memcpy(pin.p + raw_off[b], audio[b], raw_bytes[b]);
+            descs[b].in = e->raw_stage + raw_off[b];
+        }
+        ProfScope ps(e, "h2d_pcm", (double)raw_total);
+        if (raw_total > 0) {
+            HIPCHK(hipMemcpyAsync(e->raw_stage, pin.p, raw_total, hipMemcpyHostToDevice, e->st));
+            if (!pin.copied) HIPCHK(hipEventCreateWithFlags(&pin.copied, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(pin.copied, e->st));
+            pin.pending = true;
+        }
+    } else {
+        for (int b = 0; b < B; b++) descs[b].in = audio[b];
+    }
+    std::vector<const int16_t *> base((size_t)B, nullptr);
+    std::vector<int32_t> n16((size_t)B, 0);
+    if (run_audio_convert(e, descs, base, (double)raw_total, flops)) return -1;
+    for (int b = 0; b < B; b++) {
+        nasr_stream *s = streams[b];
+        n16[b] = (int32_t)descs[b].n_out;
+        s->aud_in += n_frames[b];
+        s->aud_out += n16[b];
+        if (n_frames[b] > 0) s->aud_par ^= 1;
+    }
+    return step_tail(e, streams, B, base.data(), n16.data(), tokens_out, tokens_cap, n_tokens, flags & ~(uint32_t)NASR_FLAG_PCM_DEVICE);
+}
+
+extern "C" int64_t nasr_engine_convert_audio(nasr_engine *e, const nasr_audio_format *f, const void *audio, int64_t n_frames,
+                                             int16_t *out, int64_t cap, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (check_audio_format(f)) return -1;
+    if (n_frames < 0 || n_frames > INT32_MAX) return fail("n_frames out of range");
+    if (n_frames > 0 && (!audio || !out)) return fail("null audio / out");
+    if ((flags & NASR_FLAG_PCM_DEVICE) && (((uintptr_t)audio % (size_t)nasr_rs::bytes_per_sample(f->encoding)) || ((uintptr_t)out & 1)))
+        return fail("device audio / out must be naturally aligned (2 bytes for s16, 4 for f32)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    nasr_rs::Plan p;
+    nasr_rs::make_plan(f->sample_rate, &p);
+    const long long n_out = nasr_rs::out_total(p, n_frames);
+    if (n_out > cap) return fail("output buffer too small (%lld > %lld)", n_out, (long long)cap);
+    if (n_out == 0) return 0;
+    const float *table = nullptr;
+    if (ensure_audio_table(e, p, &table)) return -1;
+    const bool on_device = (flags & NASR_FLAG_PCM_DEVICE) != 0;
+    const size_t in_bytes = (size_t)n_frames * f->channels * nasr_rs::bytes_per_sample(f->encoding);
+    void *din = nullptr, *dout = nullptr;
+    int rc = 0;
+    auto done = [&](int r) { if (!on_device) { if (din) hipFree(din); if (dout) hipFree(dout); } return r; };
+    if (!on_device) {
+        if (hipMalloc(&din, in_bytes) != hipSuccess || hipMalloc(&dout, (size_t)n_out * 2) != hipSuccess) return done(fail("hipMalloc failed (one-shot audio conversion)"));
+        if (hipMemcpyAsync(din, audio, in_bytes, hipMemcpyHostToDevice, e->st) != hipSuccess) return done(fail("hipMemcpyAsync failed (one-shot audio conversion)"));
+    }
+    std::vector<AudioDesc> descs(1);
+    fill_audio_desc(e, descs[0], p, *f, table);
+    descs[0].in = on_device ? audio : din; descs[0].out = on_device ? out : (int16_t *)dout;
+    descs[0].n_push = n_frames; descs[0].n_out = n_out;
+    const AudioDesc *dd;
+    if (stage_desc(e, descs, &dd)) return done(-1);
+    {
+        ProfScope ps(e, "audio_convert", (double)in_bytes + (double)n_out * 2, audio_flops(p, (double)n_out));
+        launch_audio_convert(dd, 1, n_out, e->st);
+        if (hipGetLastError() != hipSuccess) return done(fail("k_audio_convert launch failed (one-shot audio conversion)"));
+    }
+    if (!on_device && hipMemcpyAsync(out, dout, (size_t)n_out * 2, hipMemcpyDeviceToHost, e->st) != hipSuccess) rc = fail("hipMemcpyAsync failed (one-shot audio conversion)");
+    if (hipStreamSynchronize(e->st) != hipSuccess) rc = fail("one-shot audio conversion failed on the device");
+    return done(rc ? -1 : (int64_t)n_out);
 }
 
 extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams, int B, const float *const *mel,
@@ -493,6 +773,7 @@ extern "C" int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams,
     if (validate_batch(e, streams, B)) return -1;
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
+    if (audio_flush(e, streams, B)) return -1;          // streams with an audio format of their own: the converter's tail goes through the front end first
     // src/nemo-stream.cpp:1234-1258: frames > 9 -> n_valid = (frames-9)/8 outputs of one zero-padded step
     std::vector<nasr_stream *> rows;
     std::vector<int> nd;
@@ -722,6 +1003,15 @@ extern "C" int64_t nasr_stream_get_tap(nasr_stream *s, int which, int index, flo
         if ((int64_t)(ks1 * D) > cap) return fail("tap buffer too small");
         HIPCHK(hipMemcpy(out, e->cc_pool[index] + (slot * 2 + s->cc_par) * ks1 * D, ks1 * D * 4, hipMemcpyDeviceToHost));
         return (int64_t)(ks1 * D);
+    }
+    case NASR_TAP_PCM16: {
+        if (!e->debug) return fail("debug taps not enabled");
+        const int64_t n = e->tap_pcm_n[slot];
+        if (n > cap) return fail("tap buffer too small");
+        std::vector<int16_t> h((size_t)n);
+        if (n > 0) HIPCHK(hipMemcpy(h.data(), e->tap_pcm + e->tap_pcm_off[slot], (size_t)n * 2, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; i++) out[i] = (float)h[(size_t)i];
+        return n;
     }
     case NASR_TAP_DEC_STATE: {
         if (cap < 4 * HID + 1) return fail("tap buffer too small");

@@ -496,6 +496,7 @@ extern "C" int nasr_engine_create_ex(nasr_engine **out, int device_id, int dtype
     rc |= dalloc(e, &e->abuf, S * 2 * ABUF_CAP);
     rc |= dalloc(e, &e->last_sample, S);
     rc |= dalloc(e, &e->mel_ring, S * MEL_RING * NMEL);
+    rc |= dalloc(e, &e->aud_hist, S * 2 * nasr_rs::HIST_MAX);
     e->kv_pool.resize(Lr); e->cc_pool.resize(Lr);
     for (size_t l = 0; l < Lr && !rc; l++) {
         char *kp;
@@ -545,6 +546,8 @@ extern "C" int nasr_engine_create_ex(nasr_engine **out, int device_id, int dtype
     e->slots.assign(S, nullptr);
     e->tap_mel_frames.assign(S, 0);
     e->tap_mel_row.assign(S, 0);
+    e->tap_pcm_off.assign(S, 0);
+    e->tap_pcm_n.assign(S, 0);
     if (hipStreamSynchronize(e->st) != hipSuccess) { engine_destroy_impl(e); return fail("engine init sync failed"); }
     *out = e;
     return 0;
@@ -655,6 +658,9 @@ void engine_destroy_impl(nasr_engine *e) {
     if (e->pcm_stage) hipFree(e->pcm_stage);
     for (auto &pin : e->pcm_pin) { if (pin.p) hipHostFree(pin.p); if (pin.copied) hipEventDestroy(pin.copied); }
     if (e->mel_stage) hipFree(e->mel_stage);
+    if (e->raw_stage) hipFree(e->raw_stage);
+    for (auto &pin : e->raw_pin) { if (pin.p) hipHostFree(pin.p); if (pin.copied) hipEventDestroy(pin.copied); }
+    if (e->tap_pcm) hipFree(e->tap_pcm);
     if (e->tap_mel) hipFree(e->tap_mel);
     if (e->tap_sub) hipFree(e->tap_sub);
     if (e->tap_layers) hipFree(e->tap_layers);
@@ -686,6 +692,7 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     rp.keep_reference_state = keep_reference_state ? 1 : 0;
     rp.abuf = e->abuf; rp.last_sample = e->last_sample; rp.mel_ring = e->mel_ring; rp.dec_h = e->dec_h; rp.dec_c = e->dec_c; rp.ctrl = e->ctrl;
     if (e->opt_phrase_boost) { rp.boost_state = e->boost_state; rp.boost_init = s->boost_enabled ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF; }
+    rp.aud_hist = e->aud_hist;
     launch_stream_reset(rp, e->st);
     HIPCHK(hipGetLastError());
     if (!keep_reference_state) {
@@ -700,6 +707,8 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     s->chunks = 0;
     s->tok_read = 0;
     s->samples_in = 0;
+    s->aud_in = s->aud_out = 0;                // the audio converter starts over in both modes; the format stays
+    s->aud_par = 0;
     s->last_T = 0;
     s->last_ws = 0;
     return 0;

@@ -103,6 +103,13 @@ struct nasr_stream {
     bool alive;
     bool boost_enabled = true;       // nasr_stream_set_boost (engine option "phrase_boost")
     std::vector<int32_t> tok_queue;  // tokens gathered from the device, not yet handed to the caller
+    // audio input conversion (nasr_stream_set_audio_format, nasr_resample.h): the format survives a reset, the counters and the parity do not
+    nasr_audio_format fmt = {16000, NASR_AUDIO_S16, 1, 0};
+    nasr_rs::Plan aud_plan = {16000, 1, 1, 0, 1};
+    const float *aud_table = nullptr;      // device coefficients of fmt.sample_rate (the engine's cache owns them)
+    int64_t aud_in = 0, aud_out = 0;       // input frames taken / 16 kHz samples produced since create or reset
+    int aud_par = 0;                       // parity of the history buffer that holds the frames before the next push
+    bool default_format() const { return fmt.sample_rate == 16000 && fmt.encoding == NASR_AUDIO_S16 && fmt.channels == 1 && fmt.channel == 0; }
 };
 
 struct nasr_engine {
@@ -246,6 +253,17 @@ struct nasr_engine {
     struct { int16_t *p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool pending = false; } pcm_pin[4];   // copied: recorded behind the block's H2D copy
     unsigned pcm_pin_next = 0;
     float *mel_stage = nullptr; size_t mel_stage_cap = 0;
+    // audio input conversion: per-stream history [slot][2][nasr_rs::HIST_MAX] (allocated with the stream pool), one coefficient table per
+    // rate in use (built and uploaded once), the raw staging area of nasr_engine_step_audio with its rotating pinned blocks (the
+    // discipline of pcm_pin), and the debug copy behind NASR_TAP_PCM16
+    float *aud_hist = nullptr;
+    bool opt_audio_lds_table = true;        // option "audio_lds_table": k_audio_convert reads the coefficients of the L <= 2 rates from an LDS copy (same bits; 0.343 -> 0.253 ms per step at 512 streams x 48 kHz: profiles/audio_input.md)
+    std::map<int, float *> aud_tables;
+    char *raw_stage = nullptr; size_t raw_stage_cap = 0;
+    struct { char *p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool pending = false; } raw_pin[4];
+    unsigned raw_pin_next = 0;
+    int16_t *tap_pcm = nullptr; size_t tap_pcm_cap = 0;
+    std::vector<int64_t> tap_pcm_off, tap_pcm_n;         // per slot: where the last call's samples are in tap_pcm, and how many
     // debug taps
     bool debug = false;
     float *tap_mel = nullptr; int tap_mel_cap = 0;      // [max_streams][tap_mel_cap][128] by batch row
@@ -380,6 +398,10 @@ int try_graph_step(nasr_engine *e, nasr_stream *const *streams, int B, const int
                           const int32_t *n_samples, int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens);
 int push_piece(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *base, const int32_t *n_samples,
                       int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, uint32_t flags);
+// what nasr_engine_step and nasr_engine_step_audio share once base[] points at every stream's 16 kHz s16 samples on the device
+int step_tail(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *base, const int32_t *n_samples,
+              int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, uint32_t flags);
+int ensure_audio_table(nasr_engine *e, const nasr_rs::Plan &p, const float **out);
 void prof_flush(nasr_engine *e);
 __global__ void k_collect(const int *slots, const int *tok_read, int B, const DecCtrl *ctrl, const int *tok_ring, int *out, int stride, const int *n_active);
 inline int max_frames_per_push(int TS) { return 8 * TS + 16; }  // TS = frames of encoder output the push completes (+ what a first push leaves over)

@@ -6,6 +6,7 @@
 #include "nasr_boost.h"
 #include "nasr_topk.h"
 #include "nasr_align.h"
+#include "nasr_resample.h"
 
 namespace nasr {
 
@@ -207,8 +208,24 @@ struct StreamResetParams {      // one launch per stream start / reset (kernels_
     float *abuf, *last_sample, *mel_ring, *dec_h, *dec_c;
     DecCtrl *ctrl;
     int *boost_state; int boost_init;   // engine option "phrase_boost" (null when off): the slot's automaton state goes back to the root (or 0 = disabled)
+    float *aud_hist;            // [slot][2][nasr_rs::HIST_MAX] input history of the audio converter: cleared in both modes
 };
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st);
+
+// audio input conversion (kernels_audio.hip, nasr_resample.h): one per stream of a launch
+struct AudioDesc {
+    const void *in;             // the push: n_push interleaved input frames (device memory)
+    const float *table;         // coefficients of the stream's rate, c[j + half]
+    int16_t *out;               // n_out samples at 16 kHz: outputs out_first .. out_first + n_out - 1 of the stream
+    float *hist;                // the slot's [2][nasr_rs::HIST_MAX], or null: nothing before the push, no history kept
+    long long n_before, n_push; // input frames taken before this launch / in it
+    long long out_first, n_out;
+    int enc, channels, channel; // nasr_rs::ENC_*, 1 .. 8, channel index or -1 = mean
+    int L, M, half, par;        // par: parity of hist that holds the frames before the push (the launch writes the other)
+    int lds_table;              // 1: the workgroup copies the table into LDS first (only where 2 half + 1 <= LDS_TABLE_MAX)
+};
+constexpr int LDS_TABLE_MAX = 256;
+void launch_audio_convert(const AudioDesc *descs, int B, long long max_out, hipStream_t st);
 
 void launch_sub_conv0_dw(const RowDesc *rows, int B, int chunk_mel, const float *mel_ring, const float *w0t, const float *b0,
                          const float *w2t, const float *b2, void *out, int out_bf16, int H1, int W1, hipStream_t st);

@@ -323,8 +323,9 @@ static std::string absorb(nemo_stream_context *s, const int32_t *tok, int n) {
     return text;
 }
 
-bool nemo_stream_process_batch(nemo_stream_context *const *sctx, int B, const int16_t *const *audio,
-                               const int *n_samples, std::string *out) {
+// one engine call for B streams: nasr_engine_step on s16 16 kHz mono, or (own_format) nasr_engine_step_audio on each stream's own format
+static bool process_batch(nemo_stream_context *const *sctx, int B, const void *const *audio, const int *n_samples, std::string *out, bool own_format,
+                          const char *who) {
     if (!sctx || B <= 0 || !audio || !n_samples) return false;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<nasr_stream *> st((size_t)B);
@@ -335,24 +336,26 @@ bool nemo_stream_process_batch(nemo_stream_context *const *sctx, int B, const in
         if (!sctx[b]) return false;
         st[b] = sctx[b]->stream;
         ns[b] = n_samples[b] > 0 ? n_samples[b] : 0;
-        cap[b] = (ns[b] / 1280 + 16) * 10;                   // <= 10 symbols per 80 ms frame
+        cap[b] = (ns[b] / (own_format ? 640 : 1280) + 16) * 10;      // <= 10 symbols per 80 ms frame (640 input frames at 8 kHz)
         buf[b].resize((size_t)cap[b]);
         ptr[b] = buf[b].data();
     }
-    if (nasr_engine_step(sctx[0]->nctx->engine, st.data(), B, audio, ns.data(), ptr.data(), cap.data(), cnt.data(), 0) < 0) {
-        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+    const int rc = own_format ? nasr_engine_step_audio(sctx[0]->nctx->engine, st.data(), B, audio, ns.data(), ptr.data(), cap.data(), cnt.data(), 0)
+                              : nasr_engine_step(sctx[0]->nctx->engine, st.data(), B, (const int16_t *const *)audio, ns.data(), ptr.data(), cap.data(), cnt.data(), 0);
+    if (rc < 0) {
+        fprintf(stderr, "%s: %s\n", who, nasr_last_error());
         return false;
     }
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (int b = 0; b < B; b++) {
         nemo_stream_context *s = sctx[b];
-        s->total_audio_seconds += (double)ns[b] / s->config.sample_rate;
+        s->total_audio_seconds += (double)ns[b] / (own_format ? s->audio_rate : s->config.sample_rate);
         s->total_compute_seconds += dt / B;
         std::string text = absorb(s, buf[b].data(), cnt[b]);
         // a full buffer: more tokens may be queued on the stream (nothing is dropped below the ABI) -- fetch them now
         while (cnt[b] >= cap[b]) {
             if (nasr_engine_collect(s->nctx->engine, &st[b], 1, &ptr[b], &cap[b], &cnt[b]) < 0) {
-                fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+                fprintf(stderr, "%s: %s\n", who, nasr_last_error());
                 return false;
             }
             text += absorb(s, buf[b].data(), cnt[b]);
@@ -363,6 +366,29 @@ bool nemo_stream_process_batch(nemo_stream_context *const *sctx, int B, const in
         if (nasr_stream_get_progress(s->stream, &stt) == 0) s->total_chunks_processed = stt.chunks;
     }
     return true;
+}
+
+bool nemo_stream_process_batch(nemo_stream_context *const *sctx, int B, const int16_t *const *audio,
+                               const int *n_samples, std::string *out) {
+    return process_batch(sctx, B, (const void *const *)audio, n_samples, out, false, __func__);
+}
+
+bool nemo_stream_set_audio_format(nemo_stream_context *sctx, int sample_rate, int encoding, int channels, int channel) {
+    if (!sctx) return false;
+    const nasr_audio_format f = {sample_rate, encoding, channels, channel};
+    if (nasr_stream_set_audio_format(sctx->stream, &f) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    sctx->audio_rate = sample_rate; sctx->audio_encoding = encoding; sctx->audio_channels = channels; sctx->audio_channel = channel;
+    return true;
+}
+
+std::string nemo_stream_process_audio(nemo_stream_context *sctx, const void *audio, int n_frames) {
+    if (!sctx || !audio || n_frames <= 0) return "";
+    std::string out;
+    if (!process_batch(&sctx, 1, &audio, &n_frames, &out, true, __func__)) return "";
+    return out;
 }
 
 std::string nemo_stream_process_incremental(nemo_stream_context *sctx, const int16_t *audio, int n_samples) {

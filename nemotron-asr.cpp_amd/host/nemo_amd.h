@@ -50,6 +50,7 @@ struct nemo_stream_context {        // reference src/nemo-stream.h:177-262 (host
     nemo_cache_config config;
     nasr_stream *stream = nullptr;
     int prompt_index = -1;
+    int audio_rate = 16000, audio_encoding = 0, audio_channels = 1, audio_channel = 0;      // nemo_stream_set_audio_format (default: s16 16 kHz mono)
     std::vector<int> tokens;
     std::string transcript;
     double total_audio_seconds = 0, total_compute_seconds = 0;
@@ -99,6 +100,12 @@ nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_s
 nemo_stream_context *nemo_stream_init(nemo_context *ctx, const nemo_cache_config *config = nullptr);
 bool nemo_stream_set_language(nemo_stream_context *sctx, const char *lang);
 std::string nemo_stream_process_incremental(nemo_stream_context *sctx, const int16_t *audio, int n_samples);
+// MI355X extension: audio in another format, converted on the device (nasr_stream_set_audio_format / nasr_engine_step_audio): sample_rate 8000,
+// 11025, 16000, 22050, 24000, 32000, 44100 or 48000; encoding NASR_AUDIO_S16 / F32 / MULAW / ALAW; channels 1 .. 8 interleaved; channel = an
+// index, or -1 for the mean.  Set it before the stream's first audio (or right after a reset); then push with nemo_stream_process_audio, whose
+// n_frames counts sample times with all channels.  nemo_stream_finalize flushes the converter's tail.
+bool nemo_stream_set_audio_format(nemo_stream_context *sctx, int sample_rate, int encoding, int channels, int channel);
+std::string nemo_stream_process_audio(nemo_stream_context *sctx, const void *audio, int n_frames);
 std::string nemo_stream_finalize(nemo_stream_context *sctx);
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx);
 const std::vector<int> &nemo_stream_get_tokens(nemo_stream_context *sctx);

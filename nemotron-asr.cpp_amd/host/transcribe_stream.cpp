@@ -2,9 +2,13 @@
 // `nemotron-asr.cpp` binary (reference src/transcribe_stream.cpp:33-297): positional
 // `model.gguf audio.pcm [chunk_ms] [right_context]`, s16le 16 kHz mono from a file or stdin ("-"),
 // text deltas on stdout as they are produced, configuration and the RTF summary on stderr.
+// --input-rate / --input-encoding / --input-channels / --input-channel: audio in another format, converted on the device; a file that
+// starts with RIFF....WAVE sets them from its header (wav_header.h).
 // --diarize <diarize.gguf> [--rttm F] [--speaker-text F] [--json F] [--num-speakers K] [--sub-shift SEC] run the
 // diarization pipeline beside the ASR stream like the reference's CLI (:146-170, :243-290).
+#include <algorithm>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,12 +19,18 @@
 
 #include "diarize_pipeline_amd.h"
 #include "nemo_amd.h"
+#include "nemotron_asr_amd.h"
+#include "wav_header.h"
 #include "word_confidence.h"
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]]\n"
-            "  audio: raw s16le, 16 kHz, mono.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
+            "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
+            "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
+            "  --input-channel I|mix: the channel to transcribe, or the mean of all (default: mix when there are several).  A file that starts with\n"
+            "                   RIFF....WAVE (PCM 16-bit, IEEE float 32-bit, mu-law, A-law) sets rate, encoding and channels from its header\n"
             "  --read-chunks N: read N chunks of audio per call (default 1 = the reference's read size); a file is\n"
             "                   transcribed fastest with N = 256 and --pipeline 4: same transcript, the chunks of a read share one\n"
             "                   launch sequence and consecutive reads run side by side\n"
@@ -54,6 +64,7 @@ int main(int argc, char **argv) {
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
     float sub_shift_sec = 0.75f, vad_onset = -1.0f, vad_offset = -1.0f;
+    int in_rate = 16000, in_enc = NASR_AUDIO_S16, in_channels = 1, in_channel = -2;      // -2: not given (one channel: 0, several: the mean)
     std::string diarize_gguf, rttm_path, speaker_text_path, json_path;
     const bool from_stdin = strcmp(audio_path, "-") == 0 || strcmp(audio_path, "--stdin") == 0;
     for (int i = 3; i < argc; i++) {
@@ -77,6 +88,14 @@ int main(int argc, char **argv) {
         else if (a == "--pipeline3") pipeline = 3;
         else if (a == "--pipeline4") pipeline = 4;
         else if (a == "--read-chunks" && i + 1 < argc) read_chunks = atoi(argv[++i]);
+        else if (a == "--input-rate" && i + 1 < argc) in_rate = atoi(argv[++i]);
+        else if (a == "--input-encoding" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            in_enc = v == "s16" ? NASR_AUDIO_S16 : v == "f32" ? NASR_AUDIO_F32 : v == "mulaw" ? NASR_AUDIO_MULAW : v == "alaw" ? NASR_AUDIO_ALAW : -1;
+            if (in_enc < 0) { fprintf(stderr, "--input-encoding must be s16, f32, mulaw or alaw (got %s)\n", v.c_str()); return 1; }
+        }
+        else if (a == "--input-channels" && i + 1 < argc) in_channels = atoi(argv[++i]);
+        else if (a == "--input-channel" && i + 1 < argc) in_channel = strcmp(argv[i + 1], "mix") == 0 ? (++i, -1) : atoi(argv[++i]);
         else if (a == "--diarize" && i + 1 < argc) diarize_gguf = argv[++i];
         else if (a == "--rttm" && i + 1 < argc) rttm_path = argv[++i];
         else if (a == "--speaker-text" && i + 1 < argc) speaker_text_path = argv[++i];
@@ -135,27 +154,77 @@ int main(int argc, char **argv) {
     std::vector<float> f32;
     FILE *in = from_stdin ? stdin : fopen(audio_path, "rb");
     if (!in) { fprintf(stderr, "Failed to open audio file: %s\n", audio_path); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
-    // like the reference, the read size is the model's chunk (chunk_ms is validated and printed only)
-    std::vector<int16_t> buf((size_t)cfg.get_chunk_samples() + (size_t)(read_chunks - 1) * 1280u * (size_t)(1 + right_context));
+    // a WAVE header names the format and is skipped; whatever was read past it is the first audio
+    // (12 bytes tell: a live stream of raw audio is not made to wait for more than that before its first chunk)
+    std::vector<uint8_t> pending(12);
+    pending.resize(fread(pending.data(), 1, pending.size(), in));
+    if (pending.size() == 12 && !memcmp(pending.data(), "RIFF", 4) && !memcmp(pending.data() + 8, "WAVE", 4)) {
+        pending.resize(4096);
+        pending.resize(12 + fread(pending.data() + 12, 1, pending.size() - 12, in));
+    }
+    size_t data_left = SIZE_MAX;                     // bytes of the data chunk still to come (raw audio: to the end of the file)
+    for (;;) {
+        wav_header::Info wi;
+        char err[160];
+        const int rc = wav_header::parse(pending.data(), pending.size(), &wi, err, sizeof(err));
+        if (rc == wav_header::NOT_WAV) break;
+        if (rc == wav_header::OK) {
+            in_rate = wi.sample_rate; in_enc = wi.encoding; in_channels = wi.channels;
+            if (wi.data_bytes != 0 && wi.data_bytes != 0xFFFFFFFFu) data_left = wi.data_bytes;
+            pending.erase(pending.begin(), pending.begin() + (long)wi.data_offset);
+            fprintf(stderr, "  WAV header:     %d Hz, %d channel(s), format tag %d at %d bits\n\n", wi.sample_rate, wi.channels, wi.format_tag, wi.bits);
+            break;
+        }
+        // the data chunk may lie behind chunks longer than what has been read: read on (up to 1 MiB), unless the file has ended
+        const size_t have = pending.size();
+        if ((rc == wav_header::ERR_NO_DATA || rc == wav_header::ERR_NO_FMT || rc == wav_header::ERR_TRUNCATED) && have < (1u << 20)) {
+            pending.resize(2 * have);
+            pending.resize(have + fread(pending.data() + have, 1, have, in));
+            if (pending.size() > have) continue;
+        }
+        fprintf(stderr, "%s\n", err);
+        nemo_stream_free(sctx); nemo_free(ctx);
+        return 1;
+    }
+    if (in_channel == -2) in_channel = in_channels > 1 ? -1 : 0;
+    const bool own_format = !(in_rate == 16000 && in_enc == NASR_AUDIO_S16 && in_channels == 1 && in_channel == 0);
+    if (own_format) {
+        if (dp) { fprintf(stderr, "--diarize takes s16le 16 kHz mono audio\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
+        if (!nemo_stream_set_audio_format(sctx, in_rate, in_enc, in_channels, in_channel)) { fprintf(stderr, "Unsupported input format\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
+        fprintf(stderr, "  Input:          %d Hz, encoding %d, %d channel(s), channel %d (converted on the GPU)\n\n", in_rate, in_enc, in_channels, in_channel);
+    }
+    // like the reference, the read size is the model's chunk (chunk_ms is validated and printed only); in another format, the input frames of as much time
+    const size_t frame_bytes = (size_t)in_channels * (in_enc == NASR_AUDIO_S16 ? 2 : in_enc == NASR_AUDIO_F32 ? 4 : 1);
+    const size_t read_samples = (size_t)cfg.get_chunk_samples() + (size_t)(read_chunks - 1) * 1280u * (size_t)(1 + right_context);
+    const size_t read_frames = (read_samples * (size_t)in_rate + 15999) / 16000;
+    std::vector<uint8_t> raw(read_frames * frame_bytes + 8);
+    uint8_t *buf = raw.data() + (8 - (uintptr_t)raw.data() % 8) % 8;            // aligned for s16 / f32 reads
     size_t total = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
-        const size_t got = fread(buf.data(), sizeof(int16_t), buf.size(), in);
+        const size_t want = std::min(read_frames * frame_bytes, data_left);
+        size_t have = std::min(want, pending.size());
+        memcpy(buf, pending.data(), have);
+        pending.erase(pending.begin(), pending.begin() + (long)have);
+        if (have < want) have += fread(buf + have, 1, want - have, in);
+        if (data_left != SIZE_MAX) data_left -= have;
+        const size_t got = have / frame_bytes;                                   // a cut last frame is dropped
         if (got == 0) break;
         total += got;
-        handle_text(nemo_stream_process_incremental(sctx, buf.data(), (int)got), total);
+        // handle_text's sample count feeds the diarization pipeline only, which runs on the default format: there frames are 16 kHz samples
+        handle_text(own_format ? nemo_stream_process_audio(sctx, buf, (int)got) : nemo_stream_process_incremental(sctx, (const int16_t *)buf, (int)got), total);
         if (dp) {
             f32.resize(got);
-            for (size_t k = 0; k < got; k++) f32[k] = (float)buf[k] / 32768.0f;
+            for (size_t k = 0; k < got; k++) f32[k] = (float)((const int16_t *)buf)[k] / 32768.0f;
             diarize_pipeline_push_audio(dp, f32.data(), got);
         }
-        if (got < buf.size()) break;
+        if (have < want || data_left == 0) break;
     }
     handle_text(nemo_stream_finalize(sctx), total);
     printf("\n");
     if (!from_stdin) fclose(in);
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const double audio_s = (double)total / 16000.0;
+    const double audio_s = (double)total / (double)in_rate;
     fprintf(stderr, "\nAudio duration:   %.2f s\nProcessing time:  %.3f s\nReal-time factor: %.4f (%.1fx real time)\nChunks: %d\n",
             audio_s, wall, audio_s > 0 ? wall / audio_s : 0.0, wall > 0 ? audio_s / wall : 0.0, sctx->total_chunks_processed);
     if (timestamps && !confidence) printf("%s\n", tokens_to_text(nemo_stream_get_timed_tokens(sctx), ctx->vocab, true).c_str());
