@@ -321,7 +321,8 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * "graph_replays" (calls served by a hipGraph, pipelined ones included), "eager_steps" (calls that were not graph-eligible: ragged
  * pushes, streams that complete different chunk counts), "pipelined_steps", "grouped_steps", "lanes" (HIP streams the engine found
  * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
- * 2 with no phrases; 0 when engine option "phrase_boost" is off).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
+ * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
+ * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);
 /* enable recording of NASR_TAP_MEL / SUBSAMPLED / LAYER_OUT (costs extra copies) */

@@ -657,8 +657,7 @@ void launch_decode_candidates(const DecParams &p, hipStream_t st) {
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a
 // blindly enqueued (graph-captured) sequence cost only their launch slots.
-void launch_decode_iter(const DecParams &p, int iter, hipStream_t st) {
-    (void)iter;
+void launch_decode_iter(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);

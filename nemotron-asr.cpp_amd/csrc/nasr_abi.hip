@@ -1,5 +1,6 @@
 // nasr_abi.hip -- the step driver (graph step when eligible, eager sub-push loop otherwise) and the entry points of
 // include/nemotron_asr_amd.h that are not life cycle: options, step / finalize / collect, counters, taps, profiling, device helpers.
+// Which path a push takes and how it is cut is nasr_step_plan.h; the staging areas grow through grow_device, host buffers cross in PinBlocks.
 #include "nasr_engine_priv.h"
 
 namespace nasr_eng {
@@ -160,27 +161,10 @@ namespace nasr_eng {
 int try_graph_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm_dev,
                           const int32_t *n_samples, int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens) {
     const int T = streams[0]->T, R = streams[0]->R;
-    const int chunk_mel = PRE_CACHE + 8 * T, shift = 8 * T;
-    int G = -1;
-    for (int b = 0; b < B; b++) {
-        const nasr_stream *s = streams[b];
-        const int n = n_samples[b];
-        if (n <= 0 || n > MAX_PUSH) return 0;
-        const int avail = s->abuf_cnt + n;
-        const int nf = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
-        const int mc = s->mel_count + nf;
-        if (mc < chunk_mel) return 0;
-        const int g = (mc - chunk_mel) / shift + 1;               // chunks this push completes
-        if (G < 0) G = g;
-        if (g != G) return 0;                                     // every stream must complete the same number
-        if (nf > max_frames_per_push(T * G)) return 0;
-    }
-    if (G > 1) {
-        // G consecutive chunks of a stream are one launch sequence (same results: a chunk's layer-l
-        // inputs do not depend on the previous chunk's layer-l outputs, only on its K/V and conv state).
-        // Needs the fused small-M path and the new rows to fit in the K/V ring next to the 70-row window.
-        if (!e->opt_multichunk || B * G * T > e->w_rows || G * T > MAXNEW) return 0;
-    }
+    std::vector<int> cnt((size_t)2 * B);          // [abuf_cnt B][mel_count B]
+    for (int b = 0; b < B; b++) { cnt[(size_t)b] = streams[b]->abuf_cnt; cnt[(size_t)B + b] = streams[b]->mel_count; }
+    const int G = graph_step_chunks(cnt.data(), cnt.data() + B, n_samples, B, T, e->w_rows, e->opt_multichunk);
+    if (G == 0) return 0;
     if (e->opt_pipeline) {
         if (!e->pipe_ready && ensure_pipe(e, 0)) return -1;          // picks the lanes
         if (gp_eligible(e, B, T, G)) return gp_step(e, streams, B, pcm_dev, n_samples, G, tokens_out, tokens_cap, n_tokens);
@@ -194,12 +178,7 @@ int try_graph_step(nasr_engine *e, nasr_stream *const *streams, int B, const int
     if (it == e->graphs.end()) {
         HIPCHK(hipStreamSynchronize(e->st));
         while ((int)e->graphs.size() >= e->opt_graph_cache) {          // bounded cache, least recently used shape first
-            int64_t victim = 0, oldest = INT64_MAX;
-            for (auto &kv : e->graphs) {
-                auto u = e->graph_used.find(kv.first);
-                const int64_t t = u == e->graph_used.end() ? 0 : u->second;
-                if (t < oldest) { oldest = t; victim = kv.first; }
-            }
+            const int64_t victim = lru_victim(e->graphs, e->graph_used, 0);
             hipGraphExecDestroy(e->graphs[victim]);
             e->graphs.erase(victim);
             e->graph_used.erase(victim);
@@ -212,71 +191,19 @@ int try_graph_step(nasr_engine *e, nasr_stream *const *streams, int B, const int
         }
         it = e->graphs.emplace(key, ex).first;
     }
-    const GraphDescLayout L = graph_desc_layout(B, G);
-    RowDesc *gh_rows = (RowDesc *)(e->gh + L.rows), *gh_vrows = (RowDesc *)(e->gh + L.vrows);
-    PcmDesc *gh_pcm = (PcmDesc *)(e->gh + L.pcm);
-    int *gh_meta = (int *)(e->gh + L.meta);
-    int *gh_active = e->gh_collect + (size_t)B * (1 + COLLECT_STRIDE);      // k_collect appends n_active to its records
-    for (int b = 0; b < B; b++) {
-        nasr_stream *s = streams[b];
-        PcmDesc &d = gh_pcm[b];
-        memset(&d, 0, sizeof(d));
-        d.pcm = pcm_dev[b]; d.slot = s->slot; d.n = n_samples[b]; d.cnt = s->abuf_cnt; d.par = s->abuf_par;
-        const int avail = d.cnt + d.n;
-        d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
-        d.mel_wpos = (s->mel_start + s->mel_count) & (MEL_RING - 1);
-        d.consumed = d.n_frames * HOP;
-        fill_row_desc(gh_rows[b], s, T * G);
-        for (int g = 0; g < G; g++) {
-            RowDesc &v = gh_vrows[b * G + g];
-            v = gh_rows[b];
-            v.mel_start = (s->mel_start + g * shift) & (MEL_RING - 1);
-        }
-        gh_meta[b] = s->slot;
-        gh_meta[B + b] = s->tok_read;
-    }
+    fill_step_descs(e->gh, streams, B, T, G, pcm_dev, n_samples);
+    int *gh_meta = (int *)(e->gh + graph_desc_layout(B, G).meta);
+    for (int b = 0; b < B; b++) { gh_meta[b] = streams[b]->slot; gh_meta[B + b] = streams[b]->tok_read; }
     HIPCHK(hipGraphLaunch(it->second, e->st));
     HIPCHK(hipStreamSynchronize(e->st));
     e->graph_replays++;
-    for (int b = 0; b < B; b++) {
-        nasr_stream *s = streams[b];
-        const PcmDesc &d = gh_pcm[b];
-        s->abuf_cnt = d.cnt + d.n - d.consumed;
-        if (d.n_frames > 0) s->abuf_par ^= 1;
-        s->mel_count += d.n_frames;
-    }
-    if (*gh_active < 0) {          // reported once: the flag is cleared so that the steps after this one are judged on their own (advisor, round 5: it was sticky)
-        hipMemsetAsync(e->n_active + 3, 0, sizeof(int), e->st);
-        return fail("a chained GEMM launch gave up waiting for its head workgroups (GemmParams::chain): results of this step are invalid");
-    }
-    if (*gh_active != 0) {   // some stream emitted more symbols than the graph's iteration budget: finish eagerly
-        DecParams dp;
-        make_dec_params(e, (const RowDesc *)(e->g_desc + L.rows), B, T * G, dp);
-        int itn = decode_blind_iterations(T * G), round = T * G > 1 ? 8 : 4;   // idle iterations ~10 us each, a round trip ~40 us
-        e->decode_fallbacks++;
-        for (;;) {
-            e->decode_fallback_rounds++;
-            enqueue_decode_iters(e, dp, B, round, itn);
-            HIPCHK(hipMemcpyAsync(gh_active, e->n_active, sizeof(int), hipMemcpyDeviceToHost, e->st));
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (*gh_active == 0) break;
-            if (itn > T * G * MAX_SYMBOLS + 64) return fail("decode did not terminate");
-            round = std::min(2 * round, 32);
-        }
-        for (int b = 0; b < B; b++) {
-            const int par = streams[b]->cc_par;
-            for (int g = 0; g < G; g++) chunk_bookkeeping(streams[b], b);
-            streams[b]->cc_par = par ^ 1;          // one launch = one conv-cache buffer flip, whatever G is
-            streams[b]->last_T = T * G; streams[b]->last_row = b;
-        }
-        return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens) ? -1 : 1;
-    }
-    for (int b = 0; b < B; b++) {
-        const int par = streams[b]->cc_par;
-        for (int g = 0; g < G; g++) chunk_bookkeeping(streams[b], b);
-        streams[b]->cc_par = par ^ 1;
-        streams[b]->last_T = T * G; streams[b]->last_row = b;
-    }
+    mirror_step(streams, B, T, G, e->gh, 0, true, false);          // the audio counts before the decode's outcome is looked at ...
+    // ... which the eager completion (rounds from 4 iterations at one frame) leaves in the token ring: collect_tokens
+    const int fell_back = finish_step_decode(e, StepDecode{e->g_desc, e->encproj, nullptr, e->collect_dev, e->gh_collect, B, T, G}, e->st,
+                                             decode_blind_iterations(T * G), T * G > 1 ? 8 : 4, true, false);
+    if (fell_back < 0) return -1;
+    mirror_step(streams, B, T, G, e->gh, 0, false, true);          // ... the chunk bookkeeping after
+    if (fell_back) return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens) ? -1 : 1;
     if (consume_collect(e, e->gh_collect, streams, B)) return -1;
     deliver(streams, B, tokens_out, tokens_cap, n_tokens);
     return 1;
@@ -307,13 +234,7 @@ int push_piece(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t
             memset(&d, 0, sizeof(d));
             d.pcm = base[b] + off[b];
             d.slot = s->slot;
-            d.n = (int)std::min<int64_t>(rem, MAX_PUSH);
-            d.cnt = s->abuf_cnt;
-            d.par = s->abuf_par;
-            const int avail = d.cnt + d.n;
-            d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;   // src/preprocessor.cpp:320-328
-            d.mel_wpos = (s->mel_start + s->mel_count) & (MEL_RING - 1);
-            d.consumed = d.n_frames * HOP;
+            fill_pcm_counts(d, (int)std::min<int64_t>(rem, MAX_PUSH), s->abuf_cnt, s->abuf_par, s->mel_start, s->mel_count);
             pd.push_back(d);
             who.push_back(b);
             max_frames = std::max(max_frames, d.n_frames);
@@ -334,9 +255,7 @@ int push_piece(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t
         for (size_t i = 0; i < pd.size(); i++) {
             nasr_stream *s = streams[who[i]];
             off[who[i]] += pd[i].n;
-            s->abuf_cnt = pd[i].cnt + pd[i].n - pd[i].consumed;
-            if (pd[i].n_frames > 0) s->abuf_par ^= 1;
-            s->mel_count += pd[i].n_frames;
+            apply_pcm_counts(pd[i], s->abuf_cnt, s->abuf_par, s->mel_count);
             if (e->debug) { e->tap_mel_frames[s->slot] = pd[i].n_frames; e->tap_mel_row[s->slot] = (int)i; }
         }
         if (drain_chunks(e, streams, B)) return -1;
@@ -347,6 +266,27 @@ int push_piece(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t
     }
     return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens);
 }
+
+}  // namespace nasr_eng
+int PinBlock::acquire(size_t bytes, size_t slack, hipStream_t st) {
+    if (pending) { HIPCHK(hipEventSynchronize(copied)); pending = false; }
+    if (bytes <= cap) return 0;
+    HIPCHK(hipStreamSynchronize(st));
+    if (p) hipHostFree(p);
+    p = nullptr;
+    cap = bytes + slack;
+    HIPCHK(hipHostMalloc((void **)&p, cap, hipHostMallocDefault));
+    return 0;
+}
+int PinBlock::copy_to(void *dev, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return 0;
+    HIPCHK(hipMemcpyAsync(dev, p, bytes, hipMemcpyHostToDevice, st));
+    if (!copied) HIPCHK(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(copied, st));
+    pending = true;
+    return 0;
+}
+namespace nasr_eng {
 
 // s16 16 kHz mono in: host buffers are gathered into the device staging area (device buffers are read in place), then the step
 static int step_s16(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm, const int32_t *n_samples,
@@ -360,36 +300,17 @@ static int step_s16(nasr_engine *e, nasr_stream *const *streams, int B, const in
     }
     if (!(flags & NASR_FLAG_PCM_DEVICE)) {
         // hand-over of host buffers: one gather into the device staging area
-        if (total > e->pcm_stage_cap) {
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (e->pcm_stage) hipFree(e->pcm_stage);
-            e->pcm_stage_cap = total + 65536;
-            HIPCHK(hipMalloc((void **)&e->pcm_stage, e->pcm_stage_cap * 2));
-        }
-        auto &pin = e->pcm_pin[e->pcm_pin_next++ & 3];
-        // the block is reused every fourth call: its last copy must have been executed (round-3 advisor: the grouped pipeline keeps
-        // eight calls in flight and nothing ordered the host's memcpy behind copy n - 4; in steady state the event is long complete)
-        if (pin.pending) { HIPCHK(hipEventSynchronize(pin.copied)); pin.pending = false; }
-        if (total > pin.cap) {
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (pin.p) hipHostFree(pin.p);
-            pin.p = nullptr;
-            pin.cap = total + 65536;
-            HIPCHK(hipHostMalloc((void **)&pin.p, pin.cap * 2, hipHostMallocDefault));
-        }
+        if (grow_device(e, &e->pcm_stage, &e->pcm_stage_cap, total, 65536)) return -1;
+        PinBlock &pin = e->pcm_pin[e->pcm_pin_next++ & 3];
+        if (pin.acquire(total * 2, 65536 * 2, e->st)) return -1;
         size_t o = 0;
         for (int b = 0; b < B; b++) {
-            if (n_samples[b] > 0) memcpy(pin.p + o, pcm[b], (size_t)n_samples[b] * 2);
+            if (n_samples[b] > 0) memcpy(pin.p + o * 2, pcm[b], (size_t)n_samples[b] * 2);
             base[b] = e->pcm_stage + o;
             o += (size_t)n_samples[b];
         }
         ProfScope ps(e, "h2d_pcm", (double)total * 2);
-        if (total > 0) {
-            HIPCHK(hipMemcpyAsync(e->pcm_stage, pin.p, total * 2, hipMemcpyHostToDevice, e->st));
-            if (!pin.copied) HIPCHK(hipEventCreateWithFlags(&pin.copied, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(pin.copied, e->st));
-            pin.pending = true;
-        }
+        if (pin.copy_to(e->pcm_stage, total * 2, e->st)) return -1;
     } else {
         for (int b = 0; b < B; b++) base[b] = pcm[b];
     }
@@ -400,13 +321,7 @@ static int step_s16(nasr_engine *e, nasr_stream *const *streams, int B, const in
 static int record_pcm_tap(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *base, const int32_t *n_samples) {
     size_t total = 0;
     for (int b = 0; b < B; b++) total += (size_t)n_samples[b];
-    if (total > e->tap_pcm_cap) {
-        HIPCHK(hipStreamSynchronize(e->st));
-        if (e->tap_pcm) hipFree(e->tap_pcm);
-        e->tap_pcm = nullptr;
-        e->tap_pcm_cap = total + 65536;
-        HIPCHK(hipMalloc((void **)&e->tap_pcm, e->tap_pcm_cap * 2));
-    }
+    if (grow_device(e, &e->tap_pcm, &e->tap_pcm_cap, total, 65536)) return -1;
     std::fill(e->tap_pcm_n.begin(), e->tap_pcm_n.end(), 0);
     size_t o = 0;
     for (int b = 0; b < B; b++) {
@@ -426,9 +341,7 @@ int step_tail(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
     // A push longer than one launch sequence can take (MAXNEW encoder frames per stream, w_rows rows in all) is
     // cut into pieces of whole chunks; each piece is a multi-chunk step when the streams are aligned.
     const int T = streams[0]->T;
-    int gcap = std::min(MAXNEW / T, e->w_rows / (B * T));
-    if (gcap < 1) gcap = 1;
-    const int64_t piece = (int64_t)gcap * 8 * T * HOP;
+    const int64_t piece = piece_samples(T, B, e->w_rows);
     bool multi = false;
     for (int b = 0; b < B; b++) multi = multi || n_samples[b] > piece;
     if (!multi) return push_piece(e, streams, B, base, n_samples, tokens_out, tokens_cap, n_tokens, flags);
@@ -490,13 +403,7 @@ static int run_audio_convert(nasr_engine *e, std::vector<AudioDesc> &descs, std:
     size_t total = 0;
     long long max_out = 0;
     for (auto &d : descs) { total += (size_t)d.n_out; max_out = std::max(max_out, d.n_out); }
-    if (total > e->pcm_stage_cap) {
-        HIPCHK(hipStreamSynchronize(e->st));
-        if (e->pcm_stage) hipFree(e->pcm_stage);
-        e->pcm_stage = nullptr;
-        e->pcm_stage_cap = total + 65536;
-        HIPCHK(hipMalloc((void **)&e->pcm_stage, e->pcm_stage_cap * 2));
-    }
+    if (grow_device(e, &e->pcm_stage, &e->pcm_stage_cap, total, 65536)) return -1;
     size_t o = 0;
     for (size_t b = 0; b < descs.size(); b++) {
         descs[b].out = e->pcm_stage + o;
@@ -627,33 +534,15 @@ extern "C" int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *stream
     }
     if (!(flags & NASR_FLAG_PCM_DEVICE)) {
         // hand-over of host buffers as in nasr_engine_step: one gather into a rotating pinned block, one copy into the raw staging area
-        if (raw_total > e->raw_stage_cap) {
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (e->raw_stage) hipFree(e->raw_stage);
-            e->raw_stage = nullptr;
-            e->raw_stage_cap = raw_total + 65536;
-            HIPCHK(hipMalloc((void **)&e->raw_stage, e->raw_stage_cap));
-        }
-        auto &pin = e->raw_pin[e->raw_pin_next++ & 3];
-        if (pin.pending) { HIPCHK(hipEventSynchronize(pin.copied)); pin.pending = false; }
-        if (raw_total > pin.cap) {
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (pin.p) hipHostFree(pin.p);
-            pin.p = nullptr;
-            pin.cap = raw_total + 65536;
-            HIPCHK(hipHostMalloc((void **)&pin.p, pin.cap, hipHostMallocDefault));
-        }
+        if (grow_device(e, &e->raw_stage, &e->raw_stage_cap, raw_total, 65536)) return -1;
+        PinBlock &pin = e->raw_pin[e->raw_pin_next++ & 3];
+        if (pin.acquire(raw_total, 65536, e->st)) return -1;
         for (int b = 0; b < B; b++) {
             if (raw_bytes[b] > 0) memcpy(pin.p + raw_off[b], audio[b], raw_bytes[b]);
             descs[b].in = e->raw_stage + raw_off[b];
         }
         ProfScope ps(e, "h2d_pcm", (double)raw_total);
-        if (raw_total > 0) {
-            HIPCHK(hipMemcpyAsync(e->raw_stage, pin.p, raw_total, hipMemcpyHostToDevice, e->st));
-            if (!pin.copied) HIPCHK(hipEventCreateWithFlags(&pin.copied, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(pin.copied, e->st));
-            pin.pending = true;
-        }
+        if (pin.copy_to(e->raw_stage, raw_total, e->st)) return -1;
     } else {
         for (int b = 0; b < B; b++) descs[b].in = audio[b];
     }
@@ -741,12 +630,7 @@ extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams,
         }
         if (pd.empty()) break;
         const size_t need = pd.size() * (size_t)piece * NMEL;
-        if (need > e->mel_stage_cap) {
-            HIPCHK(hipStreamSynchronize(e->st));
-            if (e->mel_stage) hipFree(e->mel_stage);
-            e->mel_stage_cap = need;
-            HIPCHK(hipMalloc((void **)&e->mel_stage, need * 4));
-        }
+        if (grow_device(e, &e->mel_stage, &e->mel_stage_cap, need, 0)) return -1;
         for (size_t i = 0; i < pd.size(); i++)
             HIPCHK(hipMemcpyAsync(e->mel_stage + i * (size_t)piece * NMEL, mel[who[i]] + (size_t)off[who[i]] * NMEL,
                                   (size_t)pd[i].n_frames * NMEL * 4, hipMemcpyHostToDevice, e->st));
@@ -897,6 +781,8 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "graph_shapes")) *value = shapes;
     else if (!strcmp(name, "graph_evictions")) *value = e->graph_evictions;
     else if (!strcmp(name, "graph_replays")) *value = e->graph_replays;
+    else if (!strcmp(name, "decode_fallbacks")) *value = e->decode_fallbacks;              // graph steps whose decode was completed eagerly ...
+    else if (!strcmp(name, "decode_fallback_rounds")) *value = e->decode_fallback_rounds;  // ... and the host round trips that took
     else if (!strcmp(name, "eager_steps")) *value = e->eager_steps;
     else if (!strcmp(name, "pipelined_steps")) *value = e->pipe_steps;
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;

@@ -473,7 +473,22 @@ void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParam
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st) {
     ProfScope ps(e, "k_dec_iter", (double)n * (4.0 * 4 * HID * HID * 4 + (double)JNT * HID * 4 + (double)VOCAB * JNT * 4),
                  (double)n * 2.0 * B * (4.0 * 4 * HID * HID + JNT * HID + VOCAB * JNT));
-    for (int k = 0; k < n; k++) launch_decode_iter(dp, it++, st ? st : e->st);
+    for (int k = 0; k < n; k++) launch_decode_iter(dp, st ? st : e->st);
+    it += n;
+}
+
+int decode_until_idle(nasr_engine *e, const DecParams &dp, int B, hipStream_t st, int *landing, int it, int round, int frames, int64_t *rounds,
+                      const char *what) {
+    while (frames > 0) {
+        if (rounds) ++*rounds;
+        enqueue_decode_iters(e, dp, B, round, it, st);
+        HIPCHK(hipMemcpyAsync(landing, dp.n_active, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (*landing == 0) break;
+        if (it > frames * MAX_SYMBOLS + 64) return fail("%s did not terminate", what);
+        round = std::min(2 * round, 32);      // a burst (up to 10 symbols per frame): double the round, few syncs
+    }
+    return 0;
 }
 
 // host mirror of the stream manager bookkeeping after a chunk (:1085, :1189-1195)
@@ -512,16 +527,8 @@ int run_chunk(nasr_engine *e, const std::vector<nasr_stream *> &rows_s, const st
     launch_decode_begin(dp, st);
     int max_dec = 0;
     for (int b = 0; b < B; b++) max_dec = std::max(max_dec, n_dec[b]);
-    int it = 0, budget = decode_blind_iterations(max_dec);
-    int *h_active = (int *)e->pin;   // first 256 bytes of the pinned arena are reserved for this
-    while (max_dec > 0) {
-        enqueue_decode_iters(e, dp, B, budget, it);
-        HIPCHK(hipMemcpyAsync(h_active, e->n_active, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (*h_active == 0) break;
-        if (it > max_dec * MAX_SYMBOLS + 64) return fail("decode did not terminate");
-        budget = std::min(2 * budget, 32);      // a burst (up to 10 symbols per frame): double the round, few syncs
-    }
+    // the landing word: the first 256 bytes of the pinned arena are reserved for it
+    if (decode_until_idle(e, dp, B, st, (int *)e->pin, 0, decode_blind_iterations(max_dec), max_dec)) return -1;
     for (int b = 0; b < B; b++) chunk_bookkeeping(rows_s[b], b);
     return 0;
 }

@@ -656,10 +656,10 @@ void engine_destroy_impl(nasr_engine *e) {
     if (e->pin) hipHostFree(e->pin);
     if (e->ddesc) hipFree(e->ddesc);
     if (e->pcm_stage) hipFree(e->pcm_stage);
-    for (auto &pin : e->pcm_pin) { if (pin.p) hipHostFree(pin.p); if (pin.copied) hipEventDestroy(pin.copied); }
     if (e->mel_stage) hipFree(e->mel_stage);
     if (e->raw_stage) hipFree(e->raw_stage);
-    for (auto &pin : e->raw_pin) { if (pin.p) hipHostFree(pin.p); if (pin.copied) hipEventDestroy(pin.copied); }
+    for (auto *ring : {e->pcm_pin, e->raw_pin})
+        for (int i = 0; i < 4; i++) { if (ring[i].p) hipHostFree(ring[i].p); if (ring[i].copied) hipEventDestroy(ring[i].copied); }
     if (e->tap_pcm) hipFree(e->tap_pcm);
     if (e->tap_mel) hipFree(e->tap_mel);
     if (e->tap_sub) hipFree(e->tap_sub);

@@ -2,9 +2,13 @@
 // driver, pipeline, graph cache and ABI).  nasr_engine.hip = weights, pools, engine / stream life cycle; nasr_encoder.hip = the
 // chunk step (encoder + decode launch sequences); nasr_pipeline.hip = hipGraph steps, lanes, pipelined and grouped steps;
 // nasr_abi.hip = the step driver and the remaining entry points of include/nemotron_asr_amd.h.  Internal functions live in
-// namespace nasr_eng (nothing but the extern "C" ABI is meant to be bound from outside).
+// namespace nasr_eng (nothing but the extern "C" ABI is meant to be bound from outside).  The host arithmetic of a push is
+// nasr_step_plan.h (pure: namespace nasr_step); what the synchronous, pipelined and grouped graph steps share around their launches
+// is declared below: fill_step_descs, mirror_step, finish_step_decode, decode_until_idle, gp_capture, capture_decode_graph,
+// step_mel_params, lru_victim; the staging helpers grow_device and PinBlock.
 #pragma once
 #include "nasr_internal.h"
+#include "nasr_step_plan.h"
 #include "nemotron_asr_amd.h"
 
 #include <algorithm>
@@ -22,6 +26,7 @@
 #include <vector>
 
 using namespace nasr;
+using namespace nasr_step;
 
 namespace nasr_eng {
 int fail(const char *fmt, ...);                 // fills nasr_last_error() of the calling thread, returns -1
@@ -110,6 +115,15 @@ struct nasr_stream {
     int64_t aud_in = 0, aud_out = 0;       // input frames taken / 16 kHz samples produced since create or reset
     int aud_par = 0;                       // parity of the history buffer that holds the frames before the next push
     bool default_format() const { return fmt.sample_rate == 16000 && fmt.encoding == NASR_AUDIO_S16 && fmt.channels == 1 && fmt.channel == 0; }
+};
+
+// A rotating pinned block of a host hand-over: the streams' buffers are gathered into it and cross PCIe as ONE asynchronous copy.  A block
+// is reused four calls later, so its last copy must have been executed by then (the grouped pipeline keeps eight calls in flight and
+// nothing else orders the host's memcpy behind copy n - 4; in steady state the event is long complete).
+struct PinBlock {
+    char *p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool pending = false;   // copied: recorded behind the block's H2D copy
+    int acquire(size_t bytes, size_t slack, hipStream_t st);      // waits for the block's last copy; grows it (with slack) behind st
+    int copy_to(void *dev, size_t bytes, hipStream_t st);         // p -> dev on st, and the event behind it
 };
 
 struct nasr_engine {
@@ -250,7 +264,7 @@ struct nasr_engine {
     // host PCM hand-over: the streams' buffers are gathered into a pinned block and cross PCIe as ONE copy.  The copy is
     // asynchronous and a pipelined call returns before it has run, so the pinned blocks rotate (a block is reused four
     // calls later; up to pipeline + 1 = 5 steps are in flight, but the copy sits in piece 0 of its step, and the NEXT call launches piece 1 of that step only after the host has seen piece 0 complete).
-    struct { int16_t *p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool pending = false; } pcm_pin[4];   // copied: recorded behind the block's H2D copy
+    PinBlock pcm_pin[4];
     unsigned pcm_pin_next = 0;
     float *mel_stage = nullptr; size_t mel_stage_cap = 0;
     // audio input conversion: per-stream history [slot][2][nasr_rs::HIST_MAX] (allocated with the stream pool), one coefficient table per
@@ -260,7 +274,7 @@ struct nasr_engine {
     bool opt_audio_lds_table = true;        // option "audio_lds_table": k_audio_convert reads the coefficients of the L <= 2 rates from an LDS copy (same bits; 0.343 -> 0.253 ms per step at 512 streams x 48 kHz: profiles/audio_input.md)
     std::map<int, float *> aud_tables;
     char *raw_stage = nullptr; size_t raw_stage_cap = 0;
-    struct { char *p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool pending = false; } raw_pin[4];
+    PinBlock raw_pin[4];
     unsigned raw_pin_next = 0;
     int16_t *tap_pcm = nullptr; size_t tap_pcm_cap = 0;
     std::vector<int64_t> tap_pcm_off, tap_pcm_n;         // per slot: where the last call's samples are in tap_pcm, and how many
@@ -361,6 +375,10 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
 void bind_dec_weights(const nasr_engine *e, DecParams &dp);     // the decoder's weights (prediction net, joint) into dp
 void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp);
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st = nullptr);
+// Rounds of decode iterations on st until no stream is active: `round` iterations, dp.n_active read into *landing, the round doubled (32 at
+// most).  `it` = iterations enqueued so far; more than frames * MAX_SYMBOLS + 64 is the error "<what> did not terminate".  rounds: counted if given
+int decode_until_idle(nasr_engine *e, const DecParams &dp, int B, hipStream_t st, int *landing, int it, int round, int frames,
+                      int64_t *rounds = nullptr, const char *what = "decode");
 void chunk_bookkeeping(nasr_stream *s, int row);
 void fill_row_desc(RowDesc &rd, const nasr_stream *s, int n_dec);
 int run_chunk(nasr_engine *e, const std::vector<nasr_stream *> &rows_s, const std::vector<int> &n_dec);
@@ -373,6 +391,16 @@ int collect_tokens(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *
 int ensure_debug_buffers(nasr_engine *e);
 GraphDescLayout graph_desc_layout(int B, int G);
 int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t *out);
+// the PcmDesc / RowDesc / virtual-row part of the pinned descriptor block gh of a graph step (graph_desc_layout), written in place
+void fill_step_descs(char *gh, nasr_stream *const *streams, int B, int T, int G, const int16_t *const *pcm_dev, const int32_t *n_samples);
+// host mirror of a queued graph step: the audio counts of gh's PcmDescs (audio), the G chunks under one conv-cache flip (chunks); ws_slot = last_ws
+void mirror_step(nasr_stream *const *streams, int B, int T, int G, const char *gh, int ws_slot, bool audio = true, bool chunks = true);
+MelParams step_mel_params(const nasr_engine *e, const PcmDesc *desc, int B, int T, int G);
+int64_t lru_victim(const std::map<int64_t, hipGraphExec_t> &m, const std::map<int64_t, int64_t> &graph_used, int64_t key_tag);
+// What follows a graph step's decode graph, whose k_collect left n_active behind gh_collect's B records: the chained-GEMM give-up flag, the
+// eager completion on st from `iters` iterations on if the graph's budget fell short (and `fallback` allows it), then -- recollect -- k_collect again
+struct StepDecode { const char *g_desc; float *encproj; const int *g_dmeta; int *collect_dev, *gh_collect; int B, T, G; };
+int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int iters, int round, bool fallback, bool recollect);
 int pipe_blind_iterations(int frames, int cap);
 double spin_us(hipStream_t a, hipStream_t b);
 int pick_lanes(nasr_engine *e);
@@ -387,8 +415,8 @@ int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
                      int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens);
 bool gp_eligible(const nasr_engine *e, int B, int T, int G);
 int gp_enqueue_chain(nasr_engine *e, int c, const int *slot_of_stage, int B, int T, int R, int G);
-int gp_capture(nasr_engine *e, hipGraphExec_t *out, const std::function<int()> &body, hipStream_t st);
-int gp_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipGraphExec_t *out);
+int gp_capture(nasr_engine *e, hipGraphExec_t *out, const std::function<int()> &body, hipStream_t st, const char *what);
+int capture_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipStream_t cs, int iters, const char *what, hipGraphExec_t *out);
 int gp_call(nasr_engine *e, int new_slot, int64_t key, int B, int T, int R, int G);
 int gp_finish_decode(nasr_engine *e);
 int gp_drain(nasr_engine *e);
@@ -404,7 +432,6 @@ int step_tail(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
 int ensure_audio_table(nasr_engine *e, const nasr_rs::Plan &p, const float **out);
 void prof_flush(nasr_engine *e);
 __global__ void k_collect(const int *slots, const int *tok_read, int B, const DecCtrl *ctrl, const int *tok_ring, int *out, int stride, const int *n_active);
-inline int max_frames_per_push(int TS) { return 8 * TS + 16; }  // TS = frames of encoder output the push completes (+ what a first push leaves over)
 inline bool streams_overlap(hipStream_t a, hipStream_t b, double alone_us) { return spin_us(a, b) < 1.5 * alone_us; }
 inline bool dec_behind_last_piece(const nasr_engine *e, const nasr_engine::Pipe &P) { return P.nseg >= e->n_lanes; }
 inline hipStream_t dec_stream(nasr_engine *e, const nasr_engine::Pipe &P) { return e->lane[e->n_lanes - 1]; }
@@ -423,6 +450,18 @@ inline int stage_desc(nasr_engine *e, const std::vector<Tp> &host, const Tp **de
     e->pin_off += bytes;
     e->ddesc_off += bytes;
     *dev_out = (const Tp *)dp;
+    return 0;
+}
+// grow-on-demand staging: room for `need` elements (+ slack), behind everything queued on the engine's stream
+template <typename Tp>
+inline int grow_device(nasr_engine *e, Tp **ptr, size_t *cap, size_t need, size_t slack) {
+    if (need <= *cap) return 0;
+    HIPCHK(hipStreamSynchronize(e->st));
+    if (*ptr) hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    HIPCHK(hipMalloc((void **)ptr, (need + slack) * sizeof(Tp)));
+    *cap = need + slack;
     return 0;
 }
 template <typename Tp>

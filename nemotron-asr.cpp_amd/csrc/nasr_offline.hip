@@ -352,15 +352,8 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         if (K) { dp.alt_key = o->alt_key; dp.alt_id = o->alt_id; dp.alt_lp = o->alt_lp; dp.alt_k = K; }
         if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
         launch_decode_begin(dp, st);
-        int it = 0, budget = decode_blind_iterations(max_dec), h_active = 0;
-        while (max_dec > 0) {
-            enqueue_decode_iters(e, dp, n, budget, it);
-            HIPCHK(hipMemcpyAsync(&h_active, o->n_active, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (h_active == 0) break;
-            if (it > max_dec * MAX_SYMBOLS + 64) return fail("offline decode did not terminate");
-            budget = std::min(2 * budget, 32);
-        }
+        int h_active = 0;
+        if (decode_until_idle(e, dp, n, st, &h_active, 0, decode_blind_iterations(max_dec), max_dec, nullptr, "offline decode")) return -1;
         // tokens of this window: at most 256 x 10 < TOK_CAP per slot, so the ring holds all of them
         HIPCHK(hipMemcpyAsync(hctrl.data(), o->ctrl, (size_t)n * sizeof(DecCtrl), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
@@ -507,12 +500,8 @@ static int offline_mel(nasr_engine *e, OfflineState *o, int B, const int16_t *co
                 if (rem <= 0) continue;
                 PcmDesc d;
                 memset(&d, 0, sizeof(d));
-                d.pcm = src[k] + done[k]; d.slot = k; d.n = (int)std::min<int64_t>(rem, MAX_PUSH);
-                d.cnt = cnt[k]; d.par = par[k];
-                const int avail = d.cnt + d.n;
-                d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
-                d.mel_wpos = 0;                                  // every sub-push writes from ring row 0; the frames are copied out below
-                d.consumed = d.n_frames * HOP;
+                d.pcm = src[k] + done[k]; d.slot = k;
+                fill_pcm_counts(d, (int)std::min<int64_t>(rem, MAX_PUSH), cnt[k], par[k], 0, 0);      // every sub-push writes from ring row 0; the frames are copied out below
                 pd.push_back(d); who.push_back(k);
                 max_frames = std::max(max_frames, d.n_frames); max_n = std::max(max_n, d.n);
             }

@@ -9,6 +9,7 @@
 #pragma once
 #include <stdint.h>
 #include <vector>
+#include "nasr_step_plan.h"
 
 namespace nasr_plan {
 
@@ -18,10 +19,7 @@ constexpr int OFFLINE_MAX_UTTS = 256;      // utterances per sub-batch (decoder 
 inline int sub_len(int n) { return n / 2 + 1; }
 // log-mel frames of a whole utterance of n samples = what the reference preprocessor returns for it (src/preprocessor.cpp:320-328:
 // 256 zero samples in front, 512-sample frames every 160 samples)
-inline int mel_frames(int64_t n_samples) {
-    const int64_t avail = 256 + (n_samples > 0 ? n_samples : 0);
-    return avail < 512 ? 0 : (int)((avail - 512) / 160 + 1);
-}
+inline int mel_frames(int64_t n_samples) { return nasr_step::push_frames(256, n_samples > 0 ? n_samples : 0); }
 // most samples whose encoder frames stay within the limit
 inline int64_t max_samples() { return (int64_t)(16377 - 1) * 160 + 512 - 256 + 159; }
 inline int enc_frames(int n_mel) { return n_mel <= 0 ? 0 : sub_len(sub_len(sub_len(n_mel))); }

@@ -1,5 +1,6 @@
 // nasr_pipeline.hip -- hipGraph replay of the steady-state step, the lanes (HIP streams measured to overlap), pipelined steps (engine
-// option "pipeline" = 1..4) and the grouped pipeline (= 8), the bounded graph cache.
+// option "pipeline" = 1..4) and the grouped pipeline (= 8), the bounded graph cache.  In front of them what every graph step shares: the
+// capture wrapper, the descriptor fill and the host mirror, the decode graph of a slot, the completion of a decode (finish_step_decode).
 #include "nasr_engine_priv.h"
 
 // ---- hipGraph replay of the steady-state step ----------------------------------------------------
@@ -19,21 +20,36 @@ GraphDescLayout graph_desc_layout(int B, int G) {
     return l;
 }
 
-int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t *out) {
-    hipStream_t st = e->st;
+MelParams step_mel_params(const nasr_engine *e, const PcmDesc *desc, int B, int T, int G) {
+    MelParams mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.desc = desc; mp.B = B; mp.max_frames = max_frames_per_push(T * G); mp.abuf = e->abuf; mp.last_sample = e->last_sample;
+    mp.mel_ring = e->mel_ring; mp.window = e->window; mp.fbT = e->fbT; mp.fb_band = e->fb_band; mp.cos_t = e->cos_t; mp.sin_t = e->sin_t;
+    return mp;
+}
+
+// the one capture sequence: begin on st, body, end, instantiate; what = the graph's name in the messages ("" or " (... graph)")
+int gp_capture(nasr_engine *e, hipGraphExec_t *out, const std::function<int()> &body, hipStream_t st, const char *what) {
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    auto body = [&]() -> int {
+    const int rc = body();
+    hipError_t ce = hipStreamEndCapture(st, &graph);
+    if (rc) { if (graph) hipGraphDestroy(graph); return -1; }
+    if (ce != hipSuccess) return fail("hipStreamEndCapture%s failed: %s", what, hipGetErrorString(ce));
+    hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (ie != hipSuccess) return fail("hipGraphInstantiate%s failed: %s", what, hipGetErrorString(ie));
+    return 0;
+}
+
+int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t *out) {
+    hipStream_t st = e->st;
+    return gp_capture(e, out, [&]() -> int {
         const GraphDescLayout L = graph_desc_layout(B, G);
         const RowDesc *g_rows = (const RowDesc *)(e->g_desc + L.rows), *g_vrows = (const RowDesc *)(e->g_desc + L.vrows);
-        const PcmDesc *g_pcm = (const PcmDesc *)(e->g_desc + L.pcm);
         const int *g_meta = (const int *)(e->g_desc + L.meta);
         HIPCHK(hipMemcpyAsync(e->g_desc, e->gh, L.total, hipMemcpyHostToDevice, st));
-        MelParams mp;
-        memset(&mp, 0, sizeof(mp));
-        mp.desc = g_pcm; mp.B = B; mp.max_frames = max_frames_per_push(T * G); mp.abuf = e->abuf; mp.last_sample = e->last_sample;
-        mp.mel_ring = e->mel_ring; mp.window = e->window; mp.fbT = e->fbT; mp.fb_band = e->fb_band; mp.cos_t = e->cos_t; mp.sin_t = e->sin_t;
+        const MelParams mp = step_mel_params(e, (const PcmDesc *)(e->g_desc + L.pcm), B, T, G);
         launch_mel(mp, mp.max_frames * HOP + NFFT, st);
         if (enqueue_encoder(e, g_rows, G > 1 ? g_vrows : g_rows, nullptr, B, T, R, G)) return -1;
         DecParams dp;
@@ -44,15 +60,87 @@ int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t 
         hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, st, g_meta, g_meta + B, B, e->ctrl, e->tok_ring, e->collect_dev, COLLECT_STRIDE, e->n_active);
         HIPCHK(hipMemcpyAsync(e->gh_collect, e->collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         return 0;
-    };
-    rc = body();
-    hipError_t ce = hipStreamEndCapture(st, &graph);
-    if (rc) { if (graph) hipGraphDestroy(graph); return -1; }
-    if (ce != hipSuccess) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-    hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-    return 0;
+    }, st, "");
+}
+
+// the least recently used shape of a graph cache (graph_used is keyed by shape key | key_tag)
+int64_t lru_victim(const std::map<int64_t, hipGraphExec_t> &m, const std::map<int64_t, int64_t> &graph_used, int64_t key_tag) {
+    int64_t victim = 0, oldest = INT64_MAX;
+    for (auto &kv : m) {
+        auto u = graph_used.find(kv.first | key_tag);
+        const int64_t t = u == graph_used.end() ? 0 : u->second;
+        if (t < oldest) { oldest = t; victim = kv.first; }
+    }
+    return victim;
+}
+
+void fill_step_descs(char *gh, nasr_stream *const *streams, int B, int T, int G, const int16_t *const *pcm_dev, const int32_t *n_samples) {
+    const GraphDescLayout L = graph_desc_layout(B, G);
+    RowDesc *gh_rows = (RowDesc *)(gh + L.rows), *gh_vrows = (RowDesc *)(gh + L.vrows);
+    PcmDesc *gh_pcm = (PcmDesc *)(gh + L.pcm);
+    for (int b = 0; b < B; b++) {
+        const nasr_stream *s = streams[b];
+        PcmDesc &d = gh_pcm[b];
+        memset(&d, 0, sizeof(d));
+        d.pcm = pcm_dev[b]; d.slot = s->slot;
+        fill_pcm_counts(d, n_samples[b], s->abuf_cnt, s->abuf_par, s->mel_start, s->mel_count);
+        fill_row_desc(gh_rows[b], s, T * G);
+        for (int g = 0; g < G; g++) {
+            RowDesc &v = gh_vrows[b * G + g];
+            v = gh_rows[b];
+            v.mel_start = (s->mel_start + g * 8 * T) & (MEL_RING - 1);
+        }
+    }
+}
+
+void mirror_step(nasr_stream *const *streams, int B, int T, int G, const char *gh, int ws_slot, bool audio, bool chunks) {
+    const PcmDesc *gh_pcm = (const PcmDesc *)(gh + graph_desc_layout(B, G).pcm);
+    for (int b = 0; b < B; b++) {
+        nasr_stream *s = streams[b];
+        if (audio) apply_pcm_counts(gh_pcm[b], s->abuf_cnt, s->abuf_par, s->mel_count);          // every count is a pure function of the samples pushed
+        if (!chunks) continue;
+        const int par = s->cc_par;
+        for (int g = 0; g < G; g++) chunk_bookkeeping(s, b);
+        s->cc_par = par ^ 1;          // one launch = one conv-cache buffer flip, whatever G is
+        s->last_T = T * G; s->last_row = b; s->last_ws = ws_slot;
+    }
+}
+
+// the decode graph of slot p, captured on cs: the k_collect meta, `iters` blind iterations, the token gather into the slot's landing zone
+int capture_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipStream_t cs, int iters, const char *what, hipGraphExec_t *out) {
+    nasr_engine::Pipe &P = e->pipe[p];
+    return gp_capture(e, out, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(P.g_dmeta, P.gh_dmeta, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, cs));
+        DecParams dp;
+        make_dec_params(e, (const RowDesc *)(P.g_desc + graph_desc_layout(B, G).rows), B, T * G, dp);
+        dp.encproj = P.encproj;
+        launch_decode_begin(dp, cs);
+        for (int k = 0; k < iters; k++) launch_decode_iter(dp, cs);
+        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
+        HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));
+        return 0;
+    }, cs, what);
+}
+
+int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int iters, int round, bool fallback, bool recollect) {
+    int *gh_active = d.gh_collect + (size_t)d.B * (1 + COLLECT_STRIDE);      // k_collect appends n_active to its records
+    if (*gh_active < 0) {          // reported once: the flag is cleared so that the steps after this one are judged on their own (advisor, round 5: it was sticky)
+        hipMemsetAsync(e->n_active + 3, 0, sizeof(int), e->st);
+        return fail("a chained GEMM launch gave up waiting for its head workgroups (GemmParams::chain): results of this step are invalid");
+    }
+    if (*gh_active == 0 || !fallback) return 0;
+    // some stream emitted more symbols than the graph's iteration budget: finish eagerly (idle iterations ~10 us each, a round trip ~40 us)
+    DecParams dp;
+    make_dec_params(e, (const RowDesc *)(d.g_desc + graph_desc_layout(d.B, d.G).rows), d.B, d.T * d.G, dp);
+    dp.encproj = d.encproj;
+    e->decode_fallbacks++;
+    if (decode_until_idle(e, dp, d.B, st, gh_active, iters, round, d.T * d.G, &e->decode_fallback_rounds)) return -1;
+    if (recollect) {
+        hipLaunchKernelGGL(k_collect, dim3(d.B), dim3(64), 0, st, d.g_dmeta, d.g_dmeta + d.B, d.B, e->ctrl, e->tok_ring, d.collect_dev, COLLECT_STRIDE, e->n_active);
+        HIPCHK(hipMemcpyAsync(d.gh_collect, d.collect_dev, ((size_t)d.B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return 1;
 }
 
 // ---- pipelined graph steps (engine option "pipeline" = E, 1..4) ----------------------------------------------------------
@@ -171,9 +259,7 @@ int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nse
     const RowDesc *g_rows = (const RowDesc *)(P.g_desc + L.rows), *g_vrows = (const RowDesc *)(P.g_desc + L.vrows);
     const PcmDesc *g_pcm = (const PcmDesc *)(P.g_desc + L.pcm);
     float *const encproj_saved = e->encproj;
-    auto capture = [&](hipStream_t st, const char *what, hipGraphExec_t *out, const std::function<int()> &body) -> int {
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    auto in_slot = [&](auto &&body) -> int {          // the launches below take the slot's workspace set and joint.enc buffer
         e->encproj = P.encproj;
         use_ws(e, e->ws[p]);
 #ifdef NASR_STAMPS
@@ -182,43 +268,26 @@ int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nse
         const int rc = body();
         e->encproj = encproj_saved;
         use_ws(e, e->ws[0]);
-        hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (rc) { if (graph) hipGraphDestroy(graph); return -1; }
-        if (ce != hipSuccess) return fail("hipStreamEndCapture (%s graph) failed: %s", what, hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail("hipGraphInstantiate (%s graph) failed: %s", what, hipGetErrorString(ie));
-        return 0;
+        return rc;
     };
     for (int k = 0; k < nseg; k++) {
         // captured on the engine's stream (the enqueue functions launch there), replayed on lane k
-        if (capture(e->st, "encoder piece", &seg_out[k], [&]() -> int {
-                if (k == 0) {       // descriptors, front end
-                    HIPCHK(hipMemcpyAsync(P.g_desc, P.gh, L.total, hipMemcpyHostToDevice, e->st));
-                    MelParams mp;
-                    memset(&mp, 0, sizeof(mp));
-                    mp.desc = g_pcm; mp.B = B; mp.max_frames = max_frames_per_push(T * G); mp.abuf = e->abuf; mp.last_sample = e->last_sample;
-                    mp.mel_ring = e->mel_ring; mp.window = e->window; mp.fbT = e->fbT; mp.fb_band = e->fb_band; mp.cos_t = e->cos_t; mp.sin_t = e->sin_t;
-                    if (!(e->opt_ablate & 16)) launch_mel(mp, mp.max_frames * HOP + NFFT, e->st);
-                }
-                return enqueue_encoder(e, g_rows, G > 1 ? g_vrows : g_rows, nullptr, B, T, R, G, k, nseg) ? -1 : 0;
-            })) return -1;
+        if (gp_capture(e, &seg_out[k], [&]() -> int {
+                return in_slot([&]() -> int {
+                    if (k == 0) {       // descriptors, front end
+                        HIPCHK(hipMemcpyAsync(P.g_desc, P.gh, L.total, hipMemcpyHostToDevice, e->st));
+                        const MelParams mp = step_mel_params(e, g_pcm, B, T, G);
+                        if (!(e->opt_ablate & 16)) launch_mel(mp, mp.max_frames * HOP + NFFT, e->st);
+                    }
+                    return enqueue_encoder(e, g_rows, G > 1 ? g_vrows : g_rows, nullptr, B, T, R, G, k, nseg) ? -1 : 0;
+                });
+            }, e->st, " (encoder piece graph)")) return -1;
     }
-    // decode graph on the decode stream
-    hipStream_t cs = e->lane[e->n_lanes - 1];       // where the decode graph is captured (it is replayed on dec_stream())
-    if (capture(cs, "decode", dec_out, [&]() -> int {
-            HIPCHK(hipMemcpyAsync(P.g_dmeta, P.gh_dmeta, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, cs));
-            DecParams dp;
-            make_dec_params(e, g_rows, B, T * G, dp);
-            dp.encproj = P.encproj;
-            launch_decode_begin(dp, cs);
-            int it = 0;
-            for (int k = 0, n = (e->opt_ablate & 8) ? 0 : pipe_blind_iterations(T * G, e->opt_decode_graph_iters); k < n; k++) launch_decode_iter(dp, it++, cs);
-            hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
-            HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));
-            return 0;
-        })) return -1;
-    return 0;
+    // decode graph: captured on the last lane, replayed on dec_stream()
+    return in_slot([&]() -> int {
+        return capture_decode_graph(e, p, B, T, G, e->lane[e->n_lanes - 1], (e->opt_ablate & 8) ? 0 : pipe_blind_iterations(T * G, e->opt_decode_graph_iters),
+                                    " (decode graph)", dec_out);
+    });
 }
 
 // next encoder piece of the step in slot p: queued on its lane behind the previous piece's event.  That wait is short in
@@ -265,31 +334,8 @@ int pipe_finish(nasr_engine *e, int p) {
     const int B = (int)P.streams.size(), TS = P.T * P.G;
     hipStream_t ds = dec_stream(e, P);
     { HostTimer ht(e->host_wait_s); HIPCHK(hipEventSynchronize(P.dec_done)); }
-    int *gh_active = P.gh_collect + (size_t)B * (1 + COLLECT_STRIDE);      // k_collect appends n_active to its records
-    if (*gh_active < 0) {          // reported once: the flag is cleared so that the steps after this one are judged on their own (advisor, round 5: it was sticky)
-        hipMemsetAsync(e->n_active + 3, 0, sizeof(int), e->st);
-        return fail("a chained GEMM launch gave up waiting for its head workgroups (GemmParams::chain): results of this step are invalid");
-    }
-    if (*gh_active != 0 && !(e->opt_ablate & 8)) {
-        const GraphDescLayout L = graph_desc_layout(B, P.G);
-        DecParams dp;
-        make_dec_params(e, (const RowDesc *)(P.g_desc + L.rows), B, TS, dp);
-        dp.encproj = P.encproj;
-        int itn = pipe_blind_iterations(TS, e->opt_decode_graph_iters), round = 8;
-        e->decode_fallbacks++;
-        for (;;) {
-            e->decode_fallback_rounds++;
-            enqueue_decode_iters(e, dp, B, round, itn, ds);
-            HIPCHK(hipMemcpyAsync(gh_active, e->n_active, sizeof(int), hipMemcpyDeviceToHost, ds));
-            HIPCHK(hipStreamSynchronize(ds));
-            if (*gh_active == 0) break;
-            if (itn > TS * MAX_SYMBOLS + 64) return fail("decode did not terminate");
-            round = std::min(2 * round, 32);
-        }
-        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, ds, P.g_dmeta, P.g_dmeta + B, B, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
-        HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, ds));
-        HIPCHK(hipStreamSynchronize(ds));
-    }
+    if (finish_step_decode(e, StepDecode{P.g_desc, P.encproj, P.g_dmeta, P.collect_dev, P.gh_collect, B, P.T, P.G}, ds,
+                           pipe_blind_iterations(TS, e->opt_decode_graph_iters), 8, !(e->opt_ablate & 8), true) < 0) return -1;
     P.stage = 0;
     return consume_collect(e, P.gh_collect, P.streams.data(), B);
 }
@@ -308,7 +354,7 @@ int pipe_drain(nasr_engine *e) {
 
 int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm_dev, const int32_t *n_samples, int G,
                      int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens) {
-    const int T = streams[0]->T, R = streams[0]->R, shift = 8 * T;
+    const int T = streams[0]->T, R = streams[0]->R;
     if (ensure_pipe(e, (int)(e->pipe_seq % nasr_engine::LSLOT))) return -1;     // also picks the lanes
     int nseg = std::max(1, std::min({e->opt_pipeline, e->n_lanes, e->max_lanes, (int)nasr_engine::MAXSEG, (int)e->hp.n_layers}));
     // From 3 584 rows a step's GEMMs fill the chip by themselves, and every further lane is another GEMM's working set in the same L2s: fewer
@@ -346,12 +392,7 @@ int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
             nasr_engine::Pipe &Q = e->pipe[q];
             if (Q.seg_graphs[0].count(key)) continue;
             while ((int)Q.seg_graphs[0].size() >= e->opt_graph_cache) {
-                int64_t victim = 0, oldest = INT64_MAX;
-                for (auto &kv : Q.seg_graphs[0]) {
-                    auto u = e->graph_used.find(kv.first | ((int64_t)1 << 62));
-                    const int64_t t = u == e->graph_used.end() ? 0 : u->second;
-                    if (t < oldest) { oldest = t; victim = kv.first; }
-                }
+                const int64_t victim = lru_victim(Q.seg_graphs[0], e->graph_used, (int64_t)1 << 62);
                 for (auto &m : Q.seg_graphs) { auto f = m.find(victim); if (f != m.end()) { if (f->second) hipGraphExecDestroy(f->second); m.erase(f); } }
                 auto f = Q.dec_graphs.find(victim);
                 if (f != Q.dec_graphs.end()) { if (f->second) hipGraphExecDestroy(f->second); Q.dec_graphs.erase(f); }
@@ -370,38 +411,10 @@ int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
         }
         ge = P.seg_graphs[0].find(key);
     }
-    const GraphDescLayout L = graph_desc_layout(B, G);
-    RowDesc *gh_rows = (RowDesc *)(P.gh + L.rows), *gh_vrows = (RowDesc *)(P.gh + L.vrows);
-    PcmDesc *gh_pcm = (PcmDesc *)(P.gh + L.pcm);
-    for (int b = 0; b < B; b++) {
-        nasr_stream *s = streams[b];
-        PcmDesc &d = gh_pcm[b];
-        memset(&d, 0, sizeof(d));
-        d.pcm = pcm_dev[b]; d.slot = s->slot; d.n = n_samples[b]; d.cnt = s->abuf_cnt; d.par = s->abuf_par;
-        const int avail = d.cnt + d.n;
-        d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
-        d.mel_wpos = (s->mel_start + s->mel_count) & (MEL_RING - 1);
-        d.consumed = d.n_frames * HOP;
-        fill_row_desc(gh_rows[b], s, T * G);
-        for (int g = 0; g < G; g++) {
-            RowDesc &v = gh_vrows[b * G + g];
-            v = gh_rows[b];
-            v.mel_start = (s->mel_start + g * shift) & (MEL_RING - 1);
-        }
-    }
+    fill_step_descs(P.gh, streams, B, T, G, pcm_dev, n_samples);
     { HostTimer ht(e->host_launch_s); HIPCHK(hipGraphLaunch(ge->second, e->st)); }
     HIPCHK(hipEventRecord(P.seg_done[0], e->st));
-    for (int b = 0; b < B; b++) {                          // every count is a pure function of the samples pushed
-        nasr_stream *s = streams[b];
-        const PcmDesc &d = gh_pcm[b];
-        s->abuf_cnt = d.cnt + d.n - d.consumed;
-        if (d.n_frames > 0) s->abuf_par ^= 1;
-        s->mel_count += d.n_frames;
-        const int par = s->cc_par;
-        for (int g = 0; g < G; g++) chunk_bookkeeping(s, b);
-        s->cc_par = par ^ 1;
-        s->last_T = T * G; s->last_row = b; s->last_ws = p;
-    }
+    mirror_step(streams, B, T, G, P.gh, p);
     P.stage = 1;
     P.seq = seq;
     P.nseg = nseg;
@@ -465,10 +478,7 @@ int gp_enqueue_chain(nasr_engine *e, int c, const int *slot_of_stage, int B, int
         const hipError_t he = hipMemcpyAsync(P.g_desc, P.gh, L.total, hipMemcpyHostToDevice, e->st);
         if (he != hipSuccess) rc = fail("hipMemcpyAsync (grouped pipeline descriptors) failed: %s", hipGetErrorString(he));
         if (!rc) {
-            MelParams mp;
-            memset(&mp, 0, sizeof(mp));
-            mp.desc = (const PcmDesc *)(P.g_desc + L.pcm); mp.B = B; mp.max_frames = max_frames_per_push(T * G); mp.abuf = e->abuf; mp.last_sample = e->last_sample;
-            mp.mel_ring = e->mel_ring; mp.window = e->window; mp.fbT = e->fbT; mp.fb_band = e->fb_band; mp.cos_t = e->cos_t; mp.sin_t = e->sin_t;
+            const MelParams mp = step_mel_params(e, (const PcmDesc *)(P.g_desc + L.pcm), B, T, G);
             launch_mel(mp, mp.max_frames * HOP + NFFT, e->st);
             rc = enqueue_encoder(e, g_rows, G > 1 ? g_vrows : g_rows, nullptr, B, T, R, G, 0, 1, 1);
         }
@@ -501,39 +511,6 @@ int gp_enqueue_chain(nasr_engine *e, int c, const int *slot_of_stage, int B, int
     e->encproj = encproj_saved;
     use_ws(e, e->ws[0]);
     return rc ? -1 : 0;
-}
-
-int gp_capture(nasr_engine *e, hipGraphExec_t *out, const std::function<int()> &body, hipStream_t st) {
-    hipGraph_t graph = nullptr;
-    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = body();
-    hipError_t ce = hipStreamEndCapture(st, &graph);
-    if (rc) { if (graph) hipGraphDestroy(graph); return -1; }
-    if (ce != hipSuccess) return fail("hipStreamEndCapture (grouped pipeline) failed: %s", hipGetErrorString(ce));
-    hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (ie != hipSuccess) return fail("hipGraphInstantiate (grouped pipeline) failed: %s", hipGetErrorString(ie));
-    return 0;
-}
-
-// the decode graph of slot p (same content as the lanes mode's)
-int gp_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipGraphExec_t *out) {
-    nasr_engine::Pipe &P = e->pipe[p];
-    const GraphDescLayout L = graph_desc_layout(B, G);
-    const RowDesc *g_rows = (const RowDesc *)(P.g_desc + L.rows);
-    hipStream_t cs = e->lane[nasr_engine::GP_C - 1];
-    return gp_capture(e, out, [&]() -> int {
-        HIPCHK(hipMemcpyAsync(P.g_dmeta, P.gh_dmeta, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, cs));
-        DecParams dp;
-        make_dec_params(e, g_rows, B, T * G, dp);
-        dp.encproj = P.encproj;
-        launch_decode_begin(dp, cs);
-        int it = 0;
-        for (int k = 0, n = pipe_blind_iterations(T * G, e->opt_decode_graph_iters); k < n; k++) launch_decode_iter(dp, it++, cs);
-        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
-        HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));
-        return 0;
-    }, cs);
 }
 
 // one call of the grouped pipeline: every step in flight advances one stage (new_slot >= 0: a new step enters at stage 0); the step
@@ -607,31 +584,8 @@ int gp_finish_decode(nasr_engine *e) {
     const int nB = (int)P.streams.size();
     hipStream_t ds = e->lane[nasr_engine::GP_C - 1];
     { HostTimer ht(e->host_wait_s); HIPCHK(hipEventSynchronize(P.dec_done)); }
-    int *gh_active = P.gh_collect + (size_t)nB * (1 + COLLECT_STRIDE);
-    if (*gh_active < 0) {          // reported once: the flag is cleared so that the steps after this one are judged on their own (advisor, round 5: it was sticky)
-        hipMemsetAsync(e->n_active + 3, 0, sizeof(int), e->st);
-        return fail("a chained GEMM launch gave up waiting for its head workgroups (GemmParams::chain): results of this step are invalid");
-    }
-    if (*gh_active != 0) {                                      // a burst beyond the graph's iteration budget: finish eagerly
-        const GraphDescLayout L = graph_desc_layout(nB, P.G);
-        DecParams dp;
-        make_dec_params(e, (const RowDesc *)(P.g_desc + L.rows), nB, P.T * P.G, dp);
-        dp.encproj = P.encproj;
-        int itn = pipe_blind_iterations(P.T * P.G, e->opt_decode_graph_iters), round = 8;
-        e->decode_fallbacks++;
-        for (;;) {
-            e->decode_fallback_rounds++;
-            enqueue_decode_iters(e, dp, nB, round, itn, ds);
-            HIPCHK(hipMemcpyAsync(gh_active, e->n_active, sizeof(int), hipMemcpyDeviceToHost, ds));
-            HIPCHK(hipStreamSynchronize(ds));
-            if (*gh_active == 0) break;
-            if (itn > P.T * P.G * MAX_SYMBOLS + 64) return fail("decode did not terminate");
-            round = std::min(2 * round, 32);
-        }
-        hipLaunchKernelGGL(k_collect, dim3(nB), dim3(64), 0, ds, P.g_dmeta, P.g_dmeta + nB, nB, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
-        HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)nB * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, ds));
-        HIPCHK(hipStreamSynchronize(ds));
-    }
+    if (finish_step_decode(e, StepDecode{P.g_desc, P.encproj, P.g_dmeta, P.collect_dev, P.gh_collect, nB, P.T, P.G}, ds,
+                           pipe_blind_iterations(P.T * P.G, e->opt_decode_graph_iters), 8, true, true) < 0) return -1;
     return consume_collect(e, P.gh_collect, P.streams.data(), nB);
 }
 
@@ -645,7 +599,7 @@ int gp_drain(nasr_engine *e) {
 
 int gp_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm_dev, const int32_t *n_samples, int G,
                    int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens) {
-    const int T = streams[0]->T, R = streams[0]->R, shift = 8 * T;
+    const int T = streams[0]->T, R = streams[0]->R;
     const int64_t key = ((int64_t)B << 40) | ((int64_t)T << 24) | ((int64_t)G << 8) | (int64_t)nasr_engine::GP_S;
     // lanes-mode steps in flight, or grouped steps of another shape or other streams: complete them first
     for (int q = 0; q < nasr_engine::LSLOT; q++)
@@ -672,7 +626,7 @@ int gp_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *c
             if (ensure_pipe(e, q)) return -1;
             if (e->pipe[q].dec_graphs.count(key)) continue;
             hipGraphExec_t dec = nullptr;
-            if (gp_decode_graph(e, q, B, T, G, &dec)) return -1;
+            if (capture_decode_graph(e, q, B, T, G, e->lane[nasr_engine::GP_C - 1], pipe_blind_iterations(T * G, e->opt_decode_graph_iters), " (grouped pipeline)", &dec)) return -1;
             e->pipe[q].dec_graphs[key] = dec;
         }
         for (int q = 0; q < nasr_engine::NSLOT; q++) {
@@ -680,41 +634,13 @@ int gp_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *c
             for (int j = 0; j < nasr_engine::GP_S; j++) sos[j] = (q - j + 2 * nasr_engine::NSLOT) % nasr_engine::NSLOT;
             for (int c = 0; c < nasr_engine::GP_C; c++) {
                 hipGraphExec_t ex = nullptr;
-                if (gp_capture(e, &ex, [&]() -> int { return gp_enqueue_chain(e, c, sos, B, T, R, G); }, e->st)) return -1;
+                if (gp_capture(e, &ex, [&]() -> int { return gp_enqueue_chain(e, c, sos, B, T, R, G); }, e->st, " (grouped pipeline)")) return -1;
                 e->gp_graphs[q][c][key] = ex;
             }
         }
     }
-    const GraphDescLayout L = graph_desc_layout(B, G);
-    RowDesc *gh_rows = (RowDesc *)(P.gh + L.rows), *gh_vrows = (RowDesc *)(P.gh + L.vrows);
-    PcmDesc *gh_pcm = (PcmDesc *)(P.gh + L.pcm);
-    for (int b = 0; b < B; b++) {
-        nasr_stream *s = streams[b];
-        PcmDesc &d = gh_pcm[b];
-        memset(&d, 0, sizeof(d));
-        d.pcm = pcm_dev[b]; d.slot = s->slot; d.n = n_samples[b]; d.cnt = s->abuf_cnt; d.par = s->abuf_par;
-        const int avail = d.cnt + d.n;
-        d.n_frames = avail < NFFT ? 0 : (avail - NFFT + HOP) / HOP;
-        d.mel_wpos = (s->mel_start + s->mel_count) & (MEL_RING - 1);
-        d.consumed = d.n_frames * HOP;
-        fill_row_desc(gh_rows[b], s, T * G);
-        for (int g = 0; g < G; g++) {
-            RowDesc &v = gh_vrows[b * G + g];
-            v = gh_rows[b];
-            v.mel_start = (s->mel_start + g * shift) & (MEL_RING - 1);
-        }
-    }
-    for (int b = 0; b < B; b++) {                          // every count is a pure function of the samples pushed
-        nasr_stream *s = streams[b];
-        const PcmDesc &d = gh_pcm[b];
-        s->abuf_cnt = d.cnt + d.n - d.consumed;
-        if (d.n_frames > 0) s->abuf_par ^= 1;
-        s->mel_count += d.n_frames;
-        const int par = s->cc_par;
-        for (int g = 0; g < G; g++) chunk_bookkeeping(s, b);
-        s->cc_par = par ^ 1;
-        s->last_T = T * G; s->last_row = b; s->last_ws = p;
-    }
+    fill_step_descs(P.gh, streams, B, T, G, pcm_dev, n_samples);
+    mirror_step(streams, B, T, G, P.gh, p);
     P.streams.assign(streams, streams + B);
     P.T = T; P.G = G; P.key = key; P.seq = -1; P.stage = 0;
     if (gp_call(e, p, key, B, T, R, G)) return -1;
