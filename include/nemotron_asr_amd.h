@@ -163,6 +163,15 @@ int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t 
  * [count][K] row-major; same contract as nasr_stream_get_token_logprobs: completes steps in flight, tokens counted from
  * create/reset, only the most recent 4096 kept, returns the number of TOKENS written, < 0 on error (also when the option is off) */
 int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t first, int32_t count, int32_t *ids_out, float *logprobs_out);
+/* per-frame blank log-probabilities (the reference has no such output; engine option "frame_blank_logprobs" = 1): for encoder frames
+ * [first, first + count) of this stream, counted from create/reset (both reset modes restart the count at 0), ln P(blank) under the joint's
+ * softmax over all 1025 outputs at the LAST joint evaluation the greedy decode made on that frame: usually the one where blank won, the value
+ * then in [-ln 1025, 0]; on a frame left by the cap of 10 symbols the evaluation that emitted the 10th, the value then any finite number <= 0.
+ * With phrase boosting it stays the MODEL's probability (blank never gets a bonus).  Frames of the nasr_engine_finalize tail are included.
+ * Same contract as nasr_stream_get_token_logprobs: completes steps in flight, returns the number written, < 0 on error -- also when the option
+ * is off.  Only the most recent 4096 frames are kept: a range whose first frame is older returns 0.  With out == NULL it returns the number of
+ * frames decoded so far. */
+int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out);
 /* phrase boosting for this stream (engine option "phrase_boost"; default: enabled).  Completes steps in flight.  Every call, with either
  * value, resets the stream's boost history (the emitted tokens a phrase can continue from), not its decoder state.  Fails when the option is off. */
 int nasr_stream_set_boost(nasr_stream *s, int enable);
@@ -309,7 +318,14 @@ enum {
  * (nasr_stream_get_token_alternatives, nasr_engine_offline_token_alternatives).  The ranking is the model's also under "phrase_boost": the
  * emitted token then need not be entry 0; without phrases it is.  The results for K are the first K columns of those for any larger K.
  * Tokens, frames, iteration counts and decoder state are bit-identical to 0.  It selects the decode kernels that are captured into the step
- * graphs and allocates two rings per stream, so it is REJECTED after the first step or offline call. */
+ * graphs and allocates two rings per stream, so it is REJECTED after the first step or offline call.
+ * "frame_blank_logprobs" (0 default / 1): a capability like "token_logprobs" and independent of it -- with 1 the device decode also keeps, for
+ * every encoder frame it has finished, the natural-log softmax probability of BLANK over the 1025 joint outputs at the last joint evaluation
+ * it made on that frame (nasr_stream_get_frame_blank_logprobs, nasr_engine_offline_frame_blank_logprobs): the frame-level silence signal an
+ * endpoint detector needs (csrc/nasr_endpoint.h).  Under "phrase_boost" the value stays the model's.  Tokens, frames, iteration counts, decoder
+ * state and the values of "token_logprobs" / "token_alternatives" are bit-identical to 0.  It selects the decode kernels that are captured
+ * into the step graphs (those of "token_logprobs" plus one small launch per iteration) and allocates a ring per stream, so it is REJECTED
+ * after the first step or offline call. */
 int nasr_engine_set_option(nasr_engine *e, const char *key, int value);
 /* replaces the engine's boost set (engine option "phrase_boost" = N): phrase i = tokens[i][0 .. lens[i]), 1 .. 32 non-blank token ids
  * (0 .. 1023), with bonus[i], finite, 0 < bonus <= 1e4, in natural-log units (added to the joint's logits).  n_phrases = 0 clears the set.
@@ -384,6 +400,10 @@ int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, flo
  * token, see nasr_stream_get_token_logprobs).  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
  * call forgets the values of the one before. */
 int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
+/* ln P(blank) at the last joint evaluation of every encoder frame of utterance u of the LAST offline call (either entry; engine option
+ * "frame_blank_logprobs" = 1): out[t], t = 0 .. T - 1, see nasr_stream_get_frame_blank_logprobs.  Returns the number written (<= cap), with
+ * out == NULL the number available (T), or < 0.  Every offline call forgets the values of the one before. */
+int nasr_engine_offline_frame_blank_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
 /* the K alternatives (engine option "token_alternatives" = K) of every token of
  * utterance u of the LAST offline call; cap in tokens; ids_out == NULL: the number available.  [tokens][K] row-major, row i belongs to
  * tokens_out[u][i].  Returns the number of tokens written (<= cap) or < 0.  Every offline call forgets the values of the one before. */

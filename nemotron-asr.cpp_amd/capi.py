@@ -40,6 +40,7 @@ EXPORTS = [
     "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
     "nasr_stream_get_token_alternatives", "nasr_engine_offline_token_alternatives",
     "nasr_engine_align_mel", "nasr_engine_align", "nasr_engine_align_lattice",
+    "nasr_stream_get_frame_blank_logprobs", "nasr_engine_offline_frame_blank_logprobs",
     "nasr_stream_set_audio_format", "nasr_engine_step_audio", "nasr_engine_convert_audio", "nasr_audio_out_ready", "nasr_audio_out_total",
 ]
 ALIGN_MAX_TOKENS = 1024
@@ -142,6 +143,8 @@ def lib():
         L.nasr_stream_set_boost.argtypes = [vp, C.c_int]
         L.nasr_stream_get_token_alternatives.argtypes = [vp, C.c_int64, C.c_int32, ip, C.POINTER(C.c_float)]
         L.nasr_engine_offline_token_alternatives.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_float), C.c_int32]
+        L.nasr_stream_get_frame_blank_logprobs.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
+        L.nasr_engine_offline_frame_blank_logprobs.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
         dp = C.POINTER(C.c_double)
         L.nasr_engine_align_mel.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
         L.nasr_engine_align.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
@@ -264,6 +267,15 @@ class Stream:
         lps = np.zeros((max(count, 1), max(K, 1)), np.float32)
         n = _chk(lib().nasr_stream_get_token_alternatives(self.h, first, count, ids.ctypes.data_as(C.POINTER(C.c_int32)), lps.ctypes.data_as(C.POINTER(C.c_float))))
         return ids[:n].copy(), lps[:n].copy()
+
+    def frame_blank_logprobs(self, first=0, count=None) -> np.ndarray:
+        """ln P(blank) under the joint's softmax at the last joint evaluation of encoder frames [first, first + count) since create/reset
+        (count None: up to the last frame decoded), f32; needs engine option "frame_blank_logprobs" = 1 (set before the first step)"""
+        if count is None:
+            count = max(_chk(lib().nasr_stream_get_frame_blank_logprobs(self.h, 0, 0, None)) - first, 0)
+        out = np.zeros(max(count, 1), np.float32)
+        n = _chk(lib().nasr_stream_get_frame_blank_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:n].copy()
 
     def set_boost(self, enable=True):
         """phrase boosting on / off for this stream (engine option "phrase_boost"); either way its boost history restarts"""
@@ -676,6 +688,15 @@ class Engine:
         cap = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, None, 0))
         out = np.zeros(max(cap, 1), np.float32)
         n = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
+        return out[:n].copy()
+
+    def offline_frame_blank_logprobs(self, u) -> np.ndarray:
+        """ln P(blank) at the last joint evaluation of every encoder frame of utterance u of the last offline call (engine option
+        "frame_blank_logprobs" = 1)"""
+        L = lib()
+        cap = _chk(L.nasr_engine_offline_frame_blank_logprobs(self.h, u, None, 0))
+        out = np.zeros(max(cap, 1), np.float32)
+        n = _chk(L.nasr_engine_offline_frame_blank_logprobs(self.h, u, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
         return out[:n].copy()
 
     # ---- measurement ------------------------------------------------------------------

@@ -526,12 +526,27 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 }
 
 // ---- commit: walk each stream's evaluated frames up to its first non-blank -------------------------
-template <bool LP, bool BOOST, bool ALT>
+// FB (engine option "frame_blank_logprobs", always with LP): first the whole workgroup, one thread per rowmap row, leaves ln P(blank) of every row
+// this iteration's joint kernel evaluated in fb_row (indexed like key; nasr_lp::blank_lp over the row's softmax parts, whose last part is blank
+// alone; one writer per element).  That is row-parallel work inside the launch that exists: as a kernel of its own between the joint and the
+// commit it cost a launch slot in EVERY iteration of a captured decode, idle ones included -- 10 % of a pipelined 1-stream step against 6 %
+// here, 0.9 % against 0.6 % at 64 streams x R = 13 (profiles/frame_blank.md).  Then the stream's thread copies the values of the frames this iteration leaves -- [t0, new t): the blanks
+// before the token, every frame when there is no token, and the token's own frame when it reaches MAX_SYMBOLS.  All of them are in rowmap
+// (build_lists lists every frame from t to n_frames), so the value copied is that of the LAST evaluation on the frame
+template <bool LP, bool BOOST, bool ALT, bool FB>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
+    static_assert(LP || !FB, "the blank log-probabilities come from the softmax parts");
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
     const int nd = *p.n_dirty;
     for (int i = threadIdx.x; i < nd; i += 256) p.ctrl[p.rows[p.dlist[i]].slot].dirty = 0;   // candidates are fresh now
+    if (FB) {
+        const int nr = *p.n_rows, np = nasr_lp::n_parts(p.B * p.T);
+        for (int i = threadIdx.x; i < nr; i += 256) {
+            const int ki = nasr_lp::key_index(p.rowmap[i], p.T);
+            p.fb_row[ki] = (float)nasr_lp::blank_lp(p.lp_part + nasr_lp::scratch_index(ki, 0, np), np);
+        }
+    }
     __syncthreads();
     for (int b = threadIdx.x; b < p.B; b += 256) {
         const int slot = p.rows[b].slot;
@@ -591,6 +606,11 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
             ct->symbols = sym;
             if (t >= nf) ct->active = 0;
         }
+        if (FB) {
+            float *ring = p.frame_blank + (size_t)slot * FRAME_CAP;
+            const int t1 = ct->t, g0 = ct->frame0;
+            for (int g = t0; g < t1; g++) ring[(unsigned)(g0 + g) & (unsigned)(FRAME_CAP - 1)] = p.fb_row[(size_t)b * p.T + g];
+        }
     }
     __threadfence_block();
     build_lists(p, sh);
@@ -647,7 +667,13 @@ static void launch_joint_commit(const DecParams &p, hipStream_t st) {
     const int rows = p.B * p.T;
     if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT>), dim3(1), dim3(256), 0, st, p);
+    if constexpr (LP) {
+        if (p.frame_blank) {                           // "frame_blank_logprobs": the commit variant that also fills the ring
+            hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, true>), dim3(1), dim3(256), 0, st, p);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, false>), dim3(1), dim3(256), 0, st, p);
 }
 void launch_decode_candidates(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
@@ -663,7 +689,8 @@ void launch_decode_iter(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
     // engine options "token_logprobs" (lp_part) and "phrase_boost" (boost_bonus): the variants that also leave the softmax parts / the token's
     // log-probability, and that add the phrase bonus to the arg-max key; with both off these are the kernels without either.  "token_alternatives"
-    // (alt_key; lp_part comes with it) takes the variants that also leave every slice's largest keys / the token's K best outputs
+    // (alt_key; lp_part comes with it) takes the variants that also leave every slice's largest keys / the token's K best outputs.
+    // "frame_blank_logprobs" (frame_blank; lp_part comes with it) takes the commit variant that also fills the ring (launch_joint_commit)
     if (p.alt_key) { if (p.boost_bonus) launch_joint_commit<true, true, true>(p, st); else launch_joint_commit<true, false, true>(p, st); }
     else if (p.lp_part) { if (p.boost_bonus) launch_joint_commit<true, true, false>(p, st); else launch_joint_commit<true, false, false>(p, st); }
     else { if (p.boost_bonus) launch_joint_commit<false, true, false>(p, st); else launch_joint_commit<false, false, false>(p, st); }

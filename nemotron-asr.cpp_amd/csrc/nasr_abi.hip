@@ -111,6 +111,19 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         }
         e->opt_token_alt = value;
     }
+    else if (!strcmp(key, "frame_blank_logprobs")) {
+        // like "token_alternatives": picks the decode launches that get captured (the LP kernels and the commit variant that fills
+        // the ring) and allocates the scratch and a ring per stream; the softmax parts' buffers come with it
+        if (value != 0 && value != 1) return fail("frame_blank_logprobs must be 0 or 1");
+        if (e->dec_started || e->off) return fail("frame_blank_logprobs must be set before the first step or offline call (the decode kernels are already chosen)");
+        if (value && !e->frame_blank) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (!e->lp_part && (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP))) return -1;
+            if (dalloc(e, &e->fb_row, (size_t)e->w_rows) || dalloc(e, &e->frame_blank, (size_t)e->max_streams * FRAME_CAP)) return -1;
+        }
+        e->opt_frame_blank = value != 0;
+    }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
     else if (!strcmp(key, "wide_min_rows")) e->opt_wide_min_rows = value;
@@ -735,6 +748,28 @@ extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t firs
     std::vector<float> ring(TOK_CAP);
     HIPCHK(hipMemcpy(ring.data(), e->tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
+    return count;
+}
+
+extern "C" int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out) {
+    ApiGuard api_guard;
+    if (!s) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative frame range");
+    nasr_engine *e = s->e;
+    if (!e->opt_frame_blank) return fail("no per-frame blank log-probabilities: engine option \"frame_blank_logprobs\" is off (set it to 1 before the first step)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    HIPCHK(hipStreamSynchronize(e->st));
+    DecCtrl c;
+    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    const int64_t n_frames = (int64_t)c.frame0 + c.t;          // frames the decode has left since create / reset
+    if (!out) return (int)n_frames;
+    if (first + count > n_frames) count = first < n_frames ? (int32_t)(n_frames - first) : 0;
+    if (n_frames - first > FRAME_CAP) return 0;               // the range starts before the most recent FRAME_CAP frames: nothing of it can be written from its first frame on
+    if (count <= 0) return 0;
+    std::vector<float> ring(FRAME_CAP);
+    HIPCHK(hipMemcpy(ring.data(), e->frame_blank + (size_t)s->slot * FRAME_CAP, FRAME_CAP * sizeof(float), hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (FRAME_CAP - 1))];
     return count;
 }
 

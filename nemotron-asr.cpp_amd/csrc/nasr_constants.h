@@ -37,6 +37,7 @@ constexpr int ABUF_CAP = MAX_PUSH + NFFT + 64;
 constexpr int MAX_KS   = 32;          // max depthwise kernel size supported
 constexpr int FUSE_MAX_M = 2;         // rows up to which attention / depthwise conv are fused into the following GEMM's prologue
 constexpr int TOK_CAP  = 4096;        // per-stream device token ring between collects
+constexpr int FRAME_CAP = 4096;       // per-stream device ring of per-frame blank log-probabilities (engine option "frame_blank_logprobs"): 5.5 minutes of 80 ms frames
 
 // ---- per-step descriptors (uploaded by the host for every launch sequence) -----------
 struct RowDesc {          // one per batch row (= stream taking part in this chunk step)

@@ -464,10 +464,11 @@ void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParam
     bind_dec_weights(e, dp);
     dp.predg = e->predg; dp.key = e->key; dp.n_active = e->n_active; dp.n_dirty = e->n_active + 1; dp.n_rows = e->n_active + 2;
     dp.dlist = e->dlist; dp.rowmap = e->rowmap; dp.tok_ring = e->tok_ring; dp.tok_frame = e->tok_frame;
-    if (e->opt_token_logprobs || e->opt_token_alt) { dp.lp_part = e->lp_part; dp.tok_logprob = e->tok_logprob; }
+    if (e->opt_token_logprobs || e->opt_token_alt || e->opt_frame_blank) { dp.lp_part = e->lp_part; dp.tok_logprob = e->tok_logprob; }
+    if (e->opt_frame_blank) { dp.fb_row = e->fb_row; dp.frame_blank = e->frame_blank; }
     if (e->opt_token_alt) { dp.alt_key = e->alt_key; dp.alt_id = e->alt_id; dp.alt_lp = e->alt_lp; dp.alt_k = e->opt_token_alt; }
     if (e->opt_phrase_boost) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = e->boost_state; dp.boost_raw = e->boost_raw; }
-    e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost" and "token_alternatives" are no longer taken
+    e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost", "token_alternatives" and "frame_blank_logprobs" are no longer taken
 }
 
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st) {

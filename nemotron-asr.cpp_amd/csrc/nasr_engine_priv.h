@@ -256,6 +256,13 @@ struct nasr_engine {
     int opt_token_alt = 0, alt_cap = 0;                            // K in use, K the buffers were allocated for
     unsigned long long *alt_key = nullptr;                         // scratch beside lp_part: [row][slice][K] largest keys of every vocab slice
     int32_t *alt_id = nullptr; float *alt_lp = nullptr;            // [slot][TOK_CAP][K] each, beside tok_ring / tok_frame / tok_logprob
+    // option "frame_blank_logprobs": ln P(blank) at the last joint evaluation of every frame the decode has left.  Taken like "token_alternatives"
+    // (LP kernels, so lp_part / tok_logprob are allocated with it).  The ring is indexed by the absolute frame number since create / reset and is
+    // never cleared: nasr_stream_get_frame_blank_logprobs clips to the frames decoded since then (DecCtrl::frame0 + t, which k_stream_reset
+    // zeroes), so what an earlier stream or an earlier life of this one left in a slot's ring is never visible
+    bool opt_frame_blank = false;
+    float *fb_row = nullptr;         // scratch beside key: [w_rows] ln P(blank) of the rows of a decode iteration
+    float *frame_blank = nullptr;    // [slot][FRAME_CAP]
     int *collect_dev;                // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;

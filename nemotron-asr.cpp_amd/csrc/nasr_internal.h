@@ -232,6 +232,9 @@ struct DecParams {
     int32_t *alt_id;             // [slot][TOK_CAP][alt_k] ids of the alt_k largest joint outputs where each token was emitted, descending
     float *alt_lp;               // [slot][TOK_CAP][alt_k] their natural-log softmax probabilities
     int alt_k;
+    // engine option "frame_blank_logprobs" (both null when it is off; lp_part and the LP kernels come with it)
+    float *fb_row;               // [B * T] indexed like key: ln P(blank) of every row the iteration's joint kernel evaluated (k_dec_commit, FB)
+    float *frame_blank;          // [slot][FRAME_CAP] ring by absolute frame number: the value at the last evaluation of every frame the decode has left
 };
 void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, hipStream_t st);

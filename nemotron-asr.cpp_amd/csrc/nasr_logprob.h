@@ -103,6 +103,28 @@ NASR_LP_HD float finish(float logit, const Part *parts, int n_parts) {
     return (logit - m) - logf(s);
 }
 
+// engine option "frame_blank_logprobs": lp of BLANK from a row's parts.  Blank is vocabulary entry 1024 = LP_VOCAB - 1, and in both layouts the last
+// part holds that entry alone: 1024 = 64 * 16 is entry 0 of tile 64 (the 65th part of width 16), whose other 15 entries lie past the vocabulary,
+// and 1024 = 16 * 64 is entry 0 of workgroup 16 (the 17th part of width 64), whose tiles 65 .. 67 do not exist (empty parts).  lane4 with one valid
+// entry leaves m = that entry, and merging with empty parts keeps m, so parts[n_parts - 1].m is blank's raw logit bit for bit and the joint kernels
+// need nothing new.  Blank never gets a phrase bonus, so the raw logit is also what the arg-max saw.
+static_assert((LP_VOCAB - 1) % TILE_W == 0 && (LP_VOCAB - 1) / TILE_W == TILE_PARTS - 1, "blank is alone in the last 16-entry part");
+static_assert((LP_VOCAB - 1) % WG_W == 0 && (LP_VOCAB - 1) / WG_W == WG_PARTS - 1, "blank is alone in the last 64-entry part");
+// blank_lp = finish(parts[n_parts - 1].m, parts, n_parts): the same parts in the same ascending order, but the sum, the difference and the
+// logarithm are taken in f64 and the caller rounds to f32 once (k_dec_commit).  Two reasons, both specific to blank.  Blank is mostly NOT
+// the arg-max where a token is emitted, so logit - m is not 0 and the value can be large (-150 at a sharp joint): an f32 subtraction there
+// rounds at half an ulp of 128 .. 256 = 7.6e-6, and the final one again.  And where blank does not win many parts contribute the same small
+// term, which an f32 running sum rounds the same way 65 times over: 3.5e-6 on the "large negative logits" row of tests/test_frame_blank_math.py.
+// In f64 the value stays within 2e-6 of the float64 softmax at every magnitude and the ring holds its nearest f32.  One thread does this once
+// per evaluated row, at most 65 terms: the wider arithmetic costs nothing measurable
+NASR_LP_HD double blank_lp(const Part *parts, int n_parts) {
+    float m = neg_inf();
+    for (int i = 0; i < n_parts; i++) m = fmaxf(m, parts[i].m);
+    double s = 0.0;
+    for (int i = 0; i < n_parts; i++) s += (double)(parts[i].s * expf(parts[i].m - m));
+    return ((double)parts[n_parts - 1].m - (double)m) - log(s);
+}
+
 // host restatement of what a kernel leaves in the scratch for one row: `width` = TILE_W or WG_W, out[n_parts_of_width(width)]
 NASR_LP_HD int parts_of_width(int width) { return (LP_VOCAB + width - 1) / width; }
 NASR_LP_HD Part tile_of(const float *logits, int nt) {                  // 16-entry tile nt of a row's 1025 logits

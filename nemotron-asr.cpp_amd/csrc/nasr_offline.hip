@@ -32,6 +32,8 @@ struct OfflineState {
     bool no_boost = false;                                         // NASR_FLAG_NO_BOOST of the call in progress
     unsigned long long *alt_key = nullptr; int32_t *alt_id = nullptr; float *alt_lp = nullptr;      // engine option "token_alternatives"
     std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // ... of the last call, by utterance: [tokens][K] each
+    float *fb_row = nullptr, *frame_blank = nullptr;               // engine option "frame_blank_logprobs": scratch [U * W] and a ring [U][FRAME_CAP] (T <= 2048 < FRAME_CAP)
+    std::vector<std::vector<float>> frame_blank_lps;               // ... of the last call, by utterance: [T] (nasr_engine_offline_frame_blank_logprobs)
     std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
     // forced alignment (nasr_engine_align*): the prediction-network rows g, the lattice of the sub-batch in flight (two values and one
     // back-pointer byte per cell), its descriptors and its results
@@ -142,7 +144,11 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
             rc |= off_alloc(o, (void **)&o->alt_id, U * TOK_CAP * e->opt_token_alt * 4);
             rc |= off_alloc(o, (void **)&o->alt_lp, U * TOK_CAP * e->opt_token_alt * 4);
         }
-        if (e->opt_token_logprobs || e->opt_token_alt) {
+        if (e->opt_frame_blank) {
+            rc |= off_alloc(o, (void **)&o->fb_row, U * W * 4);
+            rc |= off_alloc(o, (void **)&o->frame_blank, U * FRAME_CAP * 4);
+        }
+        if (e->opt_token_logprobs || e->opt_token_alt || e->opt_frame_blank) {
             rc |= off_alloc(o, (void **)&o->lp_part, nasr_lp::scratch_parts((int)(U * W)) * sizeof(nasr_lp::Part));
             rc |= off_alloc(o, (void **)&o->tok_logprob, U * TOK_CAP * 4);
         }
@@ -325,6 +331,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
     std::vector<DecCtrl> hctrl(n);
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
     std::vector<float> ringl(e->opt_token_logprobs ? (size_t)n * TOK_CAP : 0);
+    std::vector<float> ringb(e->opt_frame_blank ? (size_t)n * FRAME_CAP : 0);
     const int K = e->opt_token_alt;
     std::vector<int32_t> ringai((size_t)n * TOK_CAP * K);
     std::vector<float> ringal((size_t)n * TOK_CAP * K);
@@ -350,6 +357,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
         dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs" or "token_alternatives"
         if (K) { dp.alt_key = o->alt_key; dp.alt_id = o->alt_id; dp.alt_lp = o->alt_lp; dp.alt_k = K; }
+        dp.fb_row = o->fb_row; dp.frame_blank = o->frame_blank;         // null unless "frame_blank_logprobs"
         if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
         launch_decode_begin(dp, st);
         int h_active = 0;
@@ -359,6 +367,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
         HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ringf.data(), o->tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
         if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!ringb.empty()) HIPCHK(hipMemcpyAsync(ringb.data(), o->frame_blank, ringb.size() * 4, hipMemcpyDeviceToHost, st));
         if (K) {
             HIPCHK(hipMemcpyAsync(ringai.data(), o->alt_id, ringai.size() * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(ringal.data(), o->alt_lp, ringal.size() * 4, hipMemcpyDeviceToHost, st));
@@ -379,6 +388,12 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const float *const
                 }
             }
             tok_read[k] = hctrl[k].n_tok;
+            // the frames of this window: the slot's frame count starts at 0 with the utterance, so frame g sits at ring position g
+            if (!ringb.empty()) {
+                const int nd = std::min(std::max(T[k] - w0, 0), OFF_DEC_WIN);
+                if (hctrl[k].frame0 + hctrl[k].t != w0 + nd && nd > 0) return fail("offline decode left %d frames of utterance %d, expected %d", hctrl[k].frame0 + hctrl[k].t, first + k, w0 + nd);
+                for (int g = w0; g < w0 + nd; g++) o->frame_blank_lps[first + k].push_back(ringb[(size_t)k * FRAME_CAP + (g & (FRAME_CAP - 1))]);
+            }
         }
     }
     if (e->debug && fetch_offline_taps(e, o, ob)) return -1;
@@ -415,6 +430,7 @@ static int transcribe_core(nasr_engine *e, int B, const float *const *mel, const
     }
     if (ensure_offline_pos(e, o)) return -1;
     o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
+    o->frame_blank_lps.assign(e->opt_frame_blank ? B : 0, {});
     o->alt_ids.assign(e->opt_token_alt ? B : 0, {}); o->alt_lps.assign(e->opt_token_alt ? B : 0, {});
     if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
     std::vector<std::vector<int32_t>> toks(B), frs(B);
@@ -442,7 +458,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     if (!e->off) e->off = new OfflineState();
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
-    o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear();
+    o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear(); o->frame_blank_lps.clear();
     o->lat_valid = false; o->lat_b.clear(); o->lat_t.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
     return 0;
@@ -609,6 +625,19 @@ extern "C" int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *
     OfflineState *o = e->off;
     if (!o || u < 0 || u >= (int)o->logprobs.size()) return fail("no offline token log-probabilities of utterance %d (they are those of the last offline call)", u);
     const std::vector<float> &src = o->logprobs[u];
+    if (!out) return (int)src.size();                       // size query
+    const int n = std::min<int>((int)src.size(), std::max(cap, 0));
+    memcpy(out, src.data(), (size_t)n * 4);
+    return n;
+}
+
+extern "C" int nasr_engine_offline_frame_blank_logprobs(nasr_engine *e, int u, float *out, int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->opt_frame_blank) return fail("no per-frame blank log-probabilities: engine option \"frame_blank_logprobs\" is off (set it to 1 before the first step or offline call)");
+    OfflineState *o = e->off;
+    if (!o || u < 0 || u >= (int)o->frame_blank_lps.size()) return fail("no offline blank log-probabilities of utterance %d (they are those of the last offline call)", u);
+    const std::vector<float> &src = o->frame_blank_lps[u];
     if (!out) return (int)src.size();                       // size query
     const int n = std::min<int>((int)src.size(), std::max(cap, 0));
     memcpy(out, src.data(), (size_t)n * 4);

@@ -74,6 +74,64 @@ std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx) {
     return out;
 }
 
+std::vector<float> nemo_stream_get_frame_blank_logprobs(nemo_stream_context *sctx) {
+    std::vector<float> out;
+    if (!sctx) return out;
+    const int n = nasr_stream_get_frame_blank_logprobs(sctx->stream, 0, 0, nullptr);      // frames decoded so far
+    if (n < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
+    const int first = n > 4096 ? n - 4096 : 0;          // older values have left the device ring
+    std::vector<float> lp((size_t)(n - first) + 1);
+    const int got = nasr_stream_get_frame_blank_logprobs(sctx->stream, first, n - first, lp.data());
+    if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
+    out.assign((size_t)first, NAN);
+    out.insert(out.end(), lp.begin(), lp.begin() + got);
+    return out;
+}
+
+bool nemo_stream_set_endpointing(nemo_stream_context *sctx, const nasr_endpoint::Config *cfg) {
+    if (!sctx) return false;
+    const int n = nasr_stream_get_frame_blank_logprobs(sctx->stream, 0, 0, nullptr);      // fails when the option is off
+    nasr_stream_stats stats;
+    if (n < 0 || nasr_stream_get_stats(sctx->stream, &stats) < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return false; }
+    sctx->ep_on = true;
+    sctx->ep_cfg = cfg ? *cfg : nasr_endpoint::Config();
+    sctx->ep_state = nasr_endpoint::State();
+    sctx->ep_state.utt_start = n;
+    sctx->ep_frames = n;
+    sctx->ep_tokens = stats.tokens;
+    sctx->ep_events.clear();
+    return true;
+}
+
+const std::vector<nasr_endpoint::Event> &nemo_stream_get_endpoints(nemo_stream_context *sctx) {
+    static const std::vector<nasr_endpoint::Event> empty;
+    if (!sctx || !sctx->ep_on) return empty;
+    const int n = nasr_stream_get_frame_blank_logprobs(sctx->stream, 0, 0, nullptr);
+    nasr_stream_stats stats;
+    if (n < 0 || nasr_stream_get_stats(sctx->stream, &stats) < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return sctx->ep_events; }
+    if (n <= sctx->ep_frames) return sctx->ep_events;
+    // the new frames' values (those that have left the ring: NaN, not silent) and the frames of the device's new tokens, in token order
+    const int64_t first = std::max<int64_t>(sctx->ep_frames, (int64_t)n - 4096);
+    std::vector<float> lp((size_t)(n - first));
+    if (nasr_stream_get_frame_blank_logprobs(sctx->stream, first, (int32_t)(n - first), lp.data()) != n - first) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return sctx->ep_events; }
+    const int64_t tok_first = std::max<int64_t>(sctx->ep_tokens, (int64_t)stats.tokens - 4096);
+    std::vector<int32_t> tf((size_t)(stats.tokens - tok_first) + 1);
+    const int got = nasr_stream_get_token_frames(sctx->stream, tok_first, (int32_t)(stats.tokens - tok_first), tf.data());
+    if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return sctx->ep_events; }
+    size_t ti = 0;
+    int carried = (int)(tok_first - sctx->ep_tokens);      // tokens whose frames have left the ring: counted on the first new frame
+    for (int64_t f = sctx->ep_frames; f < n; f++) {
+        int on_frame = carried;
+        carried = 0;
+        while (ti < (size_t)got && tf[ti] <= f) { on_frame++; ti++; }
+        nasr_endpoint::Event ev;
+        if (nasr_endpoint::advance(sctx->ep_state, sctx->ep_cfg, f, f >= first ? lp[(size_t)(f - first)] : NAN, on_frame, &ev)) sctx->ep_events.push_back(ev);
+    }
+    sctx->ep_frames = n;
+    sctx->ep_tokens = stats.tokens;
+    return sctx->ep_events;
+}
+
 nemo_token_alternatives nemo_stream_get_token_alternatives(nemo_stream_context *sctx) {
     nemo_token_alternatives out;
     if (!sctx || !sctx->nctx || sctx->nctx->token_alternatives <= 0) return out;
@@ -173,6 +231,15 @@ nemo_context *nemo_init(const char *model_path) { return nemo_init_with_device(m
 bool nemo_set_token_logprobs(nemo_context *ctx, bool on) {
     if (!ctx || !ctx->engine) return false;
     if (nasr_engine_set_option(ctx->engine, "token_logprobs", on ? 1 : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool nemo_set_frame_blank_logprobs(nemo_context *ctx, bool on) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "frame_blank_logprobs", on ? 1 : 0) < 0) {
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return false;
     }
@@ -489,6 +556,9 @@ void nemo_stream_reset(nemo_stream_context *sctx) {
     sctx->transcript.clear();
     sctx->total_audio_seconds = sctx->total_compute_seconds = 0;
     sctx->total_chunks_processed = 0;
+    sctx->ep_state = nasr_endpoint::State();          // the engine's frame and token counts restart at 0 with the reset
+    sctx->ep_frames = sctx->ep_tokens = 0;
+    sctx->ep_events.clear();
 }
 
 void nemo_stream_free(nemo_stream_context *sctx) {

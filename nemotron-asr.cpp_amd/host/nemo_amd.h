@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "nasr_endpoint.h"          // csrc/: the endpoint detector, pure host code
+
 struct nasr_engine;
 struct nasr_stream;
 
@@ -52,6 +54,12 @@ struct nemo_stream_context {        // reference src/nemo-stream.h:177-262 (host
     int prompt_index = -1;
     int audio_rate = 16000, audio_encoding = 0, audio_channels = 1, audio_channel = 0;      // nemo_stream_set_audio_format (default: s16 16 kHz mono)
     std::vector<int> tokens;
+    // nemo_stream_set_endpointing / nemo_stream_get_endpoints: the detector's state, the frames and device tokens it has consumed, the events so far
+    bool ep_on = false;
+    nasr_endpoint::Config ep_cfg;
+    nasr_endpoint::State ep_state;
+    int64_t ep_frames = 0, ep_tokens = 0;
+    std::vector<nasr_endpoint::Event> ep_events;
     std::string transcript;
     double total_audio_seconds = 0, total_compute_seconds = 0;
     int total_chunks_processed = 0;
@@ -70,6 +78,9 @@ bool nemo_set_language(nemo_context *ctx, const char *lang);  // default prompt 
 // next; nemo_stream_process_incremental then returns each text delta one call later, nemo_stream_finalize returns the rest
 // MI355X extension: per-token log-probabilities (nasr_engine_set_option "token_logprobs"); before the first stream processes audio
 bool nemo_set_token_logprobs(nemo_context *ctx, bool on);
+// MI355X extension: per-frame blank log-probabilities (nasr_engine_set_option "frame_blank_logprobs"), the input of the endpoint detector; before
+// the first stream processes audio
+bool nemo_set_frame_blank_logprobs(nemo_context *ctx, bool on);
 // MI355X extension: the K = 1 .. 8 most probable joint outputs at every emission (nasr_engine_set_option "token_alternatives"; 0 = off); before
 // the first stream processes audio
 bool nemo_set_token_alternatives(nemo_context *ctx, int k);
@@ -141,6 +152,17 @@ std::vector<timed_token> nemo_stream_get_timed_tokens(nemo_stream_context *sctx)
 // ln P(token) of every token of the stream since init/reset (needs nemo_set_token_logprobs; NaN for tokens that have left the
 // engine's 4096-token ring, as their frame is -1); word confidences from them: word_confidence.h
 std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx);
+// ln P(blank) at the last joint evaluation of every encoder frame of the stream since init/reset (needs nemo_set_frame_blank_logprobs; NaN for
+// frames that have left the engine's 4096-frame ring).  Completes steps in flight
+std::vector<float> nemo_stream_get_frame_blank_logprobs(nemo_stream_context *sctx);
+// endpointing (csrc/nasr_endpoint.h; needs nemo_set_frame_blank_logprobs): nemo_stream_set_endpointing turns it on with the given rules (nullptr:
+// the defaults) and restarts the detector at the stream's next frame.  nemo_stream_get_endpoints completes steps in flight, runs the detector
+// over the frames decoded since the last call -- their blank log-probabilities and the frames of the device's tokens (timed_token.frame_idx) --
+// and returns every event since set_endpointing / reset: utterance = frames [utt_start, frame], `tokens` tokens; the utterances' tokens follow one
+// another in the stream's token order, so utterance i starts at token sum(tokens of events before i).  Call it at least every 4096 frames
+// (5.5 minutes): frames that have left the engine's ring count as not silent
+bool nemo_stream_set_endpointing(nemo_stream_context *sctx, const nasr_endpoint::Config *cfg);
+const std::vector<nasr_endpoint::Event> &nemo_stream_get_endpoints(nemo_stream_context *sctx);
 // the K alternatives of every token of the stream since init/reset (needs nemo_set_token_alternatives): row i of ids / logprobs [n_tokens][k]
 // belongs to token i, descending probability, ids 0 .. 1024 (1024 = blank), logprobs = ln P; tokens that have left the engine's
 // 4096-token ring get ids -1 and NaN.  k = 0 and empty when the option is off

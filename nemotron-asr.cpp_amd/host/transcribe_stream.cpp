@@ -25,7 +25,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
             "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
@@ -41,6 +41,11 @@ static void usage(const char *prog) {
             "                   with K = 1 .. 8 pairs: i = the token's index from 0, then the K most probable joint outputs at that emission (id 1024 =\n"
             "                   blank: the model nearly emitted nothing) with p = their softmax probability as %%.4f, in descending order; without\n"
             "                   --boost-file the first id is the token.  The first line and the --print-tokens line stay as they are\n"
+            "  --endpoints:     after the transcript one line per utterance, `endpoint <start s> <end s> rule <r> tokens <n>:<text>`: the stream cut where the\n"
+            "                   decoder says the speaker stopped.  rule 1: silence with nothing decoded, 2: silence after speech, 3: maximum length, 0: the\n"
+            "                   open utterance at the end of the audio (only if it has tokens).  A frame (80 ms) is silent if it emitted no token and\n"
+            "                   P(blank) >= --endpoint-blank-prob P (default 0: every token-less frame).  --endpoint-silence S (rule 2, default 1.2 s),\n"
+            "                   --endpoint-idle S (rule 1, default 2.4 s), --endpoint-max S (rule 3, default 20 s); 0 disables a rule\n"
             "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
             "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
             "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
@@ -60,6 +65,8 @@ int main(int argc, char **argv) {
     bool print_tokens = false, timestamps = false, confidence = false;
     const char *boost_file = nullptr;
     int alternatives = 0;
+    bool endpoints = false;
+    nasr_endpoint::Config ep_cfg;
     float boost_bonus = 4.0f;
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
@@ -76,6 +83,11 @@ int main(int argc, char **argv) {
         else if (a == "--timestamps") timestamps = true;
         else if (a == "--confidence") confidence = true;
         else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
+        else if (a == "--endpoints") endpoints = true;
+        else if (a == "--endpoint-silence" && i + 1 < argc) ep_cfg.silence_frames_after_speech = (int)std::lround(atof(argv[++i]) / 0.08);
+        else if (a == "--endpoint-idle" && i + 1 < argc) ep_cfg.silence_frames_idle = (int)std::lround(atof(argv[++i]) / 0.08);
+        else if (a == "--endpoint-max" && i + 1 < argc) ep_cfg.max_utterance_frames = (int)std::lround(atof(argv[++i]) / 0.08);
+        else if (a == "--endpoint-blank-prob" && i + 1 < argc) { const double pb = atof(argv[++i]); ep_cfg.min_blank_logprob = pb > 0.0 ? (float)std::log(pb) : -INFINITY; }
         else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
         else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
         else if (a == "--cpu" || a == "--cuda" || a == "--metal")      // reference src/transcribe_stream.cpp:86-88
@@ -117,6 +129,7 @@ int main(int argc, char **argv) {
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
     if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
+    if (endpoints && !nemo_set_frame_blank_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable per-frame blank log-probabilities\n"); nemo_free(ctx); return 1; }
     if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
@@ -124,6 +137,8 @@ int main(int argc, char **argv) {
     cfg.att_right_context = right_context;
     nemo_stream_context *sctx = nemo_stream_init(ctx, &cfg);
     if (!sctx) { fprintf(stderr, "Failed to create streaming context\n"); nemo_free(ctx); return 1; }
+
+    if (endpoints && !nemo_stream_set_endpointing(sctx, &ep_cfg)) { fprintf(stderr, "Failed to enable endpointing\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
 
     diarize_pipeline *dp = nullptr;
     if (!diarize_gguf.empty()) {                       // reference :146-170
@@ -248,6 +263,19 @@ int main(int argc, char **argv) {
             for (int j = 0; j < alt.k; j++) printf(" %d:%.4f", alt.ids[i * alt.k + j], std::exp((double)alt.logprobs[i * alt.k + j]));
             printf("\n");
         }
+    }
+    if (endpoints) {
+        const std::vector<nasr_endpoint::Event> evs = nemo_stream_get_endpoints(sctx);
+        const std::vector<int> &all = nemo_stream_get_tokens(sctx);
+        size_t t0i = 0;
+        auto line = [&](int64_t start, int64_t end, int rule, size_t n_tok) {
+            const size_t a = std::min(t0i, all.size()), b = std::min(t0i + n_tok, all.size());
+            printf("endpoint %.2f %.2f rule %d tokens %zu:%s\n", (double)start * 0.08, (double)end * 0.08, rule, n_tok,
+                   tokens_to_text(std::vector<int>(all.begin() + (long)a, all.begin() + (long)b), ctx->vocab).c_str());
+            t0i += n_tok;
+        };
+        for (const nasr_endpoint::Event &ev : evs) line(ev.utt_start, ev.frame + 1, ev.rule, (size_t)ev.tokens);
+        if (sctx->ep_state.tokens > 0) line(sctx->ep_state.utt_start, sctx->ep_frames, 0, (size_t)sctx->ep_state.tokens);
     }
     if (print_tokens) {
         printf("TOKENS:");
