@@ -443,6 +443,38 @@ int nasr_engine_align(nasr_engine *e, int B, const int16_t *const *pcm, const in
  * pointer, with both NULL the number available, or < 0.  Every align call or offline call forgets the lattice of the call before. */
 int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_blank_out, float *lp_token_out, int64_t cap);
 
+/* ---- frame-synchronous beam search (offline): the N best DISTINCT transcripts of each utterance with comparable scores.  The rules are
+ * csrc/nasr_beam.h: per encoder frame up to max_symbols rounds; in a round every hypothesis of the active set A
+ * arrives in the frame's set C with its score + ln P(blank), and A's successors are the `beam` best of the children (parent + token) over
+ * each parent's largest non-blank joint outputs; C keeps its `beam` best and is the next frame's A.  Two arrivals with the same token
+ * sequence are one hypothesis -- the higher score stays, with that path's frames -- so a score is always the score of ONE lattice path,
+ * final blank of every frame included: a double sum of the f32 ln-softmax values nasr_engine_align_lattice exposes, never above `best`
+ * of nasr_engine_align for that transcript.  Better = the higher score; among equal scores the earlier arrival wins.
+ * beam = 1 is NOT the greedy decode of nasr_engine_transcribe: greedy emits the arg-max whenever it is not blank, the search may drop a
+ * token whose continuation scores below the blank.  Phrase boosting ("phrase_boost") is NOT applied in beam calls: the scores are the
+ * model's probabilities, as in alignment.  An utterance with no encoder frame gives one hypothesis: empty, score 0.
+ * The contract is that of nasr_engine_transcribe(_mel): the same encoder, frame-count rule and NASR_OFFLINE_MAX_FRAMES failure, the same
+ * packing into sub-batches of "offline_rows", the call completes steps in flight, touches no stream state, runs eagerly and rejects
+ * NASR_FLAG_NO_SYNC; results are bit-identical whatever else is in the batch.  nasr_engine_offline_tap works after a beam call made with
+ * debug on.  Bad parameters fail the call with a message and leave the engine usable. */
+typedef struct nasr_beam_params {
+    int32_t beam;          /* W, 1 .. 8 */
+    int32_t nbest;         /* N, 1 .. beam; 0 = beam */
+    int32_t max_symbols;   /* S, 1 .. 10: tokens one frame may take; 0 = the default, 4 */
+    int32_t reserved;      /* 0 */
+} nasr_beam_params;
+/* n_hyps[b] = hypotheses found for utterance b, 1 .. nbest (fewer than nbest only when the search kept fewer) */
+int nasr_engine_transcribe_beam_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, const int32_t *prompt_index,
+                                    const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags);
+/* the same from s16 PCM: pcm / n_samples and NASR_FLAG_PCM_DEVICE as for nasr_engine_transcribe */
+int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples, const int32_t *prompt_index,
+                                const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags);
+/* hypothesis `rank` (0 = best) of utterance u of the LAST beam call: returns its token count and writes min(count, cap) tokens, encoder
+ * frames and per-token ln P; *score_out = its score.  Any pointer may be NULL (cap 0: the count).  < 0 for a bad u or rank.  Every offline,
+ * align or beam call forgets the hypotheses of the call before. */
+int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens_out, int32_t *frames_out, float *token_logprobs_out,
+                                int32_t cap, double *score_out);
+
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =
  * the tensors of diarize.gguf ("vad.*" and/or "spk.*", F32, layouts of scripts/convert_diarize_to_gguf.py:129-158),

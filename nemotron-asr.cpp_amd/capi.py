@@ -42,8 +42,10 @@ EXPORTS = [
     "nasr_engine_align_mel", "nasr_engine_align", "nasr_engine_align_lattice",
     "nasr_stream_get_frame_blank_logprobs", "nasr_engine_offline_frame_blank_logprobs",
     "nasr_stream_set_audio_format", "nasr_engine_step_audio", "nasr_engine_convert_audio", "nasr_audio_out_ready", "nasr_audio_out_total",
+    "nasr_engine_transcribe_beam_mel", "nasr_engine_transcribe_beam", "nasr_engine_beam_hypothesis",
 ]
 ALIGN_MAX_TOKENS = 1024
+BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
 FLAG_NO_BOOST = 1 << 3
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
@@ -53,6 +55,11 @@ class HParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_mels", "d_model", "n_heads", "d_head", "d_ff", "n_layers", "vocab_size", "decoder_dim",
         "joint_dim", "subsampling_factor", "att_left_context", "kernel_size", "num_prompts")]
+
+
+class BeamParams(C.Structure):
+    """nasr_beam_params: beam W in 1 .. 8, nbest N in 1 .. W (0 = W), max_symbols S in 1 .. 10 (0 = the default, 4)"""
+    _fields_ = [(n, C.c_int32) for n in ("beam", "nbest", "max_symbols", "reserved")]
 
 
 class WeightDesc(C.Structure):
@@ -150,6 +157,9 @@ def lib():
         L.nasr_engine_align.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
         L.nasr_engine_align_lattice.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64]
         L.nasr_engine_align_lattice.restype = C.c_int64
+        L.nasr_engine_transcribe_beam_mel.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(BeamParams), ip, C.c_uint32]
+        L.nasr_engine_transcribe_beam.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(BeamParams), ip, C.c_uint32]
+        L.nasr_engine_beam_hypothesis.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.POINTER(C.c_float), C.c_int32, dp]
         L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
         L.nasr_engine_step_audio.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_convert_audio.argtypes = [vp, C.POINTER(AudioFormat), vp, C.c_int64, vp, C.c_int64, C.c_uint32]
@@ -654,6 +664,48 @@ class Engine:
         fp = C.POINTER(C.c_float)
         n = _chk(L.nasr_engine_align_lattice(self.h, u, b.ctypes.data_as(fp), t.ctypes.data_as(fp), n))
         return b[:n].reshape(-1, U + 1).copy(), t[:n].reshape(-1, U + 1).copy()
+
+    # ---- beam search: N-best offline transcripts -------------------------------------------------
+    def beam_hypothesis(self, u, rank):
+        """hypothesis `rank` of utterance u of the last beam call: (score, tokens, frames, token_logprobs)"""
+        L = lib()
+        n = _chk(L.nasr_engine_beam_hypothesis(self.h, u, rank, None, None, None, 0, None))
+        tok, fr, lp = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        score = C.c_double(0.0)
+        ipt = C.POINTER(C.c_int32)
+        n = _chk(L.nasr_engine_beam_hypothesis(self.h, u, rank, tok.ctypes.data_as(ipt), fr.ctypes.data_as(ipt), lp.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(score)))
+        return float(score.value), tok[:n].tolist(), fr[:n].tolist(), lp[:n].copy()
+
+    def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags):
+        B = len(ns)
+        pr = (C.c_int32 * B)(*[int(p) for p in prompts]) if prompts is not None else None
+        params = BeamParams(int(beam), int(nbest), int(max_symbols), 0)
+        nh = (C.c_int32 * B)()
+        _chk(fn(self.h, B, ptrs, (C.c_int32 * B)(*[int(v) for v in ns]), pr, C.byref(params), nh, flags))
+        return [[self.beam_hypothesis(b, r) for r in range(nh[b])] for b in range(B)]
+
+    def transcribe_beam_mel(self, mels, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0):
+        """frame-synchronous beam search over whole utterances (mels as for transcribe_mel): per utterance the list, best first, of
+        (score, tokens, frames, token_logprobs) of its nbest distinct transcripts (nbest 0 = beam; max_symbols 0 = the default).  Beam 1
+        is not the greedy decode, and phrase boosting is not applied (include/nemotron_asr_amd.h)."""
+        if len(mels) == 0:
+            return []
+        arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._beam(lib().nasr_engine_transcribe_beam_mel, ptrs, [a.shape[0] for a in arrs], beam, nbest, max_symbols, prompts, flags)
+
+    def transcribe_beam(self, pcms, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0):
+        """the same from int16 PCM, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE)"""
+        if len(pcms) == 0:
+            return []
+        if flags & FLAG_PCM_DEVICE:
+            ptrs = (C.c_void_p * len(pcms))(*[p for p, _ in pcms])
+            ns = [n for _, n in pcms]
+        else:
+            arrs = [np.ascontiguousarray(p, np.int16) for p in pcms]
+            ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+            ns = [a.size for a in arrs]
+        return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags)
 
     def set_boost_phrases(self, phrases, bonus=None):
         """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token

@@ -1,0 +1,135 @@
+// kernels_beam.hip -- frame-synchronous beam search of the offline path (nasr_engine_transcribe_beam*; the rules, the trie, the slot
+// binding and the backtrace are nasr_beam.h, shared with the host and tested there).
+//   k_beam_init     the root hypothesis of every utterance: fresh decoder state in slot 0, frame 0's encoder row, the first work lists
+//   k_beam_select   one round of one utterance per workgroup, between two evaluations (launch_decode_rows: the decode's own LSTM / joint.pred
+//                   launches over the new hypotheses, then k_dec_joint_tiled in its LP + ALT form over every live hypothesis):
+//                   merges the alternatives' slices of each of the <= W rows and finishes their ln P from the softmax parts, applies the C / D
+//                   rules in double, creates the trie nodes, gathers each child's committed state from its parent's candidate state, rebinds
+//                   the rows' slots and lists the rows of the next evaluation
+//   k_beam_final    the N best of Beam_T: tokens, frames, ln P and scores
+// The host enqueues T_max * (S + 1) rounds blind; a finished utterance's workgroup returns at once and lists nothing.  No kernel waits on
+// another workgroup: the lists of the next evaluation are filled through two atomic tickets per utterance, and the counters alternate between
+// two pairs -- round r's evaluation reads pair r & 1, its select zeroes that pair (one thread; nobody adds to it in this launch) and adds to
+// the other.  The order inside the lists is that of the tickets; every row of the evaluation is an independent accumulation chain, so the
+// order cannot change a result.  Every loop bound is a launch parameter or at most W * 8, except same_seq's walk, bounded by the length.
+#include "nasr_internal.h"
+
+namespace nasr {
+
+using nasr_beam::Beam;
+using nasr_beam::KTOP;
+using nasr_beam::WMAX;
+
+__device__ __forceinline__ void beam_fresh_ctrl(DecCtrl *ct, int prev_token) {
+    DecCtrl d;
+    d.t = 0; d.n_frames = 0; d.symbols = 0; d.prev_token = prev_token;
+    d.cur = 0; d.n_tok = 0; d.active = 0; d.iterations = 0; d.row = 0;
+    d.dirty = 1; d.frame0 = 0; d.frame_next = 0;
+    *ct = d;
+}
+
+__global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
+    const int k = blockIdx.x, W = p.W, slot0 = k * nasr_beam::n_slots(W);
+    const BeamUtt ud = p.utt[k];
+    for (int i = threadIdx.x; i < 4 * HID; i += 256) { p.h[(size_t)slot0 * 4 * HID + i] = 0.f; p.c[(size_t)slot0 * 4 * HID + i] = 0.f; }
+    for (int i = threadIdx.x; i < W * JNT; i += 256)
+        p.enc[((size_t)k * W + i / JNT) * JNT + i % JNT] = p.encproj[(size_t)ud.enc_row * JNT + i % JNT];
+    if (threadIdx.x == 0) {
+        Beam bm;
+        nasr_beam::beam_begin(bm, ud.T);
+        p.beam[k] = bm;
+        beam_fresh_ctrl(&p.ctrl[slot0], BLANK);
+        p.rows[k * W].slot = slot0;
+        p.dlist[atomicAdd(&p.cnt_next[0], 1)] = k * W;
+        p.rowmap[atomicAdd(&p.cnt_next[1], 1)] = (unsigned)(k * W);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
+    __shared__ Beam bm;
+    __shared__ float lb[WMAX], ex_lp[WMAX * KTOP];
+    __shared__ int32_t ex_tok[WMAX * KTOP];
+    __shared__ int ex_n[WMAX];
+    __shared__ nasr_beam::Child ch[WMAX];
+    __shared__ nasr_beam::Hyp sel[WMAX];
+    __shared__ int n_ch, adv;
+    const int k = blockIdx.x, W = p.W, slot0 = k * nasr_beam::n_slots(W);
+    if (k == 0 && threadIdx.x < 2) p.cnt_zero[threadIdx.x] = 0;
+    const BeamUtt ud = p.utt[k];
+    if (threadIdx.x == 0) bm = p.beam[k];
+    __syncthreads();
+    if (bm.t >= bm.T) return;                                 // finished (the same answer in every thread)
+    if ((int)threadIdx.x < bm.na) {                           // one thread per live hypothesis: its row's ln P(blank) and expansion list
+        const int j = threadIdx.x, row = k * W + j;
+        const nasr_lp::Part *parts = p.lp_part + nasr_lp::scratch_index(row, 0, nasr_lp::WG_PARTS);
+        float m, log_s;
+        nasr_topk::row_softmax(parts, nasr_lp::WG_PARTS, &m, &log_s);
+        lb[j] = (float)nasr_lp::blank_lp(parts, nasr_lp::WG_PARTS);
+        nasr_topk::RowTop rt;
+        nasr_topk::row_begin(rt);
+        nasr_topk::row_merge(rt, KTOP, p.alt_key + nasr_topk::scratch_index(row, 0, nasr_lp::WG_PARTS, KTOP), nasr_lp::WG_PARTS);
+        ex_n[j] = nasr_beam::expand(rt.top, W, m, log_s, ex_tok + j * KTOP, ex_lp + j * KTOP);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bool a = false;
+        int n = nasr_beam::round_step(bm, W, p.S, p.prune != 0, lb, ex_tok, ex_lp, ex_n, p.nodes + ud.node0, nasr_beam::node_bound(ud.T, W, p.S), ch, &a, sel);
+        if (n < 0) { *p.err = 1; bm.t = bm.T; n = 0; }       // cannot happen within node_bound; the utterance stops and the host reports it
+        n_ch = n; adv = a ? 1 : 0;
+        p.beam[k] = bm;
+        const int live = bm.t < bm.T ? bm.na : 0;
+        if (live > 0) {
+            const int base = atomicAdd(&p.cnt_next[1], live);
+            for (int j = 0; j < live; j++) {
+                p.rows[k * W + j].slot = slot0 + bm.a[j].slot;
+                p.rowmap[base + j] = (unsigned)(k * W + j);
+            }
+        }
+        if (n > 0) {
+            const int base = atomicAdd(&p.cnt_next[0], n);
+            for (int j = 0; j < n; j++) {
+                p.dlist[base + j] = k * W + j;
+                beam_fresh_ctrl(&p.ctrl[slot0 + ch[j].slot], ch[j].token);
+            }
+        }
+    }
+    __syncthreads();
+    // each child's committed state (version 0 of its slot) = its parent's candidate (version 1 of the parent's slot): h', c' -> h, c
+    for (int i = threadIdx.x; i < n_ch * 2 * HID; i += 256) {
+        const int j = i / (2 * HID), el = i % (2 * HID);
+        const size_t src = ((size_t)(slot0 + ch[j].parent_slot) * 2 + 1) * 2 * HID + el, dst = ((size_t)(slot0 + ch[j].slot) * 2) * 2 * HID + el;
+        p.h[dst] = p.h[src];
+        p.c[dst] = p.c[src];
+    }
+    if (adv && bm.t < bm.T)                                   // the next frame's encoder row, once per row of the utterance
+        for (int i = threadIdx.x; i < W * JNT; i += 256)
+            p.enc[((size_t)k * W + i / JNT) * JNT + i % JNT] = p.encproj[(size_t)(ud.enc_row + bm.t) * JNT + i % JNT];
+}
+
+__global__ __launch_bounds__(64) void k_beam_final(BeamParams p) {
+    const int k = blockIdx.x, r = threadIdx.x;
+    const BeamUtt ud = p.utt[k];
+    const Beam *bm = &p.beam[k];
+    const int n = bm->na < p.N ? bm->na : p.N;
+    if (r == 0) p.out_n[k] = bm->t >= bm->T ? n : -1;         // -1: the rounds enqueued did not finish the utterance
+    if (r >= n) return;
+    const long long cap = (long long)ud.T * p.S;
+    const nasr_beam::Hyp h = bm->a[r];
+    p.out_len[k * WMAX + r] = h.len;
+    p.out_score[k * WMAX + r] = h.score;
+    if (h.len > cap) return;
+    const long long at = ud.out0 + (long long)r * cap;
+    nasr_beam::backtrace(p.nodes + ud.node0, h.node, h.len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
+}
+
+void launch_beam_init(const BeamParams &p, hipStream_t st) {
+    if (p.n > 0) hipLaunchKernelGGL(k_beam_init, dim3(p.n), dim3(256), 0, st, p);
+}
+void launch_beam_select(const BeamParams &p, hipStream_t st) {
+    if (p.n > 0) hipLaunchKernelGGL(k_beam_select, dim3(p.n), dim3(256), 0, st, p);
+}
+void launch_beam_final(const BeamParams &p, hipStream_t st) {
+    if (p.n > 0) hipLaunchKernelGGL(k_beam_final, dim3(p.n), dim3(64), 0, st, p);
+}
+
+}  // namespace nasr

@@ -680,6 +680,12 @@ void launch_decode_candidates(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
 }
+// beam search (kernels_beam.hip): the candidates of the rows in dlist, then the tiled joint with softmax parts and alternatives over rowmap --
+// always this kernel, so the logits of a row do not depend on how many rows the sub-batch has
+void launch_decode_rows(const DecParams &p, hipStream_t st) {
+    launch_decode_candidates(p, st);
+    hipLaunchKernelGGL((k_dec_joint_tiled<true, false, true>), dim3((VOCAB + 63) / 64, (p.B * p.T + 63) / 64), dim3(256), 0, st, p);
+}
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a
 // blindly enqueued (graph-captured) sequence cost only their launch slots.

@@ -7,6 +7,7 @@
 #include "nasr_boost.h"
 #include "nasr_topk.h"
 #include "nasr_align.h"
+#include "nasr_beam.h"
 #include "nasr_resample.h"
 
 namespace nasr {
@@ -270,6 +271,31 @@ struct AlignRecParams {
     int32_t *frames; float *tok_lp;   // [sum U]
 };
 void launch_align_recursion(const AlignRecParams &p, int n, hipStream_t st);
+
+// ---- frame-synchronous beam search of the offline path (kernels_beam.hip, nasr_beam.h) ---------------------------------------------
+// the evaluation of a round: launch_decode_candidates over p.dlist, then k_dec_joint_tiled in its LP + ALT form over p.rowmap whatever the
+// row count (one kernel form, so a sub-batch gives the bits an utterance gives alone); no commit.  p.alt_k = 8, 17 parts per row
+void launch_decode_rows(const DecParams &p, hipStream_t st);
+struct BeamUtt { int enc_row, T; long long node0, out0; };      // first packed encoder row, frames, first node of its pool, first output entry
+struct BeamParams {
+    const BeamUtt *utt; int n;   // live utterances of the sub-batch, one workgroup each; hypothesis j of utterance k is batch row k * W + j
+    int W, N, S, prune;
+    nasr_beam::Beam *beam;       // [n]
+    nasr_beam::Node *nodes;      // the pools, utterance k at utt[k].node0
+    const float *encproj;        // [M][640] packed rows of the sub-batch
+    float *enc;                  // [n * W][640] the current frame's row of every batch row (the joint's encproj, T = 1)
+    RowDesc *rows;               // [n * W] the slot of every batch row
+    DecCtrl *ctrl; float *h, *c; // [n * 3 W] decoder slots
+    const nasr_lp::Part *lp_part; const unsigned long long *alt_key;   // what the joint left: [n * W][17], [n * W][17][8]
+    int *cnt_next, *cnt_zero;    // (n_dirty, n_rows) of the next evaluation / of the one that just ran
+    int *dlist; unsigned *rowmap;
+    int *err;
+    int32_t *out_n, *out_len; double *out_score;   // [n], [n][8], [n][8]
+    int32_t *out_tok, *out_frame; float *out_lp;   // utterance k, rank r at utt[k].out0 + r * T * S
+};
+void launch_beam_init(const BeamParams &p, hipStream_t st);
+void launch_beam_select(const BeamParams &p, hipStream_t st);
+void launch_beam_final(const BeamParams &p, hipStream_t st);
 
 // ---- fused small-M kernels (M <= 16): prologue + weight-streaming GEMM + epilogue in one launch ----
 enum Pro { PRO_LN = 0, PRO_PLAIN = 1, PRO_ATTN = 2, PRO_DWCONV = 3 };

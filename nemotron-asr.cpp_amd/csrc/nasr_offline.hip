@@ -44,6 +44,14 @@ struct OfflineState {
     size_t al_g_cap = 0, al_lpb_cap = 0, al_lpt_cap = 0, al_tlp_cap = 0, al_bp_cap = 0, al_tiles_cap = 0, al_tok_cap = 0, al_frames_cap = 0;
     bool lat_valid = false;                                        // the last call was an align call with debug on
     std::vector<std::vector<float>> lat_b, lat_t;                  // ... its lattices by utterance: lp_blank, lp_token [T][U + 1]
+    // beam search (nasr_engine_transcribe_beam*): its own decoder slots (3 W per utterance), batch rows (W per utterance), the joint's LP + ALT
+    // scratch whatever the engine options are, the search state and trie of the sub-batch in flight, and the results of the last call
+    struct BeamBuf { void *p = nullptr; size_t cap = 0; };
+    BeamBuf bm_utt, bm_beam, bm_nodes, bm_enc, bm_rows, bm_ctrl, bm_h, bm_c, bm_predg, bm_key, bm_part, bm_alt, bm_cnt, bm_dlist, bm_rowmap,
+            bm_out_n, bm_out_len, bm_out_score, bm_out_tok, bm_out_frame, bm_out_lp;
+    struct BeamHyp { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; };
+    bool beam_valid = false;
+    std::vector<std::vector<BeamHyp>> beam_res;                    // by utterance, best first
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
     std::vector<std::vector<float>> tap_mel, tap_sub, tap_enc;
@@ -460,6 +468,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
     o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear(); o->frame_blank_lps.clear();
     o->lat_valid = false; o->lat_b.clear(); o->lat_t.clear();
+    o->beam_valid = false; o->beam_res.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
     return 0;
 }
@@ -870,4 +879,206 @@ extern "C" int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_bl
     if (lp_blank_out) memcpy(lp_blank_out, o->lat_b[u].data(), (size_t)n * 4);
     if (lp_token_out) memcpy(lp_token_out, o->lat_t[u].data(), (size_t)n * 4);
     return n;
+}
+
+// ---- frame-synchronous beam search: N-best transcripts with scores (rules: nasr_beam.h, kernels: kernels_beam.hip) -----------------------
+namespace nasr_eng {
+static int beam_buf(nasr_engine *e, OfflineState *o, OfflineState::BeamBuf &b, size_t bytes) { return grow(e, o, &b.p, b.cap, bytes); }
+
+// the search over one sub-batch whose encoder projection is in o->encproj: T_max * (S + 1) rounds enqueued blind, five launches each (the
+// decode's two LSTM layers, joint.pred and tiled joint, then k_beam_select), no host round trip inside
+static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W, int N, int S) {
+    hipStream_t st = e->st;
+    std::vector<int> live;
+    std::vector<BeamUtt> ud;
+    long long nodes = 0, outs = 0;
+    int maxT = 0;
+    for (int k = 0; k < ob.n; k++) {
+        const int b = ob.first + k;
+        if (ob.T[k] == 0) { o->beam_res[b].assign(1, OfflineState::BeamHyp{0.0, {}, {}, {}}); continue; }     // no frame: the empty hypothesis, score 0
+        BeamUtt u;
+        u.enc_row = ob.off[k]; u.T = ob.T[k]; u.node0 = nodes; u.out0 = outs;
+        nodes += nasr_beam::node_bound(u.T, W, S);
+        outs += (long long)N * u.T * S;
+        maxT = std::max(maxT, u.T);
+        ud.push_back(u); live.push_back(k);
+    }
+    const int n = (int)live.size();
+    if (n == 0) return 0;
+    const size_t rows = (size_t)n * W, slots = (size_t)n * nasr_beam::n_slots(W);
+    if (beam_buf(e, o, o->bm_utt, n * sizeof(BeamUtt)) || beam_buf(e, o, o->bm_beam, n * sizeof(nasr_beam::Beam)) ||
+        beam_buf(e, o, o->bm_nodes, (size_t)nodes * sizeof(nasr_beam::Node)) || beam_buf(e, o, o->bm_enc, rows * JNT * 4) ||
+        beam_buf(e, o, o->bm_rows, rows * sizeof(RowDesc)) || beam_buf(e, o, o->bm_ctrl, slots * sizeof(DecCtrl)) ||
+        beam_buf(e, o, o->bm_h, slots * 4 * HID * 4) || beam_buf(e, o, o->bm_c, slots * 4 * HID * 4) || beam_buf(e, o, o->bm_predg, slots * JNT * 4) ||
+        beam_buf(e, o, o->bm_key, rows * 8) || beam_buf(e, o, o->bm_part, rows * nasr_lp::WG_PARTS * sizeof(nasr_lp::Part)) ||
+        beam_buf(e, o, o->bm_alt, rows * nasr_lp::WG_PARTS * nasr_beam::KTOP * 8) || beam_buf(e, o, o->bm_cnt, 8 * 4) ||
+        beam_buf(e, o, o->bm_dlist, rows * 4) || beam_buf(e, o, o->bm_rowmap, rows * 4) || beam_buf(e, o, o->bm_out_n, n * 4) ||
+        beam_buf(e, o, o->bm_out_len, (size_t)n * nasr_beam::WMAX * 4) || beam_buf(e, o, o->bm_out_score, (size_t)n * nasr_beam::WMAX * 8) ||
+        beam_buf(e, o, o->bm_out_tok, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_frame, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_lp, (size_t)outs * 4))
+        return -1;
+    HIPCHK(hipMemcpyAsync(o->bm_utt.p, ud.data(), n * sizeof(BeamUtt), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(o->bm_rows.p, 0, rows * sizeof(RowDesc), st));
+    HIPCHK(hipMemsetAsync(o->bm_key.p, 0, rows * 8, st));
+    HIPCHK(hipMemsetAsync(o->bm_cnt.p, 0, 8 * 4, st));
+    int *cnt = (int *)o->bm_cnt.p;
+    BeamParams bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.utt = (const BeamUtt *)o->bm_utt.p; bp.n = n; bp.W = W; bp.N = N; bp.S = S; bp.prune = 1;
+    bp.beam = (nasr_beam::Beam *)o->bm_beam.p; bp.nodes = (nasr_beam::Node *)o->bm_nodes.p; bp.encproj = o->encproj; bp.enc = (float *)o->bm_enc.p;
+    bp.rows = (RowDesc *)o->bm_rows.p; bp.ctrl = (DecCtrl *)o->bm_ctrl.p; bp.h = (float *)o->bm_h.p; bp.c = (float *)o->bm_c.p;
+    bp.lp_part = (const nasr_lp::Part *)o->bm_part.p; bp.alt_key = (const unsigned long long *)o->bm_alt.p;
+    bp.dlist = (int *)o->bm_dlist.p; bp.rowmap = (unsigned *)o->bm_rowmap.p; bp.err = cnt + 4;
+    bp.out_n = (int32_t *)o->bm_out_n.p; bp.out_len = (int32_t *)o->bm_out_len.p; bp.out_score = (double *)o->bm_out_score.p;
+    bp.out_tok = (int32_t *)o->bm_out_tok.p; bp.out_frame = (int32_t *)o->bm_out_frame.p; bp.out_lp = (float *)o->bm_out_lp.p;
+    DecParams dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.rows = bp.rows; dp.B = (int)rows; dp.T = 1; dp.ctrl = bp.ctrl; dp.h = bp.h; dp.c = bp.c; dp.encproj = bp.enc;
+    bind_dec_weights(e, dp);
+    dp.predg = (float *)o->bm_predg.p; dp.key = (unsigned long long *)o->bm_key.p; dp.n_active = cnt + 5;
+    dp.dlist = bp.dlist; dp.rowmap = bp.rowmap; dp.lp_part = (nasr_lp::Part *)o->bm_part.p; dp.alt_key = (unsigned long long *)o->bm_alt.p; dp.alt_k = nasr_beam::KTOP;
+    bp.cnt_next = cnt; bp.cnt_zero = cnt + 2;
+    ProfScope ps(e, "beam_search", 0, 0);                      // one scope for the whole search: thousands of rounds would each cost an event pair
+    launch_beam_init(bp, st);
+    const long long R = nasr_beam::rounds(maxT, S);
+    for (long long r = 0; r < R; r++) {
+        const int par = (int)(r & 1);
+        dp.n_dirty = cnt + 2 * par; dp.n_rows = cnt + 2 * par + 1;
+        launch_decode_rows(dp, st);
+        bp.cnt_zero = cnt + 2 * par; bp.cnt_next = cnt + 2 * (par ^ 1);
+        launch_beam_select(bp, st);
+    }
+    launch_beam_final(bp, st);
+    std::vector<int32_t> hn(n), hlen((size_t)n * nasr_beam::WMAX), htok((size_t)outs), hfr((size_t)outs);
+    std::vector<double> hsc((size_t)n * nasr_beam::WMAX);
+    std::vector<float> hlp((size_t)outs);
+    int herr[1] = {0};
+    HIPCHK(hipMemcpyAsync(hn.data(), bp.out_n, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hlen.data(), bp.out_len, hlen.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hsc.data(), bp.out_score, hsc.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(htok.data(), bp.out_tok, htok.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hfr.data(), bp.out_frame, hfr.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hlp.data(), bp.out_lp, hlp.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(herr, bp.err, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (herr[0]) return fail("beam search: the trie of an utterance outgrew its bound");
+    for (int k = 0; k < n; k++) {
+        const int b = ob.first + live[k];
+        if (hn[k] < 1 || hn[k] > N) return fail("beam search left utterance %d unfinished", b);
+        const long long cap = (long long)ud[k].T * S;
+        for (int r = 0; r < hn[k]; r++) {
+            const int len = hlen[(size_t)k * nasr_beam::WMAX + r];
+            if (len < 0 || len > cap) return fail("beam search: hypothesis %d of utterance %d has %d tokens", r, b, len);
+            const size_t at = (size_t)(ud[k].out0 + r * cap);
+            OfflineState::BeamHyp h;
+            h.score = hsc[(size_t)k * nasr_beam::WMAX + r];
+            h.tokens.assign(htok.begin() + at, htok.begin() + at + len);
+            h.frames.assign(hfr.begin() + at, hfr.begin() + at + len);
+            h.lps.assign(hlp.begin() + at, hlp.begin() + at + len);
+            o->beam_res[b].push_back(std::move(h));
+        }
+    }
+    return 0;
+}
+
+// every beam call forgets the hypotheses of the call before, also one that fails on its parameters
+static void beam_forget(nasr_engine *e) {
+    if (e->off) { e->off->beam_valid = false; e->off->beam_res.clear(); }
+}
+
+static int beam_check_params(const nasr_beam_params *params, int *W, int *N, int *S) {
+    if (!params) return fail("null beam parameters");
+    *W = params->beam; *N = params->nbest == 0 ? params->beam : params->nbest; *S = params->max_symbols == 0 ? nasr_beam::S_DEFAULT : params->max_symbols;
+    if (*W < 1 || *W > nasr_beam::WMAX) return fail("beam = %d outside 1 .. %d", params->beam, nasr_beam::WMAX);
+    if (*N < 1 || *N > *W) return fail("nbest = %d outside 1 .. beam = %d", params->nbest, *W);
+    if (*S < 1 || *S > nasr_beam::SMAX) return fail("max_symbols = %d outside 1 .. %d (0: the default, %d)", params->max_symbols, nasr_beam::SMAX, nasr_beam::S_DEFAULT);
+    if (params->reserved != 0) return fail("the reserved field of nasr_beam_params must be 0");
+    return 0;
+}
+
+static int beam_core(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, bool mel_device, const int32_t *prompt_index,
+                     int W, int N, int S, int32_t *n_hyps) {
+    OfflineState *o = e->off;
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> batches;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_frames, B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, batches, &bad)) {
+        if (bad >= 0 && n_frames[bad] >= 0)
+            return fail("utterance %d: %d mel frames give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len)",
+                        bad, n_frames[bad], nasr_plan::enc_frames(n_frames[bad]), NASR_OFFLINE_MAX_FRAMES);
+        return fail("offline plan rejected the call");
+    }
+    if (ensure_offline_pos(e, o)) return -1;
+    if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
+    o->beam_res.assign(B, {});
+    for (const auto &bt : batches) {
+        OffBatch ob;
+        if (run_offline_encoder(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, ob)) { o->beam_res.clear(); return -1; }
+        if (beam_batch(e, o, ob, W, N, S)) { o->beam_res.clear(); return -1; }
+        if (e->debug && ob.M > 0 && fetch_offline_taps(e, o, ob)) { o->beam_res.clear(); return -1; }
+    }
+    o->beam_valid = true;
+    for (int b = 0; b < B; b++) n_hyps[b] = (int32_t)o->beam_res[b].size();
+    return 0;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_transcribe_beam_mel(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, const int32_t *prompt_index,
+                                               const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    int W, N, S;
+    beam_forget(e);
+    if (beam_check_params(params, &W, &N, &S)) return -1;
+    if (B == 0) return 0;
+    if (!mel || !n_frames) return fail("null mel / n_frames");
+    for (int b = 0; b < B; b++)
+        if (n_frames[b] < 0 || (n_frames[b] > 0 && !mel[b])) return fail("bad mel input for utterance %d", b);
+    if (begin_call(e, B, prompt_index, n_hyps, flags, "nasr_engine_transcribe_beam_mel")) return -1;
+    return beam_core(e, B, mel, n_frames, false, prompt_index, W, N, S, n_hyps);
+}
+
+extern "C" int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples, const int32_t *prompt_index,
+                                           const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (B < 0) return fail("B < 0");
+    int W, N, S;
+    beam_forget(e);
+    if (beam_check_params(params, &W, &N, &S)) return -1;
+    if (B == 0) return 0;
+    if (!pcm || !n_samples) return fail("null pcm / n_samples");
+    std::vector<int32_t> n_mel(B);
+    for (int b = 0; b < B; b++) {
+        if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail("bad pcm input for utterance %d", b);
+        n_mel[b] = nasr_plan::mel_frames(n_samples[b]);
+    }
+    if (begin_call(e, B, prompt_index, n_hyps, flags, "nasr_engine_transcribe_beam")) return -1;
+    // the limit is checked before any work, as in nasr_engine_transcribe
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> bt;
+    int bad = -1;
+    if (nasr_plan::plan_offline(n_mel.data(), B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, bt, &bad))
+        return fail("utterance %d: %d samples give %d encoder frames, more than NASR_OFFLINE_MAX_FRAMES = %d (the reference's max_pos_len, %.1f s)",
+                    bad, bad >= 0 ? n_samples[bad] : -1, bad >= 0 ? nasr_plan::enc_frames(n_mel[bad]) : -1, NASR_OFFLINE_MAX_FRAMES, nasr_plan::max_samples() / 16000.0);
+    std::vector<const float *> mel;
+    if (offline_mel(e, e->off, B, pcm, n_samples, (flags & NASR_FLAG_PCM_DEVICE) != 0, n_mel, mel)) return -1;
+    return beam_core(e, B, mel.data(), n_mel.data(), true, prompt_index, W, N, S, n_hyps);
+}
+
+extern "C" int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens_out, int32_t *frames_out, float *token_logprobs_out,
+                                           int32_t cap, double *score_out) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    OfflineState *o = e->off;
+    if (!o || !o->beam_valid || u < 0 || u >= (int)o->beam_res.size())
+        return fail("no beam hypotheses of utterance %d (they are those of the last offline call, which must be a beam call)", u);
+    if (rank < 0 || rank >= (int)o->beam_res[u].size()) return fail("utterance %d has %d hypotheses, no rank %d", u, (int)o->beam_res[u].size(), rank);
+    const OfflineState::BeamHyp &h = o->beam_res[u][rank];
+    const int n = std::min<int>((int)h.tokens.size(), std::max(cap, 0));
+    if (tokens_out) memcpy(tokens_out, h.tokens.data(), (size_t)n * 4);
+    if (frames_out) memcpy(frames_out, h.frames.data(), (size_t)n * 4);
+    if (token_logprobs_out) memcpy(token_logprobs_out, h.lps.data(), (size_t)n * 4);
+    if (score_out) *score_out = h.score;
+    return (int)h.tokens.size();
 }

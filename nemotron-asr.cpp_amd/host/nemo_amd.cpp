@@ -349,6 +349,43 @@ nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_s
     return out;
 }
 
+std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest, int max_symbols) {
+    std::vector<nemo_hypothesis> out;
+    if (!ctx || !ctx->engine || n_samples < 0 || (n_samples > 0 && !audio)) return out;
+    const int32_t prompt = ctx->prompt_index;
+    const int32_t *pp = ctx->hparams.num_prompts > 0 ? &prompt : nullptr;
+    if (beam == 0) {                                           // greedy: at most 10 tokens per 80 ms frame
+        nemo_hypothesis h;
+        const int32_t cap = n_samples / 128 + 16;
+        h.tokens.assign((size_t)cap, 0); h.frames.assign((size_t)cap, 0);
+        int32_t *tp = h.tokens.data(), *fp = h.frames.data(), n = 0;
+        if (nasr_engine_transcribe(ctx->engine, 1, &audio, &n_samples, pp, &tp, &cap, &n, &fp, 0) < 0) {
+            fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+            return out;
+        }
+        h.tokens.resize((size_t)std::min(n, cap)); h.frames.resize(h.tokens.size());
+        h.score = NAN;
+        out.push_back(h);
+        return out;
+    }
+    nasr_beam_params bp;
+    bp.beam = beam; bp.nbest = nbest; bp.max_symbols = max_symbols; bp.reserved = 0;
+    int32_t n_hyps = 0;
+    if (nasr_engine_transcribe_beam(ctx->engine, 1, &audio, &n_samples, pp, &bp, &n_hyps, 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return out;
+    }
+    for (int r = 0; r < n_hyps; r++) {
+        nemo_hypothesis h;
+        const int n = nasr_engine_beam_hypothesis(ctx->engine, 0, r, nullptr, nullptr, nullptr, 0, nullptr);
+        if (n < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); out.clear(); return out; }
+        h.tokens.assign((size_t)n, 0); h.frames.assign((size_t)n, 0); h.logprobs.assign((size_t)n, 0.0f);
+        nasr_engine_beam_hypothesis(ctx->engine, 0, r, h.tokens.data(), h.frames.data(), h.logprobs.data(), n, &h.score);
+        out.push_back(h);
+    }
+    return out;
+}
+
 bool nemo_set_language(nemo_context *ctx, const char *lang) {
     if (!ctx || !lang) return false;
     return lookup_lang(ctx, lang, __func__, ctx->prompt_index);

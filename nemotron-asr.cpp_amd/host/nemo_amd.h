@@ -107,6 +107,18 @@ struct nemo_alignment {
 };
 nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_samples, const std::vector<int32_t> &tokens);
 
+// MI355X extension: offline transcription of one whole utterance with the frame-synchronous beam search (nasr_engine_transcribe_beam): the
+// nbest distinct transcripts, best first, each with its score (the ln P of its best-scoring lattice path), the encoder frame of every token
+// and its ln P.  beam 1 .. 8, nbest 0 = beam, max_symbols 0 = the default; beam = 0 is the greedy offline transcription
+// (nasr_engine_transcribe: one hypothesis, score NAN, no log-probabilities).  Phrase boosting is not applied in beam calls.  Empty on failure
+// (the reason on stderr)
+struct nemo_hypothesis {
+    double score = 0.0;
+    std::vector<int32_t> tokens, frames;
+    std::vector<float> logprobs;
+};
+std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest = 0, int max_symbols = 0);
+
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
 nemo_stream_context *nemo_stream_init(nemo_context *ctx, const nemo_cache_config *config = nullptr);
 bool nemo_stream_set_language(nemo_stream_context *sctx, const char *lang);

@@ -1,0 +1,69 @@
+// nemotron-transcribe-amd -- offline (full-context) transcription of one whole utterance on the MI355X engine: the greedy decode
+// (nasr_engine_transcribe), or with --beam the N best distinct transcripts of the frame-synchronous beam search
+// (nasr_engine_transcribe_beam, through nemo_transcribe_beam).  The reference's counterpart is nemo_transcribe_audio (greedy only).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "nemo_amd.h"
+
+static void usage(const char *prog) {
+    fprintf(stderr,
+            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--f32] [--device N] [--lang CODE] [--print-tokens]\n"
+            "  audio: raw s16le, 16 kHz, mono, one whole utterance (up to 2048 encoder frames = 163.8 s)\n"
+            "  without --beam: the greedy transcript, one line\n"
+            "  --beam W (1 .. 8): one line per hypothesis, best first: rank score text   (score = ln P of the hypothesis's best path;\n"
+            "  --nbest N <= W hypotheses, default W; --max-symbols S tokens per 80 ms frame, 1 .. 10, default 4).  Beam 1 is not the greedy decode\n"
+            "  --print-tokens: after each line `tokens ...` and `frames ...`, the ids and the encoder frame each is emitted at\n",
+            prog);
+}
+
+int main(int argc, char **argv) {
+    if (argc < 3) { usage(argv[0]); return 1; }
+    const char *model_path = argv[1], *audio_path = argv[2], *lang = nullptr;
+    int device = 0, dtype = 1, beam = 0, nbest = 0, max_symbols = 0;
+    bool print_tokens = false;
+    for (int i = 3; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--lang" && i + 1 < argc) lang = argv[++i];
+        else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
+        else if (a == "--beam" && i + 1 < argc) beam = atoi(argv[++i]);
+        else if (a == "--nbest" && i + 1 < argc) nbest = atoi(argv[++i]);
+        else if (a == "--max-symbols" && i + 1 < argc) max_symbols = atoi(argv[++i]);
+        else if (a == "--f32") dtype = 0;
+        else if (a == "--print-tokens") print_tokens = true;
+        else { usage(argv[0]); return 1; }
+    }
+    if (beam == 0 && (nbest != 0 || max_symbols != 0)) { fprintf(stderr, "--nbest and --max-symbols go with --beam\n"); return 1; }
+    if (beam < 0) { fprintf(stderr, "--beam must be 1 .. 8\n"); return 1; }
+    FILE *in = fopen(audio_path, "rb");
+    if (!in) { fprintf(stderr, "Failed to open audio file: %s\n", audio_path); return 1; }
+    std::vector<int16_t> pcm;
+    std::vector<int16_t> buf(1 << 16);
+    for (size_t got; (got = fread(buf.data(), sizeof(int16_t), buf.size(), in)) > 0;) pcm.insert(pcm.end(), buf.begin(), buf.begin() + (long)got);
+    fclose(in);
+
+    nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
+    if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
+    if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
+    const std::vector<nemo_hypothesis> hyps = nemo_transcribe_beam(ctx, pcm.data(), (int)pcm.size(), beam, nbest, max_symbols);
+    if (hyps.empty()) { nemo_free(ctx); return 1; }
+    for (size_t r = 0; r < hyps.size(); r++) {
+        const std::vector<int> toks(hyps[r].tokens.begin(), hyps[r].tokens.end());
+        const std::string text = tokens_to_text(toks, ctx->vocab);
+        if (beam == 0) printf("%s\n", text.c_str());
+        else printf("%zu %.6f %s\n", r, hyps[r].score, text.c_str());
+        if (print_tokens) {
+            printf("tokens");
+            for (int t : toks) printf(" %d", t);
+            printf("\nframes");
+            for (int f : hyps[r].frames) printf(" %d", f);
+            printf("\n");
+        }
+    }
+    nemo_free(ctx);
+    return 0;
+}
