@@ -475,6 +475,43 @@ int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t *const *pcm
 int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens_out, int32_t *frames_out, float *token_logprobs_out,
                                 int32_t cap, double *score_out);
 
+/* ---- shallow fusion: a back-off n-gram language model in the beam search (csrc/nasr_lm.h, csrc/nasr_beam.h).
+ * The model is over the transducer's own token ids (a sub-word LM; the engine has no word lexicon): tokens 0 .. 1023, NASR_LM_BOS only as
+ * the first token of an n-gram, NASR_LM_EOS only as the last, never 1024 (blank).  Each n-gram has its tokens (oldest first), logprob
+ * (natural log, finite, <= 0) and backoff (natural log, finite, any sign; NULL = all 0); unk_logprob (finite, <= 0) is the unigram value of
+ * every token and of EOS without a unigram of its own.  Standard ARPA back-off semantics.  A duplicate n-gram, a length outside 1 .. order,
+ * an id out of place, a non-finite value, an n-gram whose context (all tokens but the last) is not an n-gram of the set, or more than 2^24
+ * n-grams fail the call with a message that names the n-gram.
+ * While a model is attached EVERY beam call ranks by total = score + weight * lm + token_bonus * (tokens), lm = the sum of the tokens' LM
+ * terms, everywhere the LM-free search compares scores; at the end lm gains the EOS term when some n-gram ends in EOS.  The LM re-scores the
+ * candidates the transducer proposes (each hypothesis' `beam` largest non-blank outputs); it does not propose any.  score stays the model's
+ * path score.  weight and token_bonus are finite in [0, 100]; with both 0 every result equals the LM-free call bit for bit.  The search
+ * prunes only when token_bonus == 0 and no logprob or backoff is positive; otherwise it runs unpruned (same results, more work).
+ * nasr_engine_transcribe, align, live streams and step graphs never see the model.  nasr_engine_set_lm completes steps in flight, builds
+ * the tables on the host, uploads them and replaces the previous model; NULL detaches; a failure leaves the previous model in force and the
+ * engine usable.  Counters: "lm_ngrams", "lm_states", "lm_max_probe" (0 when detached). */
+#define NASR_LM_MAX_ORDER 5
+#define NASR_LM_BOS 1025
+#define NASR_LM_EOS 1026
+typedef struct nasr_lm_desc {
+    int32_t order, flags;            /* 1 .. 5; 0 */
+    int64_t n_ngrams;
+    const int32_t *lengths;          /* [n] */
+    const int32_t *tokens;           /* concatenated, oldest first */
+    const float *logprob;            /* [n] natural log */
+    const float *backoff;            /* [n] or NULL = all 0 */
+    float unk_logprob, weight, token_bonus, reserved;
+} nasr_lm_desc;
+int nasr_engine_set_lm(nasr_engine *e, const nasr_lm_desc *lm);              /* NULL detaches */
+int nasr_engine_set_lm_weights(nasr_engine *e, float weight, float token_bonus);
+/* the LM side of hypothesis `rank` of utterance u of the LAST beam call, which must have run with a model attached (else < 0; ranks are by
+ * total): *lm_logprob_out = lm with the EOS term included when the model has one, *total_out = score + weight * that + token_bonus *
+ * tokens, both as the device computed them; token_lm_logprobs_out gets min(count, cap) per-token LM terms (EOS not among them), recomputed
+ * on the host by the same lookup.  Returns the token count.  Any pointer may be NULL.  A nasr_engine_set_lm after the beam call (another
+ * model or NULL) ends this read-out: the call then fails; nasr_engine_set_lm_weights does not. */
+int nasr_engine_beam_hypothesis_lm(nasr_engine *e, int u, int rank, double *lm_logprob_out, double *total_out,
+                                   float *token_lm_logprobs_out, int32_t cap);
+
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =
  * the tensors of diarize.gguf ("vad.*" and/or "spk.*", F32, layouts of scripts/convert_diarize_to_gguf.py:129-158),

@@ -43,9 +43,11 @@ EXPORTS = [
     "nasr_stream_get_frame_blank_logprobs", "nasr_engine_offline_frame_blank_logprobs",
     "nasr_stream_set_audio_format", "nasr_engine_step_audio", "nasr_engine_convert_audio", "nasr_audio_out_ready", "nasr_audio_out_total",
     "nasr_engine_transcribe_beam_mel", "nasr_engine_transcribe_beam", "nasr_engine_beam_hypothesis",
+    "nasr_engine_set_lm", "nasr_engine_set_lm_weights", "nasr_engine_beam_hypothesis_lm",
 ]
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
+LM_MAX_ORDER, LM_BOS, LM_EOS = 5, 1025, 1026
 FLAG_NO_BOOST = 1 << 3
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
@@ -60,6 +62,13 @@ class HParams(C.Structure):
 class BeamParams(C.Structure):
     """nasr_beam_params: beam W in 1 .. 8, nbest N in 1 .. W (0 = W), max_symbols S in 1 .. 10 (0 = the default, 4)"""
     _fields_ = [(n, C.c_int32) for n in ("beam", "nbest", "max_symbols", "reserved")]
+
+
+class LmDesc(C.Structure):
+    """nasr_lm_desc: a back-off n-gram model over token ids for the beam search's shallow fusion"""
+    _fields_ = [("order", C.c_int32), ("flags", C.c_int32), ("n_ngrams", C.c_int64), ("lengths", C.POINTER(C.c_int32)), ("tokens", C.POINTER(C.c_int32)),
+                ("logprob", C.POINTER(C.c_float)), ("backoff", C.POINTER(C.c_float)), ("unk_logprob", C.c_float), ("weight", C.c_float),
+                ("token_bonus", C.c_float), ("reserved", C.c_float)]
 
 
 class WeightDesc(C.Structure):
@@ -160,6 +169,9 @@ def lib():
         L.nasr_engine_transcribe_beam_mel.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(BeamParams), ip, C.c_uint32]
         L.nasr_engine_transcribe_beam.argtypes = [vp, C.c_int, C.POINTER(vp), ip, ip, C.POINTER(BeamParams), ip, C.c_uint32]
         L.nasr_engine_beam_hypothesis.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.POINTER(C.c_float), C.c_int32, dp]
+        L.nasr_engine_set_lm.argtypes = [vp, C.POINTER(LmDesc)]
+        L.nasr_engine_set_lm_weights.argtypes = [vp, C.c_float, C.c_float]
+        L.nasr_engine_beam_hypothesis_lm.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
         L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
         L.nasr_engine_step_audio.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_convert_audio.argtypes = [vp, C.POINTER(AudioFormat), vp, C.c_int64, vp, C.c_int64, C.c_uint32]
@@ -676,25 +688,63 @@ class Engine:
         n = _chk(L.nasr_engine_beam_hypothesis(self.h, u, rank, tok.ctypes.data_as(ipt), fr.ctypes.data_as(ipt), lp.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(score)))
         return float(score.value), tok[:n].tolist(), fr[:n].tolist(), lp[:n].copy()
 
-    def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags):
+    def beam_hypothesis_lm(self, u, rank):
+        """the LM side of hypothesis `rank` of utterance u of the last beam call (made with a model attached): (lm_logprob, total,
+        token_lm_logprobs) -- lm_logprob includes the EOS term when the model has one, the per-token values do not"""
+        L = lib()
+        n = _chk(L.nasr_engine_beam_hypothesis_lm(self.h, u, rank, None, None, None, 0))
+        lps = np.zeros(max(n, 1), np.float32)
+        lm, total = C.c_double(0.0), C.c_double(0.0)
+        n = _chk(L.nasr_engine_beam_hypothesis_lm(self.h, u, rank, C.byref(lm), C.byref(total), lps.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return float(lm.value), float(total.value), lps[:n].copy()
+
+    def set_lm(self, ngrams, order=0, unk_logprob=-20.0, weight=0.0, token_bonus=0.0):
+        """attach a back-off n-gram language model to every later beam call (None detaches).  ngrams: {token tuple: logprob} or
+        {token tuple: (logprob, backoff)} or an iterable of (tokens, logprob[, backoff]); natural logs; LM_BOS only first, LM_EOS only last.
+        order 0 = the longest n-gram.  weight and token_bonus in [0, 100] (include/nemotron_asr_amd.h)."""
+        if ngrams is None:
+            _chk(lib().nasr_engine_set_lm(self.h, None))
+            return
+        items = []
+        for it in (ngrams.items() if isinstance(ngrams, dict) else ngrams):
+            toks, val = (it[0], it[1:]) if len(it) != 2 else it
+            val = tuple(np.atleast_1d(np.asarray(val, np.float64)).tolist())
+            items.append((tuple(int(t) for t in toks), float(val[0]), float(val[1]) if len(val) > 1 else 0.0))
+        n = len(items)
+        lengths = np.asarray([len(t) for t, _, _ in items], np.int32)
+        tokens = np.asarray([k for t, _, _ in items for k in t] or [0], np.int32)
+        lp = np.asarray([v for _, v, _ in items] or [0.0], np.float32)
+        bo = np.asarray([b for _, _, b in items] or [0.0], np.float32)
+        ipt, fpt = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        d = LmDesc(int(order) or int(lengths.max(initial=1)), 0, n, np.ascontiguousarray(lengths if n else np.zeros(1, np.int32)).ctypes.data_as(ipt),
+                   tokens.ctypes.data_as(ipt), lp.ctypes.data_as(fpt), bo.ctypes.data_as(fpt), float(unk_logprob), float(weight), float(token_bonus), 0.0)
+        _chk(lib().nasr_engine_set_lm(self.h, C.byref(d)))
+
+    def set_lm_weights(self, weight, token_bonus=0.0):
+        _chk(lib().nasr_engine_set_lm_weights(self.h, float(weight), float(token_bonus)))
+
+    def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm=False):
         B = len(ns)
         pr = (C.c_int32 * B)(*[int(p) for p in prompts]) if prompts is not None else None
         params = BeamParams(int(beam), int(nbest), int(max_symbols), 0)
         nh = (C.c_int32 * B)()
         _chk(fn(self.h, B, ptrs, (C.c_int32 * B)(*[int(v) for v in ns]), pr, C.byref(params), nh, flags))
+        if lm:
+            return [[self.beam_hypothesis(b, r) + self.beam_hypothesis_lm(b, r) for r in range(nh[b])] for b in range(B)]
         return [[self.beam_hypothesis(b, r) for r in range(nh[b])] for b in range(B)]
 
-    def transcribe_beam_mel(self, mels, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0):
+    def transcribe_beam_mel(self, mels, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False):
         """frame-synchronous beam search over whole utterances (mels as for transcribe_mel): per utterance the list, best first, of
         (score, tokens, frames, token_logprobs) of its nbest distinct transcripts (nbest 0 = beam; max_symbols 0 = the default).  Beam 1
-        is not the greedy decode, and phrase boosting is not applied (include/nemotron_asr_amd.h)."""
+        is not the greedy decode, and phrase boosting is not applied (include/nemotron_asr_amd.h).  lm=True (a model is attached, set_lm):
+        each tuple gains (lm_logprob, total, token_lm_logprobs)."""
         if len(mels) == 0:
             return []
         arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        return self._beam(lib().nasr_engine_transcribe_beam_mel, ptrs, [a.shape[0] for a in arrs], beam, nbest, max_symbols, prompts, flags)
+        return self._beam(lib().nasr_engine_transcribe_beam_mel, ptrs, [a.shape[0] for a in arrs], beam, nbest, max_symbols, prompts, flags, lm)
 
-    def transcribe_beam(self, pcms, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0):
+    def transcribe_beam(self, pcms, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False):
         """the same from int16 PCM, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE)"""
         if len(pcms) == 0:
             return []
@@ -705,7 +755,7 @@ class Engine:
             arrs = [np.ascontiguousarray(p, np.int16) for p in pcms]
             ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
             ns = [a.size for a in arrs]
-        return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags)
+        return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm)
 
     def set_boost_phrases(self, phrases, bonus=None):
         """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token

@@ -7,6 +7,10 @@
 //                   rules in double, creates the trie nodes, gathers each child's committed state from its parent's candidate state, rebinds
 //                   the rows' slots and lists the rows of the next evaluation
 //   k_beam_final    the N best of Beam_T: tokens, frames, ln P and scores
+// Shallow fusion (nasr_engine_set_lm, nasr_lm.h): the LM instantiations of k_beam_select and k_beam_final.  Between the row phase and the serial
+// rule phase one thread per (live hypothesis, expansion entry), at most 64, looks its token up in the n-gram tables in HBM (plain loads; the
+// loops are bounded by the table header's order and max_probe) and leaves the term and the next LM state in LDS beside ex_lp / ex_tok; the
+// final adds the EOS term per hypothesis and one thread re-ranks the <= 8 entries.  No launch and no host round trip is added.
 // The host enqueues T_max * (S + 1) rounds blind; a finished utterance's workgroup returns at once and lists nothing.  No kernel waits on
 // another workgroup: the lists of the next evaluation are filled through two atomic tickets per utterance, and the counters alternate between
 // two pairs -- round r's evaluation reads pair r & 1, its select zeroes that pair (one thread; nobody adds to it in this launch) and adds to
@@ -36,7 +40,7 @@ __global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
         p.enc[((size_t)k * W + i / JNT) * JNT + i % JNT] = p.encproj[(size_t)ud.enc_row * JNT + i % JNT];
     if (threadIdx.x == 0) {
         Beam bm;
-        nasr_beam::beam_begin(bm, ud.T);
+        nasr_beam::beam_begin(bm, ud.T, p.lm_on ? p.lm.start : 0);
         p.beam[k] = bm;
         beam_fresh_ctrl(&p.ctrl[slot0], BLANK);
         p.rows[k * W].slot = slot0;
@@ -45,8 +49,12 @@ __global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
     }
 }
 
+template <bool LM>
 __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
     __shared__ Beam bm;
+    __shared__ double ex_lm[LM ? WMAX * KTOP : 1];
+    __shared__ int32_t ex_state[LM ? WMAX * KTOP : 1];
+    __shared__ nasr_topk::RowTop row_top[LM ? WMAX : 1];     // LM form: the merge's 8 keys per live hypothesis, named here so that they cannot end up in scratch
     __shared__ float lb[WMAX], ex_lp[WMAX * KTOP];
     __shared__ int32_t ex_tok[WMAX * KTOP];
     __shared__ int ex_n[WMAX];
@@ -56,7 +64,9 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
     const int k = blockIdx.x, W = p.W, slot0 = k * nasr_beam::n_slots(W);
     if (k == 0 && threadIdx.x < 2) p.cnt_zero[threadIdx.x] = 0;
     const BeamUtt ud = p.utt[k];
-    if (threadIdx.x == 0) bm = p.beam[k];
+    static_assert(sizeof(Beam) % 4 == 0, "the beam is copied word by word");
+    for (int i = threadIdx.x; i < (int)(sizeof(Beam) / 4); i += 256)      // all threads copy the beam in and, after the round, out again
+        reinterpret_cast<uint32_t *>(&bm)[i] = reinterpret_cast<const uint32_t *>(&p.beam[k])[i];
     __syncthreads();
     if (bm.t >= bm.T) return;                                 // finished (the same answer in every thread)
     if ((int)threadIdx.x < bm.na) {                           // one thread per live hypothesis: its row's ln P(blank) and expansion list
@@ -65,18 +75,28 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
         float m, log_s;
         nasr_topk::row_softmax(parts, nasr_lp::WG_PARTS, &m, &log_s);
         lb[j] = (float)nasr_lp::blank_lp(parts, nasr_lp::WG_PARTS);
-        nasr_topk::RowTop rt;
+        nasr_topk::RowTop rt_own;
+        nasr_topk::RowTop &rt = LM ? row_top[j] : rt_own;
         nasr_topk::row_begin(rt);
         nasr_topk::row_merge(rt, KTOP, p.alt_key + nasr_topk::scratch_index(row, 0, nasr_lp::WG_PARTS, KTOP), nasr_lp::WG_PARTS);
         ex_n[j] = nasr_beam::expand(rt.top, W, m, log_s, ex_tok + j * KTOP, ex_lp + j * KTOP);
     }
     __syncthreads();
+    if (LM) {                                                 // one thread per (hypothesis, expansion entry): the LM term and the next LM state
+        const int i = threadIdx.x / KTOP, j = threadIdx.x % KTOP;
+        if (i < bm.na && j < ex_n[i]) {
+            int32_t next = 0;
+            ex_lm[i * KTOP + j] = nasr_lm::lookup(p.lm, bm.a[i].lm_state, ex_tok[i * KTOP + j], &next);
+            ex_state[i * KTOP + j] = next;
+        }
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         bool a = false;
-        int n = nasr_beam::round_step(bm, W, p.S, p.prune != 0, lb, ex_tok, ex_lp, ex_n, p.nodes + ud.node0, nasr_beam::node_bound(ud.T, W, p.S), ch, &a, sel);
+        int n = nasr_beam::round_step_t<LM>(bm, W, p.S, p.prune != 0, lb, ex_tok, ex_lp, ex_n, p.nodes + ud.node0, nasr_beam::node_bound(ud.T, W, p.S), ch, &a, sel,
+                                            p.lm_weight, p.lm_bonus, ex_lm, ex_state);
         if (n < 0) { *p.err = 1; bm.t = bm.T; n = 0; }       // cannot happen within node_bound; the utterance stops and the host reports it
         n_ch = n; adv = a ? 1 : 0;
-        p.beam[k] = bm;
         const int live = bm.t < bm.T ? bm.na : 0;
         if (live > 0) {
             const int base = atomicAdd(&p.cnt_next[1], live);
@@ -94,6 +114,8 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
         }
     }
     __syncthreads();
+    for (int i = threadIdx.x; i < (int)(sizeof(Beam) / 4); i += 256)
+        reinterpret_cast<uint32_t *>(&p.beam[k])[i] = reinterpret_cast<const uint32_t *>(&bm)[i];
     // each child's committed state (version 0 of its slot) = its parent's candidate (version 1 of the parent's slot): h', c' -> h, c
     for (int i = threadIdx.x; i < n_ch * 2 * HID; i += 256) {
         const int j = i / (2 * HID), el = i % (2 * HID);
@@ -125,11 +147,48 @@ __global__ __launch_bounds__(64) void k_beam_final(BeamParams p) {
 void launch_beam_init(const BeamParams &p, hipStream_t st) {
     if (p.n > 0) hipLaunchKernelGGL(k_beam_init, dim3(p.n), dim3(256), 0, st, p);
 }
+// the LM form of k_beam_final: lm_final = lm + the EOS term (when some n-gram ends in EOS), then the N best by the final key
+__global__ __launch_bounds__(64) void k_beam_final_lm(BeamParams p) {
+    __shared__ double lm_final[WMAX], total[WMAX];
+    __shared__ int32_t rank[WMAX];
+    __shared__ int n_out;
+    const int k = blockIdx.x, r = threadIdx.x;
+    const BeamUtt ud = p.utt[k];
+    const Beam *bm = &p.beam[k];
+    const int na = bm->na < WMAX ? bm->na : WMAX;
+    if (r < na) {
+        int32_t next = 0;
+        const nasr_beam::Hyp h = bm->a[r];
+        lm_final[r] = p.lm.has_eos ? h.lm + nasr_lm::lookup(p.lm, h.lm_state, nasr_lm::EOS, &next) : h.lm;
+    }
+    __syncthreads();
+    if (r == 0) {
+        n_out = nasr_beam::final_rank(bm->a, na, p.N, lm_final, p.lm_weight, p.lm_bonus, rank, total);
+        p.out_n[k] = bm->t >= bm->T ? n_out : -1;
+    }
+    __syncthreads();
+    if (r >= n_out) return;
+    const long long cap = (long long)ud.T * p.S;
+    const nasr_beam::Hyp h = bm->a[rank[r]];
+    p.out_len[k * WMAX + r] = h.len;
+    p.out_score[k * WMAX + r] = h.score;
+    p.out_lm[k * WMAX + r] = h.lm;
+    p.out_lm_final[k * WMAX + r] = lm_final[rank[r]];
+    p.out_total[k * WMAX + r] = total[rank[r]];
+    if (h.len > cap) return;
+    const long long at = ud.out0 + (long long)r * cap;
+    nasr_beam::backtrace(p.nodes + ud.node0, h.node, h.len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
+}
+
 void launch_beam_select(const BeamParams &p, hipStream_t st) {
-    if (p.n > 0) hipLaunchKernelGGL(k_beam_select, dim3(p.n), dim3(256), 0, st, p);
+    if (p.n <= 0) return;
+    if (p.lm_on) hipLaunchKernelGGL(k_beam_select<true>, dim3(p.n), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_beam_select<false>, dim3(p.n), dim3(256), 0, st, p);
 }
 void launch_beam_final(const BeamParams &p, hipStream_t st) {
-    if (p.n > 0) hipLaunchKernelGGL(k_beam_final, dim3(p.n), dim3(64), 0, st, p);
+    if (p.n <= 0) return;
+    if (p.lm_on) hipLaunchKernelGGL(k_beam_final_lm, dim3(p.n), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL(k_beam_final, dim3(p.n), dim3(64), 0, st, p);
 }
 
 }  // namespace nasr

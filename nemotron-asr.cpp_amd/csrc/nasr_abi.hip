@@ -22,7 +22,61 @@ static int upload_boost_set(nasr_engine *e, int n_phrases, const int32_t *const 
     e->boost_states = a.n_states;
     return 0;
 }
+
+// builds the n-gram tables on the host (nasr_lm.h) and, only if that and the upload succeed, replaces the engine's model; the caller has
+// completed the steps in flight.  One device block: states, unigrams, arcs
+static int upload_lm(nasr_engine *e, const nasr_lm_desc *d) {
+    if (d->flags != 0 || d->reserved != 0.0f) return fail("language model: flags and reserved must be 0");
+    if (!nasr_beam::valid_weights(d->weight, d->token_bonus)) return fail("language model: weight and token_bonus must be finite in [0, 100]");
+    HIPCHK(hipStreamSynchronize(e->st));                       // before anything is allocated: a failure here leaves nothing behind
+    nasr_lm::Model *m = new nasr_lm::Model();
+    std::string err;
+    if (nasr_lm::build(d->order, d->n_ngrams, d->lengths, d->tokens, d->logprob, d->backoff, d->unk_logprob, *m, err)) {
+        delete m;
+        return fail("language model: %s", err.c_str());
+    }
+    auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t b_states = up16(m->states.size() * sizeof(nasr_lm::State)), b_uni = up16(m->uni.size() * sizeof(nasr_lm::Uni)), b_arcs = m->arcs.size() * sizeof(nasr_lm::Arc);
+    char *dev = nullptr;
+    if (hipMalloc((void **)&dev, b_arcs + b_uni + b_states) != hipSuccess) { (void)hipGetLastError(); delete m; return fail("language model: out of device memory"); }
+    if (hipMemcpy(dev, m->arcs.data(), b_arcs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + b_arcs, m->uni.data(), m->uni.size() * sizeof(nasr_lm::Uni), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dev + b_arcs + b_uni, m->states.data(), m->states.size() * sizeof(nasr_lm::State), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); hipFree(dev); delete m;
+        return fail("language model: the upload failed");
+    }
+    delete e->lm;
+    if (e->lm_dev) hipFree(e->lm_dev);
+    e->lm = m; e->lm_dev = dev; e->lm_generation++;
+    e->lm_view = m->view();
+    e->lm_view.arcs = (const nasr_lm::Arc *)dev; e->lm_view.uni = (const nasr_lm::Uni *)(dev + b_arcs); e->lm_view.states = (const nasr_lm::State *)(dev + b_arcs + b_uni);
+    e->lm_weight = d->weight; e->lm_bonus = d->token_bonus;
+    return 0;
+}
 }  // namespace nasr_eng
+
+extern "C" int nasr_engine_set_lm(nasr_engine *e, const nasr_lm_desc *lm) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    if (lm) return upload_lm(e, lm);
+    HIPCHK(hipStreamSynchronize(e->st));
+    delete e->lm;
+    if (e->lm_dev) hipFree(e->lm_dev);
+    e->lm_generation++;
+    e->lm = nullptr; e->lm_dev = nullptr; e->lm_view = nasr_lm::View{}; e->lm_weight = e->lm_bonus = 0.0f;
+    return 0;
+}
+
+extern "C" int nasr_engine_set_lm_weights(nasr_engine *e, float weight, float token_bonus) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->lm) return fail("no language model attached (nasr_engine_set_lm)");
+    if (!nasr_beam::valid_weights(weight, token_bonus)) return fail("language model: weight and token_bonus must be finite in [0, 100]");
+    e->lm_weight = weight; e->lm_bonus = token_bonus;      // kernel parameters of the next beam call: nothing on the device changes
+    return 0;
+}
 
 extern "C" int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *const *tokens, const int32_t *lens, const float *bonus) {
     ApiGuard api_guard;
@@ -822,6 +876,9 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "pipelined_steps")) *value = e->pipe_steps;
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;
     else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
+    else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)
+    else if (!strcmp(name, "lm_states")) *value = e->lm ? (int64_t)e->lm->states.size() : 0;
+    else if (!strcmp(name, "lm_max_probe")) *value = e->lm ? e->lm->max_probe : 0;
     else if (!strcmp(name, "lanes")) *value = e->pipe_ready ? e->n_lanes : 0;      // HIP streams found to overlap (0: not picked yet)
     else return fail("unknown counter '%s'", name);
     return 0;

@@ -40,8 +40,24 @@
 // frames needs at most T * S * W nodes (node_bound); a sub-batch's pool is the sum.
 // Slots: a hypothesis owns one decoder slot (committed LSTM state, candidate, g).  A hypothesis parked in C keeps its slot while A's slots are
 // reused, so an utterance has 3 W slots: <= W in C, <= W in A, <= W for A's children.
+//
+// Shallow fusion with a back-off n-gram language model over the token ids (nasr_lm.h; nasr_engine_set_lm), the *_lm overloads below.
+// A hypothesis also carries lm = the DOUBLE sum of its tokens' nasr_lm::lookup results in token order, and lm_state.  A child of h with
+// token k has score = h.score + ly as above, lm = h.lm + lookup(h.lm_state, k), lm_state = that lookup's next state.  Everywhere a score is
+// compared above -- insert_sorted, c_arrive's strictly-greater test, the selection of A from D, the prune's floor -- the key is
+//     total = score + (double)weight * lm + (double)token_bonus * len
+// evaluated as exactly that expression in double from the running sums (no fused multiply-add).  score keeps its meaning: the model's
+// probability of one lattice path.  Two arrivals of the same sequence have the same lm and len, so the merge rule is unchanged in effect.
+// The expansion list is unchanged: the LM re-scores the candidates, it does not propose them.  weight and token_bonus are finite in
+// [0, 100].  With weight 0 and bonus 0, total == score bit for bit.
+// The prune's proof needs every increment of the key to be <= 0: ln P <= 0 always, weight * (an LM term) <= 0 only when every logprob and
+// every backoff of the model is <= 0 (nasr_lm's all_nonpositive), and token_bonus * 1 <= 0 only when token_bonus == 0.  So the prune is
+// applied only when token_bonus == 0 and all_nonpositive; otherwise the search runs unpruned (prune_allowed).
+// At the end, if some n-gram ends in EOS, every hypothesis of Beam_T gets lm_final = lm + lookup(lm_state, EOS) (else lm_final = lm) and the N
+// best are taken by score + weight * lm_final + token_bonus * len, stable on ties (Beam_T's order): final_rank.
 #pragma once
 #include "nasr_topk.h"
+#include "nasr_lm.h"
 
 namespace nasr_beam {
 
@@ -54,8 +70,11 @@ struct Hyp {
     double score;
     unsigned long long hash;            // of the token sequence: a pre-filter for same_seq
     int32_t node, len;                  // last trie node (-1: empty), tokens
-    int32_t slot, pad;                  // decoder slot within the utterance, 0 .. 3 W - 1
+    int32_t slot, lm_state;             // decoder slot within the utterance, 0 .. 3 W - 1; LM state after the sequence (0 without an LM)
+    double lm;                          // sum of the tokens' LM terms (0 without an LM)
 };
+// what the fused rules need beside the LM-free ones: the weights and, per (hypothesis of A, expansion entry), the LM term and next state
+struct Fusion { float weight, token_bonus; const double *ex_lm; const int32_t *ex_state; };
 struct Beam {                           // the search state of one utterance
     Hyp a[WMAX], c[WMAX];
     int32_t na, nc;
@@ -82,29 +101,61 @@ NASR_LP_HD bool same_seq(const Node *nodes, int a, int a_len, int b, int b_len) 
     return true;
 }
 
-// place h behind the entries of list[0 .. n) whose score is not lower; the list keeps at most W entries.  Returns false when h fell off
-NASR_LP_HD bool insert_sorted(Hyp *list, int32_t &n, int W, const Hyp &h) {
+// score + weight * lm + token_bonus * len, each product and sum rounded on its own: no fused multiply-add, so host and device agree bit for bit
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))                // g++ contracts by default where the target has fused multiply-add
+#endif
+NASR_LP_HD double fused_total(double score, float weight, double lm, float token_bonus, int len) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double a = (double)weight * lm;
+    const double b = (double)token_bonus * (double)len;
+    return score + a + b;
+}
+// the ordering key.  LM = false: the score itself
+template <bool LM>
+NASR_LP_HD double total_of(const Hyp &h, float weight, float token_bonus) {
+    return LM ? fused_total(h.score, weight, h.lm, token_bonus, h.len) : h.score;
+}
+NASR_LP_HD bool valid_weights(float weight, float token_bonus) {
+    return weight >= 0.0f && weight <= 100.0f && token_bonus >= 0.0f && token_bonus <= 100.0f;       // false for NaN
+}
+NASR_LP_HD bool prune_allowed(float token_bonus, bool all_nonpositive) { return token_bonus == 0.0f && all_nonpositive; }
+
+// dst = src field by field: on the device a whole-struct copy of these 40 bytes may go through scratch memory, which the select kernel keeps clear of
+NASR_LP_HD void copy_hyp(Hyp &dst, const Hyp &src) {
+    dst.score = src.score; dst.hash = src.hash; dst.node = src.node; dst.len = src.len; dst.slot = src.slot; dst.lm_state = src.lm_state; dst.lm = src.lm;
+}
+
+// place h behind the entries of list[0 .. n) whose key is not lower; the list keeps at most W entries.  Returns false when h fell off
+template <bool LM>
+NASR_LP_HD bool insert_sorted_t(Hyp *list, int32_t &n, int W, const Hyp &h, float weight, float token_bonus) {
     int pos = n;
-    while (pos > 0 && list[pos - 1].score < h.score) pos--;
+    const double key = total_of<LM>(h, weight, token_bonus);
+    while (pos > 0 && total_of<LM>(list[pos - 1], weight, token_bonus) < key) pos--;
     if (pos >= W) return false;
     const int last = n < W ? n : W - 1;
-    for (int i = last; i > pos; i--) list[i] = list[i - 1];
-    list[pos] = h;
+    for (int i = last; i > pos; i--) copy_hyp(list[i], list[i - 1]);
+    copy_hyp(list[pos], h);
     if (n < W) n++;
     return true;
 }
+NASR_LP_HD bool insert_sorted(Hyp *list, int32_t &n, int W, const Hyp &h) { return insert_sorted_t<false>(list, n, W, h, 0.0f, 0.0f); }
 
 // an arrival in C: merge with the entry of the same sequence (strictly greater replaces), else insert and keep the W best
-NASR_LP_HD void c_arrive(Beam &b, int W, const Node *nodes, const Hyp &h) {
+template <bool LM>
+NASR_LP_HD void c_arrive_t(Beam &b, int W, const Node *nodes, const Hyp &h, float weight, float token_bonus) {
     for (int i = 0; i < b.nc; i++) {
         if (b.c[i].hash != h.hash || !same_seq(nodes, b.c[i].node, b.c[i].len, h.node, h.len)) continue;
-        if (!(h.score > b.c[i].score)) return;
-        for (int j = i; j + 1 < b.nc; j++) b.c[j] = b.c[j + 1];
+        if (!(total_of<LM>(h, weight, token_bonus) > total_of<LM>(b.c[i], weight, token_bonus))) return;
+        for (int j = i; j + 1 < b.nc; j++) copy_hyp(b.c[j], b.c[j + 1]);
         b.nc--;
         break;
     }
-    insert_sorted(b.c, b.nc, W, h);
+    insert_sorted_t<LM>(b.c, b.nc, W, h, weight, token_bonus);
 }
+NASR_LP_HD void c_arrive(Beam &b, int W, const Node *nodes, const Hyp &h) { c_arrive_t<false>(b, W, nodes, h, 0.0f, 0.0f); }
 
 // the expansion list of a row from its 8 largest keys (sorted descending) and its softmax (m, log s): tokens and their f32 ln P
 NASR_LP_HD int expand(const nasr_topk::tkey *top, int W, float m, float log_s, int32_t *tok, float *lp) {
@@ -129,32 +180,38 @@ NASR_LP_HD int take_slot(unsigned &used, int W) {
 // ends a frame: A is then C, whose states exist).  *advanced = the round ended the frame.  nodes: the utterance's pool of node_cap nodes;
 // returns -1 if it would overflow (it cannot within node_bound).  sel: room for WMAX candidates (the kernel passes LDS: one thread runs
 // the round, and a local array would be scratch memory of every lane of the launch)
-NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
-                          Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel) {
+template <bool LM>
+NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
+                            Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel, float wt, float tb, const double *ex_lm,
+                            const int32_t *ex_state) {
     *advanced = false;
     if (b.t >= b.T) return 0;
     for (int i = 0; i < b.na; i++) {
-        Hyp h = b.a[i];
+        Hyp h;
+        copy_hyp(h, b.a[i]);
         h.score += (double)lb[i];
-        c_arrive(b, W, nodes, h);
+        c_arrive_t<LM>(b, W, nodes, h, wt, tb);
     }
     if (b.v == S) {                                           // the frame is over: Beam_{t+1} = C
-        for (int i = 0; i < b.nc; i++) b.a[i] = b.c[i];
+        for (int i = 0; i < b.nc; i++) copy_hyp(b.a[i], b.c[i]);
         b.na = b.nc; b.nc = 0; b.t++; b.v = 0;
         *advanced = true;
         return 0;
     }
-    // the W best of D in arrival order; sel[].node = parent index in A, .len = position in its expansion list, until the nodes are made
+    // the W best of D in arrival order; sel[].node = parent index in A, .slot = position in its expansion list, until the nodes are made
     int32_t ns = 0;
     const bool full = b.nc >= W;
-    const double floor_c = full ? b.c[W - 1].score : 0.0;
+    const double floor_c = full ? total_of<LM>(b.c[W - 1], wt, tb) : 0.0;
     for (int i = 0; i < b.na; i++)
         for (int k = 0; k < ex_n[i]; k++) {
             Hyp h;
             h.score = b.a[i].score + (double)ex_lp[i * KTOP + k];
-            if (prune && full && !(h.score > floor_c)) continue;
-            h.hash = 0; h.node = i; h.len = k; h.slot = 0; h.pad = 0;
-            insert_sorted(sel, ns, W, h);
+            h.len = b.a[i].len + 1;
+            h.lm = LM ? b.a[i].lm + ex_lm[i * KTOP + k] : 0.0;
+            h.lm_state = LM ? ex_state[i * KTOP + k] : 0;
+            if (prune && full && !(total_of<LM>(h, wt, tb) > floor_c)) continue;
+            h.hash = 0; h.node = i; h.slot = k;
+            insert_sorted_t<LM>(sel, ns, W, h, wt, tb);
         }
     unsigned used = 0;
     for (int i = 0; i < b.nc; i++) used |= 1u << b.c[i].slot;
@@ -162,25 +219,55 @@ NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, co
     if (b.n_nodes + ns > node_cap) return -1;
     for (int j = 0; j < ns; j++) {
         const Hyp &par = b.a[sel[j].node];
-        const int tok = ex_tok[sel[j].node * KTOP + sel[j].len];
+        const int tok = ex_tok[sel[j].node * KTOP + sel[j].slot];
         Node nd;
-        nd.parent = par.node; nd.token = tok; nd.frame = b.t; nd.lp = ex_lp[sel[j].node * KTOP + sel[j].len];
+        nd.parent = par.node; nd.token = tok; nd.frame = b.t; nd.lp = ex_lp[sel[j].node * KTOP + sel[j].slot];
         nodes[b.n_nodes] = nd;
         children[j].parent_slot = par.slot; children[j].token = tok; children[j].slot = take_slot(used, W); children[j].pad = 0;
         if (children[j].slot < 0) return -1;                  // cannot happen: C, A and A's children hold at most 3 W slots
         Hyp h;
-        h.score = sel[j].score; h.hash = hash_next(par.hash, tok); h.node = b.n_nodes; h.len = par.len + 1; h.slot = children[j].slot; h.pad = 0;
-        sel[j] = h;
+        h.score = sel[j].score; h.hash = hash_next(par.hash, tok); h.node = b.n_nodes; h.len = par.len + 1; h.slot = children[j].slot;
+        h.lm_state = sel[j].lm_state; h.lm = sel[j].lm;
+        copy_hyp(sel[j], h);
         b.n_nodes++;
     }
-    for (int j = 0; j < ns; j++) b.a[j] = sel[j];
+    for (int j = 0; j < ns; j++) copy_hyp(b.a[j], sel[j]);
     b.na = ns; b.v++;
     return ns;
 }
+NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
+                          Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel) {
+    return round_step_t<false>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes, node_cap, children, advanced, sel, 0.0f, 0.0f, nullptr, nullptr);
+}
+// the fused round: fu.ex_lm / fu.ex_state [i][KTOP] beside ex_lp / ex_tok.  `prune` is the caller's wish; it is applied only where
+// prune_allowed holds (the caller passes prune && prune_allowed(...))
+NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
+                          Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel, const Fusion &fu) {
+    return round_step_t<true>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes, node_cap, children, advanced, sel, fu.weight, fu.token_bonus, fu.ex_lm, fu.ex_state);
+}
 
-NASR_LP_HD void beam_begin(Beam &b, int T) {
+// the final order with an LM: rank[0 .. return value) = indices into a[0 .. na), the N best by score + weight * lm_final + token_bonus * len,
+// stable on ties; total_final[i] = that key of a[i].  One thread runs it over <= 8 entries
+NASR_LP_HD int final_rank(const Hyp *a, int na, int N, const double *lm_final, float weight, float token_bonus, int32_t *rank, double *total_final) {
+    int32_t n = 0;
+    for (int i = 0; i < na; i++) {
+        Hyp h = a[i];
+        h.lm = lm_final[i];
+        total_final[i] = total_of<true>(h, weight, token_bonus);
+        int pos = n;
+        while (pos > 0 && total_final[rank[pos - 1]] < total_final[i]) pos--;
+        if (pos >= N) continue;
+        const int last = n < N ? n : N - 1;
+        for (int j = last; j > pos; j--) rank[j] = rank[j - 1];
+        rank[pos] = i;
+        if (n < N) n++;
+    }
+    return n;
+}
+
+NASR_LP_HD void beam_begin(Beam &b, int T, int lm_start = 0) {
     b.na = 1; b.nc = 0; b.t = 0; b.v = 0; b.n_nodes = 0; b.T = T;
-    b.a[0].score = 0.0; b.a[0].hash = hash0(); b.a[0].node = -1; b.a[0].len = 0; b.a[0].slot = 0; b.a[0].pad = 0;
+    b.a[0].score = 0.0; b.a[0].hash = hash0(); b.a[0].node = -1; b.a[0].len = 0; b.a[0].slot = 0; b.a[0].lm_state = lm_start; b.a[0].lm = 0.0;
 }
 
 // tokens, frames and ln P of a hypothesis, from its last node back to the root
@@ -196,22 +283,29 @@ NASR_LP_HD void backtrace(const Node *nodes, int node, int len, int32_t *tokens,
 #if !defined(__HIPCC__)
 #include <vector>
 namespace nasr_beam {
-struct Result { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; };
+struct Result {
+    double score; std::vector<int32_t> tokens, frames; std::vector<float> lps;
+    double lm = 0.0, lm_final = 0.0, total = 0.0;       // the fused search only (total = the final key; without an LM they stay 0)
+};
 // A whole search on the host.  eval(t, tokens, len, &lb, top[KTOP], &m, &log_s) gives, for the state after `tokens`, ln P(blank), the row's 8
 // largest packed keys in the alternatives' order (blank among them or not) and its softmax (m, log s): what the joint kernels leave per row.
 // After every round it checks the slot binding: each child's slot lies in 0 .. 3 W - 1 and is held by no entry of C, no parent and no other
-// child.  Returns the node count, -1 if the trie or the slots ran out, -2 if a slot was bound twice
-template <class Eval>
-long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out) {
+// child.  Returns the node count, -1 if the trie or the slots ran out, -2 if a slot was bound twice.
+// lm != nullptr: the fused search (weight, token_bonus as in the header); *pruned = whether the prune was applied
+template <bool LM, class Eval>
+long long search_t(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const nasr_lm::View *lm, float weight, float token_bonus,
+                   bool *pruned) {
     out.clear();
-    if (T <= 0) { out.push_back(Result{0.0, {}, {}, {}}); return 0; }
-    const long long cap = node_bound(T, W, S);
-    std::vector<Node> nodes((size_t)cap);
+    if (LM) prune = prune && prune_allowed(token_bonus, lm->all_nonpositive != 0);
+    if (pruned) *pruned = prune;
+    const long long cap = node_bound(T > 0 ? T : 0, W, S);
+    std::vector<Node> nodes((size_t)cap + 1);
     Beam b;
-    beam_begin(b, T);
-    for (long long r = 0; r < rounds(T, S); r++) {
+    beam_begin(b, T > 0 ? T : 0, LM ? lm->start : 0);
+    for (long long r = 0; T > 0 && r < rounds(T, S); r++) {
         float lb[WMAX], ex_lp[WMAX * KTOP];
-        int32_t ex_tok[WMAX * KTOP];
+        int32_t ex_tok[WMAX * KTOP], ex_state[WMAX * KTOP];
+        double ex_lm[WMAX * KTOP];
         int ex_n[WMAX];
         for (int i = 0; i < b.na; i++) {
             std::vector<int32_t> seq((size_t)b.a[i].len), fr((size_t)b.a[i].len);
@@ -221,13 +315,14 @@ long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<
             float m = 0.0f, log_s = 0.0f;
             eval(b.t, seq.data(), b.a[i].len, &lb[i], top, &m, &log_s);
             ex_n[i] = expand(top, W, m, log_s, ex_tok + i * KTOP, ex_lp + i * KTOP);
+            for (int k = 0; LM && k < ex_n[i]; k++) ex_lm[i * KTOP + k] = nasr_lm::lookup(*lm, b.a[i].lm_state, ex_tok[i * KTOP + k], &ex_state[i * KTOP + k]);
         }
         unsigned parents = 0;
         for (int i = 0; i < b.na; i++) parents |= 1u << b.a[i].slot;
         Child ch[WMAX];
         Hyp sel[WMAX];
         bool adv;
-        const int n = round_step(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes.data(), cap, ch, &adv, sel);
+        const int n = round_step_t<LM>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes.data(), cap, ch, &adv, sel, weight, token_bonus, ex_lm, ex_state);
         if (n < 0) return -1;
         unsigned held = parents;
         for (int i = 0; i < b.nc; i++) held |= 1u << b.c[i].slot;
@@ -236,14 +331,36 @@ long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<
             held |= 1u << ch[j].slot;
         }
     }
-    for (int i = 0; i < b.na && i < N; i++) {
+    int32_t rank[WMAX];
+    double lm_final[WMAX], total[WMAX];
+    int n_out = b.na < N ? b.na : N;
+    for (int i = 0; i < n_out; i++) rank[i] = i;
+    if (LM) {
+        for (int i = 0; i < b.na; i++) {
+            int32_t next;
+            lm_final[i] = lm->has_eos ? b.a[i].lm + nasr_lm::lookup(*lm, b.a[i].lm_state, nasr_lm::EOS, &next) : b.a[i].lm;
+        }
+        n_out = final_rank(b.a, b.na, N, lm_final, weight, token_bonus, rank, total);
+    }
+    for (int j = 0; j < n_out; j++) {
+        const Hyp &h = b.a[rank[j]];
         Result r;
-        r.score = b.a[i].score;
-        r.tokens.resize((size_t)b.a[i].len); r.frames.resize((size_t)b.a[i].len); r.lps.resize((size_t)b.a[i].len);
-        backtrace(nodes.data(), b.a[i].node, b.a[i].len, r.tokens.data(), r.frames.data(), r.lps.data());
+        r.score = h.score;
+        r.tokens.resize((size_t)h.len); r.frames.resize((size_t)h.len); r.lps.resize((size_t)h.len);
+        backtrace(nodes.data(), h.node, h.len, r.tokens.data(), r.frames.data(), r.lps.data());
+        if (LM) { r.lm = h.lm; r.lm_final = lm_final[rank[j]]; r.total = total[rank[j]]; }
         out.push_back(r);
     }
     return b.n_nodes;
+}
+template <class Eval>
+long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out) {
+    return search_t<false>(T, W, N, S, prune, eval, out, nullptr, 0.0f, 0.0f, nullptr);
+}
+template <class Eval>
+long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const nasr_lm::View &lm, float weight, float token_bonus,
+                 bool *pruned = nullptr) {
+    return search_t<true>(T, W, N, S, prune, eval, out, &lm, weight, token_bonus, pruned);
 }
 }  // namespace nasr_beam
 #endif

@@ -627,6 +627,8 @@ void engine_destroy_impl(nasr_engine *e) {
         fprintf(stderr, "nasr: grouped pipeline: %lld steps, chain launches %lld through graphs, %lld eager\n", (long long)e->gp_steps,
                 (long long)e->gp_graph_chains, (long long)e->gp_eager_chains);
     offline_destroy(e);
+    delete e->lm;
+    if (e->lm_dev) hipFree(e->lm_dev);
     for (auto *s : e->slots) delete s;
     for (void *p : e->allocs) hipFree(p);
     for (auto &kv : e->graphs) hipGraphExecDestroy(kv.second);

@@ -251,6 +251,12 @@ struct nasr_engine {
     float *boost_bonus = nullptr; int32_t *boost_next = nullptr;   // [capacity][1040] each
     int *boost_state = nullptr;      // [slot] automaton state of every stream's emitted history
     float *boost_raw = nullptr;      // scratch beside lp_part: raw logit of every part's winner (read only when both options are on)
+    // nasr_engine_set_lm (nasr_lm.h): the compiled n-gram model on the host (the read-out of per-token values) and, in one device block, the
+    // tables the beam kernels read.  Only beam calls see it
+    nasr_lm::Model *lm = nullptr; void *lm_dev = nullptr;
+    nasr_lm::View lm_view = {};      // device pointers
+    float lm_weight = 0.0f, lm_bonus = 0.0f;
+    long long lm_generation = 0;     // counts nasr_engine_set_lm calls that changed the model: a beam call's LM read-out is tied to the model it ran with
     // option "token_alternatives" = K (0: off, 1 .. 8), nasr_topk.h: the K largest joint outputs with their log-probabilities where every token was
     // emitted.  Taken like "token_logprobs"; its kernels also leave the softmax parts, so lp_part / tok_logprob are allocated with it
     int opt_token_alt = 0, alt_cap = 0;                            // K in use, K the buffers were allocated for

@@ -292,6 +292,10 @@ struct BeamParams {
     int *err;
     int32_t *out_n, *out_len; double *out_score;   // [n], [n][8], [n][8]
     int32_t *out_tok, *out_frame; float *out_lp;   // utterance k, rank r at utt[k].out0 + r * T * S
+    // shallow fusion (nasr_engine_set_lm; lm_on = 0: none of this is read): the tables in device memory, the weights, the LM outputs
+    int lm_on; float lm_weight, lm_bonus;
+    nasr_lm::View lm;
+    double *out_lm, *out_lm_final, *out_total;     // [n][8] each
 };
 void launch_beam_init(const BeamParams &p, hipStream_t st);
 void launch_beam_select(const BeamParams &p, hipStream_t st);

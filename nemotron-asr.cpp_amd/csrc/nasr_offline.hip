@@ -47,10 +47,11 @@ struct OfflineState {
     // beam search (nasr_engine_transcribe_beam*): its own decoder slots (3 W per utterance), batch rows (W per utterance), the joint's LP + ALT
     // scratch whatever the engine options are, the search state and trie of the sub-batch in flight, and the results of the last call
     struct BeamBuf { void *p = nullptr; size_t cap = 0; };
-    BeamBuf bm_utt, bm_beam, bm_nodes, bm_enc, bm_rows, bm_ctrl, bm_h, bm_c, bm_predg, bm_key, bm_part, bm_alt, bm_cnt, bm_dlist, bm_rowmap,
+    BeamBuf bm_utt, bm_beam, bm_nodes, bm_enc, bm_rows, bm_ctrl, bm_h, bm_c, bm_predg, bm_key, bm_part, bm_alt, bm_cnt, bm_dlist, bm_rowmap, bm_out_lm,
             bm_out_n, bm_out_len, bm_out_score, bm_out_tok, bm_out_frame, bm_out_lp;
-    struct BeamHyp { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; };
-    bool beam_valid = false;
+    struct BeamHyp { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; double lm_final = 0.0, total = 0.0; };
+    long long beam_lm_generation = 0;                              // the engine's lm_generation at that call
+    bool beam_valid = false, beam_lm = false;                      // beam_lm: the last beam call ran with a language model (nasr_engine_set_lm)
     std::vector<std::vector<BeamHyp>> beam_res;                    // by utterance, best first
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
@@ -895,7 +896,19 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     int maxT = 0;
     for (int k = 0; k < ob.n; k++) {
         const int b = ob.first + k;
-        if (ob.T[k] == 0) { o->beam_res[b].assign(1, OfflineState::BeamHyp{0.0, {}, {}, {}}); continue; }     // no frame: the empty hypothesis, score 0
+        if (ob.T[k] == 0) {                                   // no frame: the empty hypothesis, score 0 (with an LM: its EOS term alone)
+            OfflineState::BeamHyp h{0.0, {}, {}, {}};
+            if (e->lm) {
+                const nasr_lm::View v = e->lm->view();
+                int32_t next = 0;
+                nasr_beam::Hyp z;
+                z.score = 0.0; z.len = 0;
+                z.lm = h.lm_final = v.has_eos ? nasr_lm::lookup(v, v.start, nasr_lm::EOS, &next) : 0.0;
+                h.total = nasr_beam::total_of<true>(z, e->lm_weight, e->lm_bonus);
+            }
+            o->beam_res[b].assign(1, h);
+            continue;
+        }
         BeamUtt u;
         u.enc_row = ob.off[k]; u.T = ob.T[k]; u.node0 = nodes; u.out0 = outs;
         nodes += nasr_beam::node_bound(u.T, W, S);
@@ -914,7 +927,8 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
         beam_buf(e, o, o->bm_alt, rows * nasr_lp::WG_PARTS * nasr_beam::KTOP * 8) || beam_buf(e, o, o->bm_cnt, 8 * 4) ||
         beam_buf(e, o, o->bm_dlist, rows * 4) || beam_buf(e, o, o->bm_rowmap, rows * 4) || beam_buf(e, o, o->bm_out_n, n * 4) ||
         beam_buf(e, o, o->bm_out_len, (size_t)n * nasr_beam::WMAX * 4) || beam_buf(e, o, o->bm_out_score, (size_t)n * nasr_beam::WMAX * 8) ||
-        beam_buf(e, o, o->bm_out_tok, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_frame, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_lp, (size_t)outs * 4))
+        beam_buf(e, o, o->bm_out_tok, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_frame, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_lp, (size_t)outs * 4) ||
+        (e->lm && beam_buf(e, o, o->bm_out_lm, (size_t)n * nasr_beam::WMAX * 8 * 3)))
         return -1;
     HIPCHK(hipMemcpyAsync(o->bm_utt.p, ud.data(), n * sizeof(BeamUtt), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(o->bm_rows.p, 0, rows * sizeof(RowDesc), st));
@@ -930,6 +944,11 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     bp.dlist = (int *)o->bm_dlist.p; bp.rowmap = (unsigned *)o->bm_rowmap.p; bp.err = cnt + 4;
     bp.out_n = (int32_t *)o->bm_out_n.p; bp.out_len = (int32_t *)o->bm_out_len.p; bp.out_score = (double *)o->bm_out_score.p;
     bp.out_tok = (int32_t *)o->bm_out_tok.p; bp.out_frame = (int32_t *)o->bm_out_frame.p; bp.out_lp = (float *)o->bm_out_lp.p;
+    if (e->lm) {                                               // shallow fusion: the prune only where its proof holds (nasr_beam.h)
+        bp.lm_on = 1; bp.lm = e->lm_view; bp.lm_weight = e->lm_weight; bp.lm_bonus = e->lm_bonus;
+        bp.prune = nasr_beam::prune_allowed(e->lm_bonus, e->lm->all_nonpositive) ? 1 : 0;
+        bp.out_lm = (double *)o->bm_out_lm.p; bp.out_lm_final = bp.out_lm + (size_t)n * nasr_beam::WMAX; bp.out_total = bp.out_lm_final + (size_t)n * nasr_beam::WMAX;
+    }
     DecParams dp;
     memset(&dp, 0, sizeof(dp));
     dp.rows = bp.rows; dp.B = (int)rows; dp.T = 1; dp.ctrl = bp.ctrl; dp.h = bp.h; dp.c = bp.c; dp.encproj = bp.enc;
@@ -949,7 +968,7 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     }
     launch_beam_final(bp, st);
     std::vector<int32_t> hn(n), hlen((size_t)n * nasr_beam::WMAX), htok((size_t)outs), hfr((size_t)outs);
-    std::vector<double> hsc((size_t)n * nasr_beam::WMAX);
+    std::vector<double> hsc((size_t)n * nasr_beam::WMAX), hlm(e->lm ? (size_t)n * nasr_beam::WMAX * 3 : 0);
     std::vector<float> hlp((size_t)outs);
     int herr[1] = {0};
     HIPCHK(hipMemcpyAsync(hn.data(), bp.out_n, n * 4, hipMemcpyDeviceToHost, st));
@@ -959,6 +978,7 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     HIPCHK(hipMemcpyAsync(hfr.data(), bp.out_frame, hfr.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hlp.data(), bp.out_lp, hlp.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(herr, bp.err, 4, hipMemcpyDeviceToHost, st));
+    if (e->lm) HIPCHK(hipMemcpyAsync(hlm.data(), bp.out_lm, hlm.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (herr[0]) return fail("beam search: the trie of an utterance outgrew its bound");
     for (int k = 0; k < n; k++) {
@@ -971,6 +991,7 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
             const size_t at = (size_t)(ud[k].out0 + r * cap);
             OfflineState::BeamHyp h;
             h.score = hsc[(size_t)k * nasr_beam::WMAX + r];
+            if (e->lm) { h.lm_final = hlm[((size_t)n + k) * nasr_beam::WMAX + r]; h.total = hlm[((size_t)2 * n + k) * nasr_beam::WMAX + r]; }
             h.tokens.assign(htok.begin() + at, htok.begin() + at + len);
             h.frames.assign(hfr.begin() + at, hfr.begin() + at + len);
             h.lps.assign(hlp.begin() + at, hlp.begin() + at + len);
@@ -1010,6 +1031,7 @@ static int beam_core(nasr_engine *e, int B, const float *const *mel, const int32
     if (ensure_offline_pos(e, o)) return -1;
     if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
     o->beam_res.assign(B, {});
+    o->beam_lm = e->lm != nullptr; o->beam_lm_generation = e->lm_generation;
     for (const auto &bt : batches) {
         OffBatch ob;
         if (run_offline_encoder(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, ob)) { o->beam_res.clear(); return -1; }
@@ -1080,5 +1102,31 @@ extern "C" int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int3
     if (frames_out) memcpy(frames_out, h.frames.data(), (size_t)n * 4);
     if (token_logprobs_out) memcpy(token_logprobs_out, h.lps.data(), (size_t)n * 4);
     if (score_out) *score_out = h.score;
+    return (int)h.tokens.size();
+}
+
+// the language-model side of a hypothesis of the last beam call, which must have run with an LM attached: lm_final (the EOS term included
+// when the model has one) and the final key, both as the device computed them; the per-token values are recomputed here by the same
+// nasr_lm::lookup over the returned tokens (the trie node does not carry them)
+extern "C" int nasr_engine_beam_hypothesis_lm(nasr_engine *e, int u, int rank, double *lm_logprob_out, double *total_out, float *token_lm_logprobs_out,
+                                              int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    OfflineState *o = e->off;
+    if (!o || !o->beam_valid || u < 0 || u >= (int)o->beam_res.size())
+        return fail("no beam hypotheses of utterance %d (they are those of the last offline call, which must be a beam call)", u);
+    if (!o->beam_lm || !e->lm) return fail("the last beam call ran without a language model (nasr_engine_set_lm)");
+    if (o->beam_lm_generation != e->lm_generation)
+        return fail("the language model was replaced after the last beam call (nasr_engine_set_lm): its hypotheses have no LM read-out any more");
+    if (rank < 0 || rank >= (int)o->beam_res[u].size()) return fail("utterance %d has %d hypotheses, no rank %d", u, (int)o->beam_res[u].size(), rank);
+    const OfflineState::BeamHyp &h = o->beam_res[u][rank];
+    if (lm_logprob_out) *lm_logprob_out = h.lm_final;
+    if (total_out) *total_out = h.total;
+    const int n = std::min<int>((int)h.tokens.size(), std::max(cap, 0));
+    if (token_lm_logprobs_out) {
+        const nasr_lm::View v = e->lm->view();
+        int32_t state = v.start;
+        for (int i = 0; i < n; i++) token_lm_logprobs_out[i] = (float)nasr_lm::lookup(v, state, h.tokens[(size_t)i], &state);
+    }
     return (int)h.tokens.size();
 }

@@ -8,6 +8,7 @@
 
 #include "boost_phrases.h"
 #include "gguf_reader.h"
+#include "lm_arpa.h"
 #include "nemotron_asr_amd.h"
 
 using nasr_host::GgufFile;
@@ -283,6 +284,39 @@ bool nemo_load_boost_file(nemo_context *ctx, const char *path, float default_bon
     return apply_boost_phrases(ctx, r, __func__);
 }
 
+bool nemo_load_lm_arpa(nemo_context *ctx, const char *path, float weight, float token_bonus, float unk_logprob) {
+    if (!ctx || !ctx->engine || !path) return false;
+    lm_arpa::Model m;
+    const std::string err = lm_arpa::parse_file(path, ctx->vocab, m);
+    if (!err.empty()) { fprintf(stderr, "%s: %s: %s\n", __func__, path, err.c_str()); return false; }
+    if (!m.has_unk && std::isnan(unk_logprob)) {
+        fprintf(stderr, "%s: %s has no <unk> unigram: give unk_logprob\n", __func__, path);
+        return false;
+    }
+    if (m.skipped_unk) fprintf(stderr, "%s: %lld n-grams with <unk> inside were skipped\n", __func__, m.skipped_unk);
+    nasr_lm_desc d;
+    memset(&d, 0, sizeof(d));
+    d.order = m.order; d.n_ngrams = (int64_t)m.lengths.size();
+    d.lengths = m.lengths.data(); d.tokens = m.tokens.data(); d.logprob = m.logprob.data(); d.backoff = m.backoff.data();
+    d.unk_logprob = std::isnan(unk_logprob) ? m.unk_logprob : unk_logprob; d.weight = weight; d.token_bonus = token_bonus;
+    if (nasr_engine_set_lm(ctx->engine, &d) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    ctx->lm_attached = true;
+    return true;
+}
+
+bool nemo_clear_lm(nemo_context *ctx) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_lm(ctx->engine, nullptr) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    ctx->lm_attached = false;
+    return true;
+}
+
 bool nemo_stream_set_boost(nemo_stream_context *sctx, bool enable) {
     if (!sctx || !sctx->stream) return false;
     if (nasr_stream_set_boost(sctx->stream, enable ? 1 : 0) < 0) {
@@ -381,6 +415,14 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
         if (n < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); out.clear(); return out; }
         h.tokens.assign((size_t)n, 0); h.frames.assign((size_t)n, 0); h.logprobs.assign((size_t)n, 0.0f);
         nasr_engine_beam_hypothesis(ctx->engine, 0, r, h.tokens.data(), h.frames.data(), h.logprobs.data(), n, &h.score);
+        if (ctx->lm_attached) {
+            if (nasr_engine_beam_hypothesis_lm(ctx->engine, 0, r, &h.lm_logprob, &h.total, nullptr, 0) < 0) {
+                fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+                out.clear();
+                return out;
+            }
+            h.has_lm = true;
+        }
         out.push_back(h);
     }
     return out;

@@ -4,6 +4,7 @@
 // so a caller written against the reference (src/transcribe_stream.cpp, src/nemo-server.cpp)
 // compiles against this header unchanged.  The GGUF file is read with host/gguf_reader (no ggml).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -29,6 +30,7 @@ struct nemo_context {               // reference: nemo_context / nemo_model (src
     nasr_engine *engine = nullptr;
     int max_streams = 0;
     int token_alternatives = 0;      // K of nemo_set_token_alternatives (0: off)
+    bool lm_attached = false;        // nemo_load_lm_arpa succeeded and nemo_clear_lm has not been called
     int workspace_rows = 0;          // rows one engine call may carry (streams x chunks x (1 + right_context)); nasr_engine_create_ex
 };
 
@@ -116,8 +118,18 @@ struct nemo_hypothesis {
     double score = 0.0;
     std::vector<int32_t> tokens, frames;
     std::vector<float> logprobs;
+    bool has_lm = false;             // a language model was attached (nemo_load_lm_arpa): ranks are by `total`
+    double lm_logprob = 0.0, total = 0.0;      // ln P_LM of the transcript (EOS term included when the model has one); score + weight * lm + bonus * tokens
 };
 std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest = 0, int max_symbols = 0);
+
+// MI355X extension: shallow fusion of a back-off n-gram language model in nemo_transcribe_beam (nasr_engine_set_lm).
+// The ARPA file is over the vocabulary's pieces (lm_arpa.h: one piece or `ids:N` per word, <s>, </s>, <unk>; log10 values).  weight and
+// token_bonus in [0, 100]; unk_logprob (natural log, <= 0) is needed only when the file has no <unk> unigram (NAN = take the file's).  The model
+// re-scores the candidates the transducer proposes; greedy transcription and streams never see it.  false on failure (the reason on stderr;
+// the previous model stays).  nemo_clear_lm detaches it.
+bool nemo_load_lm_arpa(nemo_context *ctx, const char *path, float weight, float token_bonus = 0.0f, float unk_logprob = NAN);
+bool nemo_clear_lm(nemo_context *ctx);
 
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
 nemo_stream_context *nemo_stream_init(nemo_context *ctx, const nemo_cache_config *config = nullptr);

@@ -12,11 +12,15 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--f32] [--device N] [--lang CODE] [--print-tokens]\n"
+            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--f32] [--device N] [--lang CODE] [--print-tokens]\n"
             "  audio: raw s16le, 16 kHz, mono, one whole utterance (up to 2048 encoder frames = 163.8 s)\n"
             "  without --beam: the greedy transcript, one line\n"
             "  --beam W (1 .. 8): one line per hypothesis, best first: rank score text   (score = ln P of the hypothesis's best path;\n"
             "  --nbest N <= W hypotheses, default W; --max-symbols S tokens per 80 ms frame, 1 .. 10, default 4).  Beam 1 is not the greedy decode\n"
+            "  --lm FILE.arpa (with --beam): shallow fusion of a back-off n-gram model over the vocabulary's pieces (one piece or ids:N per ARPA\n"
+            "  word, <s>, </s>, <unk>; up to 5-grams); hypotheses rank by total = score + X * lm + Y * tokens (--lm-weight X, default 0.5;\n"
+            "  --token-bonus Y, default 0; both 0 .. 100) and the lines read: rank score lm total text.  The model re-scores the transducer's\n"
+            "  candidates, it proposes none\n"
             "  --print-tokens: after each line `tokens ...` and `frames ...`, the ids and the encoder frame each is emitted at\n",
             prog);
 }
@@ -26,6 +30,9 @@ int main(int argc, char **argv) {
     const char *model_path = argv[1], *audio_path = argv[2], *lang = nullptr;
     int device = 0, dtype = 1, beam = 0, nbest = 0, max_symbols = 0;
     bool print_tokens = false;
+    const char *lm_path = nullptr;
+    float lm_weight = 0.5f, token_bonus = 0.0f;
+    bool lm_opts = false;
     for (int i = 3; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lang" && i + 1 < argc) lang = argv[++i];
@@ -33,12 +40,17 @@ int main(int argc, char **argv) {
         else if (a == "--beam" && i + 1 < argc) beam = atoi(argv[++i]);
         else if (a == "--nbest" && i + 1 < argc) nbest = atoi(argv[++i]);
         else if (a == "--max-symbols" && i + 1 < argc) max_symbols = atoi(argv[++i]);
+        else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
+        else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = true; }
+        else if (a == "--token-bonus" && i + 1 < argc) { token_bonus = strtof(argv[++i], nullptr); lm_opts = true; }
         else if (a == "--f32") dtype = 0;
         else if (a == "--print-tokens") print_tokens = true;
         else { usage(argv[0]); return 1; }
     }
     if (beam == 0 && (nbest != 0 || max_symbols != 0)) { fprintf(stderr, "--nbest and --max-symbols go with --beam\n"); return 1; }
     if (beam < 0) { fprintf(stderr, "--beam must be 1 .. 8\n"); return 1; }
+    if (lm_path && beam == 0) { fprintf(stderr, "--lm goes with --beam\n"); return 1; }
+    if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
     FILE *in = fopen(audio_path, "rb");
     if (!in) { fprintf(stderr, "Failed to open audio file: %s\n", audio_path); return 1; }
     std::vector<int16_t> pcm;
@@ -49,12 +61,14 @@ int main(int argc, char **argv) {
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
+    if (lm_path && !nemo_load_lm_arpa(ctx, lm_path, lm_weight, token_bonus)) { nemo_free(ctx); return 1; }
     const std::vector<nemo_hypothesis> hyps = nemo_transcribe_beam(ctx, pcm.data(), (int)pcm.size(), beam, nbest, max_symbols);
     if (hyps.empty()) { nemo_free(ctx); return 1; }
     for (size_t r = 0; r < hyps.size(); r++) {
         const std::vector<int> toks(hyps[r].tokens.begin(), hyps[r].tokens.end());
         const std::string text = tokens_to_text(toks, ctx->vocab);
         if (beam == 0) printf("%s\n", text.c_str());
+        else if (hyps[r].has_lm) printf("%zu %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].lm_logprob, hyps[r].total, text.c_str());
         else printf("%zu %.6f %s\n", r, hyps[r].score, text.c_str());
         if (print_tokens) {
             printf("tokens");
