@@ -51,6 +51,7 @@ enum {
     NASR_FLAG_NO_SYNC    = 1u << 1, /* do not copy tokens back / synchronise; poll with nasr_engine_collect() */
     NASR_FLAG_AUDIO_S16  = 1u << 2, /* nasr_diar_*: audio[] point at s16 PCM (sample / 32768), e.g. the ASR streams' own buffers */
     NASR_FLAG_NO_BOOST   = 1u << 3, /* nasr_engine_transcribe / _transcribe_mel only: decode the utterances of this call without phrase boosting */
+    NASR_FLAG_BEAM_BOOST = 1u << 4, /* nasr_engine_transcribe_beam / _beam_mel only: apply the engine's boost phrases inside the search (needs "phrase_boost") */
 };
 
 /* model hyper-parameters = the `nemo.*` GGUF keys read at src/nemo-ggml.cpp:108-142
@@ -451,8 +452,8 @@ int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_blank_out, fl
  * final blank of every frame included: a double sum of the f32 ln-softmax values nasr_engine_align_lattice exposes, never above `best`
  * of nasr_engine_align for that transcript.  Better = the higher score; among equal scores the earlier arrival wins.
  * beam = 1 is NOT the greedy decode of nasr_engine_transcribe: greedy emits the arg-max whenever it is not blank, the search may drop a
- * token whose continuation scores below the blank.  Phrase boosting ("phrase_boost") is NOT applied in beam calls: the scores are the
- * model's probabilities, as in alignment.  An utterance with no encoder frame gives one hypothesis: empty, score 0.
+ * token whose continuation scores below the blank.  Phrase boosting ("phrase_boost") is NOT applied unless the call carries
+ * NASR_FLAG_BEAM_BOOST (below); either way the scores are the model's probabilities, as in alignment.  An utterance with no encoder frame gives one hypothesis: empty, score 0.
  * The contract is that of nasr_engine_transcribe(_mel): the same encoder, frame-count rule and NASR_OFFLINE_MAX_FRAMES failure, the same
  * packing into sub-batches of "offline_rows", the call completes steps in flight, touches no stream state, runs eagerly and rejects
  * NASR_FLAG_NO_SYNC; results are bit-identical whatever else is in the batch.  nasr_engine_offline_tap works after a beam call made with
@@ -511,6 +512,28 @@ int nasr_engine_set_lm_weights(nasr_engine *e, float weight, float token_bonus);
  * model or NULL) ends this read-out: the call then fails; nasr_engine_set_lm_weights does not. */
 int nasr_engine_beam_hypothesis_lm(nasr_engine *e, int u, int rank, double *lm_logprob_out, double *total_out,
                                    float *token_lm_logprobs_out, int32_t cap);
+
+/* ---- phrase boosting inside the beam search (csrc/nasr_beam.h, csrc/nasr_boost.h).  A beam call with
+ * NASR_FLAG_BEAM_BOOST applies the engine's boost set (nasr_engine_set_boost_phrases; the bonus definition is that of the greedy decode).  The
+ * flag needs engine option "phrase_boost" > 0 and excludes NASR_FLAG_NO_BOOST: otherwise the call fails with a message and the engine stays
+ * usable.  Without the flag a beam call is what it was: same kernels, same bits.
+ * A hypothesis carries boost_state, the automaton state after its tokens from the root (blank never moves it), and boost, the double sum of
+ * bonus(state before y_i, y_i) over its tokens.
+ * Proposal: a hypothesis in state s expands from its row's 8 largest keys of logit[v] + bonus(s, v) (the f32 sum of the greedy boosted
+ * decode; descending, the lower id first among equal bits), blank dropped, the first `beam` of the rest kept -- so a boosted token outside the
+ * row's largest raw outputs IS proposed, which the language model never does.  The per-token ln P stays the MODEL's, from the raw logit.
+ * Ranking: everywhere the search compares keys the key is (score + weight * lm + token_bonus * tokens) + boost, or score + boost without a
+ * model; boost is added last as one rounded double add.  score, the per-token ln P and the frames keep their meaning: one lattice path.
+ * A boosted call with a non-empty set runs unpruned (a positive bonus breaks the prune's proof).  With the empty set every result equals the
+ * unflagged call bit for bit, with or without a model.
+ * Known limit: no retraction -- a partial match that later fails keeps the bonus it was paid, as in the greedy decode.
+ * nasr_engine_beam_hypothesis_boost reads the boost side of hypothesis `rank` of utterance u of the LAST beam call, which must have been
+ * boosted (else < 0): *boost_out = boost and *total_out = the ranking key, both as the device computed them (after a boosted call with a
+ * model attached nasr_engine_beam_hypothesis_lm's total_out is this same key); token_bonus_out gets min(count, cap) per-token bonuses, fixed
+ * when the call ended from the set it ran with -- a later nasr_engine_set_boost_phrases does not change them.  Returns the token count.  Any
+ * pointer may be NULL. */
+int nasr_engine_beam_hypothesis_boost(nasr_engine *e, int u, int rank, double *boost_out, double *total_out, float *token_bonus_out,
+                                      int32_t cap);
 
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =

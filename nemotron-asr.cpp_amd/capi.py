@@ -44,11 +44,13 @@ EXPORTS = [
     "nasr_stream_set_audio_format", "nasr_engine_step_audio", "nasr_engine_convert_audio", "nasr_audio_out_ready", "nasr_audio_out_total",
     "nasr_engine_transcribe_beam_mel", "nasr_engine_transcribe_beam", "nasr_engine_beam_hypothesis",
     "nasr_engine_set_lm", "nasr_engine_set_lm_weights", "nasr_engine_beam_hypothesis_lm",
+    "nasr_engine_beam_hypothesis_boost",
 ]
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
 LM_MAX_ORDER, LM_BOS, LM_EOS = 5, 1025, 1026
 FLAG_NO_BOOST = 1 << 3
+FLAG_BEAM_BOOST = 1 << 4
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
 
@@ -172,6 +174,7 @@ def lib():
         L.nasr_engine_set_lm.argtypes = [vp, C.POINTER(LmDesc)]
         L.nasr_engine_set_lm_weights.argtypes = [vp, C.c_float, C.c_float]
         L.nasr_engine_beam_hypothesis_lm.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
+        L.nasr_engine_beam_hypothesis_boost.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
         L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
         L.nasr_engine_step_audio.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_convert_audio.argtypes = [vp, C.POINTER(AudioFormat), vp, C.c_int64, vp, C.c_int64, C.c_uint32]
@@ -698,6 +701,16 @@ class Engine:
         n = _chk(L.nasr_engine_beam_hypothesis_lm(self.h, u, rank, C.byref(lm), C.byref(total), lps.ctypes.data_as(C.POINTER(C.c_float)), n))
         return float(lm.value), float(total.value), lps[:n].copy()
 
+    def beam_hypothesis_boost(self, u, rank):
+        """the boost side of hypothesis `rank` of utterance u of the last beam call (made with boost=True / FLAG_BEAM_BOOST): (boost, total,
+        token_bonuses) -- boost is the sum of the per-token phrase bonuses, total the key the search ranked by"""
+        L = lib()
+        n = _chk(L.nasr_engine_beam_hypothesis_boost(self.h, u, rank, None, None, None, 0))
+        bon = np.zeros(max(n, 1), np.float32)
+        boost, total = C.c_double(0.0), C.c_double(0.0)
+        n = _chk(L.nasr_engine_beam_hypothesis_boost(self.h, u, rank, C.byref(boost), C.byref(total), bon.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return float(boost.value), float(total.value), bon[:n].copy()
+
     def set_lm(self, ngrams, order=0, unk_logprob=-20.0, weight=0.0, token_bonus=0.0):
         """attach a back-off n-gram language model to every later beam call (None detaches).  ngrams: {token tuple: logprob} or
         {token tuple: (logprob, backoff)} or an iterable of (tokens, logprob[, backoff]); natural logs; LM_BOS only first, LM_EOS only last.
@@ -723,28 +736,36 @@ class Engine:
     def set_lm_weights(self, weight, token_bonus=0.0):
         _chk(lib().nasr_engine_set_lm_weights(self.h, float(weight), float(token_bonus)))
 
-    def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm=False):
+    def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm=False, boost=False):
+        if boost:
+            flags |= FLAG_BEAM_BOOST
         B = len(ns)
         pr = (C.c_int32 * B)(*[int(p) for p in prompts]) if prompts is not None else None
         params = BeamParams(int(beam), int(nbest), int(max_symbols), 0)
         nh = (C.c_int32 * B)()
         _chk(fn(self.h, B, ptrs, (C.c_int32 * B)(*[int(v) for v in ns]), pr, C.byref(params), nh, flags))
-        if lm:
-            return [[self.beam_hypothesis(b, r) + self.beam_hypothesis_lm(b, r) for r in range(nh[b])] for b in range(B)]
-        return [[self.beam_hypothesis(b, r) for r in range(nh[b])] for b in range(B)]
+        def one(b, r):
+            h = self.beam_hypothesis(b, r)
+            if lm:
+                h += self.beam_hypothesis_lm(b, r)
+            if boost:
+                h += self.beam_hypothesis_boost(b, r)
+            return h
+        return [[one(b, r) for r in range(nh[b])] for b in range(B)]
 
-    def transcribe_beam_mel(self, mels, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False):
+    def transcribe_beam_mel(self, mels, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False, boost=False):
         """frame-synchronous beam search over whole utterances (mels as for transcribe_mel): per utterance the list, best first, of
         (score, tokens, frames, token_logprobs) of its nbest distinct transcripts (nbest 0 = beam; max_symbols 0 = the default).  Beam 1
-        is not the greedy decode, and phrase boosting is not applied (include/nemotron_asr_amd.h).  lm=True (a model is attached, set_lm):
-        each tuple gains (lm_logprob, total, token_lm_logprobs)."""
+        is not the greedy decode (include/nemotron_asr_amd.h).  lm=True (a model is attached, set_lm): each tuple gains (lm_logprob, total,
+        token_lm_logprobs).  boost=True (engine option "phrase_boost", set_boost_phrases): the search is boosted (FLAG_BEAM_BOOST) and each
+        tuple gains, after the LM fields, (boost, total, token_bonuses); without it phrase boosting is not applied."""
         if len(mels) == 0:
             return []
         arrs = [np.ascontiguousarray(m, np.float32).reshape(-1, 128) for m in mels]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        return self._beam(lib().nasr_engine_transcribe_beam_mel, ptrs, [a.shape[0] for a in arrs], beam, nbest, max_symbols, prompts, flags, lm)
+        return self._beam(lib().nasr_engine_transcribe_beam_mel, ptrs, [a.shape[0] for a in arrs], beam, nbest, max_symbols, prompts, flags, lm, boost)
 
-    def transcribe_beam(self, pcms, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False):
+    def transcribe_beam(self, pcms, beam=4, nbest=0, max_symbols=0, prompts=None, flags=0, lm=False, boost=False):
         """the same from int16 PCM, one whole utterance each (or (device_ptr, n) pairs with FLAG_PCM_DEVICE)"""
         if len(pcms) == 0:
             return []
@@ -755,7 +776,7 @@ class Engine:
             arrs = [np.ascontiguousarray(p, np.int16) for p in pcms]
             ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
             ns = [a.size for a in arrs]
-        return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm)
+        return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm, boost)
 
     def set_boost_phrases(self, phrases, bonus=None):
         """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token

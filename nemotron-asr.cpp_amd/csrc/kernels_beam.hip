@@ -11,6 +11,12 @@
 // rule phase one thread per (live hypothesis, expansion entry), at most 64, looks its token up in the n-gram tables in HBM (plain loads; the
 // loops are bounded by the table header's order and max_probe) and leaves the term and the next LM state in LDS beside ex_lp / ex_tok; the
 // final adds the EOS term per hypothesis and one thread re-ranks the <= 8 entries.  No launch and no host round trip is added.
+// Phrase boosting (NASR_FLAG_BEAM_BOOST, nasr_boost.h): the BOOST instantiations, with or without the LM.  The evaluation is then the tiled joint's
+// BEAMB form (lists by logit + bonus of the row's automaton state; the raw logits of every row kept).  The row phase merges the boosted lists as
+// before; the same (hypothesis, entry) threads then read the entry's raw logit, form the MODEL's ln P from it and read the entry's bonus and next
+// automaton state from the tables -- plain loads beside the LM look-up.  Every row bound for the next evaluation gets its slot's automaton state
+// from its hypothesis (boost_state [n * 3 W], the beam's own array); k_beam_init writes the root; k_beam_final_boost re-ranks by the boosted key and
+// writes boost and that key per hypothesis.
 // The host enqueues T_max * (S + 1) rounds blind; a finished utterance's workgroup returns at once and lists nothing.  No kernel waits on
 // another workgroup: the lists of the next evaluation are filled through two atomic tickets per utterance, and the counters alternate between
 // two pairs -- round r's evaluation reads pair r & 1, its select zeroes that pair (one thread; nobody adds to it in this launch) and adds to
@@ -32,6 +38,7 @@ __device__ __forceinline__ void beam_fresh_ctrl(DecCtrl *ct, int prev_token) {
     *ct = d;
 }
 
+template <bool BOOST>
 __global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
     const int k = blockIdx.x, W = p.W, slot0 = k * nasr_beam::n_slots(W);
     const BeamUtt ud = p.utt[k];
@@ -40,8 +47,9 @@ __global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
         p.enc[((size_t)k * W + i / JNT) * JNT + i % JNT] = p.encproj[(size_t)ud.enc_row * JNT + i % JNT];
     if (threadIdx.x == 0) {
         Beam bm;
-        nasr_beam::beam_begin(bm, ud.T, p.lm_on ? p.lm.start : 0);
+        nasr_beam::beam_begin<BOOST>(bm, ud.T, p.lm_on ? p.lm.start : 0);
         p.beam[k] = bm;
+        if (BOOST) p.boost_state[slot0] = nasr_boost::STATE_ROOT;
         beam_fresh_ctrl(&p.ctrl[slot0], BLANK);
         p.rows[k * W].slot = slot0;
         p.dlist[atomicAdd(&p.cnt_next[0], 1)] = k * W;
@@ -49,12 +57,14 @@ __global__ __launch_bounds__(256) void k_beam_init(BeamParams p) {
     }
 }
 
-template <bool LM>
+template <bool LM, bool BOOST>
 __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
     __shared__ Beam bm;
     __shared__ double ex_lm[LM ? WMAX * KTOP : 1];
     __shared__ int32_t ex_state[LM ? WMAX * KTOP : 1];
-    __shared__ nasr_topk::RowTop row_top[LM ? WMAX : 1];     // LM form: the merge's 8 keys per live hypothesis, named here so that they cannot end up in scratch
+    __shared__ nasr_topk::RowTop row_top[WMAX];               // the merge's 8 keys per live hypothesis, named here so that they cannot end up in scratch
+    __shared__ float ex_bonus[BOOST ? WMAX * KTOP : 1], row_m[BOOST ? WMAX : 1], row_log_s[BOOST ? WMAX : 1];
+    __shared__ int32_t ex_bstate[BOOST ? WMAX * KTOP : 1];
     __shared__ float lb[WMAX], ex_lp[WMAX * KTOP];
     __shared__ int32_t ex_tok[WMAX * KTOP];
     __shared__ int ex_n[WMAX];
@@ -75,26 +85,34 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
         float m, log_s;
         nasr_topk::row_softmax(parts, nasr_lp::WG_PARTS, &m, &log_s);
         lb[j] = (float)nasr_lp::blank_lp(parts, nasr_lp::WG_PARTS);
-        nasr_topk::RowTop rt_own;
-        nasr_topk::RowTop &rt = LM ? row_top[j] : rt_own;
+        nasr_topk::RowTop &rt = row_top[j];
         nasr_topk::row_begin(rt);
         nasr_topk::row_merge(rt, KTOP, p.alt_key + nasr_topk::scratch_index(row, 0, nasr_lp::WG_PARTS, KTOP), nasr_lp::WG_PARTS);
-        ex_n[j] = nasr_beam::expand(rt.top, W, m, log_s, ex_tok + j * KTOP, ex_lp + j * KTOP);
+        if (BOOST) {                                          // the keys hold logit + bonus: only the ids come from them
+            ex_n[j] = nasr_beam::expand_ids(rt.top, W, ex_tok + j * KTOP);
+            row_m[j] = m; row_log_s[j] = log_s;
+        } else ex_n[j] = nasr_beam::expand(rt.top, W, m, log_s, ex_tok + j * KTOP, ex_lp + j * KTOP);
     }
     __syncthreads();
-    if (LM) {                                                 // one thread per (hypothesis, expansion entry): the LM term and the next LM state
+    if (LM || BOOST) {                                        // one thread per (hypothesis, expansion entry)
         const int i = threadIdx.x / KTOP, j = threadIdx.x % KTOP;
         if (i < bm.na && j < ex_n[i]) {
-            int32_t next = 0;
-            ex_lm[i * KTOP + j] = nasr_lm::lookup(p.lm, bm.a[i].lm_state, ex_tok[i * KTOP + j], &next);
-            ex_state[i * KTOP + j] = next;
+            const int tok = ex_tok[i * KTOP + j];
+            if (LM) {                                         // the LM term and the next LM state
+                int32_t next = 0;
+                ex_lm[i * KTOP + j] = nasr_lm::lookup(p.lm, bm.a[i].lm_state, tok, &next);
+                ex_state[i * KTOP + j] = next;
+            }
+            if (BOOST)                                        // the model's ln P from the raw logit; the bonus and the next automaton state (tok < 1025 < COLS)
+                nasr_beam::boost_entry(p.raw_logits[(size_t)(k * W + i) * nasr_boost::COLS + tok], row_m[i], row_log_s[i], p.boost_bonus, p.boost_next,
+                                       bm.a[i].boost_state, tok, &ex_lp[i * KTOP + j], &ex_bonus[i * KTOP + j], &ex_bstate[i * KTOP + j]);
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         bool a = false;
-        int n = nasr_beam::round_step_t<LM>(bm, W, p.S, p.prune != 0, lb, ex_tok, ex_lp, ex_n, p.nodes + ud.node0, nasr_beam::node_bound(ud.T, W, p.S), ch, &a, sel,
-                                            p.lm_weight, p.lm_bonus, ex_lm, ex_state);
+        int n = nasr_beam::round_step_t<LM, BOOST>(bm, W, p.S, p.prune != 0, lb, ex_tok, ex_lp, ex_n, p.nodes + ud.node0, nasr_beam::node_bound(ud.T, W, p.S), ch, &a,
+                                                   sel, p.lm_weight, p.lm_bonus, ex_lm, ex_state, ex_bonus, ex_bstate);
         if (n < 0) { *p.err = 1; bm.t = bm.T; n = 0; }       // cannot happen within node_bound; the utterance stops and the host reports it
         n_ch = n; adv = a ? 1 : 0;
         const int live = bm.t < bm.T ? bm.na : 0;
@@ -102,6 +120,7 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
             const int base = atomicAdd(&p.cnt_next[1], live);
             for (int j = 0; j < live; j++) {
                 p.rows[k * W + j].slot = slot0 + bm.a[j].slot;
+                if (BOOST) p.boost_state[slot0 + bm.a[j].slot] = bm.a[j].boost_state;
                 p.rowmap[base + j] = (unsigned)(k * W + j);
             }
         }
@@ -145,7 +164,9 @@ __global__ __launch_bounds__(64) void k_beam_final(BeamParams p) {
 }
 
 void launch_beam_init(const BeamParams &p, hipStream_t st) {
-    if (p.n > 0) hipLaunchKernelGGL(k_beam_init, dim3(p.n), dim3(256), 0, st, p);
+    if (p.n <= 0) return;
+    if (p.boost_on) hipLaunchKernelGGL(k_beam_init<true>, dim3(p.n), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_beam_init<false>, dim3(p.n), dim3(256), 0, st, p);
 }
 // the LM form of k_beam_final: lm_final = lm + the EOS term (when some n-gram ends in EOS), then the N best by the final key
 __global__ __launch_bounds__(64) void k_beam_final_lm(BeamParams p) {
@@ -180,13 +201,58 @@ __global__ __launch_bounds__(64) void k_beam_final_lm(BeamParams p) {
     nasr_beam::backtrace(p.nodes + ud.node0, h.node, h.len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
 }
 
+// the BOOST form of the final kernels, with or without the LM: boost and the final key (+ boost) per hypothesis; LM = false: the key is score + boost
+// and the order is Beam_T's (it is sorted by that key already; final_rank_t is stable)
+template <bool LM>
+__global__ __launch_bounds__(64) void k_beam_final_boost(BeamParams p) {
+    __shared__ double lm_final[WMAX], total[WMAX];
+    __shared__ int32_t rank[WMAX];
+    __shared__ int n_out;
+    const int k = blockIdx.x, r = threadIdx.x;
+    const BeamUtt ud = p.utt[k];
+    const Beam *bm = &p.beam[k];
+    const int na = bm->na < WMAX ? bm->na : WMAX;
+    if (r < na) {
+        int32_t next = 0;
+        lm_final[r] = LM && p.lm.has_eos ? bm->a[r].lm + nasr_lm::lookup(p.lm, bm->a[r].lm_state, nasr_lm::EOS, &next) : bm->a[r].lm;
+    }
+    __syncthreads();
+    if (r == 0) {
+        n_out = nasr_beam::final_rank_t<LM, true>(bm->a, na, p.N, lm_final, p.lm_weight, p.lm_bonus, rank, total);
+        p.out_n[k] = bm->t >= bm->T ? n_out : -1;
+    }
+    __syncthreads();
+    if (r >= n_out) return;
+    const long long cap = (long long)ud.T * p.S;
+    const int src = rank[r];
+    const int len = bm->a[src].len;
+    p.out_len[k * WMAX + r] = len;
+    p.out_score[k * WMAX + r] = bm->a[src].score;
+    if (LM) { p.out_lm[k * WMAX + r] = bm->a[src].lm; p.out_lm_final[k * WMAX + r] = lm_final[src]; }
+    p.out_total[k * WMAX + r] = total[src];
+    p.out_boost[k * WMAX + r] = bm->a[src].boost;
+    if (len > cap) return;
+    const long long at = ud.out0 + (long long)r * cap;
+    nasr_beam::backtrace(p.nodes + ud.node0, bm->a[src].node, len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
+}
+
 void launch_beam_select(const BeamParams &p, hipStream_t st) {
     if (p.n <= 0) return;
-    if (p.lm_on) hipLaunchKernelGGL(k_beam_select<true>, dim3(p.n), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_beam_select<false>, dim3(p.n), dim3(256), 0, st, p);
+    if (p.boost_on) {
+        if (p.lm_on) hipLaunchKernelGGL((k_beam_select<true, true>), dim3(p.n), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((k_beam_select<false, true>), dim3(p.n), dim3(256), 0, st, p);
+        return;
+    }
+    if (p.lm_on) hipLaunchKernelGGL((k_beam_select<true, false>), dim3(p.n), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_beam_select<false, false>), dim3(p.n), dim3(256), 0, st, p);
 }
 void launch_beam_final(const BeamParams &p, hipStream_t st) {
     if (p.n <= 0) return;
+    if (p.boost_on) {
+        if (p.lm_on) hipLaunchKernelGGL(k_beam_final_boost<true>, dim3(p.n), dim3(64), 0, st, p);
+        else hipLaunchKernelGGL(k_beam_final_boost<false>, dim3(p.n), dim3(64), 0, st, p);
+        return;
+    }
     if (p.lm_on) hipLaunchKernelGGL(k_beam_final_lm, dim3(p.n), dim3(64), 0, st, p);
     else hipLaunchKernelGGL(k_beam_final, dim3(p.n), dim3(64), 0, st, p);
 }

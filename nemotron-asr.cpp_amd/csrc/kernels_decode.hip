@@ -363,16 +363,21 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // and all four 16-row tiles; the relu(encproj + g) operand of a 64-deep K chunk is formed once per
 // workgroup and staged in LDS (double-buffered, 16-byte chunks XOR-swizzled with the row).  The
 // kernel is bound by the f32 MFMA (32 cycles per 16x16x4), 640 of them per wave.
+// BEAMB (the boosted beam evaluation, launch_decode_rows_boost; always with LP, BOOST and ALT): the ALT lists are built from logit + bonus(state
+// of the row's slot, v) instead of the raw logit, the softmax parts stay those of the raw logits, and every lane also leaves its four RAW logits
+// of every row in raw_logits [row][1040] -- one aligned 16-byte store per lane and m-tile from the accumulators it holds, one writer per element.
+// The per-part winner's raw logit (boost_raw) is not kept: the select kernel reads any entry's raw logit from the row
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
-template <bool LP, bool BOOST, bool ALT>
+template <bool LP, bool BOOST, bool ALT, bool BEAMB = false>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
+    static_assert(!BEAMB || (LP && BOOST && ALT), "the boosted beam form is a form of the LP + BOOST + ALT kernel");
     const int nr = *p.n_rows;
     const int m0 = blockIdx.y * 64;
     if (m0 >= nr) return;
     __shared__ __attribute__((aligned(16))) float xs[2][64 * JT_KC];
     __shared__ unsigned long long bests[4][64];
     __shared__ nasr_lp::Part lps[LP ? 4 : 1][64];      // token_logprobs: the four waves' tile parts of the 64 rows
-    __shared__ float raws[LP && BOOST ? 4 : 1][64];    // ... with phrase_boost: the raw logit of each wave's winner by boosted key
+    __shared__ float raws[LP && BOOST && !BEAMB ? 4 : 1][64];    // ... with phrase_boost: the raw logit of each wave's winner by boosted key
     // token_alternatives: the four waves' tile lists of the 64 rows, [wave][entry][row].  They take the place of the operand staging, which nobody
     // reads after the K loop's last barrier
     static_assert(sizeof(unsigned long long) * 4 * nasr_topk::KMAX * 64 <= sizeof(float) * 2 * 64 * JT_KC, "the lists fit the staging buffer");
@@ -450,8 +455,8 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 #pragma unroll
     for (int mt = 0; mt < 4; mt++) {
         unsigned long long best = 0ull;
+        float bon[4] = {0.f, 0.f, 0.f, 0.f};
         if (has_tile && mt < nmt) {
-            float bon[4] = {0.f, 0.f, 0.f, 0.f};
             if (BOOST) {
                 const nasr_boost::Bonus4 b4 = nasr_boost::bonus4_of(p.boost_bonus, bstate[mt], nt * 16 + q * 4);
                 bon[0] = b4.x; bon[1] = b4.y; bon[2] = b4.z; bon[3] = b4.w;
@@ -465,7 +470,7 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         best = kmax(best, shfl_xor_u64(best, 16));
         best = kmax(best, shfl_xor_u64(best, 32));
         if (q == 0) bests[wave][mt * 16 + r] = best;
-        if (LP && BOOST) {                             // the lane that holds the wave's winner leaves its raw logit
+        if (LP && BOOST && !BEAMB) {                   // the lane that holds the wave's winner leaves its raw logit
             const int wv = nasr_lp::key_index_of(best) - (nt * 16 + q * 4);
             if (best && wv >= 0 && wv < 4) {
                 const float a = wv == 0 ? acc[mt][0] : wv == 1 ? acc[mt][1] : wv == 2 ? acc[mt][2] : acc[mt][3];
@@ -479,9 +484,15 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
             for (int j = 0; j < 4; j++) lg[j] = acc[mt][j] + p.out_b[v0 + j < VOCAB ? v0 + j : 0];
             const nasr_lp::Part part = lp_tile_part(lg[0], lg[1], lg[2], lg[3], v0);
             if (q == 0) lps[wave][mt * 16 + r] = part;
+            if (BEAMB) {                               // the row's raw logits of this lane: columns 16 nt + 4 q .. + 3 of [row][1040], nt < 65
+                const int row = m0 + mt * 16 + r;
+                if (has_tile && row < nr)
+                    *(float4 *)(p.raw_logits + (size_t)nasr_lp::key_index(p.rowmap[row], p.T) * nasr_boost::COLS + v0) = make_float4(lg[0], lg[1], lg[2], lg[3]);
+            }
             if (ALT) {                                 // no tile: v0 = VOCAB leaves the empty list
                 unsigned long long top[nasr_topk::KMAX];
-                alt_tile_keys(lg[0], lg[1], lg[2], lg[3], v0, top);
+                if (BEAMB) alt_tile_keys(lg[0] + bon[0], lg[1] + bon[1], lg[2] + bon[2], lg[3] + bon[3], v0, top);   // bon is 0 where the wave has no tile or the m-tile no row
+                else alt_tile_keys(lg[0], lg[1], lg[2], lg[3], v0, top);
                 if (q == 0) {
 #pragma unroll
                     for (int j = 0; j < nasr_topk::KMAX; j++) alts[wave][j][mt * 16 + r] = top[j];
@@ -494,7 +505,7 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         const unsigned long long best = kmax(kmax(bests[0][threadIdx.x], bests[1][threadIdx.x]), kmax(bests[2][threadIdx.x], bests[3][threadIdx.x]));
         const unsigned rm = p.rowmap[m0 + threadIdx.x];
         if (best) atomicMax(&p.key[(size_t)(rm & 0xffffu) * p.T + (rm >> 16)], best);
-        if (LP && BOOST) {                             // the workgroup's winner is the winner of its wave: part blockIdx.x of the row
+        if (LP && BOOST && !BEAMB) {                   // the workgroup's winner is the winner of its wave: part blockIdx.x of the row
             int w = 0;
             unsigned long long kw = bests[0][threadIdx.x];
 #pragma unroll
@@ -685,6 +696,12 @@ void launch_decode_candidates(const DecParams &p, hipStream_t st) {
 void launch_decode_rows(const DecParams &p, hipStream_t st) {
     launch_decode_candidates(p, st);
     hipLaunchKernelGGL((k_dec_joint_tiled<true, false, true>), dim3((VOCAB + 63) / 64, (p.B * p.T + 63) / 64), dim3(256), 0, st, p);
+}
+// the boosted beam evaluation: the same with the tiled joint in its BEAMB form (p.boost_bonus, p.boost_state = the beam's own per-slot array,
+// p.raw_logits [B * T][1040])
+void launch_decode_rows_boost(const DecParams &p, hipStream_t st) {
+    launch_decode_candidates(p, st);
+    hipLaunchKernelGGL((k_dec_joint_tiled<true, true, true, true>), dim3((VOCAB + 63) / 64, (p.B * p.T + 63) / 64), dim3(256), 0, st, p);
 }
 // One iteration = recompute stale prediction-network outputs, evaluate every remaining (stream, frame)
 // row, commit.  Every kernel exits at once when its work list is empty, so surplus iterations of a

@@ -20,6 +20,7 @@ static int upload_boost_set(nasr_engine *e, int n_phrases, const int32_t *const 
     for (int i = 0; i < e->max_streams; i++) if (e->slots[i] && !e->slots[i]->boost_enabled) st[(size_t)i] = nasr_boost::STATE_OFF;
     HIPCHK(hipMemcpy(e->boost_state, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
     e->boost_states = a.n_states;
+    e->boost_host = std::move(a);
     return 0;
 }
 

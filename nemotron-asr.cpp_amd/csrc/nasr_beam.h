@@ -33,7 +33,8 @@
 //
 // Beam 1 is NOT the greedy decode: greedy emits the arg-max whenever it is not blank, while this search keeps, per frame, the single best of
 // "blank now" over all symbol counts -- it may drop a token whose continuation scores below the blank (4 of 16 cases differed on the
-// alignment tests' checkpoint).  Phrase boosting is not applied: the scores are the model's probabilities, as in alignment.
+// alignment tests' checkpoint).  Phrase boosting is applied only in calls that ask for it (the BOOST forms below); either way the scores are
+// the model's probabilities, as in alignment.
 // T == 0 gives one hypothesis: empty, score 0.
 //
 // Trie: every child selected into A is a node (parent, token, frame, ln P).  At most W nodes per round with v < S, so an utterance of T
@@ -55,9 +56,27 @@
 // applied only when token_bonus == 0 and all_nonpositive; otherwise the search runs unpruned (prune_allowed).
 // At the end, if some n-gram ends in EOS, every hypothesis of Beam_T gets lm_final = lm + lookup(lm_state, EOS) (else lm_final = lm) and the N
 // best are taken by score + weight * lm_final + token_bonus * len, stable on ties (Beam_T's order): final_rank.
+//
+// Phrase boosting (engine option "phrase_boost", call flag NASR_FLAG_BEAM_BOOST; nasr_boost.h defines the set, the automaton and bonus_of), the
+// BOOST forms below, with or without the LM.  A hypothesis also carries boost_state = the automaton state after its tokens from STATE_ROOT
+// (blank never moves it) and boost = the DOUBLE sum of bonus_of(state before y_i, y_i) over its tokens.
+// Proposal: a hypothesis in state s expands from its row's 8 largest keys pack_key(logit[v] + bonus(s, v), v) -- the f32 sum the greedy BOOST
+// kernels form -- descending, the lower id first among equal bits; blank is dropped and the first W of the rest are kept.  So a boosted token
+// outside the raw 8 largest outputs can be proposed.  The ln P of an entry stays the MODEL's: lp_of(raw logit, m, log s), never
+// (logit + bonus) - bonus.
+// Ranking: everywhere a key is compared (insert_sorted_t, c_arrive_t, the selection of A from D, the prune's floor, final_rank) the key is
+//     fused_total(score, weight, lm, token_bonus, len) + boost            (score + boost without an LM)
+// with boost added last as its own rounded double add.  score, the per-token ln P and the frames keep their meaning: one lattice path of the
+// model.  Two arrivals of the same sequence have equal boost, so the merge rule is unchanged.
+// Prune: a positive bonus is a positive increment of the key, so a boosted call with a non-empty set (more than the 2 fixed automaton
+// states) runs unpruned (prune_allowed).  With the empty set every bonus is 0 and boost stays 0.0: every key, list and result is that of the
+// call without boosting.
+// No retraction: a partial match that later fails keeps the bonus it was paid -- the greedy definition; the tables hold a max over the failure
+// chain, so "paid so far" is not a function of the state.
 #pragma once
 #include "nasr_topk.h"
 #include "nasr_lm.h"
+#include "nasr_boost.h"
 
 namespace nasr_beam {
 
@@ -72,6 +91,8 @@ struct Hyp {
     int32_t node, len;                  // last trie node (-1: empty), tokens
     int32_t slot, lm_state;             // decoder slot within the utterance, 0 .. 3 W - 1; LM state after the sequence (0 without an LM)
     double lm;                          // sum of the tokens' LM terms (0 without an LM)
+    double boost;                       // sum of the tokens' phrase bonuses (0 without boosting)
+    int32_t boost_state;                // automaton state after the sequence (STATE_ROOT without boosting)
 };
 // what the fused rules need beside the LM-free ones: the weights and, per (hypothesis of A, expansion entry), the LM term and next state
 struct Fusion { float weight, token_bonus; const double *ex_lm; const int32_t *ex_state; };
@@ -113,47 +134,66 @@ NASR_LP_HD double fused_total(double score, float weight, double lm, float token
     const double b = (double)token_bonus * (double)len;
     return score + a + b;
 }
-// the ordering key.  LM = false: the score itself
-template <bool LM>
+// key + boost as one rounded double add of its own
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+NASR_LP_HD double boosted_total(double key, double boost) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return key + boost;
+}
+// the ordering key.  LM = false: the score itself.  BOOST: + boost, added last
+template <bool LM, bool BOOST = false>
 NASR_LP_HD double total_of(const Hyp &h, float weight, float token_bonus) {
-    return LM ? fused_total(h.score, weight, h.lm, token_bonus, h.len) : h.score;
+    const double key = LM ? fused_total(h.score, weight, h.lm, token_bonus, h.len) : h.score;
+    return BOOST ? boosted_total(key, h.boost) : key;
 }
 NASR_LP_HD bool valid_weights(float weight, float token_bonus) {
     return weight >= 0.0f && weight <= 100.0f && token_bonus >= 0.0f && token_bonus <= 100.0f;       // false for NaN
 }
 NASR_LP_HD bool prune_allowed(float token_bonus, bool all_nonpositive) { return token_bonus == 0.0f && all_nonpositive; }
+// a boosted call: also only with the empty set (boost_states = the automaton's states, 2 = the disabled state and the root alone).  Without an LM
+// pass token_bonus 0 and all_nonpositive true
+NASR_LP_HD bool prune_allowed(float token_bonus, bool all_nonpositive, int boost_states) {
+    return prune_allowed(token_bonus, all_nonpositive) && boost_states <= nasr_boost::MIN_STATES;
+}
 
-// dst = src field by field: on the device a whole-struct copy of these 40 bytes may go through scratch memory, which the select kernel keeps clear of
+// dst = src field by field: on the device a whole-struct copy of these bytes may go through scratch memory, which the select kernel keeps clear of.
+// Without BOOST the two boost fields are neither read nor written
+template <bool BOOST = false>
 NASR_LP_HD void copy_hyp(Hyp &dst, const Hyp &src) {
     dst.score = src.score; dst.hash = src.hash; dst.node = src.node; dst.len = src.len; dst.slot = src.slot; dst.lm_state = src.lm_state; dst.lm = src.lm;
+    if (BOOST) { dst.boost = src.boost; dst.boost_state = src.boost_state; }
 }
 
 // place h behind the entries of list[0 .. n) whose key is not lower; the list keeps at most W entries.  Returns false when h fell off
-template <bool LM>
+template <bool LM, bool BOOST = false>
 NASR_LP_HD bool insert_sorted_t(Hyp *list, int32_t &n, int W, const Hyp &h, float weight, float token_bonus) {
     int pos = n;
-    const double key = total_of<LM>(h, weight, token_bonus);
-    while (pos > 0 && total_of<LM>(list[pos - 1], weight, token_bonus) < key) pos--;
+    const double key = total_of<LM, BOOST>(h, weight, token_bonus);
+    while (pos > 0 && total_of<LM, BOOST>(list[pos - 1], weight, token_bonus) < key) pos--;
     if (pos >= W) return false;
     const int last = n < W ? n : W - 1;
-    for (int i = last; i > pos; i--) copy_hyp(list[i], list[i - 1]);
-    copy_hyp(list[pos], h);
+    for (int i = last; i > pos; i--) copy_hyp<BOOST>(list[i], list[i - 1]);
+    copy_hyp<BOOST>(list[pos], h);
     if (n < W) n++;
     return true;
 }
 NASR_LP_HD bool insert_sorted(Hyp *list, int32_t &n, int W, const Hyp &h) { return insert_sorted_t<false>(list, n, W, h, 0.0f, 0.0f); }
 
 // an arrival in C: merge with the entry of the same sequence (strictly greater replaces), else insert and keep the W best
-template <bool LM>
+template <bool LM, bool BOOST = false>
 NASR_LP_HD void c_arrive_t(Beam &b, int W, const Node *nodes, const Hyp &h, float weight, float token_bonus) {
     for (int i = 0; i < b.nc; i++) {
         if (b.c[i].hash != h.hash || !same_seq(nodes, b.c[i].node, b.c[i].len, h.node, h.len)) continue;
-        if (!(total_of<LM>(h, weight, token_bonus) > total_of<LM>(b.c[i], weight, token_bonus))) return;
-        for (int j = i; j + 1 < b.nc; j++) copy_hyp(b.c[j], b.c[j + 1]);
+        if (!(total_of<LM, BOOST>(h, weight, token_bonus) > total_of<LM, BOOST>(b.c[i], weight, token_bonus))) return;
+        for (int j = i; j + 1 < b.nc; j++) copy_hyp<BOOST>(b.c[j], b.c[j + 1]);
         b.nc--;
         break;
     }
-    insert_sorted_t<LM>(b.c, b.nc, W, h, weight, token_bonus);
+    insert_sorted_t<LM, BOOST>(b.c, b.nc, W, h, weight, token_bonus);
 }
 NASR_LP_HD void c_arrive(Beam &b, int W, const Node *nodes, const Hyp &h) { c_arrive_t<false>(b, W, nodes, h, 0.0f, 0.0f); }
 
@@ -165,6 +205,43 @@ NASR_LP_HD int expand(const nasr_topk::tkey *top, int W, float m, float log_s, i
         if (top[j] == 0ull || id == BLANK_ID) continue;
         tok[n] = id; lp[n] = nasr_topk::alt_lp(top[j], m, log_s); n++;
     }
+    return n;
+}
+
+// The boosted expansion.  boosted_top: the row's 8 largest keys pack_key(logit[v] + bonus_row[v], v) over the 1025 outputs, descending (what the
+// boosted joint form leaves per row, restated for the host).  expand_ids: the list's tokens from those keys, by expand's rule.  boost_entry:
+// what one entry carries -- the MODEL's ln P from the RAW logit, the bonus and the next automaton state from the tables' rows of the state
+NASR_LP_HD void boosted_top(const float *raw, const float *bonus_row, nasr_topk::tkey *top) {
+    nasr_topk::RowTop rt;
+    nasr_topk::row_begin(rt);
+    for (int v = 0; v < nasr_lp::LP_VOCAB; v++) {
+        const nasr_topk::tkey k = nasr_lp::pack_key(raw[v] + bonus_row[v], v);
+        if (k > rt.last) nasr_topk::row_insert(rt, KTOP, k);
+    }
+    for (int j = 0; j < KTOP; j++) top[j] = rt.top[j];
+}
+NASR_LP_HD int expand_ids(const nasr_topk::tkey *top, int W, int32_t *tok) {
+    int n = 0;
+    for (int j = 0; j < KTOP && n < W; j++) {
+        const int id = nasr_topk::alt_id(top[j]);
+        if (top[j] == 0ull || id == BLANK_ID) continue;
+        tok[n++] = id;
+    }
+    return n;
+}
+NASR_LP_HD void boost_entry(float raw_logit, float m, float log_s, const float *bonus, const int32_t *next, int state, int token, float *lp, float *bon,
+                            int32_t *next_state) {
+    *lp = nasr_topk::lp_of(raw_logit, m, log_s);
+    *bon = nasr_boost::bonus_of(bonus, state, token);
+    *next_state = nasr_boost::next_of(next, state, token);
+}
+// a row's boosted expansion list from its RAW logits [1025] and the tables: tokens, raw ln P, bonus and next state
+NASR_LP_HD int expand_boost(const float *raw, const float *bonus, const int32_t *next, int state, int W, float m, float log_s, int32_t *tok, float *lp,
+                            float *bon, int32_t *next_state) {
+    nasr_topk::tkey top[KTOP];
+    boosted_top(raw, bonus + nasr_boost::table_index(state, 0), top);
+    const int n = expand_ids(top, W, tok);
+    for (int k = 0; k < n; k++) boost_entry(raw[tok[k]], m, log_s, bonus, next, state, tok[k], lp + k, bon + k, next_state + k);
     return n;
 }
 
@@ -180,20 +257,21 @@ NASR_LP_HD int take_slot(unsigned &used, int W) {
 // ends a frame: A is then C, whose states exist).  *advanced = the round ended the frame.  nodes: the utterance's pool of node_cap nodes;
 // returns -1 if it would overflow (it cannot within node_bound).  sel: room for WMAX candidates (the kernel passes LDS: one thread runs
 // the round, and a local array would be scratch memory of every lane of the launch)
-template <bool LM>
+// BOOST: ex_bonus / ex_bstate [i][KTOP] = the entry's phrase bonus and the automaton state after it
+template <bool LM, bool BOOST = false>
 NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
                             Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel, float wt, float tb, const double *ex_lm,
-                            const int32_t *ex_state) {
+                            const int32_t *ex_state, const float *ex_bonus = nullptr, const int32_t *ex_bstate = nullptr) {
     *advanced = false;
     if (b.t >= b.T) return 0;
     for (int i = 0; i < b.na; i++) {
         Hyp h;
-        copy_hyp(h, b.a[i]);
+        copy_hyp<BOOST>(h, b.a[i]);
         h.score += (double)lb[i];
-        c_arrive_t<LM>(b, W, nodes, h, wt, tb);
+        c_arrive_t<LM, BOOST>(b, W, nodes, h, wt, tb);
     }
     if (b.v == S) {                                           // the frame is over: Beam_{t+1} = C
-        for (int i = 0; i < b.nc; i++) copy_hyp(b.a[i], b.c[i]);
+        for (int i = 0; i < b.nc; i++) copy_hyp<BOOST>(b.a[i], b.c[i]);
         b.na = b.nc; b.nc = 0; b.t++; b.v = 0;
         *advanced = true;
         return 0;
@@ -201,7 +279,7 @@ NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, 
     // the W best of D in arrival order; sel[].node = parent index in A, .slot = position in its expansion list, until the nodes are made
     int32_t ns = 0;
     const bool full = b.nc >= W;
-    const double floor_c = full ? total_of<LM>(b.c[W - 1], wt, tb) : 0.0;
+    const double floor_c = full ? total_of<LM, BOOST>(b.c[W - 1], wt, tb) : 0.0;
     for (int i = 0; i < b.na; i++)
         for (int k = 0; k < ex_n[i]; k++) {
             Hyp h;
@@ -209,9 +287,10 @@ NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, 
             h.len = b.a[i].len + 1;
             h.lm = LM ? b.a[i].lm + ex_lm[i * KTOP + k] : 0.0;
             h.lm_state = LM ? ex_state[i * KTOP + k] : 0;
-            if (prune && full && !(total_of<LM>(h, wt, tb) > floor_c)) continue;
+            if (BOOST) { h.boost = b.a[i].boost + (double)ex_bonus[i * KTOP + k]; h.boost_state = ex_bstate[i * KTOP + k]; }
+            if (prune && full && !(total_of<LM, BOOST>(h, wt, tb) > floor_c)) continue;
             h.hash = 0; h.node = i; h.slot = k;
-            insert_sorted_t<LM>(sel, ns, W, h, wt, tb);
+            insert_sorted_t<LM, BOOST>(sel, ns, W, h, wt, tb);
         }
     unsigned used = 0;
     for (int i = 0; i < b.nc; i++) used |= 1u << b.c[i].slot;
@@ -228,10 +307,11 @@ NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, 
         Hyp h;
         h.score = sel[j].score; h.hash = hash_next(par.hash, tok); h.node = b.n_nodes; h.len = par.len + 1; h.slot = children[j].slot;
         h.lm_state = sel[j].lm_state; h.lm = sel[j].lm;
-        copy_hyp(sel[j], h);
+        if (BOOST) { h.boost = sel[j].boost; h.boost_state = sel[j].boost_state; }
+        copy_hyp<BOOST>(sel[j], h);
         b.n_nodes++;
     }
-    for (int j = 0; j < ns; j++) copy_hyp(b.a[j], sel[j]);
+    for (int j = 0; j < ns; j++) copy_hyp<BOOST>(b.a[j], sel[j]);
     b.na = ns; b.v++;
     return ns;
 }
@@ -248,12 +328,15 @@ NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, co
 
 // the final order with an LM: rank[0 .. return value) = indices into a[0 .. na), the N best by score + weight * lm_final + token_bonus * len,
 // stable on ties; total_final[i] = that key of a[i].  One thread runs it over <= 8 entries
-NASR_LP_HD int final_rank(const Hyp *a, int na, int N, const double *lm_final, float weight, float token_bonus, int32_t *rank, double *total_final) {
+// final_rank_t<LM, BOOST>: the same by the boosted key; LM = false: lm_final is not read and the key is score + boost
+template <bool LM, bool BOOST>
+NASR_LP_HD int final_rank_t(const Hyp *a, int na, int N, const double *lm_final, float weight, float token_bonus, int32_t *rank, double *total_final) {
     int32_t n = 0;
     for (int i = 0; i < na; i++) {
-        Hyp h = a[i];
-        h.lm = lm_final[i];
-        total_final[i] = total_of<true>(h, weight, token_bonus);
+        Hyp h;
+        copy_hyp<BOOST>(h, a[i]);
+        if (LM) h.lm = lm_final[i];
+        total_final[i] = total_of<LM, BOOST>(h, weight, token_bonus);
         int pos = n;
         while (pos > 0 && total_final[rank[pos - 1]] < total_final[i]) pos--;
         if (pos >= N) continue;
@@ -264,10 +347,15 @@ NASR_LP_HD int final_rank(const Hyp *a, int na, int N, const double *lm_final, f
     }
     return n;
 }
+NASR_LP_HD int final_rank(const Hyp *a, int na, int N, const double *lm_final, float weight, float token_bonus, int32_t *rank, double *total_final) {
+    return final_rank_t<true, false>(a, na, N, lm_final, weight, token_bonus, rank, total_final);
+}
 
+template <bool BOOST = false>
 NASR_LP_HD void beam_begin(Beam &b, int T, int lm_start = 0) {
     b.na = 1; b.nc = 0; b.t = 0; b.v = 0; b.n_nodes = 0; b.T = T;
     b.a[0].score = 0.0; b.a[0].hash = hash0(); b.a[0].node = -1; b.a[0].len = 0; b.a[0].slot = 0; b.a[0].lm_state = lm_start; b.a[0].lm = 0.0;
+    if (BOOST) { b.a[0].boost = 0.0; b.a[0].boost_state = nasr_boost::STATE_ROOT; }
 }
 
 // tokens, frames and ln P of a hypothesis, from its last node back to the root
@@ -286,35 +374,49 @@ namespace nasr_beam {
 struct Result {
     double score; std::vector<int32_t> tokens, frames; std::vector<float> lps;
     double lm = 0.0, lm_final = 0.0, total = 0.0;       // the fused search only (total = the final key; without an LM they stay 0)
+    double boost = 0.0; std::vector<float> bonuses;     // the boosted search only (then total is the boosted key, with or without an LM)
+    int32_t boost_state = 0;                            // ... the automaton state the search carried for the hypothesis
 };
+// the boost tables as the kernels see them: bonus / next [states][COLS] (nasr_boost::Automaton's vectors)
+struct BoostTables { const float *bonus; const int32_t *next; int states; };
 // A whole search on the host.  eval(t, tokens, len, &lb, top[KTOP], &m, &log_s) gives, for the state after `tokens`, ln P(blank), the row's 8
 // largest packed keys in the alternatives' order (blank among them or not) and its softmax (m, log s): what the joint kernels leave per row.
 // After every round it checks the slot binding: each child's slot lies in 0 .. 3 W - 1 and is held by no entry of C, no parent and no other
 // child.  Returns the node count, -1 if the trie or the slots ran out, -2 if a slot was bound twice.
-// lm != nullptr: the fused search (weight, token_bonus as in the header); *pruned = whether the prune was applied
-template <bool LM, class Eval>
+// lm != nullptr: the fused search (weight, token_bonus as in the header); *pruned = whether the prune was applied.
+// BOOST (bt != nullptr): the boosted search.  eval(t, tokens, len, &lb, &raw, &m, &log_s) then gives the row's RAW logits (raw -> 1025 floats that
+// stay valid until the next call) in place of the keys; the boosted list is expand_boost's
+template <bool LM, bool BOOST = false, class Eval>
 long long search_t(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const nasr_lm::View *lm, float weight, float token_bonus,
-                   bool *pruned) {
+                   bool *pruned, const BoostTables *bt = nullptr) {
     out.clear();
     if (LM) prune = prune && prune_allowed(token_bonus, lm->all_nonpositive != 0);
+    if (BOOST) prune = prune && prune_allowed(0.0f, true, bt->states);
     if (pruned) *pruned = prune;
     const long long cap = node_bound(T > 0 ? T : 0, W, S);
     std::vector<Node> nodes((size_t)cap + 1);
     Beam b;
-    beam_begin(b, T > 0 ? T : 0, LM ? lm->start : 0);
+    beam_begin<BOOST>(b, T > 0 ? T : 0, LM ? lm->start : 0);
     for (long long r = 0; T > 0 && r < rounds(T, S); r++) {
-        float lb[WMAX], ex_lp[WMAX * KTOP];
-        int32_t ex_tok[WMAX * KTOP], ex_state[WMAX * KTOP];
+        float lb[WMAX], ex_lp[WMAX * KTOP], ex_bonus[WMAX * KTOP];
+        int32_t ex_tok[WMAX * KTOP], ex_state[WMAX * KTOP], ex_bstate[WMAX * KTOP];
         double ex_lm[WMAX * KTOP];
         int ex_n[WMAX];
         for (int i = 0; i < b.na; i++) {
             std::vector<int32_t> seq((size_t)b.a[i].len), fr((size_t)b.a[i].len);
             std::vector<float> lps((size_t)b.a[i].len);
             backtrace(nodes.data(), b.a[i].node, b.a[i].len, seq.data(), fr.data(), lps.data());
-            nasr_topk::tkey top[KTOP];
             float m = 0.0f, log_s = 0.0f;
-            eval(b.t, seq.data(), b.a[i].len, &lb[i], top, &m, &log_s);
-            ex_n[i] = expand(top, W, m, log_s, ex_tok + i * KTOP, ex_lp + i * KTOP);
+            if constexpr (BOOST) {
+                const float *raw = nullptr;
+                eval(b.t, seq.data(), b.a[i].len, &lb[i], &raw, &m, &log_s);
+                ex_n[i] = expand_boost(raw, bt->bonus, bt->next, b.a[i].boost_state, W, m, log_s, ex_tok + i * KTOP, ex_lp + i * KTOP, ex_bonus + i * KTOP,
+                                       ex_bstate + i * KTOP);
+            } else {
+                nasr_topk::tkey top[KTOP];
+                eval(b.t, seq.data(), b.a[i].len, &lb[i], top, &m, &log_s);
+                ex_n[i] = expand(top, W, m, log_s, ex_tok + i * KTOP, ex_lp + i * KTOP);
+            }
             for (int k = 0; LM && k < ex_n[i]; k++) ex_lm[i * KTOP + k] = nasr_lm::lookup(*lm, b.a[i].lm_state, ex_tok[i * KTOP + k], &ex_state[i * KTOP + k]);
         }
         unsigned parents = 0;
@@ -322,7 +424,8 @@ long long search_t(int T, int W, int N, int S, bool prune, Eval eval, std::vecto
         Child ch[WMAX];
         Hyp sel[WMAX];
         bool adv;
-        const int n = round_step_t<LM>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes.data(), cap, ch, &adv, sel, weight, token_bonus, ex_lm, ex_state);
+        const int n = round_step_t<LM, BOOST>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes.data(), cap, ch, &adv, sel, weight, token_bonus, ex_lm, ex_state,
+                                              ex_bonus, ex_bstate);
         if (n < 0) return -1;
         unsigned held = parents;
         for (int i = 0; i < b.nc; i++) held |= 1u << b.c[i].slot;
@@ -340,15 +443,21 @@ long long search_t(int T, int W, int N, int S, bool prune, Eval eval, std::vecto
             int32_t next;
             lm_final[i] = lm->has_eos ? b.a[i].lm + nasr_lm::lookup(*lm, b.a[i].lm_state, nasr_lm::EOS, &next) : b.a[i].lm;
         }
-        n_out = final_rank(b.a, b.na, N, lm_final, weight, token_bonus, rank, total);
     }
+    if (LM || BOOST) n_out = final_rank_t<LM, BOOST>(b.a, b.na, N, lm_final, weight, token_bonus, rank, total);
     for (int j = 0; j < n_out; j++) {
         const Hyp &h = b.a[rank[j]];
         Result r;
         r.score = h.score;
         r.tokens.resize((size_t)h.len); r.frames.resize((size_t)h.len); r.lps.resize((size_t)h.len);
         backtrace(nodes.data(), h.node, h.len, r.tokens.data(), r.frames.data(), r.lps.data());
-        if (LM) { r.lm = h.lm; r.lm_final = lm_final[rank[j]]; r.total = total[rank[j]]; }
+        if (LM) { r.lm = h.lm; r.lm_final = lm_final[rank[j]]; }
+        if (LM || BOOST) r.total = total[rank[j]];
+        if (BOOST) {                                          // the per-token bonuses, by the tables, from the root
+            r.boost = h.boost; r.boost_state = h.boost_state;
+            int st = nasr_boost::STATE_ROOT;
+            for (int32_t tk : r.tokens) { r.bonuses.push_back(nasr_boost::bonus_of(bt->bonus, st, tk)); st = nasr_boost::next_of(bt->next, st, tk); }
+        }
         out.push_back(r);
     }
     return b.n_nodes;
@@ -361,6 +470,16 @@ template <class Eval>
 long long search(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const nasr_lm::View &lm, float weight, float token_bonus,
                  bool *pruned = nullptr) {
     return search_t<true>(T, W, N, S, prune, eval, out, &lm, weight, token_bonus, pruned);
+}
+// the boosted searches (eval gives raw logits, see search_t)
+template <class Eval>
+long long search_boost(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const BoostTables &bt, bool *pruned = nullptr) {
+    return search_t<false, true>(T, W, N, S, prune, eval, out, nullptr, 0.0f, 0.0f, pruned, &bt);
+}
+template <class Eval>
+long long search_boost(int T, int W, int N, int S, bool prune, Eval eval, std::vector<Result> &out, const BoostTables &bt, const nasr_lm::View &lm, float weight,
+                       float token_bonus, bool *pruned = nullptr) {
+    return search_t<true, true>(T, W, N, S, prune, eval, out, &lm, weight, token_bonus, pruned, &bt);
 }
 }  // namespace nasr_beam
 #endif

@@ -251,6 +251,7 @@ struct nasr_engine {
     float *boost_bonus = nullptr; int32_t *boost_next = nullptr;   // [capacity][1040] each
     int *boost_state = nullptr;      // [slot] automaton state of every stream's emitted history
     float *boost_raw = nullptr;      // scratch beside lp_part: raw logit of every part's winner (read only when both options are on)
+    nasr_boost::Automaton boost_host;   // the current set's tables on the host: a boosted beam call reads its hypotheses' per-token bonuses from them
     // nasr_engine_set_lm (nasr_lm.h): the compiled n-gram model on the host (the read-out of per-token values) and, in one device block, the
     // tables the beam kernels read.  Only beam calls see it
     nasr_lm::Model *lm = nullptr; void *lm_dev = nullptr;

@@ -227,6 +227,7 @@ struct DecParams {
     const int32_t *boost_next;   // [states][1040] state after emitting that entry
     int *boost_state;            // [slot] automaton state of the slot's emitted history (0: boosting disabled for it, 1: root)
     float *boost_raw;            // [B * T][n_parts] with "token_logprobs" too: raw logit of every part's winner by boosted key
+    float *raw_logits;           // [B * T][1040] the boosted beam evaluation only (launch_decode_rows_boost): every row's raw logits
     // engine option "token_alternatives" = alt_k (all null / 0 when it is off), nasr_topk.h; these variants always leave the softmax parts too,
     // so lp_part and tok_logprob are set with them
     unsigned long long *alt_key; // [B * T][n_parts][alt_k] the alt_k largest raw-logit keys of every vocab slice of every evaluated row
@@ -276,6 +277,8 @@ void launch_align_recursion(const AlignRecParams &p, int n, hipStream_t st);
 // the evaluation of a round: launch_decode_candidates over p.dlist, then k_dec_joint_tiled in its LP + ALT form over p.rowmap whatever the
 // row count (one kernel form, so a sub-batch gives the bits an utterance gives alone); no commit.  p.alt_k = 8, 17 parts per row
 void launch_decode_rows(const DecParams &p, hipStream_t st);
+// a boosted beam call (NASR_FLAG_BEAM_BOOST): the tiled joint's BEAMB form -- the lists by logit + bonus(state of the row's slot), the raw logits kept
+void launch_decode_rows_boost(const DecParams &p, hipStream_t st);
 struct BeamUtt { int enc_row, T; long long node0, out0; };      // first packed encoder row, frames, first node of its pool, first output entry
 struct BeamParams {
     const BeamUtt *utt; int n;   // live utterances of the sub-batch, one workgroup each; hypothesis j of utterance k is batch row k * W + j
@@ -296,6 +299,13 @@ struct BeamParams {
     int lm_on; float lm_weight, lm_bonus;
     nasr_lm::View lm;
     double *out_lm, *out_lm_final, *out_total;     // [n][8] each
+    // phrase boosting (NASR_FLAG_BEAM_BOOST; boost_on = 0: none of this is read): the engine's tables, the beam's own per-slot automaton states
+    // (the boosted joint form reads them), the raw logits it left, and the outputs.  With boost_on, out_total is written with or without an LM
+    int boost_on;
+    const float *boost_bonus; const int32_t *boost_next;
+    int *boost_state;            // [n * 3 W]
+    const float *raw_logits;     // [n * W][1040]
+    double *out_boost;           // [n][8]
 };
 void launch_beam_init(const BeamParams &p, hipStream_t st);
 void launch_beam_select(const BeamParams &p, hipStream_t st);

@@ -47,11 +47,13 @@ struct OfflineState {
     // beam search (nasr_engine_transcribe_beam*): its own decoder slots (3 W per utterance), batch rows (W per utterance), the joint's LP + ALT
     // scratch whatever the engine options are, the search state and trie of the sub-batch in flight, and the results of the last call
     struct BeamBuf { void *p = nullptr; size_t cap = 0; };
-    BeamBuf bm_utt, bm_beam, bm_nodes, bm_enc, bm_rows, bm_ctrl, bm_h, bm_c, bm_predg, bm_key, bm_part, bm_alt, bm_cnt, bm_dlist, bm_rowmap, bm_out_lm,
+    BeamBuf bm_utt, bm_beam, bm_nodes, bm_enc, bm_rows, bm_ctrl, bm_h, bm_c, bm_predg, bm_key, bm_part, bm_alt, bm_cnt, bm_dlist, bm_rowmap, bm_out_lm, bm_bstate, bm_raw, bm_out_boost,
             bm_out_n, bm_out_len, bm_out_score, bm_out_tok, bm_out_frame, bm_out_lp;
-    struct BeamHyp { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; double lm_final = 0.0, total = 0.0; };
+    struct BeamHyp { double score; std::vector<int32_t> tokens, frames; std::vector<float> lps; double lm_final = 0.0, total = 0.0;
+                     double boost = 0.0; std::vector<float> bonuses; };     // a boosted call: the sum and the per-token bonuses by the set in force during it
     long long beam_lm_generation = 0;                              // the engine's lm_generation at that call
     bool beam_valid = false, beam_lm = false;                      // beam_lm: the last beam call ran with a language model (nasr_engine_set_lm)
+    bool beam_boost = false;                                       // the last beam call was boosted (NASR_FLAG_BEAM_BOOST)
     std::vector<std::vector<BeamHyp>> beam_res;                    // by utterance, best first
     float *t_sub = nullptr, *t_lay = nullptr, *t_enc = nullptr;   // debug taps of the sub-batch in flight
     // debug taps of the last call, by utterance
@@ -890,6 +892,7 @@ static int beam_buf(nasr_engine *e, OfflineState *o, OfflineState::BeamBuf &b, s
 // decode's two LSTM layers, joint.pred and tiled joint, then k_beam_select), no host round trip inside
 static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W, int N, int S) {
     hipStream_t st = e->st;
+    const bool boost = o->beam_boost, totals = boost || e->lm;   // boosted: the BOOST kernel forms, their buffers and the final key with or without an LM
     std::vector<int> live;
     std::vector<BeamUtt> ud;
     long long nodes = 0, outs = 0;
@@ -906,6 +909,7 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
                 z.lm = h.lm_final = v.has_eos ? nasr_lm::lookup(v, v.start, nasr_lm::EOS, &next) : 0.0;
                 h.total = nasr_beam::total_of<true>(z, e->lm_weight, e->lm_bonus);
             }
+            if (boost) h.total = nasr_beam::boosted_total(h.total, 0.0);       // no token: boost 0
             o->beam_res[b].assign(1, h);
             continue;
         }
@@ -928,7 +932,9 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
         beam_buf(e, o, o->bm_dlist, rows * 4) || beam_buf(e, o, o->bm_rowmap, rows * 4) || beam_buf(e, o, o->bm_out_n, n * 4) ||
         beam_buf(e, o, o->bm_out_len, (size_t)n * nasr_beam::WMAX * 4) || beam_buf(e, o, o->bm_out_score, (size_t)n * nasr_beam::WMAX * 8) ||
         beam_buf(e, o, o->bm_out_tok, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_frame, (size_t)outs * 4) || beam_buf(e, o, o->bm_out_lp, (size_t)outs * 4) ||
-        (e->lm && beam_buf(e, o, o->bm_out_lm, (size_t)n * nasr_beam::WMAX * 8 * 3)))
+        (totals && beam_buf(e, o, o->bm_out_lm, (size_t)n * nasr_beam::WMAX * 8 * 3)) ||
+        (boost && (beam_buf(e, o, o->bm_bstate, slots * 4) || beam_buf(e, o, o->bm_raw, rows * nasr_boost::COLS * 4) ||
+                   beam_buf(e, o, o->bm_out_boost, (size_t)n * nasr_beam::WMAX * 8))))
         return -1;
     HIPCHK(hipMemcpyAsync(o->bm_utt.p, ud.data(), n * sizeof(BeamUtt), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(o->bm_rows.p, 0, rows * sizeof(RowDesc), st));
@@ -947,7 +953,12 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     if (e->lm) {                                               // shallow fusion: the prune only where its proof holds (nasr_beam.h)
         bp.lm_on = 1; bp.lm = e->lm_view; bp.lm_weight = e->lm_weight; bp.lm_bonus = e->lm_bonus;
         bp.prune = nasr_beam::prune_allowed(e->lm_bonus, e->lm->all_nonpositive) ? 1 : 0;
-        bp.out_lm = (double *)o->bm_out_lm.p; bp.out_lm_final = bp.out_lm + (size_t)n * nasr_beam::WMAX; bp.out_total = bp.out_lm_final + (size_t)n * nasr_beam::WMAX;
+    }
+    if (totals) { bp.out_lm = (double *)o->bm_out_lm.p; bp.out_lm_final = bp.out_lm + (size_t)n * nasr_beam::WMAX; bp.out_total = bp.out_lm_final + (size_t)n * nasr_beam::WMAX; }
+    if (boost) {                                               // a non-empty set pays positive bonuses: unpruned (nasr_beam.h)
+        bp.boost_on = 1; bp.boost_bonus = e->boost_bonus; bp.boost_next = e->boost_next; bp.boost_state = (int *)o->bm_bstate.p;
+        bp.raw_logits = (const float *)o->bm_raw.p; bp.out_boost = (double *)o->bm_out_boost.p;
+        bp.prune = nasr_beam::prune_allowed(e->lm ? e->lm_bonus : 0.0f, e->lm ? e->lm->all_nonpositive != 0 : true, e->boost_states) ? 1 : 0;
     }
     DecParams dp;
     memset(&dp, 0, sizeof(dp));
@@ -955,6 +966,7 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     bind_dec_weights(e, dp);
     dp.predg = (float *)o->bm_predg.p; dp.key = (unsigned long long *)o->bm_key.p; dp.n_active = cnt + 5;
     dp.dlist = bp.dlist; dp.rowmap = bp.rowmap; dp.lp_part = (nasr_lp::Part *)o->bm_part.p; dp.alt_key = (unsigned long long *)o->bm_alt.p; dp.alt_k = nasr_beam::KTOP;
+    if (boost) { dp.boost_bonus = bp.boost_bonus; dp.boost_next = bp.boost_next; dp.boost_state = bp.boost_state; dp.raw_logits = (float *)o->bm_raw.p; }
     bp.cnt_next = cnt; bp.cnt_zero = cnt + 2;
     ProfScope ps(e, "beam_search", 0, 0);                      // one scope for the whole search: thousands of rounds would each cost an event pair
     launch_beam_init(bp, st);
@@ -962,13 +974,13 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     for (long long r = 0; r < R; r++) {
         const int par = (int)(r & 1);
         dp.n_dirty = cnt + 2 * par; dp.n_rows = cnt + 2 * par + 1;
-        launch_decode_rows(dp, st);
+        if (boost) launch_decode_rows_boost(dp, st); else launch_decode_rows(dp, st);
         bp.cnt_zero = cnt + 2 * par; bp.cnt_next = cnt + 2 * (par ^ 1);
         launch_beam_select(bp, st);
     }
     launch_beam_final(bp, st);
     std::vector<int32_t> hn(n), hlen((size_t)n * nasr_beam::WMAX), htok((size_t)outs), hfr((size_t)outs);
-    std::vector<double> hsc((size_t)n * nasr_beam::WMAX), hlm(e->lm ? (size_t)n * nasr_beam::WMAX * 3 : 0);
+    std::vector<double> hsc((size_t)n * nasr_beam::WMAX), hlm(totals ? (size_t)n * nasr_beam::WMAX * 3 : 0), hbo(boost ? (size_t)n * nasr_beam::WMAX : 0);
     std::vector<float> hlp((size_t)outs);
     int herr[1] = {0};
     HIPCHK(hipMemcpyAsync(hn.data(), bp.out_n, n * 4, hipMemcpyDeviceToHost, st));
@@ -979,6 +991,8 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
     HIPCHK(hipMemcpyAsync(hlp.data(), bp.out_lp, hlp.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(herr, bp.err, 4, hipMemcpyDeviceToHost, st));
     if (e->lm) HIPCHK(hipMemcpyAsync(hlm.data(), bp.out_lm, hlm.size() * 8, hipMemcpyDeviceToHost, st));
+    else if (boost) HIPCHK(hipMemcpyAsync(hlm.data() + (size_t)2 * n * nasr_beam::WMAX, bp.out_total, (size_t)n * nasr_beam::WMAX * 8, hipMemcpyDeviceToHost, st));
+    if (boost) HIPCHK(hipMemcpyAsync(hbo.data(), bp.out_boost, hbo.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (herr[0]) return fail("beam search: the trie of an utterance outgrew its bound");
     for (int k = 0; k < n; k++) {
@@ -991,8 +1005,17 @@ static int beam_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, int W
             const size_t at = (size_t)(ud[k].out0 + r * cap);
             OfflineState::BeamHyp h;
             h.score = hsc[(size_t)k * nasr_beam::WMAX + r];
-            if (e->lm) { h.lm_final = hlm[((size_t)n + k) * nasr_beam::WMAX + r]; h.total = hlm[((size_t)2 * n + k) * nasr_beam::WMAX + r]; }
+            if (e->lm) h.lm_final = hlm[((size_t)n + k) * nasr_beam::WMAX + r];
+            if (totals) h.total = hlm[((size_t)2 * n + k) * nasr_beam::WMAX + r];
             h.tokens.assign(htok.begin() + at, htok.begin() + at + len);
+            if (boost) {                                       // the per-token bonuses are fixed now, from the set the search ran with
+                h.boost = hbo[(size_t)k * nasr_beam::WMAX + r];
+                int state = nasr_boost::STATE_ROOT;
+                for (int32_t tk : h.tokens) {
+                    h.bonuses.push_back(nasr_boost::bonus_of(e->boost_host.bonus.data(), state, tk));
+                    state = nasr_boost::next_of(e->boost_host.next.data(), state, tk);
+                }
+            }
             h.frames.assign(hfr.begin() + at, hfr.begin() + at + len);
             h.lps.assign(hlp.begin() + at, hlp.begin() + at + len);
             o->beam_res[b].push_back(std::move(h));
@@ -1016,8 +1039,16 @@ static int beam_check_params(const nasr_beam_params *params, int *W, int *N, int
     return 0;
 }
 
+// NASR_FLAG_BEAM_BOOST of a beam entry: it needs engine option "phrase_boost" and excludes NASR_FLAG_NO_BOOST
+static int beam_check_flags(nasr_engine *e, uint32_t flags) {
+    if (!(flags & NASR_FLAG_BEAM_BOOST)) return 0;
+    if (!e->opt_phrase_boost) return fail("NASR_FLAG_BEAM_BOOST needs engine option \"phrase_boost\" (set it to the state capacity before the first step or offline call)");
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_BEAM_BOOST and NASR_FLAG_NO_BOOST exclude each other");
+    return 0;
+}
+
 static int beam_core(nasr_engine *e, int B, const float *const *mel, const int32_t *n_frames, bool mel_device, const int32_t *prompt_index,
-                     int W, int N, int S, int32_t *n_hyps) {
+                     int W, int N, int S, int32_t *n_hyps, bool boost) {
     OfflineState *o = e->off;
     std::vector<int> T;
     std::vector<nasr_plan::Batch> batches;
@@ -1032,6 +1063,7 @@ static int beam_core(nasr_engine *e, int B, const float *const *mel, const int32
     if (begin_taps(e, o, B, mel, n_frames, mel_device)) return -1;
     o->beam_res.assign(B, {});
     o->beam_lm = e->lm != nullptr; o->beam_lm_generation = e->lm_generation;
+    o->beam_boost = boost;
     for (const auto &bt : batches) {
         OffBatch ob;
         if (run_offline_encoder(e, o, mel, n_frames, prompt_index, T, bt.first, bt.count, ob)) { o->beam_res.clear(); return -1; }
@@ -1051,13 +1083,13 @@ extern "C" int nasr_engine_transcribe_beam_mel(nasr_engine *e, int B, const floa
     if (B < 0) return fail("B < 0");
     int W, N, S;
     beam_forget(e);
-    if (beam_check_params(params, &W, &N, &S)) return -1;
+    if (beam_check_params(params, &W, &N, &S) || beam_check_flags(e, flags)) return -1;
     if (B == 0) return 0;
     if (!mel || !n_frames) return fail("null mel / n_frames");
     for (int b = 0; b < B; b++)
         if (n_frames[b] < 0 || (n_frames[b] > 0 && !mel[b])) return fail("bad mel input for utterance %d", b);
     if (begin_call(e, B, prompt_index, n_hyps, flags, "nasr_engine_transcribe_beam_mel")) return -1;
-    return beam_core(e, B, mel, n_frames, false, prompt_index, W, N, S, n_hyps);
+    return beam_core(e, B, mel, n_frames, false, prompt_index, W, N, S, n_hyps, (flags & NASR_FLAG_BEAM_BOOST) != 0);
 }
 
 extern "C" int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t *const *pcm, const int32_t *n_samples, const int32_t *prompt_index,
@@ -1067,7 +1099,7 @@ extern "C" int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t 
     if (B < 0) return fail("B < 0");
     int W, N, S;
     beam_forget(e);
-    if (beam_check_params(params, &W, &N, &S)) return -1;
+    if (beam_check_params(params, &W, &N, &S) || beam_check_flags(e, flags)) return -1;
     if (B == 0) return 0;
     if (!pcm || !n_samples) return fail("null pcm / n_samples");
     std::vector<int32_t> n_mel(B);
@@ -1085,7 +1117,7 @@ extern "C" int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t 
                     bad, bad >= 0 ? n_samples[bad] : -1, bad >= 0 ? nasr_plan::enc_frames(n_mel[bad]) : -1, NASR_OFFLINE_MAX_FRAMES, nasr_plan::max_samples() / 16000.0);
     std::vector<const float *> mel;
     if (offline_mel(e, e->off, B, pcm, n_samples, (flags & NASR_FLAG_PCM_DEVICE) != 0, n_mel, mel)) return -1;
-    return beam_core(e, B, mel.data(), n_mel.data(), true, prompt_index, W, N, S, n_hyps);
+    return beam_core(e, B, mel.data(), n_mel.data(), true, prompt_index, W, N, S, n_hyps, (flags & NASR_FLAG_BEAM_BOOST) != 0);
 }
 
 extern "C" int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens_out, int32_t *frames_out, float *token_logprobs_out,
@@ -1128,5 +1160,23 @@ extern "C" int nasr_engine_beam_hypothesis_lm(nasr_engine *e, int u, int rank, d
         int32_t state = v.start;
         for (int i = 0; i < n; i++) token_lm_logprobs_out[i] = (float)nasr_lm::lookup(v, state, h.tokens[(size_t)i], &state);
     }
+    return (int)h.tokens.size();
+}
+
+// the boost side of a hypothesis of the last beam call, which must have been boosted (NASR_FLAG_BEAM_BOOST): the sum of its tokens' bonuses and the
+// ranking key, both as the device computed them; the per-token bonuses were fixed when the call fetched its results, from the set it ran with
+extern "C" int nasr_engine_beam_hypothesis_boost(nasr_engine *e, int u, int rank, double *boost_out, double *total_out, float *token_bonus_out, int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    OfflineState *o = e->off;
+    if (!o || !o->beam_valid || u < 0 || u >= (int)o->beam_res.size())
+        return fail("no beam hypotheses of utterance %d (they are those of the last offline call, which must be a beam call)", u);
+    if (!o->beam_boost) return fail("the last beam call ran without phrase boosting (NASR_FLAG_BEAM_BOOST)");
+    if (rank < 0 || rank >= (int)o->beam_res[u].size()) return fail("utterance %d has %d hypotheses, no rank %d", u, (int)o->beam_res[u].size(), rank);
+    const OfflineState::BeamHyp &h = o->beam_res[u][rank];
+    if (boost_out) *boost_out = h.boost;
+    if (total_out) *total_out = h.total;
+    const int n = std::min<int>((int)h.tokens.size(), std::max(cap, 0));
+    if (token_bonus_out) memcpy(token_bonus_out, h.bonuses.data(), (size_t)n * 4);
     return (int)h.tokens.size();
 }

@@ -317,6 +317,17 @@ bool nemo_clear_lm(nemo_context *ctx) {
     return true;
 }
 
+bool nemo_set_beam_boost(nemo_context *ctx, bool enable) {
+    if (!ctx || !ctx->engine) return false;
+    int64_t cap = 0;
+    if (enable && (nasr_engine_get_counter(ctx->engine, "boost_states", &cap) < 0 || cap == 0)) {
+        fprintf(stderr, "%s: phrase boosting is off (nemo_set_phrase_boost)\n", __func__);
+        return false;
+    }
+    ctx->beam_boost = enable;
+    return true;
+}
+
 bool nemo_stream_set_boost(nemo_stream_context *sctx, bool enable) {
     if (!sctx || !sctx->stream) return false;
     if (nasr_stream_set_boost(sctx->stream, enable ? 1 : 0) < 0) {
@@ -405,7 +416,7 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
     nasr_beam_params bp;
     bp.beam = beam; bp.nbest = nbest; bp.max_symbols = max_symbols; bp.reserved = 0;
     int32_t n_hyps = 0;
-    if (nasr_engine_transcribe_beam(ctx->engine, 1, &audio, &n_samples, pp, &bp, &n_hyps, 0) < 0) {
+    if (nasr_engine_transcribe_beam(ctx->engine, 1, &audio, &n_samples, pp, &bp, &n_hyps, ctx->beam_boost ? NASR_FLAG_BEAM_BOOST : 0) < 0) {
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return out;
     }
@@ -422,6 +433,15 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
                 return out;
             }
             h.has_lm = true;
+        }
+        if (ctx->beam_boost) {
+            h.token_bonuses.assign((size_t)n, 0.0f);
+            if (nasr_engine_beam_hypothesis_boost(ctx->engine, 0, r, &h.boost, &h.total, h.token_bonuses.data(), n) < 0) {
+                fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+                out.clear();
+                return out;
+            }
+            h.has_boost = true;
         }
         out.push_back(h);
     }

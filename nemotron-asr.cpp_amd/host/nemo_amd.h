@@ -31,6 +31,7 @@ struct nemo_context {               // reference: nemo_context / nemo_model (src
     int max_streams = 0;
     int token_alternatives = 0;      // K of nemo_set_token_alternatives (0: off)
     bool lm_attached = false;        // nemo_load_lm_arpa succeeded and nemo_clear_lm has not been called
+    bool beam_boost = false;         // nemo_set_beam_boost: nemo_transcribe_beam applies the boost phrases inside the search
     int workspace_rows = 0;          // rows one engine call may carry (streams x chunks x (1 + right_context)); nasr_engine_create_ex
 };
 
@@ -112,14 +113,17 @@ nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_s
 // MI355X extension: offline transcription of one whole utterance with the frame-synchronous beam search (nasr_engine_transcribe_beam): the
 // nbest distinct transcripts, best first, each with its score (the ln P of its best-scoring lattice path), the encoder frame of every token
 // and its ln P.  beam 1 .. 8, nbest 0 = beam, max_symbols 0 = the default; beam = 0 is the greedy offline transcription
-// (nasr_engine_transcribe: one hypothesis, score NAN, no log-probabilities).  Phrase boosting is not applied in beam calls.  Empty on failure
-// (the reason on stderr)
+// (nasr_engine_transcribe: one hypothesis, score NAN, no log-probabilities; it is boosted whenever phrase boosting is on).  In beam calls
+// phrase boosting is applied only after nemo_set_beam_boost(ctx, true).  Empty on failure (the reason on stderr)
 struct nemo_hypothesis {
     double score = 0.0;
     std::vector<int32_t> tokens, frames;
     std::vector<float> logprobs;
     bool has_lm = false;             // a language model was attached (nemo_load_lm_arpa): ranks are by `total`
     double lm_logprob = 0.0, total = 0.0;      // ln P_LM of the transcript (EOS term included when the model has one); score + weight * lm + bonus * tokens
+    bool has_boost = false;          // the search was boosted (nemo_set_beam_boost): ranks are by `total`, which then also includes `boost`
+    double boost = 0.0;              // the sum of the tokens' phrase bonuses
+    std::vector<float> token_bonuses;
 };
 std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest = 0, int max_symbols = 0);
 
@@ -130,6 +134,12 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
 // the previous model stays).  nemo_clear_lm detaches it.
 bool nemo_load_lm_arpa(nemo_context *ctx, const char *path, float weight, float token_bonus = 0.0f, float unk_logprob = NAN);
 bool nemo_clear_lm(nemo_context *ctx);
+
+// MI355X extension: phrase boosting inside nemo_transcribe_beam (NASR_FLAG_BEAM_BOOST), with or without a language
+// model.  It needs nemo_set_phrase_boost and a boost set (nemo_set_boost_phrases / nemo_load_boost_file); unlike the language model the
+// boost also PROPOSES: a boosted token outside a hypothesis' largest outputs enters its expansion list.  Off by default; false when phrase
+// boosting is off
+bool nemo_set_beam_boost(nemo_context *ctx, bool enable);
 
 // ---- streaming (reference src/nemo-stream.h:271-326) -------------------------------------------------
 nemo_stream_context *nemo_stream_init(nemo_context *ctx, const nemo_cache_config *config = nullptr);

@@ -12,7 +12,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--f32] [--device N] [--lang CODE] [--print-tokens]\n"
+            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--boost-file FILE] [--boost-bonus X] [--f32] [--device N] [--lang CODE] [--print-tokens]\n"
             "  audio: raw s16le, 16 kHz, mono, one whole utterance (up to 2048 encoder frames = 163.8 s)\n"
             "  without --beam: the greedy transcript, one line\n"
             "  --beam W (1 .. 8): one line per hypothesis, best first: rank score text   (score = ln P of the hypothesis's best path;\n"
@@ -21,6 +21,10 @@ static void usage(const char *prog) {
             "  word, <s>, </s>, <unk>; up to 5-grams); hypotheses rank by total = score + X * lm + Y * tokens (--lm-weight X, default 0.5;\n"
             "  --token-bonus Y, default 0; both 0 .. 100) and the lines read: rank score lm total text.  The model re-scores the transducer's\n"
             "  candidates, it proposes none\n"
+            "  --boost-file F: phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional; natural-log units added to the logits of the\n"
+            "  tokens that start or continue a phrase; `ids:1,2,3` gives literal token ids); --boost-bonus X: the bonus of lines that give none\n"
+            "  (default 4.0).  Without --beam the greedy decode is boosted.  With --beam the search is boosted: a boosted token is proposed even outside a\n"
+            "  hypothesis' largest outputs, hypotheses rank by total = score (+ the LM terms) + boost, and the lines read: rank score [lm] boost total text\n"
             "  --print-tokens: after each line `tokens ...` and `frames ...`, the ids and the encoder frame each is emitted at\n",
             prog);
 }
@@ -32,7 +36,9 @@ int main(int argc, char **argv) {
     bool print_tokens = false;
     const char *lm_path = nullptr;
     float lm_weight = 0.5f, token_bonus = 0.0f;
-    bool lm_opts = false;
+    bool lm_opts = false, boost_opts = false;
+    const char *boost_file = nullptr;
+    float boost_bonus = 4.0f;
     for (int i = 3; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lang" && i + 1 < argc) lang = argv[++i];
@@ -43,6 +49,8 @@ int main(int argc, char **argv) {
         else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
         else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = true; }
         else if (a == "--token-bonus" && i + 1 < argc) { token_bonus = strtof(argv[++i], nullptr); lm_opts = true; }
+        else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
+        else if (a == "--boost-bonus" && i + 1 < argc) { boost_bonus = strtof(argv[++i], nullptr); boost_opts = true; }
         else if (a == "--f32") dtype = 0;
         else if (a == "--print-tokens") print_tokens = true;
         else { usage(argv[0]); return 1; }
@@ -51,6 +59,7 @@ int main(int argc, char **argv) {
     if (beam < 0) { fprintf(stderr, "--beam must be 1 .. 8\n"); return 1; }
     if (lm_path && beam == 0) { fprintf(stderr, "--lm goes with --beam\n"); return 1; }
     if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
+    if (boost_opts && !boost_file) { fprintf(stderr, "--boost-bonus goes with --boost-file\n"); return 1; }
     FILE *in = fopen(audio_path, "rb");
     if (!in) { fprintf(stderr, "Failed to open audio file: %s\n", audio_path); return 1; }
     std::vector<int16_t> pcm;
@@ -62,12 +71,19 @@ int main(int argc, char **argv) {
     if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     if (lm_path && !nemo_load_lm_arpa(ctx, lm_path, lm_weight, token_bonus)) { nemo_free(ctx); return 1; }
+    if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus) && (beam == 0 || nemo_set_beam_boost(ctx, true)))) {
+        fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file);
+        nemo_free(ctx);
+        return 1;
+    }
     const std::vector<nemo_hypothesis> hyps = nemo_transcribe_beam(ctx, pcm.data(), (int)pcm.size(), beam, nbest, max_symbols);
     if (hyps.empty()) { nemo_free(ctx); return 1; }
     for (size_t r = 0; r < hyps.size(); r++) {
         const std::vector<int> toks(hyps[r].tokens.begin(), hyps[r].tokens.end());
         const std::string text = tokens_to_text(toks, ctx->vocab);
         if (beam == 0) printf("%s\n", text.c_str());
+        else if (hyps[r].has_boost && hyps[r].has_lm) printf("%zu %.6f %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].lm_logprob, hyps[r].boost, hyps[r].total, text.c_str());
+        else if (hyps[r].has_boost) printf("%zu %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].boost, hyps[r].total, text.c_str());
         else if (hyps[r].has_lm) printf("%zu %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].lm_logprob, hyps[r].total, text.c_str());
         else printf("%zu %.6f %s\n", r, hyps[r].score, text.c_str());
         if (print_tokens) {
