@@ -6,7 +6,7 @@
 //                   merges the alternatives' slices of each of the <= W rows and finishes their ln P from the softmax parts, applies the C / D
 //                   rules in double, creates the trie nodes, gathers each child's committed state from its parent's candidate state, rebinds
 //                   the rows' slots and lists the rows of the next evaluation
-//   k_beam_final    the N best of Beam_T: tokens, frames, ln P and scores
+//   k_beam_final    the N best of Beam_T: tokens, frames, ln P and scores (<LM, BOOST>: by the final key)
 // Shallow fusion (nasr_engine_set_lm, nasr_lm.h): the LM instantiations of k_beam_select and k_beam_final.  Between the row phase and the serial
 // rule phase one thread per (live hypothesis, expansion entry), at most 64, looks its token up in the n-gram tables in HBM (plain loads; the
 // loops are bounded by the table header's order and max_probe) and leaves the term and the next LM state in LDS beside ex_lp / ex_tok; the
@@ -15,7 +15,7 @@
 // BEAMB form (lists by logit + bonus of the row's automaton state; the raw logits of every row kept).  The row phase merges the boosted lists as
 // before; the same (hypothesis, entry) threads then read the entry's raw logit, form the MODEL's ln P from it and read the entry's bonus and next
 // automaton state from the tables -- plain loads beside the LM look-up.  Every row bound for the next evaluation gets its slot's automaton state
-// from its hypothesis (boost_state [n * 3 W], the beam's own array); k_beam_init writes the root; k_beam_final_boost re-ranks by the boosted key and
+// from its hypothesis (boost_state [n * 3 W], the beam's own array); k_beam_init writes the root; k_beam_final<LM, true> re-ranks by the boosted key and
 // writes boost and that key per hypothesis.
 // The host enqueues T_max * (S + 1) rounds blind; a finished utterance's workgroup returns at once and lists nothing.  No kernel waits on
 // another workgroup: the lists of the next evaluation are filled through two atomic tickets per utterance, and the counters alternate between
@@ -147,20 +147,43 @@ __global__ __launch_bounds__(256) void k_beam_select(BeamParams p) {
             p.enc[((size_t)k * W + i / JNT) * JNT + i % JNT] = p.encproj[(size_t)(ud.enc_row + bm.t) * JNT + i % JNT];
 }
 
+// The N best of Beam_T.  <false, false>: Beam_T's order as it stands and the scores alone (out_lm*, out_total and out_boost are null).  LM: lm_final =
+// lm + the EOS term (when some n-gram ends in EOS).  LM or BOOST: one thread re-ranks the <= 8 entries by the final key (final_rank_t, stable, so
+// without an LM the order is Beam_T's: it is sorted by score + boost already); the key goes out per hypothesis, with lm and lm_final (LM) and boost (BOOST)
+template <bool LM, bool BOOST>
 __global__ __launch_bounds__(64) void k_beam_final(BeamParams p) {
+    constexpr bool RANK = LM || BOOST;
+    __shared__ double lm_final[RANK ? WMAX : 1], total[RANK ? WMAX : 1];
+    __shared__ int32_t rank[RANK ? WMAX : 1];
+    __shared__ int n_rank;
     const int k = blockIdx.x, r = threadIdx.x;
     const BeamUtt ud = p.utt[k];
     const Beam *bm = &p.beam[k];
-    const int n = bm->na < p.N ? bm->na : p.N;
-    if (r == 0) p.out_n[k] = bm->t >= bm->T ? n : -1;         // -1: the rounds enqueued did not finish the utterance
-    if (r >= n) return;
+    int n_out = bm->na < p.N ? bm->na : p.N, src = r;
+    if constexpr (RANK) {
+        const int na = bm->na < WMAX ? bm->na : WMAX;
+        if (r < na) {
+            int32_t next = 0;
+            lm_final[r] = LM && p.lm.has_eos ? bm->a[r].lm + nasr_lm::lookup(p.lm, bm->a[r].lm_state, nasr_lm::EOS, &next) : bm->a[r].lm;
+        }
+        __syncthreads();
+        if (r == 0) n_rank = nasr_beam::final_rank_t<LM, BOOST>(bm->a, na, p.N, lm_final, p.lm_weight, p.lm_bonus, rank, total);
+        __syncthreads();
+        n_out = n_rank;
+        if (r < n_out) src = rank[r];
+    }
+    if (r == 0) p.out_n[k] = bm->t >= bm->T ? n_out : -1;     // -1: the rounds enqueued did not finish the utterance
+    if (r >= n_out) return;
     const long long cap = (long long)ud.T * p.S;
-    const nasr_beam::Hyp h = bm->a[r];
-    p.out_len[k * WMAX + r] = h.len;
-    p.out_score[k * WMAX + r] = h.score;
-    if (h.len > cap) return;
+    const int len = bm->a[src].len;
+    p.out_len[k * WMAX + r] = len;
+    p.out_score[k * WMAX + r] = bm->a[src].score;
+    if constexpr (LM) { p.out_lm[k * WMAX + r] = bm->a[src].lm; p.out_lm_final[k * WMAX + r] = lm_final[src]; }
+    if constexpr (RANK) p.out_total[k * WMAX + r] = total[src];
+    if constexpr (BOOST) p.out_boost[k * WMAX + r] = bm->a[src].boost;
+    if (len > cap) return;
     const long long at = ud.out0 + (long long)r * cap;
-    nasr_beam::backtrace(p.nodes + ud.node0, h.node, h.len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
+    nasr_beam::backtrace(p.nodes + ud.node0, bm->a[src].node, len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
 }
 
 void launch_beam_init(const BeamParams &p, hipStream_t st) {
@@ -168,74 +191,6 @@ void launch_beam_init(const BeamParams &p, hipStream_t st) {
     if (p.boost_on) hipLaunchKernelGGL(k_beam_init<true>, dim3(p.n), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_beam_init<false>, dim3(p.n), dim3(256), 0, st, p);
 }
-// the LM form of k_beam_final: lm_final = lm + the EOS term (when some n-gram ends in EOS), then the N best by the final key
-__global__ __launch_bounds__(64) void k_beam_final_lm(BeamParams p) {
-    __shared__ double lm_final[WMAX], total[WMAX];
-    __shared__ int32_t rank[WMAX];
-    __shared__ int n_out;
-    const int k = blockIdx.x, r = threadIdx.x;
-    const BeamUtt ud = p.utt[k];
-    const Beam *bm = &p.beam[k];
-    const int na = bm->na < WMAX ? bm->na : WMAX;
-    if (r < na) {
-        int32_t next = 0;
-        const nasr_beam::Hyp h = bm->a[r];
-        lm_final[r] = p.lm.has_eos ? h.lm + nasr_lm::lookup(p.lm, h.lm_state, nasr_lm::EOS, &next) : h.lm;
-    }
-    __syncthreads();
-    if (r == 0) {
-        n_out = nasr_beam::final_rank(bm->a, na, p.N, lm_final, p.lm_weight, p.lm_bonus, rank, total);
-        p.out_n[k] = bm->t >= bm->T ? n_out : -1;
-    }
-    __syncthreads();
-    if (r >= n_out) return;
-    const long long cap = (long long)ud.T * p.S;
-    const nasr_beam::Hyp h = bm->a[rank[r]];
-    p.out_len[k * WMAX + r] = h.len;
-    p.out_score[k * WMAX + r] = h.score;
-    p.out_lm[k * WMAX + r] = h.lm;
-    p.out_lm_final[k * WMAX + r] = lm_final[rank[r]];
-    p.out_total[k * WMAX + r] = total[rank[r]];
-    if (h.len > cap) return;
-    const long long at = ud.out0 + (long long)r * cap;
-    nasr_beam::backtrace(p.nodes + ud.node0, h.node, h.len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
-}
-
-// the BOOST form of the final kernels, with or without the LM: boost and the final key (+ boost) per hypothesis; LM = false: the key is score + boost
-// and the order is Beam_T's (it is sorted by that key already; final_rank_t is stable)
-template <bool LM>
-__global__ __launch_bounds__(64) void k_beam_final_boost(BeamParams p) {
-    __shared__ double lm_final[WMAX], total[WMAX];
-    __shared__ int32_t rank[WMAX];
-    __shared__ int n_out;
-    const int k = blockIdx.x, r = threadIdx.x;
-    const BeamUtt ud = p.utt[k];
-    const Beam *bm = &p.beam[k];
-    const int na = bm->na < WMAX ? bm->na : WMAX;
-    if (r < na) {
-        int32_t next = 0;
-        lm_final[r] = LM && p.lm.has_eos ? bm->a[r].lm + nasr_lm::lookup(p.lm, bm->a[r].lm_state, nasr_lm::EOS, &next) : bm->a[r].lm;
-    }
-    __syncthreads();
-    if (r == 0) {
-        n_out = nasr_beam::final_rank_t<LM, true>(bm->a, na, p.N, lm_final, p.lm_weight, p.lm_bonus, rank, total);
-        p.out_n[k] = bm->t >= bm->T ? n_out : -1;
-    }
-    __syncthreads();
-    if (r >= n_out) return;
-    const long long cap = (long long)ud.T * p.S;
-    const int src = rank[r];
-    const int len = bm->a[src].len;
-    p.out_len[k * WMAX + r] = len;
-    p.out_score[k * WMAX + r] = bm->a[src].score;
-    if (LM) { p.out_lm[k * WMAX + r] = bm->a[src].lm; p.out_lm_final[k * WMAX + r] = lm_final[src]; }
-    p.out_total[k * WMAX + r] = total[src];
-    p.out_boost[k * WMAX + r] = bm->a[src].boost;
-    if (len > cap) return;
-    const long long at = ud.out0 + (long long)r * cap;
-    nasr_beam::backtrace(p.nodes + ud.node0, bm->a[src].node, len, p.out_tok + at, p.out_frame + at, p.out_lp + at);
-}
-
 void launch_beam_select(const BeamParams &p, hipStream_t st) {
     if (p.n <= 0) return;
     if (p.boost_on) {
@@ -249,12 +204,12 @@ void launch_beam_select(const BeamParams &p, hipStream_t st) {
 void launch_beam_final(const BeamParams &p, hipStream_t st) {
     if (p.n <= 0) return;
     if (p.boost_on) {
-        if (p.lm_on) hipLaunchKernelGGL(k_beam_final_boost<true>, dim3(p.n), dim3(64), 0, st, p);
-        else hipLaunchKernelGGL(k_beam_final_boost<false>, dim3(p.n), dim3(64), 0, st, p);
+        if (p.lm_on) hipLaunchKernelGGL((k_beam_final<true, true>), dim3(p.n), dim3(64), 0, st, p);
+        else hipLaunchKernelGGL((k_beam_final<false, true>), dim3(p.n), dim3(64), 0, st, p);
         return;
     }
-    if (p.lm_on) hipLaunchKernelGGL(k_beam_final_lm, dim3(p.n), dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(k_beam_final, dim3(p.n), dim3(64), 0, st, p);
+    if (p.lm_on) hipLaunchKernelGGL((k_beam_final<true, false>), dim3(p.n), dim3(64), 0, st, p);
+    else hipLaunchKernelGGL((k_beam_final<false, false>), dim3(p.n), dim3(64), 0, st, p);
 }
 
 }  // namespace nasr

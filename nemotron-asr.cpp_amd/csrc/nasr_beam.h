@@ -42,10 +42,10 @@
 // Slots: a hypothesis owns one decoder slot (committed LSTM state, candidate, g).  A hypothesis parked in C keeps its slot while A's slots are
 // reused, so an utterance has 3 W slots: <= W in C, <= W in A, <= W for A's children.
 //
-// Shallow fusion with a back-off n-gram language model over the token ids (nasr_lm.h; nasr_engine_set_lm), the *_lm overloads below.
+// Shallow fusion with a back-off n-gram language model over the token ids (nasr_lm.h; nasr_engine_set_lm), the LM forms below.
 // A hypothesis also carries lm = the DOUBLE sum of its tokens' nasr_lm::lookup results in token order, and lm_state.  A child of h with
 // token k has score = h.score + ly as above, lm = h.lm + lookup(h.lm_state, k), lm_state = that lookup's next state.  Everywhere a score is
-// compared above -- insert_sorted, c_arrive's strictly-greater test, the selection of A from D, the prune's floor -- the key is
+// compared above -- insert_sorted_t, c_arrive_t's strictly-greater test, the selection of A from D, the prune's floor -- the key is
 //     total = score + (double)weight * lm + (double)token_bonus * len
 // evaluated as exactly that expression in double from the running sums (no fused multiply-add).  score keeps its meaning: the model's
 // probability of one lattice path.  Two arrivals of the same sequence have the same lm and len, so the merge rule is unchanged in effect.
@@ -55,7 +55,7 @@
 // every backoff of the model is <= 0 (nasr_lm's all_nonpositive), and token_bonus * 1 <= 0 only when token_bonus == 0.  So the prune is
 // applied only when token_bonus == 0 and all_nonpositive; otherwise the search runs unpruned (prune_allowed).
 // At the end, if some n-gram ends in EOS, every hypothesis of Beam_T gets lm_final = lm + lookup(lm_state, EOS) (else lm_final = lm) and the N
-// best are taken by score + weight * lm_final + token_bonus * len, stable on ties (Beam_T's order): final_rank.
+// best are taken by score + weight * lm_final + token_bonus * len, stable on ties (Beam_T's order): final_rank_t.
 //
 // Phrase boosting (engine option "phrase_boost", call flag NASR_FLAG_BEAM_BOOST; nasr_boost.h defines the set, the automaton and bonus_of), the
 // BOOST forms below, with or without the LM.  A hypothesis also carries boost_state = the automaton state after its tokens from STATE_ROOT
@@ -64,7 +64,7 @@
 // kernels form -- descending, the lower id first among equal bits; blank is dropped and the first W of the rest are kept.  So a boosted token
 // outside the raw 8 largest outputs can be proposed.  The ln P of an entry stays the MODEL's: lp_of(raw logit, m, log s), never
 // (logit + bonus) - bonus.
-// Ranking: everywhere a key is compared (insert_sorted_t, c_arrive_t, the selection of A from D, the prune's floor, final_rank) the key is
+// Ranking: everywhere a key is compared (insert_sorted_t, c_arrive_t, the selection of A from D, the prune's floor, final_rank_t) the key is
 //     fused_total(score, weight, lm, token_bonus, len) + boost            (score + boost without an LM)
 // with boost added last as its own rounded double add.  score, the per-token ln P and the frames keep their meaning: one lattice path of the
 // model.  Two arrivals of the same sequence have equal boost, so the merge rule is unchanged.
@@ -94,8 +94,6 @@ struct Hyp {
     double boost;                       // sum of the tokens' phrase bonuses (0 without boosting)
     int32_t boost_state;                // automaton state after the sequence (STATE_ROOT without boosting)
 };
-// what the fused rules need beside the LM-free ones: the weights and, per (hypothesis of A, expansion entry), the LM term and next state
-struct Fusion { float weight, token_bonus; const double *ex_lm; const int32_t *ex_state; };
 struct Beam {                           // the search state of one utterance
     Hyp a[WMAX], c[WMAX];
     int32_t na, nc;
@@ -181,7 +179,6 @@ NASR_LP_HD bool insert_sorted_t(Hyp *list, int32_t &n, int W, const Hyp &h, floa
     if (n < W) n++;
     return true;
 }
-NASR_LP_HD bool insert_sorted(Hyp *list, int32_t &n, int W, const Hyp &h) { return insert_sorted_t<false>(list, n, W, h, 0.0f, 0.0f); }
 
 // an arrival in C: merge with the entry of the same sequence (strictly greater replaces), else insert and keep the W best
 template <bool LM, bool BOOST = false>
@@ -195,7 +192,6 @@ NASR_LP_HD void c_arrive_t(Beam &b, int W, const Node *nodes, const Hyp &h, floa
     }
     insert_sorted_t<LM, BOOST>(b.c, b.nc, W, h, weight, token_bonus);
 }
-NASR_LP_HD void c_arrive(Beam &b, int W, const Node *nodes, const Hyp &h) { c_arrive_t<false>(b, W, nodes, h, 0.0f, 0.0f); }
 
 // the expansion list of a row from its 8 largest keys (sorted descending) and its softmax (m, log s): tokens and their f32 ln P
 NASR_LP_HD int expand(const nasr_topk::tkey *top, int W, float m, float log_s, int32_t *tok, float *lp) {
@@ -315,16 +311,6 @@ NASR_LP_HD int round_step_t(Beam &b, int W, int S, bool prune, const float *lb, 
     b.na = ns; b.v++;
     return ns;
 }
-NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
-                          Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel) {
-    return round_step_t<false>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes, node_cap, children, advanced, sel, 0.0f, 0.0f, nullptr, nullptr);
-}
-// the fused round: fu.ex_lm / fu.ex_state [i][KTOP] beside ex_lp / ex_tok.  `prune` is the caller's wish; it is applied only where
-// prune_allowed holds (the caller passes prune && prune_allowed(...))
-NASR_LP_HD int round_step(Beam &b, int W, int S, bool prune, const float *lb, const int32_t *ex_tok, const float *ex_lp, const int *ex_n,
-                          Node *nodes, long long node_cap, Child *children, bool *advanced, Hyp *sel, const Fusion &fu) {
-    return round_step_t<true>(b, W, S, prune, lb, ex_tok, ex_lp, ex_n, nodes, node_cap, children, advanced, sel, fu.weight, fu.token_bonus, fu.ex_lm, fu.ex_state);
-}
 
 // the final order with an LM: rank[0 .. return value) = indices into a[0 .. na), the N best by score + weight * lm_final + token_bonus * len,
 // stable on ties; total_final[i] = that key of a[i].  One thread runs it over <= 8 entries
@@ -346,9 +332,6 @@ NASR_LP_HD int final_rank_t(const Hyp *a, int na, int N, const double *lm_final,
         if (n < N) n++;
     }
     return n;
-}
-NASR_LP_HD int final_rank(const Hyp *a, int na, int N, const double *lm_final, float weight, float token_bonus, int32_t *rank, double *total_final) {
-    return final_rank_t<true, false>(a, na, N, lm_final, weight, token_bonus, rank, total_final);
 }
 
 template <bool BOOST = false>

@@ -64,7 +64,7 @@ constexpr int STAMP_PER_SLOT = 8 * 24, STAMP_SLOTS = 5;
 
 // ---------------------------------------------------------------------------------------
 struct nasr_engine;
-struct OfflineState;                 // nasr_offline.hip: buffers of the offline path, allocated on its first call
+struct OfflineState;                 // nasr_offline_state.h: buffers of the offline path, allocated on its first call
 namespace nasr_eng {
 void prof_flush(nasr_engine *e);
 void offline_destroy(nasr_engine *e);
