@@ -52,6 +52,23 @@ def _w(weights, name):
     return np.asarray(weights[name], np.float64)
 
 
+def rel_pos_attention(q, k, v, pos, bias_u, bias_v) -> np.ndarray:
+    """the attention of `layer`: q, k, v [T][8][128], pos [2 T - 1][8][128] (relative positions T-1 .. -(T-1)), biases [8][128] -> context [T][1024]"""
+    T, H, dh = q.shape
+    qu = q + bias_u[None]
+    qv = q + bias_v[None]
+    quh, qvh, kh, vh = (t.transpose(1, 0, 2) for t in (qu, qv, k, v))          # [H][T][dh]
+    ac = quh @ kh.transpose(0, 2, 1)                                            # [H][i][j]
+    bd_full = qvh @ pos.transpose(1, 2, 0)                                      # [H][i][r]
+    i_idx, j_idx = np.meshgrid(np.arange(T), np.arange(T), indexing="ij")
+    bd = bd_full[:, i_idx, j_idx + T - 1 - i_idx]
+    s = (ac + bd) / np.sqrt(dh)
+    s = s - s.max(-1, keepdims=True)
+    e = np.exp(s)
+    w = e / e.sum(-1, keepdims=True)
+    return (w @ vh).transpose(1, 0, 2).reshape(T, H * dh)
+
+
 def layer(weights: dict, l: int, x: np.ndarray, kernel_size: int = 9) -> np.ndarray:
     """ConformerLayer::forward on all T rows of one utterance, float64; returns float32"""
     p = f"encoder.layers.{l}."
@@ -70,18 +87,7 @@ def layer(weights: dict, l: int, x: np.ndarray, kernel_size: int = 9) -> np.ndar
     k = (a @ W("self_attn.linear_k.weight").T).reshape(T, H, dh)
     v = (a @ W("self_attn.linear_v.weight").T).reshape(T, H, dh)
     pos = (pos_slice(T).astype(np.float64) @ W("self_attn.linear_pos.weight").T).reshape(2 * T - 1, H, dh)
-    qu = q + W("self_attn.pos_bias_u")[None]
-    qv = q + W("self_attn.pos_bias_v")[None]
-    quh, qvh, kh, vh = (t.transpose(1, 0, 2) for t in (qu, qv, k, v))          # [H][T][dh]
-    ac = quh @ kh.transpose(0, 2, 1)                                            # [H][i][j]
-    bd_full = qvh @ pos.transpose(1, 2, 0)                                      # [H][i][r]
-    i_idx, j_idx = np.meshgrid(np.arange(T), np.arange(T), indexing="ij")
-    bd = bd_full[:, i_idx, j_idx + T - 1 - i_idx]
-    s = (ac + bd) / np.sqrt(dh)
-    s = s - s.max(-1, keepdims=True)
-    e = np.exp(s)
-    w = e / e.sum(-1, keepdims=True)
-    ctx = (w @ vh).transpose(1, 0, 2).reshape(T, D)
+    ctx = rel_pos_attention(q, k, v, pos, W("self_attn.pos_bias_u"), W("self_attn.pos_bias_v"))
     x = x + ctx @ W("self_attn.linear_out.weight").T
     a = _ln(x, W("norm_conv.weight"), W("norm_conv.bias"))
     y = a @ W("conv.pointwise_conv1.weight").T

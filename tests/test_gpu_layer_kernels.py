@@ -146,10 +146,15 @@ def harness():
 class Dev:
     """device buffers of one launch (or of the launches that are compared with each other); everything is freed on exit"""
 
-    def __init__(self):
-        self.L = harness()
+    def __init__(self, lib=None, prefix="layer_harness"):
+        """lib, prefix: another harness with the same buffer entries (<prefix>_alloc, _put, _get, ...), as tests/test_gpu_offline_kernels.py passes"""
+        self.L = lib if lib is not None else harness()
+        self.prefix = prefix
         self.frozen = {}          # handle -> the whole buffer, guards included, as a launch must leave it: every input that no launch may write
-        assert self.L.layer_harness_init(0) == 0, self.err()
+        assert self.fn("init")(0) == 0, self.err()
+
+    def fn(self, name):
+        return getattr(self.L, f"{self.prefix}_{name}")
 
     def __enter__(self):
         return self
@@ -159,7 +164,7 @@ class Dev:
             if exc[0] is None:
                 self.check_inputs()
         finally:
-            self.L.layer_harness_free_all()
+            self.fn("free_all")()
 
     def check_inputs(self):
         """every read-only buffer -- operands, pools with their unused slots and poisoned rows, slack rows, weights, descriptors -- and its guards: bit for bit as uploaded"""
@@ -167,10 +172,10 @@ class Dev:
             assert np.array_equal(self.raw(h), want), f"a launch wrote into read-only buffer {h} ({want.size * 2} bytes with guards)"
 
     def err(self):
-        return self.L.layer_harness_error().decode()
+        return self.fn("error")().decode()
 
     def new(self, nbytes):
-        h = self.L.layer_harness_alloc(int(nbytes), GUARD)
+        h = self.fn("alloc")(int(nbytes), GUARD)
         assert h >= 0, self.err()
         return h
 
@@ -178,27 +183,27 @@ class Dev:
         """a buffer that holds arr, `slack_bytes` of sentinel behind it; written: a launch may write it (it is then not checked as an input)"""
         arr = np.ascontiguousarray(arr)
         h = self.new(arr.nbytes + slack_bytes)
-        assert self.L.layer_harness_put(h, 0, arr.ctypes.data, arr.nbytes) == 0, self.err()
+        assert self.fn("put")(h, 0, arr.ctypes.data, arr.nbytes) == 0, self.err()
         if not written:
-            want = np.full(self.L.layer_harness_total_bytes(h) // 2, SENT, np.uint16)
+            want = np.full(self.fn("total_bytes")(h) // 2, SENT, np.uint16)
             want[GUARD // 2:GUARD // 2 + arr.nbytes // 2] = arr.reshape(-1).view(np.uint16)
             self.frozen[h] = want
         return h
 
     def get(self, h, dtype):
         """the body as `dtype`; the guards in front of and behind it must still be sentinel"""
-        n = self.L.layer_harness_total_bytes(h)
+        n = self.fn("total_bytes")(h)
         raw = np.empty(n // 2, np.uint16)
-        assert self.L.layer_harness_get(h, raw.ctypes.data) == 0, self.err()
+        assert self.fn("get")(h, raw.ctypes.data) == 0, self.err()
         g = GUARD // 2
         assert np.all(raw[:g] == SENT), "the launch wrote in front of a buffer"
         assert np.all(raw[-g:] == SENT), "the launch wrote behind a buffer"
         return raw[g:-g].view(dtype)
 
     def raw(self, h):
-        n = self.L.layer_harness_total_bytes(h)
+        n = self.fn("total_bytes")(h)
         raw = np.empty(n // 2, np.uint16)
-        assert self.L.layer_harness_get(h, raw.ctypes.data) == 0, self.err()
+        assert self.fn("get")(h, raw.ctypes.data) == 0, self.err()
         return raw
 
     def bf16_of(self, arr_f32, slack_bytes=0):
@@ -206,14 +211,14 @@ class Dev:
         src = self.up(np.asarray(arr_f32, np.float32), slack_bytes)
         n = (np.asarray(arr_f32).size * 4 + slack_bytes) // 4
         dst = self.new(n * 2)
-        assert self.L.layer_harness_to_bf16(src, dst, n) == 0, self.err()
+        assert self.fn("to_bf16")(src, dst, n) == 0, self.err()
         self.frozen[dst] = self.raw(dst)
         return dst
 
     def packed(self, W):
         N, K = W.shape
         src, dst = self.up(np.asarray(W, np.float32)), self.new(N * K * 2)
-        assert self.L.layer_harness_pack_weight(src, dst, N, K) == 0, self.err()
+        assert self.fn("pack_weight")(src, dst, N, K) == 0, self.err()
         self.frozen[dst] = self.raw(dst)
         return dst
 
