@@ -52,6 +52,7 @@ enum {
     NASR_FLAG_AUDIO_S16  = 1u << 2, /* nasr_diar_*: audio[] point at s16 PCM (sample / 32768), e.g. the ASR streams' own buffers */
     NASR_FLAG_NO_BOOST   = 1u << 3, /* nasr_engine_transcribe / _transcribe_mel only: decode the utterances of this call without phrase boosting */
     NASR_FLAG_BEAM_BOOST = 1u << 4, /* nasr_engine_transcribe_beam / _beam_mel only: apply the engine's boost phrases inside the search (needs "phrase_boost") */
+    NASR_FLAG_NO_LM      = 0x20u,   /* bit 5; nasr_engine_transcribe / _transcribe_mel only: decode the utterances of this call without greedy LM fusion ("lm_fusion") */
 };
 
 /* model hyper-parameters = the `nemo.*` GGUF keys read at src/nemo-ggml.cpp:108-142
@@ -488,7 +489,8 @@ int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens
  * candidates the transducer proposes (each hypothesis' `beam` largest non-blank outputs); it does not propose any.  score stays the model's
  * path score.  weight and token_bonus are finite in [0, 100]; with both 0 every result equals the LM-free call bit for bit.  The search
  * prunes only when token_bonus == 0 and no logprob or backoff is positive; otherwise it runs unpruned (same results, more work).
- * nasr_engine_transcribe, align, live streams and step graphs never see the model.  nasr_engine_set_lm completes steps in flight, builds
+ * Without engine option "lm_fusion" (below) nasr_engine_transcribe, live streams and step graphs never see the model; alignment never does.
+ * nasr_engine_set_lm completes steps in flight, builds
  * the tables on the host, uploads them and replaces the previous model; NULL detaches; a failure leaves the previous model in force and the
  * engine usable.  Counters: "lm_ngrams", "lm_states", "lm_max_probe" (0 when detached). */
 #define NASR_LM_MAX_ORDER 5
@@ -512,6 +514,28 @@ int nasr_engine_set_lm_weights(nasr_engine *e, float weight, float token_bonus);
  * model or NULL) ends this read-out: the call then fails; nasr_engine_set_lm_weights does not. */
 int nasr_engine_beam_hypothesis_lm(nasr_engine *e, int u, int rank, double *lm_logprob_out, double *total_out,
                                    float *token_lm_logprobs_out, int32_t cap);
+
+/* ---- shallow fusion in the greedy decode: live streams and nasr_engine_transcribe (csrc/nasr_lm.h).
+ * Engine option "lm_fusion" (0 default / 1), a capability like "phrase_boost": it selects the decode launches that are captured into the step
+ * graphs and allocates a state and a 1040-entry bias row per stream, so it is REJECTED after the first step or offline call.  With it the
+ * model attached by nasr_engine_set_lm also biases the greedy device decode.  A stream carries an LM state s: the model's start (the state
+ * after BOS, or the empty context) after nasr_stream_create, both reset modes, nasr_stream_set_lm, nasr_engine_set_lm and at the start of every
+ * offline utterance; it runs on across steps, chunks, pipelined calls and endpoints.  With the greedy weights (weight, token_bonus):
+ *     lmbias(v) = (float)((double)weight * ln P_lm(v | s) + (double)token_bonus)   for v in 0 .. 1023, product and sum rounded on their own
+ *     lmbias(blank) = 0;  every entry 0 when no model is attached or the stream is switched off
+ *     token = arg-max_v (logit[v] + (boostbonus(v) + lmbias(v))), all f32, first maximum wins; boostbonus is "phrase_boost"'s, 0 when that is off
+ * On emission s becomes the state the lookup leads to; blank leaves it alone.  The model scores the whole vocabulary, so unlike in the beam
+ * search it can propose a token; blank gets no LM term, which token_bonus is there to offset; there is no EOS term.  The 10-symbol cap,
+ * state commit, frame numbering and the iteration statistic are unchanged, and the values of "token_logprobs", "token_alternatives" and
+ * "frame_blank_logprobs" stay the model's (raw logits), as with boosting.  With weights 0 / 0 (the default) or no model every result is
+ * bit-identical to "lm_fusion" = 0.  The beam search and alignment are untouched.
+ * nasr_engine_set_greedy_lm_weights: finite in [0, 100] each, separate from the beam's weights (the useful values differ); completes steps in
+ * flight, keeps every stream's state and takes effect at the next step -- captured graphs stay valid, as they do across nasr_engine_set_lm.
+ * nasr_stream_set_lm: per-stream switch (default on); either way the stream's LM state restarts.
+ * NASR_FLAG_NO_LM decodes one nasr_engine_transcribe / _transcribe_mel call unfused; the step, beam and align entries reject it.
+ * Both setters fail without the option. */
+int nasr_engine_set_greedy_lm_weights(nasr_engine *e, float weight, float token_bonus);
+int nasr_stream_set_lm(nasr_stream *s, int enable);
 
 /* ---- phrase boosting inside the beam search (csrc/nasr_beam.h, csrc/nasr_boost.h).  A beam call with
  * NASR_FLAG_BEAM_BOOST applies the engine's boost set (nasr_engine_set_boost_phrases; the bonus definition is that of the greedy decode).  The

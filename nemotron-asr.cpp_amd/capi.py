@@ -45,12 +45,14 @@ EXPORTS = [
     "nasr_engine_transcribe_beam_mel", "nasr_engine_transcribe_beam", "nasr_engine_beam_hypothesis",
     "nasr_engine_set_lm", "nasr_engine_set_lm_weights", "nasr_engine_beam_hypothesis_lm",
     "nasr_engine_beam_hypothesis_boost",
+    "nasr_engine_set_greedy_lm_weights", "nasr_stream_set_lm",
 ]
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
 LM_MAX_ORDER, LM_BOS, LM_EOS = 5, 1025, 1026
 FLAG_NO_BOOST = 1 << 3
 FLAG_BEAM_BOOST = 1 << 4
+FLAG_NO_LM = 1 << 5
 BOOST_MAX_STATES, BOOST_MAX_PHRASE_LEN, BOOST_MAX_BONUS = 4096, 32, 1.0e4
 OFFLINE_MAX_FRAMES = 2048
 
@@ -173,6 +175,8 @@ def lib():
         L.nasr_engine_beam_hypothesis.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.POINTER(C.c_float), C.c_int32, dp]
         L.nasr_engine_set_lm.argtypes = [vp, C.POINTER(LmDesc)]
         L.nasr_engine_set_lm_weights.argtypes = [vp, C.c_float, C.c_float]
+        L.nasr_engine_set_greedy_lm_weights.argtypes = [vp, C.c_float, C.c_float]
+        L.nasr_stream_set_lm.argtypes = [vp, C.c_int]
         L.nasr_engine_beam_hypothesis_lm.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
         L.nasr_engine_beam_hypothesis_boost.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
         L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
@@ -305,6 +309,10 @@ class Stream:
     def set_boost(self, enable=True):
         """phrase boosting on / off for this stream (engine option "phrase_boost"); either way its boost history restarts"""
         _chk(lib().nasr_stream_set_boost(self.h, int(bool(enable))))
+
+    def set_lm(self, enable=True):
+        """greedy LM fusion on / off for this stream (engine option "lm_fusion"); either way its LM state restarts at the model's start"""
+        _chk(lib().nasr_stream_set_lm(self.h, int(bool(enable))))
 
     def tap(self, which, index=0, cap=None) -> np.ndarray:
         cap = cap or 1024 * 260          # up to MAXNEW = 256 encoder frames of one launch, or a 70-row cache
@@ -712,9 +720,10 @@ class Engine:
         return float(boost.value), float(total.value), bon[:n].copy()
 
     def set_lm(self, ngrams, order=0, unk_logprob=-20.0, weight=0.0, token_bonus=0.0):
-        """attach a back-off n-gram language model to every later beam call (None detaches).  ngrams: {token tuple: logprob} or
+        """attach a back-off n-gram language model (None detaches): every later beam call is fused with it, and with engine option "lm_fusion"
+        the greedy decode of live streams and transcribe() too, by its own weights (set_greedy_lm_weights).  ngrams: {token tuple: logprob} or
         {token tuple: (logprob, backoff)} or an iterable of (tokens, logprob[, backoff]); natural logs; LM_BOS only first, LM_EOS only last.
-        order 0 = the longest n-gram.  weight and token_bonus in [0, 100] (include/nemotron_asr_amd.h)."""
+        order 0 = the longest n-gram.  weight and token_bonus (the beam's) in [0, 100] (include/nemotron_asr_amd.h)."""
         if ngrams is None:
             _chk(lib().nasr_engine_set_lm(self.h, None))
             return
@@ -735,6 +744,10 @@ class Engine:
 
     def set_lm_weights(self, weight, token_bonus=0.0):
         _chk(lib().nasr_engine_set_lm_weights(self.h, float(weight), float(token_bonus)))
+
+    def set_greedy_lm_weights(self, weight, token_bonus=0.0):
+        """the weights of the greedy decode's LM fusion (engine option "lm_fusion"), each in [0, 100]; the streams' LM states are kept"""
+        _chk(lib().nasr_engine_set_greedy_lm_weights(self.h, float(weight), float(token_bonus)))
 
     def _beam(self, fn, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm=False, boost=False):
         if boost:

@@ -228,9 +228,51 @@ __device__ __forceinline__ void pred_pass(const DecParams &p, int i0, int nd, fl
     }
 }
 
+// ---- engine option "lm_fusion" (nasr_lm.h): the bias row of a slot = phrase bonus + lmbias of every vocabulary entry in the slot's
+// states, and beside it the LM state after emitting that entry.  One thread per entry runs the lookup against the tables in device memory.  Both
+// states move only in k_dec_commit, which marks the stream dirty, so refreshing the rows of the streams in dlist keeps every row current; a
+// slot that did not emit is not touched.  boost_bonus / boost_state are null when "phrase_boost" is off
+__device__ __forceinline__ void lm_refresh_entry(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus,
+                                                 const int *boost_state, int slot, int v) {
+    int32_t next;
+    const float lb = nasr_lm::lmbias(*blk, lm_state[slot], v, &next);
+    const float bb = boost_bonus ? nasr_boost::bonus_of(boost_bonus, boost_state[slot], v) : 0.0f;
+    lm_row[(size_t)slot * nasr_lm::ROW_COLS + v] = bb + lb;
+    lm_next[(size_t)slot * nasr_lm::ROW_COLS + v] = next;
+}
+// the rows of the dirty streams, workgroups first .. first + n - 1 of the grid striding over (dirty stream, entry)
+__device__ __forceinline__ void lm_refresh_dirty(const DecParams &p, int nd, int first, int n) {
+    const int total = nd * nasr_lm::ROW_COLS;
+    for (int i = ((int)blockIdx.x - first) * 256 + (int)threadIdx.x; i < total; i += n * 256) {
+        const int d = i / nasr_lm::ROW_COLS, v = i - d * nasr_lm::ROW_COLS;
+        lm_refresh_entry(p.lm_blk, p.lm_state, p.lm_row, p.lm_next, p.boost_bonus, p.boost_state, p.rows[p.dlist[d]].slot, v);
+    }
+}
+// form (a): a launch of its own beside k_dec_pred
+__global__ __launch_bounds__(256) void k_dec_lmrows(DecParams p) {
+    const int nd = *p.n_dirty;
+    if (nd == 0) return;
+    lm_refresh_dirty(p, nd, 0, (int)gridDim.x);
+}
+// the rows of slots slot0 .. slot0 + n - 1 whatever their streams do: after nasr_engine_set_lm, the weight setter, a new phrase set, a stream's switch
+__global__ __launch_bounds__(256) void k_lm_rows_slots(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus,
+                                                       const int *boost_state, int slot0, int n) {
+    const int total = n * nasr_lm::ROW_COLS;
+    for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < total; i += (int)gridDim.x * 256) {
+        const int d = i / nasr_lm::ROW_COLS;
+        lm_refresh_entry(blk, lm_state, lm_row, lm_next, boost_bonus, boost_state, slot0 + d, i - d * nasr_lm::ROW_COLS);
+    }
+}
+static int lm_refresh_blocks(int B) { return 5 * (B < 32 ? B : 32); }      // 1040 entries = 4.06 workgroups of 256 per stream
+
+// LMROWS: form (b) of the refresh -- the workgroups past the 40 of the projection stride over the bias rows of the same dirty streams
+template <bool LMROWS = false>
 __global__ __launch_bounds__(256) void k_dec_pred(DecParams p) {
     const int nd = *p.n_dirty;
     if (nd == 0) return;
+    if (LMROWS) {
+        if ((int)blockIdx.x >= JNT / 16) { lm_refresh_dirty(p, nd, JNT / 16, (int)gridDim.x - JNT / 16); return; }
+    }
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nd; i0 += 16 * MT_MAX) {
         const int left = nd - i0;
@@ -272,7 +314,7 @@ __device__ __forceinline__ void alt_tile_keys(float x0, float x1, float x2, floa
 // its raw logit in boost_raw [row][part] (one writer per element: a key names one vocabulary entry, and one lane holds it)
 // ALT (engine option "token_alternatives", nasr_topk.h; always with LP): lane group 0 also leaves the tile's alt_k largest raw-logit keys in
 // alt_key [row][part][alt_k], beside the part
-template <int MT, bool LP, bool BOOST, bool ALT>
+template <int MT, bool LP, bool BOOST, bool ALT, bool LMF>
 __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, float (*red)[MT_MAX][64][4]) {
     const int nt = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
@@ -305,7 +347,8 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
         float lgs[4] = {0.f, 0.f, 0.f, 0.f}, bon[4] = {0.f, 0.f, 0.f, 0.f};
         if (BOOST) {
             const int slot = p.rows[p.rowmap[i < nr ? i : i0] & 0xffffu].slot;
-            const nasr_boost::Bonus4 b4 = nasr_boost::bonus4_of(p.boost_bonus, p.boost_state[slot], nt * 16 + q * 4);
+            const nasr_boost::Bonus4 b4 = LMF ? *(const nasr_boost::Bonus4 *)(p.lm_row + (size_t)slot * nasr_lm::ROW_COLS + nt * 16 + q * 4)
+                                              : nasr_boost::bonus4_of(p.boost_bonus, p.boost_state[slot], nt * 16 + q * 4);
             bon[0] = b4.x; bon[1] = b4.y; bon[2] = b4.z; bon[3] = b4.w;
         }
 #pragma unroll
@@ -345,16 +388,19 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
     }
 }
 
-template <bool LP, bool BOOST, bool ALT>
+// LMF (engine option "lm_fusion", always with BOOST): the lane's four bias entries come from the slot's row (phrase bonus + lmbias, k_dec_lmrows)
+// instead of the automaton's table; everything else is the boosted form
+template <bool LP, bool BOOST, bool ALT, bool LMF = false>
 __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
+    static_assert(BOOST || !LMF, "the fused form is a form of the boosted kernel");
     const int nr = *p.n_rows;
     if (nr == 0) return;
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nr; i0 += 16 * MT_MAX) {
         const int tiles = nasr_lp::joint_pass_tiles(nr - i0);      // 1, 2 or 4 m-tiles: 16, 32 or more rows left
-        if (tiles == 1) joint_pass<1, LP, BOOST, ALT>(p, i0, nr, red);
-        else if (tiles == 2) joint_pass<2, LP, BOOST, ALT>(p, i0, nr, red);
-        else joint_pass<4, LP, BOOST, ALT>(p, i0, nr, red);
+        if (tiles == 1) joint_pass<1, LP, BOOST, ALT, LMF>(p, i0, nr, red);
+        else if (tiles == 2) joint_pass<2, LP, BOOST, ALT, LMF>(p, i0, nr, red);
+        else joint_pass<4, LP, BOOST, ALT, LMF>(p, i0, nr, red);
     }
 }
 
@@ -368,9 +414,11 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // of every row in raw_logits [row][1040] -- one aligned 16-byte store per lane and m-tile from the accumulators it holds, one writer per element.
 // The per-part winner's raw logit (boost_raw) is not kept: the select kernel reads any entry's raw logit from the row
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
-template <bool LP, bool BOOST, bool ALT, bool BEAMB = false>
+// LMF: as in k_dec_joint -- bstate holds the row's slot, and the four bias entries are one load from the slot's row
+template <bool LP, bool BOOST, bool ALT, bool BEAMB = false, bool LMF = false>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     static_assert(!BEAMB || (LP && BOOST && ALT), "the boosted beam form is a form of the LP + BOOST + ALT kernel");
+    static_assert(!LMF || (BOOST && !BEAMB), "the fused form is a form of the boosted greedy kernel");
     const int nr = *p.n_rows;
     const int m0 = blockIdx.y * 64;
     if (m0 >= nr) return;
@@ -411,7 +459,8 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 #pragma unroll
         for (int mt = 0; mt < 4; mt++) {
             const int row = m0 + mt * 16 + r;
-            bstate[mt] = p.boost_state[p.rows[p.rowmap[row < nr ? row : m0] & 0xffffu].slot];
+            const int slot = p.rows[p.rowmap[row < nr ? row : m0] & 0xffffu].slot;
+            bstate[mt] = LMF ? slot : p.boost_state[slot];
         }
     }
     f32x4 acc[4];
@@ -458,7 +507,8 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
         float bon[4] = {0.f, 0.f, 0.f, 0.f};
         if (has_tile && mt < nmt) {
             if (BOOST) {
-                const nasr_boost::Bonus4 b4 = nasr_boost::bonus4_of(p.boost_bonus, bstate[mt], nt * 16 + q * 4);
+                const nasr_boost::Bonus4 b4 = LMF ? *(const nasr_boost::Bonus4 *)(p.lm_row + (size_t)bstate[mt] * nasr_lm::ROW_COLS + nt * 16 + q * 4)
+                                                  : nasr_boost::bonus4_of(p.boost_bonus, bstate[mt], nt * 16 + q * 4);
                 bon[0] = b4.x; bon[1] = b4.y; bon[2] = b4.z; bon[3] = b4.w;
             }
 #pragma unroll
@@ -544,9 +594,12 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 // here, 0.9 % against 0.6 % at 64 streams x R = 13 (profiles/frame_blank.md).  Then the stream's thread copies the values of the frames this iteration leaves -- [t0, new t): the blanks
 // before the token, every frame when there is no token, and the token's own frame when it reaches MAX_SYMBOLS.  All of them are in rowmap
 // (build_lists lists every frame from t to n_frames), so the value copied is that of the LAST evaluation on the frame
-template <bool LP, bool BOOST, bool ALT, bool FB>
+// LMF (engine option "lm_fusion", always with BOOST): the slot's LM state becomes the `next` the refresh left beside the bias entry of the token;
+// the phrase automaton advances where "phrase_boost" is on too (boost_next is null otherwise)
+template <bool LP, bool BOOST, bool ALT, bool FB, bool LMF = false>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
     static_assert(LP || !FB, "the blank log-probabilities come from the softmax parts");
+    static_assert(BOOST || !LMF, "the fused form is a form of the boosted kernel");
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
     const int nd = *p.n_dirty;
@@ -606,7 +659,14 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
                         if (j < K) { p.alt_id[at + j] = nasr_topk::alt_id(rt.top[j]); p.alt_lp[at + j] = nasr_topk::alt_lp(rt.top[j], m, log_s); }
                 }
             }
-            if (BOOST) p.boost_state[slot] = nasr_boost::next_of(p.boost_next, p.boost_state[slot], best);   // the history moves where the decoder state does
+            if (BOOST && (!LMF || p.boost_next)) p.boost_state[slot] = nasr_boost::next_of(p.boost_next, p.boost_state[slot], best);   // the history moves where the decoder state does
+            if (LMF) {
+                if (p.lm_relook) {                         // measurement only: look (state, token) up once more instead of reading the next-state row
+                    int32_t nx;
+                    (void)nasr_lm::lmbias(*p.lm_blk, p.lm_state[slot], best, &nx);
+                    p.lm_state[slot] = nx;
+                } else p.lm_state[slot] = p.lm_next[(size_t)slot * nasr_lm::ROW_COLS + best];
+            }
             ct->n_tok = n + 1;
             ct->prev_token = best;
             ct->cur ^= 1;
@@ -672,24 +732,28 @@ void launch_encproj(const float *x, const float *wpk, const float *bias, float *
 void launch_decode_begin(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_begin, dim3(1), dim3(256), 0, st, p);
 }
-template <bool LP, bool BOOST, bool ALT>
+template <bool LP, bool BOOST, bool ALT, bool LMF = false>
 static void launch_joint_commit(const DecParams &p, hipStream_t st) {
     static_assert(LP || !ALT, "the alternatives take their probabilities from the softmax parts");
     const int rows = p.B * p.T;
-    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT, LMF>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT, false, LMF>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
     if constexpr (LP) {
         if (p.frame_blank) {                           // "frame_blank_logprobs": the commit variant that also fills the ring
-            hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, true>), dim3(1), dim3(256), 0, st, p);
+            hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, true, LMF>), dim3(1), dim3(256), 0, st, p);
             return;
         }
     }
-    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, false>), dim3(1), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, false, LMF>), dim3(1), dim3(256), 0, st, p);
+}
+void launch_lm_rows(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus, const int *boost_state,
+                    int slot0, int n, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_lm_rows_slots, dim3(lm_refresh_blocks(n)), dim3(256), 0, st, blk, lm_state, lm_row, lm_next, boost_bonus, boost_state, slot0, n);
 }
 void launch_decode_candidates(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(k_dec_pred<false>, dim3(JNT / 16), dim3(256), 0, st, p);
 }
 // beam search (kernels_beam.hip): the candidates of the rows in dlist, then the tiled joint with softmax parts and alternatives over rowmap --
 // always this kernel, so the logits of a row do not depend on how many rows the sub-batch has
@@ -709,7 +773,20 @@ void launch_decode_rows_boost(const DecParams &p, hipStream_t st) {
 void launch_decode_iter(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_lstm<0>, dim3(HID / 4), dim3(256), 0, st, p);
     hipLaunchKernelGGL(k_dec_lstm<1>, dim3(HID / 4), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(k_dec_pred, dim3(JNT / 16), dim3(256), 0, st, p);
+    // engine option "lm_fusion" (lm_row): the bias rows of the dirty streams are refreshed beside g -- by extra workgroups of the projection
+    // (lm_fold, the form kept: profiles/greedy_lm.md) or by a launch of their own -- and the joint and the commit are the fused forms of the boosted ones
+    if (p.lm_row) {
+        if (p.lm_fold) hipLaunchKernelGGL(k_dec_pred<true>, dim3(JNT / 16 + lm_refresh_blocks(p.B)), dim3(256), 0, st, p);
+        else {
+            hipLaunchKernelGGL(k_dec_pred<false>, dim3(JNT / 16), dim3(256), 0, st, p);
+            hipLaunchKernelGGL(k_dec_lmrows, dim3(lm_refresh_blocks(p.B)), dim3(256), 0, st, p);
+        }
+        if (p.alt_key) launch_joint_commit<true, true, true, true>(p, st);
+        else if (p.lp_part) launch_joint_commit<true, true, false, true>(p, st);
+        else launch_joint_commit<false, true, false, true>(p, st);
+        return;
+    }
+    hipLaunchKernelGGL(k_dec_pred<false>, dim3(JNT / 16), dim3(256), 0, st, p);
     // engine options "token_logprobs" (lp_part) and "phrase_boost" (boost_bonus): the variants that also leave the softmax parts / the token's
     // log-probability, and that add the phrase bonus to the arg-max key; with both off these are the kernels without either.  "token_alternatives"
     // (alt_key; lp_part comes with it) takes the variants that also leave every slice's largest keys / the token's K best outputs.

@@ -164,6 +164,7 @@ __global__ __launch_bounds__(256) void k_stream_reset(StreamResetParams p) {
         c.frame0 = 0; c.frame_next = 0;
         p.ctrl[slot] = c;
         if (p.boost_state) p.boost_state[slot] = p.boost_init;             // phrase_boost: an empty history
+        if (p.lm_state) p.lm_state[slot] = nasr_lm::greedy_start(*p.lm_blk, p.lm_enabled != 0);   // lm_fusion: likewise; dirty = 1 gets the bias row refreshed before the first joint
     }
 }
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st) {

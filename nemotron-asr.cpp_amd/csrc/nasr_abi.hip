@@ -54,6 +54,28 @@ static int upload_lm(nasr_engine *e, const nasr_lm_desc *d) {
     e->lm_weight = d->weight; e->lm_bonus = d->token_bonus;
     return 0;
 }
+
+// engine option "lm_fusion": rewrites the block the decode kernels read from the engine's model and greedy weights and recomputes the bias rows
+// of every slot in one launch -- after the states were put back to the model's start (restart: a new or detached model) or with the states
+// kept (new weights, a new phrase set: the automaton states were reset by their own setter).  The caller has completed the steps in flight
+static int refresh_greedy_lm(nasr_engine *e, bool restart) {
+    if (!e->opt_lm_fusion) return 0;
+    HIPCHK(hipStreamSynchronize(e->st));
+    nasr_lm::Greedy g = {};
+    g.lm = e->lm_view; g.attached = e->lm ? 1 : 0;
+    g.weight = e->glm_weight; g.token_bonus = e->glm_bonus;
+    HIPCHK(hipMemcpy(e->lm_blk, &g, sizeof(g), hipMemcpyHostToDevice));
+    if (restart) {
+        std::vector<int32_t> st((size_t)e->max_streams);
+        for (int i = 0; i < e->max_streams; i++) st[(size_t)i] = nasr_lm::greedy_start(g, !e->slots[i] || e->slots[i]->lm_enabled);
+        HIPCHK(hipMemcpy(e->lm_state, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->boost_state : nullptr,
+                   0, e->max_streams, e->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->st));
+    return 0;
+}
 }  // namespace nasr_eng
 
 extern "C" int nasr_engine_set_lm(nasr_engine *e, const nasr_lm_desc *lm) {
@@ -61,12 +83,46 @@ extern "C" int nasr_engine_set_lm(nasr_engine *e, const nasr_lm_desc *lm) {
     if (!e) return fail("null engine");
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
-    if (lm) return upload_lm(e, lm);
+    // with "lm_fusion" the greedy decode reads the model too: the block is rewritten, every stream's LM state restarts and every bias row is recomputed
+    if (lm) return upload_lm(e, lm) ? -1 : refresh_greedy_lm(e, true);
     HIPCHK(hipStreamSynchronize(e->st));
-    delete e->lm;
-    if (e->lm_dev) hipFree(e->lm_dev);
+    nasr_lm::Model *old = e->lm; void *old_dev = e->lm_dev;
     e->lm_generation++;
     e->lm = nullptr; e->lm_dev = nullptr; e->lm_view = nasr_lm::View{}; e->lm_weight = e->lm_bonus = 0.0f;
+    const int rc = refresh_greedy_lm(e, true);                 // the block forgets the tables before they are freed
+    delete old;
+    if (old_dev) hipFree(old_dev);
+    return rc;
+}
+
+extern "C" int nasr_engine_set_greedy_lm_weights(nasr_engine *e, float weight, float token_bonus) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->opt_lm_fusion) return fail("no greedy LM fusion: engine option \"lm_fusion\" is off (set it to 1 before the first step or offline call)");
+    if (!nasr_beam::valid_weights(weight, token_bonus)) return fail("language model: weight and token_bonus must be finite in [0, 100]");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    e->glm_weight = weight; e->glm_bonus = token_bonus;
+    return refresh_greedy_lm(e, false);                        // the states stay; the rows follow the new weights
+}
+
+extern "C" int nasr_stream_set_lm(nasr_stream *s, int enable) {
+    ApiGuard api_guard;
+    if (!s) return fail("null stream");
+    nasr_engine *e = s->e;
+    if (!e->opt_lm_fusion) return fail("no greedy LM fusion: engine option \"lm_fusion\" is off (set it to 1 before the first step or offline call)");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    HIPCHK(hipStreamSynchronize(e->st));
+    nasr_lm::Greedy g = {};
+    g.lm = e->lm_view; g.attached = e->lm ? 1 : 0;
+    const int32_t state = nasr_lm::greedy_start(g, enable != 0);      // either way an empty history
+    HIPCHK(hipMemcpy(e->lm_state + s->slot, &state, sizeof(state), hipMemcpyHostToDevice));
+    s->lm_enabled = enable != 0;
+    launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->boost_state : nullptr,
+                   s->slot, 1, e->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->st));
     return 0;
 }
 
@@ -85,7 +141,8 @@ extern "C" int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, cons
     if (!e->opt_phrase_boost) return fail("no phrase boosting: engine option \"phrase_boost\" is off (set it to the state capacity before the first step or offline call)");
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
-    return upload_boost_set(e, n_phrases, tokens, lens, bonus);
+    if (upload_boost_set(e, n_phrases, tokens, lens, bonus)) return -1;
+    return refresh_greedy_lm(e, false);                        // "lm_fusion": the bias rows carry the phrase bonus
 }
 
 extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
@@ -99,6 +156,11 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
     const int state = enable ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF;      // either way an empty history
     HIPCHK(hipMemcpy(e->boost_state + s->slot, &state, sizeof(int), hipMemcpyHostToDevice));
     s->boost_enabled = enable != 0;
+    if (e->opt_lm_fusion) {                                    // the slot's bias row carries the phrase bonus
+        launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->boost_bonus, e->boost_state, s->slot, 1, e->st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->st));
+    }
     return 0;
 }
 
@@ -143,12 +205,44 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
             ApiGuard api_guard;
             HIPCHK(hipSetDevice(e->device));
             if (dalloc(e, &e->boost_bonus, nasr_boost::table_elems(value)) || dalloc(e, &e->boost_next, nasr_boost::table_elems(value)) ||
-                dalloc(e, &e->boost_state, (size_t)e->max_streams) || dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows))) return -1;
+                dalloc(e, &e->boost_state, (size_t)e->max_streams) || (!e->boost_raw && dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows)))) return -1;
             e->boost_cap = value;
             e->opt_phrase_boost = value;
             if (upload_boost_set(e, 0, nullptr, nullptr, nullptr)) { e->opt_phrase_boost = 0; return -1; }      // the empty set: the disabled state and the root
         }
         e->opt_phrase_boost = value;
+        if (e->opt_lm_fusion) {                                // "lm_fusion" set before this option: the rows gain (or lose) the phrase bonus
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (refresh_greedy_lm(e, false)) return -1;
+        }
+    }
+    else if (!strcmp(key, "lm_fusion")) {
+        // like "phrase_boost": picks the decode launches that get captured and allocates what they read at fixed addresses, so that
+        // nasr_engine_set_lm and nasr_engine_set_greedy_lm_weights only ever rewrite content and captured graphs stay valid
+        if (value != 0 && value != 1) return fail("lm_fusion must be 0 or 1");
+        if (e->dec_started || e->off) return fail("lm_fusion must be set before the first step or offline call (the decode kernels are already chosen)");
+        if (value && !e->lm_blk) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (dalloc(e, &e->lm_blk, 1) || dalloc(e, &e->lm_state, (size_t)e->max_streams) || dalloc(e, &e->lm_row, (size_t)e->max_streams * nasr_lm::ROW_COLS) ||
+                dalloc(e, &e->lm_next, (size_t)e->max_streams * nasr_lm::ROW_COLS)) return -1;
+            if (!e->boost_raw && dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows))) return -1;
+        }
+        e->opt_lm_fusion = value != 0;
+        if (value) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (refresh_greedy_lm(e, true)) { e->opt_lm_fusion = false; return -1; }
+        }
+    }
+    else if (!strcmp(key, "lm_refresh_fold")) {                // measurement only (profiles/greedy_lm.md): 0 = the bias rows are refreshed by a launch of their own; before the first step
+        if (e->dec_started || e->off) return fail("lm_refresh_fold must be set before the first step or offline call (the decode kernels are already chosen)");
+        e->opt_lm_fold = value != 0;
+    }
+    else if (!strcmp(key, "lm_commit_lookup")) {               // measurement only (profiles/greedy_lm.md): 1 = k_dec_commit looks the emitted token up again; before the first step
+        if (e->dec_started || e->off) return fail("lm_commit_lookup must be set before the first step or offline call (the decode kernels are already chosen)");
+        e->opt_lm_relook = value != 0;
     }
     else if (!strcmp(key, "token_alternatives")) {
         // like "token_logprobs": picks the decode kernels that get captured and allocates the scratch and the rings at K entries per token.  Its
@@ -518,6 +612,7 @@ extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
     if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
     if (!pcm || !n_samples) return fail("null pcm / n_samples");
     for (int b = 0; b < B; b++)
         if (!streams[b]->default_format())
@@ -574,6 +669,7 @@ extern "C" int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *stream
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
     if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
     if (!audio || !n_frames) return fail("null audio / n_frames");
     HIPCHK(hipSetDevice(e->device));
     bool all_default = true;
@@ -676,6 +772,7 @@ extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams,
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
     if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
     if (!mel || !n_frames) return fail("null mel / n_frames");
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;

@@ -468,7 +468,10 @@ void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParam
     if (e->opt_frame_blank) { dp.fb_row = e->fb_row; dp.frame_blank = e->frame_blank; }
     if (e->opt_token_alt) { dp.alt_key = e->alt_key; dp.alt_id = e->alt_id; dp.alt_lp = e->alt_lp; dp.alt_k = e->opt_token_alt; }
     if (e->opt_phrase_boost) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = e->boost_state; dp.boost_raw = e->boost_raw; }
-    e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost", "token_alternatives" and "frame_blank_logprobs" are no longer taken
+    if (e->opt_lm_fusion) {                    // the fused forms read the winner's raw logit like the boosted ones
+        dp.lm_blk = e->lm_blk; dp.lm_state = e->lm_state; dp.lm_row = e->lm_row; dp.lm_next = e->lm_next; dp.lm_fold = e->opt_lm_fold; dp.lm_relook = e->opt_lm_relook; dp.boost_raw = e->boost_raw;
+    }
+    e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost", "token_alternatives", "frame_blank_logprobs" and "lm_fusion" are no longer taken
 }
 
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st) {

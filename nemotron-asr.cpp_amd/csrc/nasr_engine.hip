@@ -694,6 +694,7 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     rp.keep_reference_state = keep_reference_state ? 1 : 0;
     rp.abuf = e->abuf; rp.last_sample = e->last_sample; rp.mel_ring = e->mel_ring; rp.dec_h = e->dec_h; rp.dec_c = e->dec_c; rp.ctrl = e->ctrl;
     if (e->opt_phrase_boost) { rp.boost_state = e->boost_state; rp.boost_init = s->boost_enabled ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF; }
+    if (e->opt_lm_fusion) { rp.lm_state = e->lm_state; rp.lm_blk = e->lm_blk; rp.lm_enabled = s->lm_enabled ? 1 : 0; }
     rp.aud_hist = e->aud_hist;
     launch_stream_reset(rp, e->st);
     HIPCHK(hipGetLastError());

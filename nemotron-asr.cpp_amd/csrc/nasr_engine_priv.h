@@ -107,6 +107,7 @@ struct nasr_stream {
     int last_T, last_row, last_ws;   // rows of the last chunk and the workspace set they are in (for taps)
     bool alive;
     bool boost_enabled = true;       // nasr_stream_set_boost (engine option "phrase_boost")
+    bool lm_enabled = true;          // nasr_stream_set_lm (engine option "lm_fusion")
     std::vector<int32_t> tok_queue;  // tokens gathered from the device, not yet handed to the caller
     // audio input conversion (nasr_stream_set_audio_format, nasr_resample.h): the format survives a reset, the counters and the parity do not
     nasr_audio_format fmt = {16000, NASR_AUDIO_S16, 1, 0};
@@ -257,6 +258,13 @@ struct nasr_engine {
     nasr_lm::Model *lm = nullptr; void *lm_dev = nullptr;
     nasr_lm::View lm_view = {};      // device pointers
     float lm_weight = 0.0f, lm_bonus = 0.0f;
+    // option "lm_fusion": shallow fusion in the greedy decode.  Like "phrase_boost" it picks the decode launches that get captured and
+    // allocates what they read at fixed addresses: the block (the model's view + the greedy weights; the setters rewrite it), a state per slot, and per
+    // slot the bias row (phrase bonus + lmbias) with the next-state row beside it
+    int opt_lm_relook = 0;           // measurement switch "lm_commit_lookup" (1: the commit runs a second lookup instead of reading the next-state row)
+    bool opt_lm_fusion = false; int opt_lm_fold = 1;      // lm_fold: measurement switch "lm_refresh_fold" (1: the refresh rides in k_dec_pred, 0: a launch of its own)
+    nasr_lm::Greedy *lm_blk = nullptr; int32_t *lm_state = nullptr; float *lm_row = nullptr; int32_t *lm_next = nullptr;
+    float glm_weight = 0.0f, glm_bonus = 0.0f;            // nasr_engine_set_greedy_lm_weights
     long long lm_generation = 0;     // counts nasr_engine_set_lm calls that changed the model: a beam call's LM read-out is tied to the model it ran with
     // option "token_alternatives" = K (0: off, 1 .. 8), nasr_topk.h: the K largest joint outputs with their log-probabilities where every token was
     // emitted.  Taken like "token_logprobs"; its kernels also leave the softmax parts, so lp_part / tok_logprob are allocated with it

@@ -153,6 +153,7 @@ struct StreamResetParams {      // one launch per stream start / reset (kernels_
     float *abuf, *last_sample, *mel_ring, *dec_h, *dec_c;
     DecCtrl *ctrl;
     int *boost_state; int boost_init;   // engine option "phrase_boost" (null when off): the slot's automaton state goes back to the root (or 0 = disabled)
+    int32_t *lm_state; const nasr_lm::Greedy *lm_blk; int lm_enabled;   // engine option "lm_fusion" (null when off): the slot's LM state goes back to the model's start (or disabled)
     float *aud_hist;            // [slot][2][nasr_rs::HIST_MAX] input history of the audio converter: cleared in both modes
 };
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st);
@@ -237,7 +238,17 @@ struct DecParams {
     // engine option "frame_blank_logprobs" (both null when it is off; lp_part and the LP kernels come with it)
     float *fb_row;               // [B * T] indexed like key: ln P(blank) of every row the iteration's joint kernel evaluated (k_dec_commit, FB)
     float *frame_blank;          // [slot][FRAME_CAP] ring by absolute frame number: the value at the last evaluation of every frame the decode has left
+    // engine option "lm_fusion" (all null when it is off: the launches are then the ones without it), nasr_lm.h / DESIGN 17
+    const nasr_lm::Greedy *lm_blk;   // the fixed block: the model's view and the greedy weights (rewritten by the setters, never moved)
+    int32_t *lm_state;           // [slot] LM state of the slot's emitted history (nasr_lm::STATE_DISABLED: switched off)
+    float *lm_row;               // [slot][1040] phrase bonus + lmbias of every vocabulary entry in the slot's states
+    int32_t *lm_next;            // [slot][1040] LM state after emitting that entry
+    int lm_fold;                 // 1: the rows are refreshed by extra workgroups of k_dec_pred, 0: by a launch of their own
+    int lm_relook;               // measurement only: 1 = k_dec_commit looks the token up again instead of reading lm_next
 };
+// the bias rows of slots slot0 .. slot0 + n - 1 from their current states (boost_bonus / boost_state null without "phrase_boost")
+void launch_lm_rows(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus, const int *boost_state,
+                    int slot0, int n, hipStream_t st);
 void launch_decode_begin(const DecParams &p, hipStream_t st);
 void launch_decode_iter(const DecParams &p, hipStream_t st);
 int decode_blind_iterations(int frames);

@@ -81,6 +81,39 @@ NASR_LP_HD double lookup(const View &lm, int state, int token, int32_t *next) {
     return acc + (double)u.lp;
 }
 
+// ---- shallow fusion in the greedy decode (engine option "lm_fusion") --------------------------------------------------------
+// A stream carries one lookup state; the arg-max key of vocabulary entry v gets lmbias(v) = (float)(weight * lookup(state, v) + token_bonus),
+// blank and the padding columns get 0, and so does every entry when no model is attached or the stream is switched off.  The state moves to
+// the lookup's `next` when a symbol is committed.  The decode kernels read the view and the weights through one fixed block of device memory,
+// so a change of model or weights rewrites the block and leaves captured graphs as they are.
+constexpr int32_t STATE_DISABLED = -1;              // nasr_stream_set_lm(s, 0) / NASR_FLAG_NO_LM: no bias, and the state never moves
+constexpr int ROW_COLS = 1040;                      // the joint kernels' padded vocabulary: a lane's four entries are one aligned 16-byte load
+struct Greedy {
+    View lm;
+    float weight, token_bonus;
+    int32_t attached, pad;                          // 0: no model (lm is all zero)
+};
+// the state of an empty history
+NASR_LP_HD int32_t greedy_start(const Greedy &g, bool enabled) { return !enabled ? STATE_DISABLED : g.attached ? g.lm.start : 0; }
+// weight * lp + token_bonus in double, product and sum rounded on their own (no fused multiply-add, like nasr_beam::fused_total), then to f32
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("fp-contract=off")))
+#endif
+NASR_LP_HD float greedy_bias_value(float weight, double lp, float token_bonus) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double a = (double)weight * lp;
+    return (float)(a + (double)token_bonus);
+}
+// lmbias(v) of a stream in `state`, v in 0 .. ROW_COLS - 1, and the state after emitting v (the state itself where v gets no bias)
+NASR_LP_HD float lmbias(const Greedy &g, int32_t state, int v, int32_t *next) {
+    *next = state;
+    if (!g.attached || state < 0 || (unsigned)v >= (unsigned)N_TOKENS) return 0.0f;
+    const double lp = lookup(g.lm, state, v, next);
+    return greedy_bias_value(g.weight, lp, g.token_bonus);
+}
+
 // ---- host: the builder ---------------------------------------------------------------------------------------------------------------
 struct Model {
     std::vector<State> states;

@@ -106,6 +106,12 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
             rc |= off_alloc(o, (void **)&o->boost_state, U * 4);
             rc |= off_alloc(o, (void **)&o->boost_raw, nasr_lp::scratch_parts((int)(U * W)) * 4);
         }
+        if (e->opt_lm_fusion) {
+            rc |= off_alloc(o, (void **)&o->lm_state, U * 4);
+            rc |= off_alloc(o, (void **)&o->lm_row, U * nasr_lm::ROW_COLS * 4);
+            rc |= off_alloc(o, (void **)&o->lm_next, U * nasr_lm::ROW_COLS * 4);
+            if (!o->boost_raw) rc |= off_alloc(o, (void **)&o->boost_raw, nasr_lp::scratch_parts((int)(U * W)) * 4);
+        }
         rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
         rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
         rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
@@ -270,6 +276,11 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
     launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
     if (o->boost_state)                                          // every utterance starts with an empty history (NASR_FLAG_NO_BOOST: in the disabled state)
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->boost_state, o->no_boost ? nasr_boost::STATE_OFF : nasr_boost::STATE_ROOT, (size_t)n, st));
+    if (o->lm_state) {                                           // ... and at the model's start (NASR_FLAG_NO_LM: switched off); the reset left every slot dirty, so the
+        nasr_lm::Greedy g = {};                                  // first iteration refreshes its bias row
+        g.lm = e->lm_view; g.attached = e->lm ? 1 : 0;
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->lm_state, nasr_lm::greedy_start(g, !o->no_lm), (size_t)n, st));
+    }
     std::vector<int> tok_read(n, 0);
     std::vector<DecCtrl> hctrl(n);
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
@@ -302,6 +313,9 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
         if (K) { dp.alt_key = o->alt_key; dp.alt_id = o->alt_id; dp.alt_lp = o->alt_lp; dp.alt_k = K; }
         dp.fb_row = o->fb_row; dp.frame_blank = o->frame_blank;         // null unless "frame_blank_logprobs"
         if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
+        if (o->lm_state) {
+            dp.lm_blk = e->lm_blk; dp.lm_state = o->lm_state; dp.lm_row = o->lm_row; dp.lm_next = o->lm_next; dp.lm_fold = e->opt_lm_fold; dp.lm_relook = e->opt_lm_relook; dp.boost_raw = o->boost_raw;
+        }
         launch_decode_begin(dp, st);
         int h_active = 0;
         if (decode_until_idle(e, dp, n, st, &h_active, 0, decode_blind_iterations(max_dec), max_dec, nullptr, "offline decode")) return -1;
@@ -369,6 +383,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     o->lat_valid = false; o->lat_b.clear(); o->lat_t.clear();
     o->beam_valid = false; o->beam_res.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
+    o->no_lm = (flags & NASR_FLAG_NO_LM) != 0;
     return 0;
 }
 
@@ -478,6 +493,7 @@ int offline_call(nasr_engine *e, int B, const OffInput &in, const int32_t *promp
     if (!e) return fail("null engine");
     if (B < 0) return fail("B < 0");
     if (m.early && m.early()) return -1;
+    if ((flags & NASR_FLAG_NO_LM) && !m.greedy) return fail("NASR_FLAG_NO_LM belongs to nasr_engine_transcribe / _transcribe_mel; the beam search is fused by nasr_engine_set_lm alone and alignment never is");
     if (B == 0) return 0;
     if (in.is_pcm) {
         if (!in.pcm || !in.n) return fail("null pcm / n_samples");
@@ -522,7 +538,7 @@ static OffMode greedy_mode(nasr_engine *e, const char *who, int32_t *const *toke
     struct Run { std::vector<std::vector<int32_t>> toks, frs; };
     auto r = std::make_shared<Run>();
     OffMode m;
-    m.who = who; m.counts = n_tokens; m.streaming_hint = true;
+    m.who = who; m.counts = n_tokens; m.streaming_hint = true; m.greedy = true;
     m.setup = [=](OfflineState *o, int B) {
         o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
         o->frame_blank_lps.assign(e->opt_frame_blank ? B : 0, {});

@@ -31,6 +31,8 @@ struct OfflineState {
     nasr_lp::Part *lp_part = nullptr; float *tok_logprob = nullptr;      // engine option "token_logprobs" (allocated with the slots when it is on)
     int *boost_state = nullptr; float *boost_raw = nullptr;        // engine option "phrase_boost": the offline slots' automaton states (the tables are the engine's)
     bool no_boost = false;                                         // NASR_FLAG_NO_BOOST of the call in progress
+    int32_t *lm_state = nullptr, *lm_next = nullptr; float *lm_row = nullptr;      // engine option "lm_fusion": the offline slots' LM states and bias / next rows (the block is the engine's)
+    bool no_lm = false;                                            // NASR_FLAG_NO_LM of the call in progress
     unsigned long long *alt_key = nullptr; int32_t *alt_id = nullptr; float *alt_lp = nullptr;      // engine option "token_alternatives"
     std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // ... of the last call, by utterance: [tokens][K] each
     float *fb_row = nullptr, *frame_blank = nullptr;               // engine option "frame_blank_logprobs": scratch [U * W] and a ring [U][FRAME_CAP] (T <= 2048 < FRAME_CAP)
@@ -76,6 +78,7 @@ inline OffInput pcm_input(const int16_t *const *pcm, const int32_t *n_samples) {
 struct OffMode {
     const char *who = "";                                          // the entry's name, for begin_call's messages
     const int32_t *counts = nullptr;                               // the entry's per-utterance count array: begin_call refuses a null one
+    bool greedy = false;                                           // the greedy mode: the only one that takes NASR_FLAG_NO_LM
     bool streaming_hint = false;                                   // the over-limit message points at the streaming path
     std::function<int()> early;                                    // checks that hold for B == 0 too, before any other argument is looked at
     std::function<int(int B)> check;                               // checks whose failure has already forgotten the call before

@@ -317,6 +317,24 @@ bool nemo_clear_lm(nemo_context *ctx) {
     return true;
 }
 
+bool nemo_set_lm_fusion(nemo_context *ctx, bool enable) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "lm_fusion", enable ? 1 : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool nemo_set_greedy_lm_weights(nemo_context *ctx, float weight, float token_bonus) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_greedy_lm_weights(ctx->engine, weight, token_bonus) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool nemo_set_beam_boost(nemo_context *ctx, bool enable) {
     if (!ctx || !ctx->engine) return false;
     int64_t cap = 0;

@@ -130,10 +130,18 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
 // MI355X extension: shallow fusion of a back-off n-gram language model in nemo_transcribe_beam (nasr_engine_set_lm).
 // The ARPA file is over the vocabulary's pieces (lm_arpa.h: one piece or `ids:N` per word, <s>, </s>, <unk>; log10 values).  weight and
 // token_bonus in [0, 100]; unk_logprob (natural log, <= 0) is needed only when the file has no <unk> unigram (NAN = take the file's).  The model
-// re-scores the candidates the transducer proposes; greedy transcription and streams never see it.  false on failure (the reason on stderr;
+// re-scores the candidates the transducer proposes; greedy transcription and streams see it only after nemo_set_lm_fusion.  false on failure (the reason on stderr;
 // the previous model stays).  nemo_clear_lm detaches it.
 bool nemo_load_lm_arpa(nemo_context *ctx, const char *path, float weight, float token_bonus = 0.0f, float unk_logprob = NAN);
 bool nemo_clear_lm(nemo_context *ctx);
+
+// MI355X extension: shallow fusion in the GREEDY decode -- live streams and nemo_transcribe_beam with beam = 0 (engine option "lm_fusion";
+// DESIGN.md section 17).  nemo_set_lm_fusion(true) right after the context is made, before any stream processes audio; the model is the one of
+// nemo_load_lm_arpa, and the greedy decode has weights of its own (both in [0, 100], default 0 / 0 = unfused): arg-max over
+// logit + weight * ln P_lm(token | the stream's emitted tokens) + token_bonus for every non-blank token, blank unbiased.  Unlike in the beam
+// search the model scores the whole vocabulary, so it can propose a token.  false on failure (the reason on stderr)
+bool nemo_set_lm_fusion(nemo_context *ctx, bool enable);
+bool nemo_set_greedy_lm_weights(nemo_context *ctx, float weight, float token_bonus = 0.0f);
 
 // MI355X extension: phrase boosting inside nemo_transcribe_beam (NASR_FLAG_BEAM_BOOST), with or without a language
 // model.  It needs nemo_set_phrase_boost and a boost set (nemo_set_boost_phrases / nemo_load_boost_file); unlike the language model the

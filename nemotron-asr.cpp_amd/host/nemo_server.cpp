@@ -484,7 +484,9 @@ void on_signal(int) { g_stop = true; if (g_listen_fd >= 0) ::shutdown(g_listen_f
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--boost-file FILE] [--boost-bonus X] [--cpu | --cuda]\n"
+        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--cpu | --cuda]\n"
+                        "  --lm: greedy shallow fusion of a back-off n-gram model (ARPA over the vocabulary's pieces) for every session, one model per engine, loaded at start;\n"
+                        "        --lm-weight X (default 0.5) and --token-bonus Y (default 0), both 0 .. 100\n"
                         "  --boost-file: phrase boosting for every session: one `phrase<TAB>bonus` per line (bonus optional, default --boost-bonus or 4.0), loaded into every engine at start\n"
                         "  --prewarm: capture the step graphs of every batch size 1..max-streams for these right_context values before listening (~20 ms each);\n"
                         "             with --pipeline the default right_context is prewarmed unless --no-prewarm\n"
@@ -502,6 +504,9 @@ int main(int argc, char **argv) {
     bool no_prewarm = false;
     const char *boost_file = nullptr;
     float boost_bonus = 4.0f;
+    const char *lm_path = nullptr;
+    float lm_weight = 0.5f, token_bonus = 0.0f;
+    bool lm_opts = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--tcp" && i + 1 < argc) tcp = argv[++i];
@@ -528,6 +533,9 @@ int main(int argc, char **argv) {
         else if (a == "--no-prewarm") no_prewarm = true;
         else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
         else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
+        else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
+        else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = true; }
+        else if (a == "--token-bonus" && i + 1 < argc) { token_bonus = strtof(argv[++i], nullptr); lm_opts = true; }
         else if (a == "--prewarm" && i + 1 < argc) {
             for (const char *p = argv[++i]; *p;) {
                 prewarm_rc.push_back(atoi(p));
@@ -537,6 +545,7 @@ int main(int argc, char **argv) {
         }
         else { fprintf(stderr, "Unknown flag: %s\n", a.c_str()); return 1; }
     }
+    if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
     if (prewarm_rc.empty() && !no_prewarm && g_pipeline > 0) prewarm_rc.push_back(g_default_rc);     // a throughput server: the default lookahead's shapes are ready when the socket opens
     for (int dev : devices) {
         std::unique_ptr<Lane> ln(new Lane());
@@ -545,6 +554,7 @@ int main(int argc, char **argv) {
         ln->model = nemo_init_with_rows(argv[1], dev, dtype, max_streams, max_streams * 14 * backlog_chunks);
         if (!ln->model) { fprintf(stderr, "Failed to load ASR model on device %d\n", dev); return 1; }
         if (boost_file && !(nemo_set_phrase_boost(ln->model, 4096) && nemo_load_boost_file(ln->model, boost_file, boost_bonus))) return 1;
+        if (lm_path && !(nemo_set_lm_fusion(ln->model, true) && nemo_load_lm_arpa(ln->model, lm_path, 0.0f) && nemo_set_greedy_lm_weights(ln->model, lm_weight, token_bonus))) return 1;
         if (g_pipeline > 0 && !nemo_set_pipeline(ln->model, g_pipeline)) return 1;
         // one step shape per batch size and right_context in use, and as many again for the multi-chunk shapes of a backlog (chunk counts are
         // powers of two): none is evicted in steady state

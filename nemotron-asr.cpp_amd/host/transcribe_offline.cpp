@@ -21,6 +21,9 @@ static void usage(const char *prog) {
             "  word, <s>, </s>, <unk>; up to 5-grams); hypotheses rank by total = score + X * lm + Y * tokens (--lm-weight X, default 0.5;\n"
             "  --token-bonus Y, default 0; both 0 .. 100) and the lines read: rank score lm total text.  The model re-scores the transducer's\n"
             "  candidates, it proposes none\n"
+            "  --lm without --beam: the greedy decode is fused instead: arg-max over logit + X * ln P_lm(token | tokens so far) + Y for every\n"
+            "  non-blank token, blank unbiased (Y offsets the deletions that follow from that); here the model can propose a token.  --lm-weight\n"
+            "  must then be given: 0.5 is the beam search's default, the greedy decode's own is 0 (nothing fused), and the useful values differ\n"
             "  --boost-file F: phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional; natural-log units added to the logits of the\n"
             "  tokens that start or continue a phrase; `ids:1,2,3` gives literal token ids); --boost-bonus X: the bonus of lines that give none\n"
             "  (default 4.0).  Without --beam the greedy decode is boosted.  With --beam the search is boosted: a boosted token is proposed even outside a\n"
@@ -36,7 +39,7 @@ int main(int argc, char **argv) {
     bool print_tokens = false;
     const char *lm_path = nullptr;
     float lm_weight = 0.5f, token_bonus = 0.0f;
-    bool lm_opts = false, boost_opts = false;
+    bool lm_opts = false, lm_weight_given = false, boost_opts = false;
     const char *boost_file = nullptr;
     float boost_bonus = 4.0f;
     for (int i = 3; i < argc; i++) {
@@ -47,7 +50,7 @@ int main(int argc, char **argv) {
         else if (a == "--nbest" && i + 1 < argc) nbest = atoi(argv[++i]);
         else if (a == "--max-symbols" && i + 1 < argc) max_symbols = atoi(argv[++i]);
         else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
-        else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = true; }
+        else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = lm_weight_given = true; }
         else if (a == "--token-bonus" && i + 1 < argc) { token_bonus = strtof(argv[++i], nullptr); lm_opts = true; }
         else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
         else if (a == "--boost-bonus" && i + 1 < argc) { boost_bonus = strtof(argv[++i], nullptr); boost_opts = true; }
@@ -57,7 +60,10 @@ int main(int argc, char **argv) {
     }
     if (beam == 0 && (nbest != 0 || max_symbols != 0)) { fprintf(stderr, "--nbest and --max-symbols go with --beam\n"); return 1; }
     if (beam < 0) { fprintf(stderr, "--beam must be 1 .. 8\n"); return 1; }
-    if (lm_path && beam == 0) { fprintf(stderr, "--lm goes with --beam\n"); return 1; }
+    if (lm_path && beam == 0 && !lm_weight_given) {
+        fprintf(stderr, "--lm without --beam fuses the greedy decode and needs --lm-weight X (0.5 is the beam search's default; the greedy decode's own is 0: nothing fused)\n");
+        return 1;
+    }
     if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
     if (boost_opts && !boost_file) { fprintf(stderr, "--boost-bonus goes with --boost-file\n"); return 1; }
     FILE *in = fopen(audio_path, "rb");
@@ -70,7 +76,9 @@ int main(int argc, char **argv) {
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
-    if (lm_path && !nemo_load_lm_arpa(ctx, lm_path, lm_weight, token_bonus)) { nemo_free(ctx); return 1; }
+    if (lm_path && beam == 0 && !nemo_set_lm_fusion(ctx, true)) { nemo_free(ctx); return 1; }      // greedy: the model biases the device decode, by weights of its own
+    if (lm_path && !nemo_load_lm_arpa(ctx, lm_path, beam == 0 ? 0.0f : lm_weight, beam == 0 ? 0.0f : token_bonus)) { nemo_free(ctx); return 1; }
+    if (lm_path && beam == 0 && !nemo_set_greedy_lm_weights(ctx, lm_weight, token_bonus)) { nemo_free(ctx); return 1; }
     if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus) && (beam == 0 || nemo_set_beam_boost(ctx, true)))) {
         fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file);
         nemo_free(ctx);

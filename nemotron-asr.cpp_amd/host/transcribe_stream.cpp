@@ -25,7 +25,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--boost-file FILE] [--boost-bonus X] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
             "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
@@ -49,6 +49,9 @@ static void usage(const char *prog) {
             "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
             "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
             "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
+            "  --lm FILE.arpa:  shallow fusion of a back-off n-gram model over the vocabulary's pieces (one piece or ids:N per ARPA word, <s>, </s>, <unk>;\n"
+            "                   up to 5-grams) in the greedy decode: arg-max over logit + X * ln P_lm(token | tokens so far) + Y for every non-blank token,\n"
+            "                   blank unbiased.  --lm-weight X (default 0.5), --token-bonus Y (default 0; it offsets the deletions an unbiased blank causes); 0 .. 100\n"
             "  --pipeline E:    consecutive reads overlap on the GPU, E = 0..4 (same transcript; each delta appears E reads later).\n"
             "                   1: decode of one read beside the encoder of the next; 2..4: the encoder in E pieces on E hardware queues\n"
             "                   (4 = the fastest way through a file).  --pipeline without a number = 1; --pipeline2 / --pipeline3 still work\n"
@@ -68,6 +71,9 @@ int main(int argc, char **argv) {
     bool endpoints = false;
     nasr_endpoint::Config ep_cfg;
     float boost_bonus = 4.0f;
+    const char *lm_path = nullptr;
+    float lm_weight = 0.5f, token_bonus = 0.0f;
+    bool lm_opts = false;
     int pipeline = 0;
     int read_chunks = 1, num_speakers = -1;
     float sub_shift_sec = 0.75f, vad_onset = -1.0f, vad_offset = -1.0f;
@@ -90,6 +96,9 @@ int main(int argc, char **argv) {
         else if (a == "--endpoint-blank-prob" && i + 1 < argc) { const double pb = atof(argv[++i]); ep_cfg.min_blank_logprob = pb > 0.0 ? (float)std::log(pb) : -INFINITY; }
         else if (a == "--boost-file" && i + 1 < argc) boost_file = argv[++i];
         else if (a == "--boost-bonus" && i + 1 < argc) boost_bonus = (float)atof(argv[++i]);
+        else if (a == "--lm" && i + 1 < argc) lm_path = argv[++i];
+        else if (a == "--lm-weight" && i + 1 < argc) { lm_weight = strtof(argv[++i], nullptr); lm_opts = true; }
+        else if (a == "--token-bonus" && i + 1 < argc) { token_bonus = strtof(argv[++i], nullptr); lm_opts = true; }
         else if (a == "--cpu" || a == "--cuda" || a == "--metal")      // reference src/transcribe_stream.cpp:86-88
             fprintf(stderr, "note: %s ignored -- this build runs on the MI355X HIP engine only\n", a.c_str());
         else if (a == "--pipeline") {
@@ -121,6 +130,7 @@ int main(int argc, char **argv) {
         else if (positional == 1) { right_context = atoi(argv[i]); positional++; }
     }
     if (read_chunks < 1 || read_chunks > 4096) { fprintf(stderr, "--read-chunks must be in 1..4096 (got %d)\n", read_chunks); return 1; }
+    if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
     if (chunk_ms < 10) { fprintf(stderr, "chunk_ms must be >= 10 (got %d)\n", chunk_ms); return 1; }
     fprintf(stderr, "Configuration:\n  Model:          %s\n  Audio:          %s\n  Chunk size:     %d ms\n  Right context:  %d\n\n",
             model_path, from_stdin ? "stdin" : audio_path, chunk_ms, right_context);
@@ -131,6 +141,11 @@ int main(int argc, char **argv) {
     if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
     if (endpoints && !nemo_set_frame_blank_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable per-frame blank log-probabilities\n"); nemo_free(ctx); return 1; }
     if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
+    if (lm_path && !(nemo_set_lm_fusion(ctx, true) && nemo_load_lm_arpa(ctx, lm_path, 0.0f) && nemo_set_greedy_lm_weights(ctx, lm_weight, token_bonus))) {
+        fprintf(stderr, "Failed to load the language model from '%s'\n", lm_path);
+        nemo_free(ctx);
+        return 1;
+    }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     nemo_cache_config cfg = nemo_cache_config::default_config();
