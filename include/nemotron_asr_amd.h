@@ -284,8 +284,13 @@ enum {
  * "t64_tiles" (default 64, per engine: the split-K GEMMs with N = 1024 take 128 x 64 tiles up to this many 128 x 128 tiles; round 3: 127),
  * "tile_bands" (-1 = the rule: above 4 row chunks the tiles of a launch are handed to the XCDs in bands of column groups, so that the panels an XCD reads stay in its L2;
  * 0 / 1 = never / always), "f32_mfma" (0: f32 GEMMs above
- * four rows on the FMA tile kernel instead of the f32 MFMA), "decode_graph_iterations" (>= 1, default 12: decode iterations a
- * pipelined step's decode graph carries before the eager fallback), "resid_epilogue" (0: every residual GEMM writes split-K partial
+ * four rows on the FMA tile kernel instead of the f32 MFMA), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
+ * fallback.  N >= 1: max(the synchronous step graph's count, min(10 frames + 1, N)).  Default 0 = auto: as 12, except that a step of ONE
+ * frame and up to four rows on a bf16 engine (one to four streams at R = 0) carries 3 -- a frame of two symbols and the closing blank; its
+ * decode graph runs behind the fourth encoder piece on a lane the host waits for in every call, so idle iterations there cost step time.
+ * A frame that emits three or more symbols is completed by the fallback: same tokens, one host round trip, counter "decode_fallbacks"),
+ * "fused_cuts" (MEASUREMENT ONLY, results are valid: the launch indices at which a step of up to four rows is cut into its four lane
+ * pieces, for a 24-layer model, 10 bits each, lowest first; 0 = built in (46 | 98 | 150 of 192).  REJECTED after the first pipelined step), "resid_epilogue" (0: every residual GEMM writes split-K partial
  * slabs and k_post adds them, as in rounds 1-4; default 1: the GEMM adds to the residual stream in its epilogue where one workgroup owns a tile's
  * whole K sum -- same bits), "gemm_prio" (default 0: round 5's GEMM loops -- k_gemm_wide2 / k_gemm_tiled3: the next chunk's fragments read under this chunk's
  * MFMAs, wave-private epilogues; 20: rounds 1-4's loops; same bits), "epilogue16" (default 1: the GEMM epilogues with 16-bit outputs store eight columns = 16 bytes
@@ -340,7 +345,8 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * pushes, streams that complete different chunk counts), "pipelined_steps", "grouped_steps", "lanes" (HIP streams the engine found
  * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
- * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
+ * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);
 /* enable recording of NASR_TAP_MEL / SUBSAMPLED / LAYER_OUT (costs extra copies) */

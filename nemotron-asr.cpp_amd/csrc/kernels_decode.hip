@@ -28,6 +28,7 @@
 // are ordered (unit u, gate g) = (r/4, r%4), which lands the four gates i,f,g,o of one hidden
 // unit in the four accumulator registers of one lane: the cell update needs no data movement.
 #include "nasr_internal.h"
+#include "nasr_step_plan.h"
 
 namespace nasr {
 
@@ -795,11 +796,7 @@ void launch_decode_iter(const DecParams &p, hipStream_t st) {
     else if (p.lp_part) { if (p.boost_bonus) launch_joint_commit<true, true, false>(p, st); else launch_joint_commit<true, false, false>(p, st); }
     else { if (p.boost_bonus) launch_joint_commit<false, true, false>(p, st); else launch_joint_commit<false, false, false>(p, st); }
 }
-// iterations enqueued before the host looks at n_active: (symbols of the busiest stream) + 1 are needed; a shortfall
-// costs one host round trip and a further round of iterations
-int decode_blind_iterations(int frames) {
-    if (frames <= 1) return 2;                  // one emission + the closing blank; a spare iteration would cost 1 % of the step
-    return frames / 2 + 4 < 16 ? frames / 2 + 4 : 16;   // an idle iteration (~10 us) is far cheaper than a host round trip
-}
+// iterations enqueued before the host looks at n_active (the arithmetic is host-tested with the rest of nasr_step_plan.h)
+int decode_blind_iterations(int frames) { return nasr_step::blind_iterations(frames); }
 
 }  // namespace nasr

@@ -166,7 +166,16 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
 
 extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value) {
     if (!e || !key) return fail("null argument");
-    if (!strcmp(key, "fused")) e->opt_fused = value != 0;
+    if (!strcmp(key, "fused")) {
+        // the family of the small steps, and with it their lane cut: nothing cut the other way may be in flight (pipe_step would drain at the
+        // next step anyway; here the option's caller pays, not the next call)
+        if (e->opt_fused != (value != 0)) {
+            ApiGuard api_guard;
+            HIPCHK(hipSetDevice(e->device));
+            if (pipe_drain(e)) return -1;
+        }
+        e->opt_fused = value != 0;
+    }
     else if (!strcmp(key, "graph")) e->opt_graph = value != 0;
     else if (!strcmp(key, "graph_cache")) { if (value < 1) return fail("graph_cache must be >= 1"); e->opt_graph_cache = value; }
     else if (!strcmp(key, "multichunk")) e->opt_multichunk = value != 0;
@@ -176,7 +185,15 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
     else if (!strcmp(key, "wide_tiles")) e->opt_wide_tiles = value;              // like "fused": set before the first step
     else if (!strcmp(key, "persistent_gemm")) e->opt_persist_gemm = value != 0;      // like "fused": set before the first step
     else if (!strcmp(key, "gemm_cores")) { if (value < -1 || value > 1) return fail("gemm_cores must be -1, 0 or 1"); e->opt_gemm_cores = value; }
-    else if (!strcmp(key, "decode_graph_iterations")) { if (value < 1) return fail("decode_graph_iterations must be >= 1"); e->opt_decode_graph_iters = value; }
+    else if (!strcmp(key, "decode_graph_iterations")) { if (value < 0) return fail("decode_graph_iterations must be >= 1, or 0 (auto)"); e->opt_decode_graph_iters = value; }
+    else if (!strcmp(key, "fused_cuts")) {
+        // measurement only: read when a step shape's piece graphs are captured, and steps in flight must all be cut alike
+        int cut4[3];
+        unpack_cut4(value, cut4);
+        if (value != 0 && !valid_cut4(cut4, e->hp.n_layers)) return fail("fused_cuts: three launch indices of a 24-layer model, 10 bits each, that leave four non-empty pieces");
+        if (e->pipe_steps || e->gp_steps) return fail("fused_cuts must be set before the first pipelined step");
+        e->opt_fused_cuts = value;
+    }
     else if (!strcmp(key, "decode_lane")) {
         // read by pick_lanes() only, and the lanes are picked once: later the option would be a silent no-op (round-4 advisor)
         if (e->pipe_ready) return fail("decode_lane must be set before the first pipelined step (the lanes are already picked)");
@@ -973,6 +990,7 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "eager_steps")) *value = e->eager_steps;
     else if (!strcmp(name, "pipelined_steps")) *value = e->pipe_steps;
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;
+    else if (!strcmp(name, "cut_drains")) *value = e->cut_drains;                           // pipelined steps that first completed the steps in flight: cut differently (piece count, family)
     else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)
     else if (!strcmp(name, "lm_states")) *value = e->lm ? (int64_t)e->lm->states.size() : 0;

@@ -226,8 +226,7 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
     // Up to 4 rows the 8-launch fused layer wins; above, its per-workgroup prologues (every workgroup redoes the
     // LayerNorm of all rows) cost more than the 6 extra launches of the unfused layer (measured at R = 0:
     // 8 rows 2.13 vs 1.89 ms, 16 rows 2.78 vs 1.96 ms per step).
-    constexpr int fused_rows = 4;
-    const bool fused = e->bf16 && e->opt_fused && !e->debug && M <= fused_rows;
+    const bool fused = fused_family(e->bf16, e->opt_fused, e->debug, M);          // up to FUSED_ROWS = 4 rows
     const int TS = G * T;                      // rows per stream in this launch
     if (G > 1 && e->debug) return fail("internal: multi-chunk steps are not available in debug mode");
     if (part != 0) {
@@ -238,29 +237,21 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
         // batch 1 0.492-0.497 ms per step against 0.498-0.500 at 7 + 9 + 8 layers (56 + 72 + 64) -- with three lanes the step is
         // no longer bound by its longest lane (tests/micro/stamps_timeline.py: the kernels of the three chains mostly alternate
         // instead of overlapping: 0 / 1 / 2 / 3 kernels in flight 29 / 40 / 20 / 10 % of the time).
-        auto bound8 = [&](int k) {
-            if (k <= 0) return 0;
-            if (k >= nseg) return 8 * nLayers;
-            if (nseg == 3 && nLayers >= 6) return (k == 1 ? 57 : 126) * nLayers / 24;
-            // four pieces: 48 + 56 + 60 + 28 launches (batch 1: 0.426 ms per step; 48 + 56 + 56 + 32 0.437, 50 + 56 + 56 + 30 0.433,
-            // 48 + 54 + 62 + 28 0.434, 48 + 56 + 64 + 24 0.440; three lanes 0.454)
-            if (nseg == 4 && nLayers >= 8) return (k == 1 ? 48 : k == 2 ? 104 : 164) * nLayers / 24;
-            return 8 * bound(k);
-        };
+        // The cut itself is nasr_step::fused_cut (host-tested; the table of the four-piece cut is there).  While the decode graph of a
+        // one-frame step carried 11 iterations, 48 + 56 + 58 + 30 launches was best (batch 1: 0.426 ms per step; 48 + 56 + 56 + 32 0.437,
+        // 50 + 56 + 56 + 30 0.433, 48 + 54 + 62 + 28 0.434, 48 + 56 + 64 + 24 0.440; three lanes 0.454); with 3 it is 46 + 52 + 52 + 42.
         // The launches of a layer that touch PER-STREAM state shared by all steps -- K3 / K4 (the layer's K/V ring) and K6 (its conv
-        // cache) -- must run on the SAME lane whatever the step's shape: steps of one stream follow each other through a layer in lane
-        // order only.  The unfused path (more than four rows) cuts at whole layers, bound(k); a fused cut may therefore only move
-        // launches that touch nothing but the step's own workspace across that boundary: K7 / K8 of the layer before it (FFN2) or
-        // K1 / K2 of the layer after it (FFN1), i.e. it must lie in [8 bound(k) - 2, 8 bound(k) + 2].  Round 2 shipped 164 for the third cut
-        // of the 24-layer model (layer 20's K3 / K4 on lane 2 for one-to-four-row steps, on lane 3 for larger ones): a stream whose steps
-        // alternate between the two forms while both are in flight could read or write that layer's ring out of order -- found in
-        // round 3 by the soak test on 8 layers (cuts 16 | 34 | 54), never seen at 24; the cut is 162 now.
-        auto snap8 = [&](int k, int b) {
-            if (k <= 0 || k >= nseg) return b;
-            const int lb = 8 * bound(k);
-            return std::min(std::max(b, lb - 2), lb + 2);
-        };
-        if (run_layers_fused(e, rows, B, T, G, snap8(seg, bound8(seg)), snap8(seg + 1, bound8(seg + 1)))) return -1;
+        // cache) -- must run on the SAME lane for every step in flight: steps of one stream follow each other through a layer in lane
+        // order only.  The unfused path (more than four rows) cuts at whole layers, bound(k), and through round 5 a fused cut was
+        // therefore snapped into [8 bound(k) - 2, 8 bound(k) + 2] (`snap8`: only K7 / K8 of the layer before or K1 / K2 of the layer after
+        // touch nothing but the step's own workspace; round 2's 164 put layer 20's K3 / K4 on another lane than the larger steps' and the
+        // round-3 soak test found a stream alternating between the two forms reading that layer's ring out of order).  That pinned the
+        // last lane at 28-30 launches.  Now the two families never share the lanes: pipe_step completes what is in flight before a step
+        // of the other family (its cut identity; counter "cut_drains"), and this cut is free to sit at any launch.
+        int cut4[3];
+        unpack_cut4(e->opt_fused_cuts, cut4);
+        const int *cuts = e->opt_fused_cuts ? cut4 : nullptr;
+        if (run_layers_fused(e, rows, B, T, G, fused_cut(nLayers, nseg, seg, cuts), fused_cut(nLayers, nseg, seg + 1, cuts))) return -1;
     } else {
     // ---- 24 cached conformer layers -----------------------------------------------------------
         const int ks = e->hp.kernel_size;

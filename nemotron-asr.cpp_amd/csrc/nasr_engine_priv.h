@@ -161,7 +161,8 @@ struct nasr_engine {
     int w_rows = 0;                  // workspace rows = max(max_streams x TMAX, MAXNEW)
     char *g_desc = nullptr;          // device mirror of the packed descriptor block (layout: graph_desc_layout)
     bool opt_multichunk = true;
-    int opt_decode_graph_iters = 12;   // blind decode iterations a pipelined step's decode graph carries at most (option "decode_graph_iterations")
+    int opt_decode_graph_iters = 0;    // blind decode iterations a pipelined step's decode graph carries at most (option "decode_graph_iterations"); 0 = auto (nasr_step::pipe_decode_iterations)
+    int opt_fused_cuts = 0;            // option "fused_cuts" (MEASUREMENT ONLY): the four-piece lane cut of the fused family, three launch indices of a 24-layer model in 10 bits each; 0 = nasr_step::FUSED_CUT4
     bool opt_decode_lane = true;       // the decode graphs get a lane of their own when a queue is free (option "decode_lane")
     int opt_gemm_cores = -1;           // -1: the engine's rule; 0 / 1: never / always the GEMM kernels of which two share a CU (option "gemm_cores")
     int opt_large_step_rows = 0;     // option "large_step_rows": the row count from which "large_step_pieces" applies (0 = the default of 5 600; round 4: 3 584)
@@ -191,7 +192,8 @@ struct nasr_engine {
     // workspace set, descriptor blocks, joint.enc buffer, token landing zone, graphs (their kernel arguments point into
     // the slot).  E + 1 steps are in flight; slot of a step = its sequence number mod NSLOT.
     static const int MAXSEG = 4, LSLOT = MAXSEG + 1;     // lanes mode: E + 1 steps in flight, slot = sequence number mod LSLOT
-    int pipe_last_nseg = 0;          // pieces of the youngest step in flight (pipe_step drains before a step that is cut differently)
+    int pipe_last_cut = 0;           // cut identity of the youngest step in flight: its piece count and its family (pipe_cut_id; pipe_step drains before a step that is cut differently)
+    int64_t cut_drains = 0;          // ... and how often it had to (counter "cut_drains")
     static const int GP_C = 2, GP_Y = FUSED_GROUP, GP_S = GP_C * GP_Y;   // grouped mode ("pipeline" = 8): 2 chains x 4 problems per launch = 8 stages
     static const int NSLOT = GP_S + 3;                    // grouped mode: 8 steps in flight + the one being decoded + the one being collected + one spare
     struct WS { float *x, *x2, *part, *q, *glu, *sub_a, *hfuse; void *a, *hbuf, *ctx, *cbuf, *sub_b; unsigned *chain_flags; };
@@ -212,7 +214,8 @@ struct nasr_engine {
         hipEvent_t seg_done[MAXSEG] = {nullptr, nullptr, nullptr, nullptr};
         hipEvent_t dec_done = nullptr;
         bool dec_launched = false;
-        std::map<int64_t, hipGraphExec_t> seg_graphs[MAXSEG], dec_graphs;     // key = (B, T, G, E)
+        std::map<int64_t, hipGraphExec_t> seg_graphs[MAXSEG], dec_graphs;     // key = (B, T, G, family, E)
+        std::map<int64_t, int> dec_iters;                 // iterations dec_graphs[key] carries: where finish_step_decode's fallback goes on
         int stage = 0;                                    // encoder pieces launched so far (0 = slot free)
         int64_t seq = -1;                                 // sequence number of the step that occupies the slot
         std::vector<nasr_stream *> streams;
@@ -423,12 +426,12 @@ int64_t lru_victim(const std::map<int64_t, hipGraphExec_t> &m, const std::map<in
 // eager completion on st from `iters` iterations on if the graph's budget fell short (and `fallback` allows it), then -- recollect -- k_collect again
 struct StepDecode { const char *g_desc; float *encproj; const int *g_dmeta; int *collect_dev, *gh_collect; int B, T, G; };
 int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int iters, int round, bool fallback, bool recollect);
-int pipe_blind_iterations(int frames, int cap);
+int pipe_blind_iterations(const nasr_engine *e, int B, int T, int G);
 double spin_us(hipStream_t a, hipStream_t b);
 int pick_lanes(nasr_engine *e);
 void release_lanes(nasr_engine *e);
 int ensure_pipe(nasr_engine *e, int p);
-int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nseg, hipGraphExec_t *seg_out, hipGraphExec_t *dec_out);
+int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nseg, hipGraphExec_t *seg_out, hipGraphExec_t *dec_out, int *dec_iters);
 int pipe_advance(nasr_engine *e, int p);
 int pipe_finish_launch(nasr_engine *e, int p);
 int pipe_finish(nasr_engine *e, int p);

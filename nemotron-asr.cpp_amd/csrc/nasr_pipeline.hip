@@ -161,10 +161,12 @@ int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int 
 // The decode graph is launched only once its input is ready: parked behind an event wait for the ~1 ms the encoder takes
 // it made every boundary of the encoder chain slower (round 1: 1.21 vs 1.07 ms per step at batch 1).
 
-int pipe_blind_iterations(int frames, int cap) {     // cap: engine option "decode_graph_iterations" (12)
-    // off the critical path an idle iteration is free: give one frame its worst case (10 symbols + the closing blank)
-    const int worst = frames * MAX_SYMBOLS + 1;
-    return std::max(decode_blind_iterations(frames), std::min(worst, cap));
+// Iterations the decode graph of a (B, T, G) step carries.  On a lane of its own an idle iteration is free, and a frame gets up to its worst
+// case (10 symbols + the closing blank, capped at 12).  With four lanes the graph runs behind the fourth encoder piece and the host waits for
+// that lane in every call: the one-frame step of the fused family carries 3 (nasr_step::pipe_decode_iterations, profiles/small_step_decode.md).
+int pipe_blind_iterations(const nasr_engine *e, int B, int T, int G) {
+    const long rows = (long)B * T * G;
+    return pipe_decode_iterations(fused_family(e->bf16, e->opt_fused, e->debug, rows) ? (int)rows : 0, T * G, e->opt_decode_graph_iters);
 }
 
 // ---- which HIP streams run side by side -------------------------------------------------------------------------------------
@@ -253,7 +255,7 @@ int ensure_pipe(nasr_engine *e, int p) {
 
 // the graphs of one (B, T, G, E) on one slot: the E encoder pieces and the decode.  Their kernel arguments point into the
 // slot's workspace set, descriptor block and joint.enc buffer.
-int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nseg, hipGraphExec_t *seg_out, hipGraphExec_t *dec_out) {
+int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nseg, hipGraphExec_t *seg_out, hipGraphExec_t *dec_out, int *dec_iters) {
     nasr_engine::Pipe &P = e->pipe[p];
     const GraphDescLayout L = graph_desc_layout(B, G);
     const RowDesc *g_rows = (const RowDesc *)(P.g_desc + L.rows), *g_vrows = (const RowDesc *)(P.g_desc + L.vrows);
@@ -284,10 +286,8 @@ int build_pipe_graphs(nasr_engine *e, int p, int B, int T, int R, int G, int nse
             }, e->st, " (encoder piece graph)")) return -1;
     }
     // decode graph: captured on the last lane, replayed on dec_stream()
-    return in_slot([&]() -> int {
-        return capture_decode_graph(e, p, B, T, G, e->lane[e->n_lanes - 1], (e->opt_ablate & 8) ? 0 : pipe_blind_iterations(T * G, e->opt_decode_graph_iters),
-                                    " (decode graph)", dec_out);
-    });
+    *dec_iters = (e->opt_ablate & 8) ? 0 : pipe_blind_iterations(e, B, T, G);
+    return in_slot([&]() -> int { return capture_decode_graph(e, p, B, T, G, e->lane[e->n_lanes - 1], *dec_iters, " (decode graph)", dec_out); });
 }
 
 // next encoder piece of the step in slot p: queued on its lane behind the previous piece's event.  That wait is short in
@@ -331,11 +331,11 @@ int pipe_finish(nasr_engine *e, int p) {
     if (P.stage == 0) return 0;
     if (pipe_finish_launch(e, p)) return -1;
     P.dec_launched = false;
-    const int B = (int)P.streams.size(), TS = P.T * P.G;
+    const int B = (int)P.streams.size();
     hipStream_t ds = dec_stream(e, P);
     { HostTimer ht(e->host_wait_s); HIPCHK(hipEventSynchronize(P.dec_done)); }
     if (finish_step_decode(e, StepDecode{P.g_desc, P.encproj, P.g_dmeta, P.collect_dev, P.gh_collect, B, P.T, P.G}, ds,
-                           pipe_blind_iterations(TS, e->opt_decode_graph_iters), 8, !(e->opt_ablate & 8), true) < 0) return -1;
+                           P.dec_iters[P.key], 8, !(e->opt_ablate & 8), true) < 0) return -1;
     P.stage = 0;
     return consume_collect(e, P.gh_collect, P.streams.data(), B);
 }
@@ -367,17 +367,22 @@ int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
     // tokens come back at most E calls later whatever the piece count.
     if ((long)B * T * G >= (e->opt_large_step_rows > 0 ? e->opt_large_step_rows : 5600) && e->opt_large_step_pieces > 0) nseg = std::min(nseg, e->opt_large_step_pieces);
     // steps in flight order their layers through the lanes (piece k of every step on lane k): a step cut differently from the ones before it
-    // must not overtake them -- complete those first (a call population that crosses 3 584 rows, or an option change; never the steady state)
-    if (e->pipe_last_nseg != nseg) {
-        if (e->pipe_last_nseg && pipe_drain(e)) return -1;
-        e->pipe_last_nseg = nseg;
+    // must not overtake them -- complete those first.  The cut identity is the piece count and the family: the fused family (up to four rows)
+    // is cut at launches of its own choosing (nasr_step::fused_cut), every other step at whole layers, so the launches of a layer that touch
+    // per-stream state (its K/V ring, its conv cache) sit on different lanes in the two.  A call population that crosses four or 5 600 rows
+    // drains, as does a change of option "fused"; never the steady state.  Counter "cut_drains".
+    const int fam = fused_family(e->bf16, e->opt_fused, e->debug, (long)B * T * G) ? 1 : 0;
+    const int cut_id = nseg | (fam << 6);
+    if (e->pipe_last_cut != cut_id) {
+        if (e->pipe_last_cut) { if (pipe_drain(e)) return -1; e->cut_drains++; }
+        e->pipe_last_cut = cut_id;
     }
     const int64_t seq = e->pipe_seq;
     const int p = (int)(seq % nasr_engine::LSLOT);
     if (ensure_pipe(e, p)) return -1;
     nasr_engine::Pipe &P = e->pipe[p];
     if (pipe_finish(e, p)) return -1;                      // the slot's previous occupant (LSLOT steps ago): done in steady state
-    const int64_t key = ((int64_t)B << 40) | ((int64_t)T << 24) | ((int64_t)G << 8) | (int64_t)nseg;
+    const int64_t key = ((int64_t)B << 40) | ((int64_t)T << 24) | ((int64_t)G << 8) | (int64_t)cut_id;
     auto ge = P.seg_graphs[0].find(key);
     e->graph_used[key | ((int64_t)1 << 62)] = ++e->graph_tick;
     if (ge == P.seg_graphs[0].end()) {
@@ -396,18 +401,21 @@ int pipe_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t 
                 for (auto &m : Q.seg_graphs) { auto f = m.find(victim); if (f != m.end()) { if (f->second) hipGraphExecDestroy(f->second); m.erase(f); } }
                 auto f = Q.dec_graphs.find(victim);
                 if (f != Q.dec_graphs.end()) { if (f->second) hipGraphExecDestroy(f->second); Q.dec_graphs.erase(f); }
+                Q.dec_iters.erase(victim);
                 if (q == p) e->graph_evictions++;
             }
             hipGraphExec_t gs[nasr_engine::MAXSEG] = {nullptr, nullptr, nullptr, nullptr}, dec = nullptr;
+            int dec_iters = 0;
             {
                 CaptureExclusive alone;
                 e->gemm_coresident = nseg >= 2;          // several launch chains side by side: co-resident GEMM variants
-                const int rc = build_pipe_graphs(e, q, B, T, R, G, nseg, gs, &dec);
+                const int rc = build_pipe_graphs(e, q, B, T, R, G, nseg, gs, &dec, &dec_iters);
                 e->gemm_coresident = false;
                 if (rc) return -1;
             }
             for (int k = 0; k < nseg; k++) Q.seg_graphs[k][key] = gs[k];
             Q.dec_graphs[key] = dec;
+            Q.dec_iters[key] = dec_iters;
         }
         ge = P.seg_graphs[0].find(key);
     }
@@ -585,7 +593,7 @@ int gp_finish_decode(nasr_engine *e) {
     hipStream_t ds = e->lane[nasr_engine::GP_C - 1];
     { HostTimer ht(e->host_wait_s); HIPCHK(hipEventSynchronize(P.dec_done)); }
     if (finish_step_decode(e, StepDecode{P.g_desc, P.encproj, P.g_dmeta, P.collect_dev, P.gh_collect, nB, P.T, P.G}, ds,
-                           pipe_blind_iterations(P.T * P.G, e->opt_decode_graph_iters), 8, true, true) < 0) return -1;
+                           P.dec_iters[P.key], 8, true, true) < 0) return -1;
     return consume_collect(e, P.gh_collect, P.streams.data(), nB);
 }
 
@@ -626,8 +634,10 @@ int gp_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *c
             if (ensure_pipe(e, q)) return -1;
             if (e->pipe[q].dec_graphs.count(key)) continue;
             hipGraphExec_t dec = nullptr;
-            if (capture_decode_graph(e, q, B, T, G, e->lane[nasr_engine::GP_C - 1], pipe_blind_iterations(T * G, e->opt_decode_graph_iters), " (grouped pipeline)", &dec)) return -1;
+            const int iters = pipe_blind_iterations(e, B, T, G);
+            if (capture_decode_graph(e, q, B, T, G, e->lane[nasr_engine::GP_C - 1], iters, " (grouped pipeline)", &dec)) return -1;
             e->pipe[q].dec_graphs[key] = dec;
+            e->pipe[q].dec_iters[key] = iters;
         }
         for (int q = 0; q < nasr_engine::NSLOT; q++) {
             int sos[nasr_engine::GP_S];

@@ -63,4 +63,65 @@ inline void apply_pcm_counts(const PcmDesc &d, int &abuf_cnt, int &abuf_par, int
     mel_count += d.n_frames;
 }
 
+// ---- the fused family, its decode-graph budget and its lane cut ---------------------------------------------------------------------------
+// Steps of up to FUSED_ROWS rows on a bf16 engine run the 8-launch fused layer (run_layers_fused), every other step the unfused layers
+// (enqueue_layers).  The two forms cut a pipelined step into lane pieces differently, so the family is part of a step's cut identity.
+constexpr int FUSED_ROWS = 4;
+inline bool fused_family(bool bf16, bool opt_fused, bool debug, long rows) { return bf16 && opt_fused && !debug && rows >= 1 && rows <= FUSED_ROWS; }
+
+// iterations enqueued before the host looks at n_active: (symbols of the busiest stream) + 1 are needed; a shortfall
+// costs one host round trip and a further round of iterations
+inline int blind_iterations(int frames) {
+    if (frames <= 1) return 2;                  // one emission + the closing blank; a spare iteration would cost 1 % of the step
+    return frames / 2 + 4 < 16 ? frames / 2 + 4 : 16;   // an idle iteration (~10 us) is far cheaper than a host round trip
+}
+
+// Decode iterations the decode graph of a pipelined step carries.  rows: the rows of a fused-family step (B T G), 0 for a step of any other
+// form; cap: engine option "decode_graph_iterations", 0 = auto.  An explicit cap gives one frame up to its worst case (MAX_SYMBOLS + the
+// closing blank), never less than the synchronous step graph carries.  Auto is a cap of 12, except for the one-frame step of the fused
+// family: its decode graph runs behind the last encoder piece on a lane the host waits for in every call, where five launches per idle
+// iteration are a dependent chain, so it carries 3 (a frame of two symbols + the closing blank; more symbols: finish_step_decode's fallback).
+constexpr int DECODE_GRAPH_CAP = 12, SMALL_STEP_DECODE_ITERS = 3;
+inline int pipe_decode_iterations(int rows, int frames, int cap) {
+    if (cap <= 0 && frames == 1 && rows >= 1 && rows <= FUSED_ROWS) return SMALL_STEP_DECODE_ITERS;
+    if (cap <= 0) cap = DECODE_GRAPH_CAP;
+    const int worst = frames * MAX_SYMBOLS + 1, blind = blind_iterations(frames);
+    const int want = worst < cap ? worst : cap;
+    return blind > want ? blind : want;
+}
+
+// Launch index (of the 8 L launches of the L fused layers) at which lane piece k of E begins; piece E - 1 ends at 8 L.  The first piece also
+// carries the front end (about 8 launches' worth of time), the last one the tail and the decode graph.  cut4: the three indices of the
+// four-piece cut of a 24-layer model (engine option "fused_cuts"), nullptr = FUSED_CUT4; other depths scale them.
+// Four pieces, batch 1, R = 0, 3-iteration decode graph, ms per step (median of 5 regions of 200 steps, spread 0.1-0.3 %; two machines, the
+// parent commit on the same machine 0.4247 / 0.4222; profiles/small_step_decode.md):
+//   48 | 104 | 162  0.4121 (the cut before: within two launches of the unfused path's layer bounds)     48 | 104 | 164  0.4131
+//   46 |  98 | 150  0.4065 / 0.4039     46 | 96 | 150  - / 0.4024     46 | 98 | 154  - / 0.4036     44 | 98 | 150  - / 0.4045
+//   46 | 102 | 154  - / 0.4048     46 | 100 | 150  - / 0.4059     46 | 98 | 152  - / 0.4060     46 | 100 | 152  - / 0.4061     46 | 100 | 154  0.4078 / -
+//   48 |  98 | 150  - / 0.4135     48 | 100 | 150  - / 0.4133     48 | 100 | 148  0.4147 / -     48 | 100 | 152  0.4153 / -     46 | 96 | 148  0.4154 / -
+//   44 |  96 | 148  0.4160 / -     48 | 102 | 156  0.4169 / -     46 | 98 | 148  - / 0.4179     50 | 104 | 156  0.4230 / -     46 | 98 | 146  0.4281 / -
+//   44 |  94 | 146  0.4282 / -
+// A plateau of 0.402-0.406 around 46 + 52 + 52 + 42 (a first piece of 48 or a last one of 44 and more leave it); with the decode
+// iterations taken out altogether ("ablate" = 8) the same cut measures 0.4044: the decode no longer binds the step.
+constexpr int FUSED_CUT4[3] = {46, 98, 150};
+inline int fused_cut(int L, int E, int k, const int *cut4 = nullptr) {
+    if (k <= 0) return 0;
+    if (k >= E) return 8 * L;
+    if (E == 4 && L >= 8) return (cut4 ? cut4 : FUSED_CUT4)[k - 1] * L / 24;
+    if (E == 3 && L >= 6) return (k == 1 ? 57 : 126) * L / 24;
+    if (E == 2 && L >= 8) return 8 * (L / 2 - 1);
+    return 8 * L * k / E;
+}
+// "fused_cuts" packs the three indices in 10 bits each (lowest first); valid when they cut 8 L launches into four non-empty pieces
+inline void unpack_cut4(int packed, int *cut4) { for (int k = 0; k < 3; k++) cut4[k] = (packed >> (10 * k)) & 1023; }
+inline bool valid_cut4(const int *cut4, int L) {
+    int prev = 0;
+    for (int k = 0; k < 3; k++) {
+        const int b = cut4[k] * L / 24;
+        if (b <= prev) return false;
+        prev = b;
+    }
+    return prev < 8 * L;
+}
+
 }  // namespace nasr_step
