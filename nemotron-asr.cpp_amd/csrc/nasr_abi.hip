@@ -18,7 +18,7 @@ static int upload_boost_set(nasr_engine *e, int n_phrases, const int32_t *const 
     HIPCHK(hipMemcpy(e->boost_next, a.next.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
     std::vector<int> st((size_t)e->max_streams, nasr_boost::STATE_ROOT);
     for (int i = 0; i < e->max_streams; i++) if (e->slots[i] && !e->slots[i]->boost_enabled) st[(size_t)i] = nasr_boost::STATE_OFF;
-    HIPCHK(hipMemcpy(e->boost_state, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->dec.boost_state, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
     e->boost_states = a.n_states;
     e->boost_host = std::move(a);
     return 0;
@@ -68,9 +68,9 @@ static int refresh_greedy_lm(nasr_engine *e, bool restart) {
     if (restart) {
         std::vector<int32_t> st((size_t)e->max_streams);
         for (int i = 0; i < e->max_streams; i++) st[(size_t)i] = nasr_lm::greedy_start(g, !e->slots[i] || e->slots[i]->lm_enabled);
-        HIPCHK(hipMemcpy(e->lm_state, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->dec.lm_state, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->boost_state : nullptr,
+    launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->dec.boost_state : nullptr,
                    0, e->max_streams, e->st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->st));
@@ -117,9 +117,9 @@ extern "C" int nasr_stream_set_lm(nasr_stream *s, int enable) {
     nasr_lm::Greedy g = {};
     g.lm = e->lm_view; g.attached = e->lm ? 1 : 0;
     const int32_t state = nasr_lm::greedy_start(g, enable != 0);      // either way an empty history
-    HIPCHK(hipMemcpy(e->lm_state + s->slot, &state, sizeof(state), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->dec.lm_state + s->slot, &state, sizeof(state), hipMemcpyHostToDevice));
     s->lm_enabled = enable != 0;
-    launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->boost_state : nullptr,
+    launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->dec.boost_state : nullptr,
                    s->slot, 1, e->st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->st));
@@ -154,13 +154,51 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
     const int state = enable ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF;      // either way an empty history
-    HIPCHK(hipMemcpy(e->boost_state + s->slot, &state, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->dec.boost_state + s->slot, &state, sizeof(int), hipMemcpyHostToDevice));
     s->boost_enabled = enable != 0;
     if (e->opt_lm_fusion) {                                    // the slot's bias row carries the phrase bonus
-        launch_lm_rows(e->lm_blk, e->lm_state, e->lm_row, e->lm_next, e->boost_bonus, e->boost_state, s->slot, 1, e->st);
+        launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->boost_bonus, e->dec.boost_state, s->slot, 1, e->st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(e->st));
     }
+    return 0;
+}
+
+// The decode options.  Each picks the decode launches that get captured into the step graphs and adds what they read to e->dec (or, engine-wide: the
+// automaton tables, the LM block) at addresses that never change, so that the setters behind them only ever rewrite content and captured graphs stay
+// valid.  A later change would be a silent no-op for the graphs that exist (and the tokens already in the ring would have no value): they are taken
+// until the first decode has been enqueued or the first offline call has run.  "lm_refresh_fold" (0 = the bias rows are refreshed by a launch of
+// their own) and "lm_commit_lookup" (1 = k_dec_commit looks the emitted token up again) are measurement only (profiles/greedy_lm.md)
+static const char *const DECODE_OPTIONS[] = {"token_logprobs", "phrase_boost", "lm_fusion", "lm_refresh_fold", "lm_commit_lookup", "token_alternatives", "frame_blank_logprobs"};
+static bool is_decode_option(const char *key) { return std::any_of(std::begin(DECODE_OPTIONS), std::end(DECODE_OPTIONS), [key](const char *k) { return !strcmp(key, k); }); }
+static int set_decode_option(nasr_engine *e, const char *key, int value) {      // key is one of DECODE_OPTIONS; the caller holds an ApiGuard
+    const auto is = [key](const char *k) { return !strcmp(key, k); };
+    if ((is("token_logprobs") || is("lm_fusion") || is("frame_blank_logprobs")) && value != 0 && value != 1) return fail("%s must be 0 or 1", key);
+    if (is("phrase_boost") && value != 0 && (value < nasr_boost::MIN_STATES || value > nasr_boost::MAX_STATES))
+        return fail("phrase_boost must be 0 or the automaton's state capacity, %d .. %d", nasr_boost::MIN_STATES, nasr_boost::MAX_STATES);
+    if (is("token_alternatives") && !nasr_topk::valid_k(value)) return fail("token_alternatives must be 0 .. %d", nasr_topk::KMAX);
+    if (e->dec_started || e->off) return fail("%s must be set before the first step or offline call (the decode kernels are already chosen)", key);
+    if (is("phrase_boost") && value && e->boost_bonus && value != e->boost_cap) return fail("phrase_boost: the capacity is already %d states", e->boost_cap);
+    HIPCHK(hipSetDevice(e->device));
+    // the option's field, and what the options now in force need of e->dec; a failure leaves the field as it was
+    const auto take = [e](auto &opt, auto v) { const auto before = opt; opt = v; if (ensure_decode_set(e)) { opt = before; return -1; } return 0; };
+    if (is("token_logprobs")) return take(e->opt_token_logprobs, value != 0);
+    if (is("token_alternatives")) return take(e->opt_token_alt, value);
+    if (is("frame_blank_logprobs")) return take(e->opt_frame_blank, value != 0);
+    if (is("lm_refresh_fold")) return take(e->opt_lm_fold, value != 0 ? 1 : 0);
+    if (is("lm_commit_lookup")) return take(e->opt_lm_relook, value != 0 ? 1 : 0);
+    if (is("phrase_boost")) {
+        const int before = e->opt_phrase_boost;
+        if (take(e->opt_phrase_boost, value)) return -1;
+        if (value && !e->boost_bonus) {                        // the automaton tables at a fixed capacity, holding the empty set: the disabled state and the root
+            if (dalloc(e, &e->boost_bonus, nasr_boost::table_elems(value)) || dalloc(e, &e->boost_next, nasr_boost::table_elems(value))) { e->opt_phrase_boost = before; return -1; }
+            e->boost_cap = value;
+            if (upload_boost_set(e, 0, nullptr, nullptr, nullptr)) { e->opt_phrase_boost = 0; return -1; }
+        }
+        return e->opt_lm_fusion ? refresh_greedy_lm(e, false) : 0;      // "lm_fusion" set before this option: the rows gain (or lose) the phrase bonus
+    }
+    if (take(e->opt_lm_fusion, value != 0)) return -1;      // "lm_fusion": the block (the model's view + the greedy weights) and the rows of every slot
+    if (value && ((!e->lm_blk && dalloc(e, &e->lm_blk, 1)) || refresh_greedy_lm(e, true))) { e->opt_lm_fusion = false; return -1; }
     return 0;
 }
 
@@ -199,97 +237,7 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         if (e->pipe_ready) return fail("decode_lane must be set before the first pipelined step (the lanes are already picked)");
         e->opt_decode_lane = value != 0;
     }
-    else if (!strcmp(key, "token_logprobs")) {
-        // selects the decode kernels that get captured into the step graphs and allocates their buffers: like "decode_lane", a later change would
-        // be a silent no-op for the graphs that exist (and the tokens already in the ring would have no value)
-        if (value != 0 && value != 1) return fail("token_logprobs must be 0 or 1");
-        if (e->dec_started || e->off) return fail("token_logprobs must be set before the first step or offline call (the decode kernels are already chosen)");
-        if (value && !e->lp_part) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP)) return -1;
-        }
-        e->opt_token_logprobs = value != 0;
-    }
-    else if (!strcmp(key, "phrase_boost")) {
-        // like "token_logprobs": picks the decode kernels that get captured and allocates the automaton tables at a fixed capacity, so that
-        // nasr_engine_set_boost_phrases only ever rewrites their content and captured graphs stay valid
-        if (value != 0 && (value < nasr_boost::MIN_STATES || value > nasr_boost::MAX_STATES))
-            return fail("phrase_boost must be 0 or the automaton's state capacity, %d .. %d", nasr_boost::MIN_STATES, nasr_boost::MAX_STATES);
-        if (e->dec_started || e->off) return fail("phrase_boost must be set before the first step or offline call (the decode kernels are already chosen)");
-        if (value && e->boost_bonus && value != e->boost_cap) return fail("phrase_boost: the capacity is already %d states", e->boost_cap);
-        if (value && !e->boost_bonus) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (dalloc(e, &e->boost_bonus, nasr_boost::table_elems(value)) || dalloc(e, &e->boost_next, nasr_boost::table_elems(value)) ||
-                dalloc(e, &e->boost_state, (size_t)e->max_streams) || (!e->boost_raw && dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows)))) return -1;
-            e->boost_cap = value;
-            e->opt_phrase_boost = value;
-            if (upload_boost_set(e, 0, nullptr, nullptr, nullptr)) { e->opt_phrase_boost = 0; return -1; }      // the empty set: the disabled state and the root
-        }
-        e->opt_phrase_boost = value;
-        if (e->opt_lm_fusion) {                                // "lm_fusion" set before this option: the rows gain (or lose) the phrase bonus
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (refresh_greedy_lm(e, false)) return -1;
-        }
-    }
-    else if (!strcmp(key, "lm_fusion")) {
-        // like "phrase_boost": picks the decode launches that get captured and allocates what they read at fixed addresses, so that
-        // nasr_engine_set_lm and nasr_engine_set_greedy_lm_weights only ever rewrite content and captured graphs stay valid
-        if (value != 0 && value != 1) return fail("lm_fusion must be 0 or 1");
-        if (e->dec_started || e->off) return fail("lm_fusion must be set before the first step or offline call (the decode kernels are already chosen)");
-        if (value && !e->lm_blk) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (dalloc(e, &e->lm_blk, 1) || dalloc(e, &e->lm_state, (size_t)e->max_streams) || dalloc(e, &e->lm_row, (size_t)e->max_streams * nasr_lm::ROW_COLS) ||
-                dalloc(e, &e->lm_next, (size_t)e->max_streams * nasr_lm::ROW_COLS)) return -1;
-            if (!e->boost_raw && dalloc(e, &e->boost_raw, nasr_lp::scratch_parts(e->w_rows))) return -1;
-        }
-        e->opt_lm_fusion = value != 0;
-        if (value) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (refresh_greedy_lm(e, true)) { e->opt_lm_fusion = false; return -1; }
-        }
-    }
-    else if (!strcmp(key, "lm_refresh_fold")) {                // measurement only (profiles/greedy_lm.md): 0 = the bias rows are refreshed by a launch of their own; before the first step
-        if (e->dec_started || e->off) return fail("lm_refresh_fold must be set before the first step or offline call (the decode kernels are already chosen)");
-        e->opt_lm_fold = value != 0;
-    }
-    else if (!strcmp(key, "lm_commit_lookup")) {               // measurement only (profiles/greedy_lm.md): 1 = k_dec_commit looks the emitted token up again; before the first step
-        if (e->dec_started || e->off) return fail("lm_commit_lookup must be set before the first step or offline call (the decode kernels are already chosen)");
-        e->opt_lm_relook = value != 0;
-    }
-    else if (!strcmp(key, "token_alternatives")) {
-        // like "token_logprobs": picks the decode kernels that get captured and allocates the scratch and the rings at K entries per token.  Its
-        // kernels always leave the softmax parts, so the buffers of "token_logprobs" come with it (that option's getters stay its own)
-        if (!nasr_topk::valid_k(value)) return fail("token_alternatives must be 0 .. %d", nasr_topk::KMAX);
-        if (e->dec_started || e->off) return fail("token_alternatives must be set before the first step or offline call (the decode kernels are already chosen)");
-        if (value && e->alt_key && value != e->alt_cap) return fail("token_alternatives: the rings already hold %d entries per token", e->alt_cap);
-        if (value && !e->alt_key) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (!e->lp_part && (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP))) return -1;
-            if (dalloc(e, &e->alt_key, nasr_topk::scratch_keys(e->w_rows, value)) || dalloc(e, &e->alt_id, (size_t)e->max_streams * TOK_CAP * value) ||
-                dalloc(e, &e->alt_lp, (size_t)e->max_streams * TOK_CAP * value)) return -1;
-            e->alt_cap = value;
-        }
-        e->opt_token_alt = value;
-    }
-    else if (!strcmp(key, "frame_blank_logprobs")) {
-        // like "token_alternatives": picks the decode launches that get captured (the LP kernels and the commit variant that fills
-        // the ring) and allocates the scratch and a ring per stream; the softmax parts' buffers come with it
-        if (value != 0 && value != 1) return fail("frame_blank_logprobs must be 0 or 1");
-        if (e->dec_started || e->off) return fail("frame_blank_logprobs must be set before the first step or offline call (the decode kernels are already chosen)");
-        if (value && !e->frame_blank) {
-            ApiGuard api_guard;
-            HIPCHK(hipSetDevice(e->device));
-            if (!e->lp_part && (dalloc(e, &e->lp_part, nasr_lp::scratch_parts(e->w_rows)) || dalloc(e, &e->tok_logprob, (size_t)e->max_streams * TOK_CAP))) return -1;
-            if (dalloc(e, &e->fb_row, (size_t)e->w_rows) || dalloc(e, &e->frame_blank, (size_t)e->max_streams * FRAME_CAP)) return -1;
-        }
-        e->opt_frame_blank = value != 0;
-    }
+    else if (is_decode_option(key)) { ApiGuard api_guard; if (set_decode_option(e, key, value)) return -1; }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
     else if (!strcmp(key, "wide_min_rows")) e->opt_wide_min_rows = value;
@@ -890,12 +838,12 @@ extern "C" int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first,
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
     if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
     if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
     if (count <= 0) return 0;
     std::vector<int> ring(TOK_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->tok_frame + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ring.data(), e->dec.tok_frame + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(int), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) frames_out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
     return count;
 }
@@ -910,12 +858,12 @@ extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t firs
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
     if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
     if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
     if (count <= 0) return 0;
     std::vector<float> ring(TOK_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ring.data(), e->dec.tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
     return count;
 }
@@ -930,14 +878,14 @@ extern "C" int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
     const int64_t n_frames = (int64_t)c.frame0 + c.t;          // frames the decode has left since create / reset
     if (!out) return (int)n_frames;
     if (first + count > n_frames) count = first < n_frames ? (int32_t)(n_frames - first) : 0;
     if (n_frames - first > FRAME_CAP) return 0;               // the range starts before the most recent FRAME_CAP frames: nothing of it can be written from its first frame on
     if (count <= 0) return 0;
     std::vector<float> ring(FRAME_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->frame_blank + (size_t)s->slot * FRAME_CAP, FRAME_CAP * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ring.data(), e->dec.frame_blank + (size_t)s->slot * FRAME_CAP, FRAME_CAP * sizeof(float), hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (FRAME_CAP - 1))];
     return count;
 }
@@ -953,14 +901,14 @@ extern "C" int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t 
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
     if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
     if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
     if (count <= 0) return 0;
     std::vector<int32_t> ids((size_t)TOK_CAP * K);
     std::vector<float> lps((size_t)TOK_CAP * K);
-    HIPCHK(hipMemcpy(ids.data(), e->alt_id + (size_t)s->slot * TOK_CAP * K, ids.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lps.data(), e->alt_lp + (size_t)s->slot * TOK_CAP * K, lps.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ids.data(), e->dec.alt_id + (size_t)s->slot * TOK_CAP * K, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lps.data(), e->dec.alt_lp + (size_t)s->slot * TOK_CAP * K, lps.size() * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < count; i++) {
         const size_t at = (size_t)((first + i) & (TOK_CAP - 1)) * K;
         memcpy(ids_out + (size_t)i * K, ids.data() + at, (size_t)K * 4);
@@ -1022,7 +970,7 @@ extern "C" int nasr_stream_get_stats(const nasr_stream *s, nasr_stream_stats *ou
     if (pipe_drain(e)) return -1;
     DecCtrl c;
     HIPCHK(hipStreamSynchronize(e->st));
-    HIPCHK(hipMemcpy(&c, e->ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
     memset(out, 0, sizeof(*out));
     out->samples_in = s->samples_in;
     out->chunks = s->chunks;
@@ -1110,9 +1058,9 @@ extern "C" int64_t nasr_stream_get_tap(nasr_stream *s, int which, int index, flo
     case NASR_TAP_DEC_STATE: {
         if (cap < 4 * HID + 1) return fail("tap buffer too small");
         DecCtrl c;
-        HIPCHK(hipMemcpy(&c, e->ctrl + slot, sizeof(c), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out, e->dec_h + (slot * 2 + c.cur) * 2 * HID, 2 * HID * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out + 2 * HID, e->dec_c + (slot * 2 + c.cur) * 2 * HID, 2 * HID * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&c, e->dec.ctrl + slot, sizeof(c), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, e->dec.h + (slot * 2 + c.cur) * 2 * HID, 2 * HID * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out + 2 * HID, e->dec.c + (slot * 2 + c.cur) * 2 * HID, 2 * HID * 4, hipMemcpyDeviceToHost));
         out[4 * HID] = (float)c.prev_token;
         return 4 * HID + 1;
     }

@@ -322,7 +322,7 @@ int enqueue_layers(nasr_engine *e, const LayerRun &r, int l0, int l1) {
             gp.chain.head_rows = 4;
             gp.chain.head_wgs = (((M + 3) / 4) + 7) & ~7;          // a multiple of 8: the tiles behind keep their XCDs
             gp.chain.flags = e->chain_flags;
-            gp.chain.error = (unsigned *)(e->n_active + 3);
+            gp.chain.error = (unsigned *)(e->dec.n_active + 3);
             has_pend = false;
         } else flush_post();
         run_gemm(e, gp, false, tag);
@@ -449,19 +449,20 @@ void bind_dec_weights(const nasr_engine *e, DecParams &dp) {
     dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
 }
 
-void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp) {
-    memset(&dp, 0, sizeof(dp));
-    dp.rows = rows; dp.B = B; dp.T = T; dp.ctrl = e->ctrl; dp.h = e->dec_h; dp.c = e->dec_c; dp.encproj = e->encproj;
+DecFeatures dec_features(const nasr_engine *e) {
+    DecFeatures f;
+    f.token_logprobs = e->opt_token_logprobs; f.alt_k = e->opt_token_alt; f.frame_blank = e->opt_frame_blank;
+    f.phrase_boost = e->opt_phrase_boost != 0; f.lm_fusion = e->opt_lm_fusion; f.lm_fold = e->opt_lm_fold; f.lm_relook = e->opt_lm_relook;
+    return f;
+}
+void bind_decode(const nasr_engine *e, const DecodeSet &set, const DecFeatures &f, DecParams &dp) {
+    dec_set_bind(set, f, DecTables{e->boost_bonus, e->boost_next, e->lm_blk}, dp);
     bind_dec_weights(e, dp);
-    dp.predg = e->predg; dp.key = e->key; dp.n_active = e->n_active; dp.n_dirty = e->n_active + 1; dp.n_rows = e->n_active + 2;
-    dp.dlist = e->dlist; dp.rowmap = e->rowmap; dp.tok_ring = e->tok_ring; dp.tok_frame = e->tok_frame;
-    if (e->opt_token_logprobs || e->opt_token_alt || e->opt_frame_blank) { dp.lp_part = e->lp_part; dp.tok_logprob = e->tok_logprob; }
-    if (e->opt_frame_blank) { dp.fb_row = e->fb_row; dp.frame_blank = e->frame_blank; }
-    if (e->opt_token_alt) { dp.alt_key = e->alt_key; dp.alt_id = e->alt_id; dp.alt_lp = e->alt_lp; dp.alt_k = e->opt_token_alt; }
-    if (e->opt_phrase_boost) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = e->boost_state; dp.boost_raw = e->boost_raw; }
-    if (e->opt_lm_fusion) {                    // the fused forms read the winner's raw logit like the boosted ones
-        dp.lm_blk = e->lm_blk; dp.lm_state = e->lm_state; dp.lm_row = e->lm_row; dp.lm_next = e->lm_next; dp.lm_fold = e->opt_lm_fold; dp.lm_relook = e->opt_lm_relook; dp.boost_raw = e->boost_raw;
-    }
+}
+
+void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp) {
+    bind_decode(e, e->dec, dec_features(e), dp);
+    dp.rows = rows; dp.B = B; dp.T = T; dp.encproj = e->encproj;
     e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost", "token_alternatives", "frame_blank_logprobs" and "lm_fusion" are no longer taken
 }
 
@@ -576,7 +577,7 @@ int consume_collect(nasr_engine *e, const int *host, nasr_stream *const *streams
             q.insert(q.end(), rec + 1, rec + 1 + n_new);
         } else {   // rare long push: fetch straight from the ring
             std::vector<int> ring(TOK_CAP);
-            HIPCHK(hipMemcpy(ring.data(), e->tok_ring + (size_t)streams[b]->slot * TOK_CAP, TOK_CAP * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ring.data(), e->dec.tok_ring + (size_t)streams[b]->slot * TOK_CAP, TOK_CAP * 4, hipMemcpyDeviceToHost));
             for (int i = 0; i < n_new; i++) q.push_back(ring[(streams[b]->tok_read + i) & (TOK_CAP - 1)]);
         }
         streams[b]->tok_read += n_new;
@@ -610,7 +611,7 @@ int collect_tokens(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *
     for (int b = 0; b < B; b++) { meta[b] = streams[b]->slot; meta[B + b] = streams[b]->tok_read; }
     const int *dmeta;
     if (stage_desc(e, meta, &dmeta)) return -1;
-    hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, e->st, dmeta, dmeta + B, B, e->ctrl, e->tok_ring, e->collect_dev, COLLECT_STRIDE, (const int *)nullptr);
+    hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, e->st, dmeta, dmeta + B, B, e->dec.ctrl, e->dec.tok_ring, e->collect_dev, COLLECT_STRIDE, (const int *)nullptr);
     std::vector<int> host((size_t)B * (1 + COLLECT_STRIDE));
     HIPCHK(hipMemcpyAsync(host.data(), e->collect_dev, host.size() * 4, hipMemcpyDeviceToHost, e->st));
     HIPCHK(hipStreamSynchronize(e->st));

@@ -452,6 +452,11 @@ void use_ws(nasr_engine *e, const nasr_engine::WS &w) {
     e->a = w.a; e->hbuf = w.hbuf; e->ctx = w.ctx; e->cbuf = w.cbuf; e->sub_b = w.sub_b; e->chain_flags = w.chain_flags;
 }
 
+// what the decode options in force need of e->dec and is not there yet (nasr_decode_set.h), recorded in e->allocs like every dalloc
+int ensure_decode_set(nasr_engine *e) {
+    return dec_set_ensure(e->dec, dec_features(e), e->max_streams, e->w_rows, [e](const char *, void **p, size_t bytes) { return dalloc(e, (char **)p, bytes); }, fail);
+}
+
 // ---------------------------------------------------------------------------------------
 }  // namespace nasr_eng
 extern "C" int nasr_engine_create(nasr_engine **out, int device_id, int dtype, const nasr_hparams *hp,
@@ -513,21 +518,12 @@ extern "C" int nasr_engine_create_ex(nasr_engine **out, int device_id, int dtype
         rc |= dalloc(e, &e->kv_ptrs_dev, Lr);
         if (!rc && hipMemcpy(e->kv_ptrs_dev, e->kv_pool.data(), Lr * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess) rc = fail("hipMemcpy (K/V ring table) failed");
     }
-    rc |= dalloc(e, &e->dec_h, S * 4 * HID);
-    rc |= dalloc(e, &e->dec_c, S * 4 * HID);
-    rc |= dalloc(e, &e->ctrl, S);
-    rc |= dalloc(e, &e->tok_ring, S * TOK_CAP);
     memset(e->ws, 0, sizeof(e->ws));
     rc |= alloc_ws(e, e->ws[0]);
     use_ws(e, e->ws[0]);
     rc |= dalloc(e, &e->encproj, M * JNT);
-    rc |= dalloc(e, &e->predg, S * JNT);
-    rc |= dalloc(e, &e->key, M);
-    rc |= dalloc(e, &e->n_active, 4);
-    if (!rc) hipMemsetAsync(e->n_active, 0, 4 * sizeof(int), e->st);      // [3] = ChainParams::error
-    rc |= dalloc(e, &e->dlist, S);
-    rc |= dalloc(e, &e->rowmap, M);
-    rc |= dalloc(e, &e->tok_frame, S * TOK_CAP);
+    rc |= ensure_decode_set(e);                       // the base part: no decode option is on yet
+    if (!rc) hipMemsetAsync(e->dec.n_active, 0, 4 * sizeof(int), e->st);      // [3] = ChainParams::error
     rc |= dalloc(e, &e->collect_dev, S * (1 + COLLECT_STRIDE) + 4);
     if (rc) { engine_destroy_impl(e); return -1; }
     e->pin_cap = 8u << 20;
@@ -692,9 +688,9 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     rp.kv_pools = e->kv_ptrs_dev; rp.esz = (int)e->esz; rp.kv_head = keep_reference_state ? s->kv_head : 0;
     rp.cc_slot_floats = 2 * (e->hp.kernel_size - 1) * D;
     rp.keep_reference_state = keep_reference_state ? 1 : 0;
-    rp.abuf = e->abuf; rp.last_sample = e->last_sample; rp.mel_ring = e->mel_ring; rp.dec_h = e->dec_h; rp.dec_c = e->dec_c; rp.ctrl = e->ctrl;
-    if (e->opt_phrase_boost) { rp.boost_state = e->boost_state; rp.boost_init = s->boost_enabled ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF; }
-    if (e->opt_lm_fusion) { rp.lm_state = e->lm_state; rp.lm_blk = e->lm_blk; rp.lm_enabled = s->lm_enabled ? 1 : 0; }
+    rp.abuf = e->abuf; rp.last_sample = e->last_sample; rp.mel_ring = e->mel_ring; rp.dec_h = e->dec.h; rp.dec_c = e->dec.c; rp.ctrl = e->dec.ctrl;
+    if (e->opt_phrase_boost) { rp.boost_state = e->dec.boost_state; rp.boost_init = s->boost_enabled ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF; }
+    if (e->opt_lm_fusion) { rp.lm_state = e->dec.lm_state; rp.lm_blk = e->lm_blk; rp.lm_enabled = s->lm_enabled ? 1 : 0; }
     rp.aud_hist = e->aud_hist;
     launch_stream_reset(rp, e->st);
     HIPCHK(hipGetLastError());

@@ -8,6 +8,7 @@
 // step_mel_params, lru_victim; the staging helpers grow_device and PinBlock.
 #pragma once
 #include "nasr_internal.h"
+#include "nasr_decode_set.h"
 #include "nasr_step_plan.h"
 #include "nemotron_asr_amd.h"
 
@@ -147,9 +148,7 @@ struct nasr_engine {
     std::vector<float *> cc_pool;    // per layer [slot][2][ks-1][1024]
     float **cc_ptrs_dev = nullptr;   // device copy of cc_pool (k_stream_reset walks the layers in one launch)
     void **kv_ptrs_dev = nullptr;    // device copy of kv_pool (same launch: the 70 window rows of a starting stream are zeroed)
-    float *dec_h, *dec_c;
-    DecCtrl *ctrl;
-    int *tok_ring;
+    DecodeSet dec;                   // the greedy decode's working set (nasr_decode_set.h), max_streams slots x w_rows rows: engine_create and the decode options fill it (ensure_decode_set)
     // workspace (sized for max_streams x TMAX rows)
     float *x, *x2, *part, *q, *glu, *encproj, *sub_a, *hfuse;
     bool opt_fused = true, opt_graph = true;
@@ -240,21 +239,13 @@ struct nasr_engine {
     int64_t pipe_steps = 0;
     void *a, *hbuf, *ctx, *cbuf, *sub_b;             // (with x, x2, part, q, glu, sub_a, hfuse: the CURRENT workspace set, see use_ws)
     unsigned *chain_flags = nullptr;                 // ... and its row-chunk counters of chained launches (a set's launches never overlap: one array per set)
-    float *predg;                    // [slot][640] cached joint.pred output of the LSTM candidate
-    unsigned long long *key;
-    int *n_active;                   // [3] = n_active, n_dirty, n_rows
-    int *dlist; unsigned *rowmap; int *tok_frame;
     // option "token_logprobs": per-token log-probabilities from the decode kernels.  It picks the kernels that get captured into step graphs and
-    // allocates the two buffers, so it is taken only until the first decode has been enqueued (dec_started) or the first offline call has run
+    // adds two buffers to `dec`, so it is taken only until the first decode has been enqueued (dec_started) or the first offline call has run
     bool opt_token_logprobs = false, dec_started = false;
-    nasr_lp::Part *lp_part = nullptr;      // [max(64 x 65, w_rows x 17)] softmax parts of the rows of a decode iteration (nasr_logprob.h)
-    float *tok_logprob = nullptr;    // [slot][TOK_CAP] beside tok_ring / tok_frame
     // option "phrase_boost" = the capacity of the automaton tables in states (0: off), nasr_boost.h.  Like "token_logprobs" it picks the kernels that
     // get captured and allocates fixed-capacity tables whose pointers never change: replacing the set rewrites their content only
     int opt_phrase_boost = 0, boost_cap = 0, boost_states = 0;      // capacity (0: off), capacity allocated; states of the current set (2 = the disabled state and the root: no phrase)
     float *boost_bonus = nullptr; int32_t *boost_next = nullptr;   // [capacity][1040] each
-    int *boost_state = nullptr;      // [slot] automaton state of every stream's emitted history
-    float *boost_raw = nullptr;      // scratch beside lp_part: raw logit of every part's winner (read only when both options are on)
     nasr_boost::Automaton boost_host;   // the current set's tables on the host: a boosted beam call reads its hypotheses' per-token bonuses from them
     // nasr_engine_set_lm (nasr_lm.h): the compiled n-gram model on the host (the read-out of per-token values) and, in one device block, the
     // tables the beam kernels read.  Only beam calls see it
@@ -266,21 +257,15 @@ struct nasr_engine {
     // slot the bias row (phrase bonus + lmbias) with the next-state row beside it
     int opt_lm_relook = 0;           // measurement switch "lm_commit_lookup" (1: the commit runs a second lookup instead of reading the next-state row)
     bool opt_lm_fusion = false; int opt_lm_fold = 1;      // lm_fold: measurement switch "lm_refresh_fold" (1: the refresh rides in k_dec_pred, 0: a launch of its own)
-    nasr_lm::Greedy *lm_blk = nullptr; int32_t *lm_state = nullptr; float *lm_row = nullptr; int32_t *lm_next = nullptr;
+    nasr_lm::Greedy *lm_blk = nullptr;
     float glm_weight = 0.0f, glm_bonus = 0.0f;            // nasr_engine_set_greedy_lm_weights
     long long lm_generation = 0;     // counts nasr_engine_set_lm calls that changed the model: a beam call's LM read-out is tied to the model it ran with
     // option "token_alternatives" = K (0: off, 1 .. 8), nasr_topk.h: the K largest joint outputs with their log-probabilities where every token was
-    // emitted.  Taken like "token_logprobs"; its kernels also leave the softmax parts, so lp_part / tok_logprob are allocated with it
-    int opt_token_alt = 0, alt_cap = 0;                            // K in use, K the buffers were allocated for
-    unsigned long long *alt_key = nullptr;                         // scratch beside lp_part: [row][slice][K] largest keys of every vocab slice
-    int32_t *alt_id = nullptr; float *alt_lp = nullptr;            // [slot][TOK_CAP][K] each, beside tok_ring / tok_frame / tok_logprob
+    // emitted.  Taken like "token_logprobs"; its kernels also leave the softmax parts, so lp_part / tok_logprob come with it
+    int opt_token_alt = 0;                                         // K in use (dec.alt_k: K the buffers were allocated for)
     // option "frame_blank_logprobs": ln P(blank) at the last joint evaluation of every frame the decode has left.  Taken like "token_alternatives"
-    // (LP kernels, so lp_part / tok_logprob are allocated with it).  The ring is indexed by the absolute frame number since create / reset and is
-    // never cleared: nasr_stream_get_frame_blank_logprobs clips to the frames decoded since then (DecCtrl::frame0 + t, which k_stream_reset
-    // zeroes), so what an earlier stream or an earlier life of this one left in a slot's ring is never visible
+    // (LP kernels, so lp_part / tok_logprob come with it; the ring's life: DecodeSet::frame_blank)
     bool opt_frame_blank = false;
-    float *fb_row = nullptr;         // scratch beside key: [w_rows] ln P(blank) of the rows of a decode iteration
-    float *frame_blank = nullptr;    // [slot][FRAME_CAP]
     int *collect_dev;                // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;
@@ -398,6 +383,9 @@ int enqueue_encoder_tail(nasr_engine *e, float *x, float *hfuse, float *encproj,
 int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, const int *tap_slots, int B, int T, int R, int G = 1, int seg = 0,
                            int nseg = 1, int part = 0);
 void bind_dec_weights(const nasr_engine *e, DecParams &dp);     // the decoder's weights (prediction net, joint) into dp
+DecFeatures dec_features(const nasr_engine *e);                 // the decode options in force (the opt_* fields)
+void bind_decode(const nasr_engine *e, const DecodeSet &set, const DecFeatures &f, DecParams &dp);     // dec_set_bind with the engine's tables + bind_dec_weights; rows, B, T, encproj: the caller's
+int ensure_decode_set(nasr_engine *e);                          // dec_set_ensure of e->dec for dec_features(e), through dalloc
 void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp);
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st = nullptr);
 // Rounds of decode iterations on st until no stream is active: `round` iterations, dp.n_active read into *landing, the round doubled (32 at

@@ -76,47 +76,15 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
         if (off_alloc(o, (void **)&o->zero_bias, 3 * D * 4)) return -1;
         HIPCHK(hipMemset(o->zero_bias, 0, 3 * D * 4));
     }
-    if (!o->ctrl) {
+    if (!o->dec.ctrl) {
         const size_t U = nasr_plan::OFFLINE_MAX_UTTS, W = OFF_DEC_WIN;
-        rc |= off_alloc(o, (void **)&o->ctrl, U * sizeof(DecCtrl));
-        rc |= off_alloc(o, (void **)&o->h, U * 4 * HID * 4);
-        rc |= off_alloc(o, (void **)&o->c, U * 4 * HID * 4);
-        rc |= off_alloc(o, (void **)&o->predg, U * JNT * 4);
+        rc |= dec_set_ensure(o->dec, dec_features(e), (int)U, (int)(U * W), [o](const char *, void **p, size_t bytes) { return off_alloc(o, p, bytes); }, fail);
         rc |= off_alloc(o, (void **)&o->win, U * W * JNT * 4);
-        rc |= off_alloc(o, (void **)&o->key, U * W * 8);
-        rc |= off_alloc(o, (void **)&o->n_active, 16);
-        rc |= off_alloc(o, (void **)&o->dlist, U * 4);
-        rc |= off_alloc(o, (void **)&o->rowmap, U * W * 4);
-        rc |= off_alloc(o, (void **)&o->tok_ring, U * TOK_CAP * 4);
-        rc |= off_alloc(o, (void **)&o->tok_frame, U * TOK_CAP * 4);
-        if (e->opt_token_alt) {
-            rc |= off_alloc(o, (void **)&o->alt_key, nasr_topk::scratch_keys((int)(U * W), e->opt_token_alt) * sizeof(unsigned long long));
-            rc |= off_alloc(o, (void **)&o->alt_id, U * TOK_CAP * e->opt_token_alt * 4);
-            rc |= off_alloc(o, (void **)&o->alt_lp, U * TOK_CAP * e->opt_token_alt * 4);
-        }
-        if (e->opt_frame_blank) {
-            rc |= off_alloc(o, (void **)&o->fb_row, U * W * 4);
-            rc |= off_alloc(o, (void **)&o->frame_blank, U * FRAME_CAP * 4);
-        }
-        if (e->opt_token_logprobs || e->opt_token_alt || e->opt_frame_blank) {
-            rc |= off_alloc(o, (void **)&o->lp_part, nasr_lp::scratch_parts((int)(U * W)) * sizeof(nasr_lp::Part));
-            rc |= off_alloc(o, (void **)&o->tok_logprob, U * TOK_CAP * 4);
-        }
-        if (e->opt_phrase_boost) {
-            rc |= off_alloc(o, (void **)&o->boost_state, U * 4);
-            rc |= off_alloc(o, (void **)&o->boost_raw, nasr_lp::scratch_parts((int)(U * W)) * 4);
-        }
-        if (e->opt_lm_fusion) {
-            rc |= off_alloc(o, (void **)&o->lm_state, U * 4);
-            rc |= off_alloc(o, (void **)&o->lm_row, U * nasr_lm::ROW_COLS * 4);
-            rc |= off_alloc(o, (void **)&o->lm_next, U * nasr_lm::ROW_COLS * 4);
-            if (!o->boost_raw) rc |= off_alloc(o, (void **)&o->boost_raw, nasr_lp::scratch_parts((int)(U * W)) * 4);
-        }
         rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
         rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
         rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
         if (rc) return -1;
-        HIPCHK(hipMemset(o->n_active, 0, 16));
+        HIPCHK(hipMemset(o->dec.n_active, 0, 16));
     }
     return 0;
 }
@@ -273,13 +241,13 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
     const std::vector<int> &off = ob.off, &T = ob.T;
     const int first = ob.first, n = ob.n, maxT = ob.maxT;
     // ---- greedy decode in windows of 256 frames per utterance (token ring: 4096 > 256 x 10 symbols) -----------------
-    launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
-    if (o->boost_state)                                          // every utterance starts with an empty history (NASR_FLAG_NO_BOOST: in the disabled state)
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->boost_state, o->no_boost ? nasr_boost::STATE_OFF : nasr_boost::STATE_ROOT, (size_t)n, st));
-    if (o->lm_state) {                                           // ... and at the model's start (NASR_FLAG_NO_LM: switched off); the reset left every slot dirty, so the
+    launch_off_dec_reset(n, o->dec.h, o->dec.c, o->dec.ctrl, st);
+    if (o->dec.boost_state)                                          // every utterance starts with an empty history (NASR_FLAG_NO_BOOST: in the disabled state)
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->dec.boost_state, o->no_boost ? nasr_boost::STATE_OFF : nasr_boost::STATE_ROOT, (size_t)n, st));
+    if (o->dec.lm_state) {                                           // ... and at the model's start (NASR_FLAG_NO_LM: switched off); the reset left every slot dirty, so the
         nasr_lm::Greedy g = {};                                  // first iteration refreshes its bias row
         g.lm = e->lm_view; g.attached = e->lm ? 1 : 0;
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->lm_state, nasr_lm::greedy_start(g, !o->no_lm), (size_t)n, st));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)o->dec.lm_state, nasr_lm::greedy_start(g, !o->no_lm), (size_t)n, st));
     }
     std::vector<int> tok_read(n, 0);
     std::vector<DecCtrl> hctrl(n);
@@ -304,30 +272,20 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
         HIPCHK(hipMemcpyAsync(o->dwin, wd.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice, st));
         launch_off_window(o->encproj.as<float>(), o->dwin, n, OFF_DEC_WIN, o->win, st);
         DecParams dp;
-        memset(&dp, 0, sizeof(dp));
-        dp.rows = o->drows; dp.B = n; dp.T = OFF_DEC_WIN; dp.ctrl = o->ctrl; dp.h = o->h; dp.c = o->c; dp.encproj = o->win;
-        bind_dec_weights(e, dp);
-        dp.predg = o->predg; dp.key = o->key; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2;
-        dp.dlist = o->dlist; dp.rowmap = o->rowmap; dp.tok_ring = o->tok_ring; dp.tok_frame = o->tok_frame;
-        dp.lp_part = o->lp_part; dp.tok_logprob = o->tok_logprob;       // null unless "token_logprobs" or "token_alternatives"
-        if (K) { dp.alt_key = o->alt_key; dp.alt_id = o->alt_id; dp.alt_lp = o->alt_lp; dp.alt_k = K; }
-        dp.fb_row = o->fb_row; dp.frame_blank = o->frame_blank;         // null unless "frame_blank_logprobs"
-        if (o->boost_state) { dp.boost_bonus = e->boost_bonus; dp.boost_next = e->boost_next; dp.boost_state = o->boost_state; dp.boost_raw = o->boost_raw; }
-        if (o->lm_state) {
-            dp.lm_blk = e->lm_blk; dp.lm_state = o->lm_state; dp.lm_row = o->lm_row; dp.lm_next = o->lm_next; dp.lm_fold = e->opt_lm_fold; dp.lm_relook = e->opt_lm_relook; dp.boost_raw = o->boost_raw;
-        }
+        bind_decode(e, o->dec, dec_features(e), dp);
+        dp.rows = o->drows; dp.B = n; dp.T = OFF_DEC_WIN; dp.encproj = o->win;
         launch_decode_begin(dp, st);
         int h_active = 0;
         if (decode_until_idle(e, dp, n, st, &h_active, 0, decode_blind_iterations(max_dec), max_dec, nullptr, "offline decode")) return -1;
         // tokens of this window: at most 256 x 10 < TOK_CAP per slot, so the ring holds all of them
-        HIPCHK(hipMemcpyAsync(hctrl.data(), o->ctrl, (size_t)n * sizeof(DecCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ring.data(), o->tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ringf.data(), o->tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
-        if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
-        if (!ringb.empty()) HIPCHK(hipMemcpyAsync(ringb.data(), o->frame_blank, ringb.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hctrl.data(), o->dec.ctrl, (size_t)n * sizeof(DecCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ring.data(), o->dec.tok_ring, ring.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ringf.data(), o->dec.tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->dec.tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!ringb.empty()) HIPCHK(hipMemcpyAsync(ringb.data(), o->dec.frame_blank, ringb.size() * 4, hipMemcpyDeviceToHost, st));
         if (K) {
-            HIPCHK(hipMemcpyAsync(ringai.data(), o->alt_id, ringai.size() * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(ringal.data(), o->alt_lp, ringal.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ringai.data(), o->dec.alt_id, ringai.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ringal.data(), o->dec.alt_lp, ringal.size() * 4, hipMemcpyDeviceToHost, st));
         }
         HIPCHK(hipStreamSynchronize(st));
         for (int k = 0; k < n; k++) {

@@ -55,15 +55,13 @@ static int align_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob, cons
     if (!tok.empty()) HIPCHK(hipMemcpyAsync(al_tok, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(o->drows, rd.data(), (size_t)n * sizeof(RowDesc), hipMemcpyHostToDevice, st));
     // ---- g[u] of every utterance: the decode's own LSTM / joint.pred launches over the utterances that still have a position u --------
-    launch_off_dec_reset(n, o->h, o->c, o->ctrl, st);
+    launch_off_dec_reset(n, o->dec.h, o->dec.c, o->dec.ctrl, st);
     DecParams dp;
-    memset(&dp, 0, sizeof(dp));
-    dp.rows = o->drows; dp.B = n; dp.T = 1; dp.ctrl = o->ctrl; dp.h = o->h; dp.c = o->c;
-    bind_dec_weights(e, dp);
-    dp.predg = o->predg; dp.n_active = o->n_active; dp.n_dirty = o->n_active + 1; dp.n_rows = o->n_active + 2; dp.dlist = o->dlist;
+    bind_decode(e, o->dec, DecFeatures(), dp);              // the base part only: teacher forcing runs none of the options' launches
+    dp.rows = o->drows; dp.B = n; dp.T = 1;
     AlignPredParams pp;
     memset(&pp, 0, sizeof(pp));
-    pp.utt = o->al_utt; pp.n = n; pp.tok = al_tok; pp.ctrl = o->ctrl; pp.dlist = o->dlist; pp.n_dirty = dp.n_dirty; pp.predg = o->predg; pp.g = al_g;
+    pp.utt = o->al_utt; pp.n = n; pp.tok = al_tok; pp.ctrl = o->dec.ctrl; pp.dlist = o->dec.dlist; pp.n_dirty = dp.n_dirty; pp.predg = o->dec.predg; pp.g = al_g;
     {
         ProfScope ps(e, "k_align_pred", 0, 0);
         for (int u = 0; u <= max_u + 1; u++) {

@@ -24,20 +24,14 @@ struct OfflineState {
     OffBuf pmel, pcm;
     OffSubDesc *sdesc = nullptr;
     std::vector<void *> pos;                     // per layer [4095][1024] act dtype
-    // decode: one slot per utterance of a sub-batch
-    DecCtrl *ctrl = nullptr; float *h = nullptr, *c = nullptr, *predg = nullptr, *win = nullptr;
-    unsigned long long *key = nullptr; int *n_active = nullptr, *dlist = nullptr, *tok_ring = nullptr, *tok_frame = nullptr;
-    unsigned *rowmap = nullptr; RowDesc *drows = nullptr; int4 *dwin = nullptr;
-    nasr_lp::Part *lp_part = nullptr; float *tok_logprob = nullptr;      // engine option "token_logprobs" (allocated with the slots when it is on)
-    int *boost_state = nullptr; float *boost_raw = nullptr;        // engine option "phrase_boost": the offline slots' automaton states (the tables are the engine's)
-    bool no_boost = false;                                         // NASR_FLAG_NO_BOOST of the call in progress
-    int32_t *lm_state = nullptr, *lm_next = nullptr; float *lm_row = nullptr;      // engine option "lm_fusion": the offline slots' LM states and bias / next rows (the block is the engine's)
-    bool no_lm = false;                                            // NASR_FLAG_NO_LM of the call in progress
-    unsigned long long *alt_key = nullptr; int32_t *alt_id = nullptr; float *alt_lp = nullptr;      // engine option "token_alternatives"
-    std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // ... of the last call, by utterance: [tokens][K] each
-    float *fb_row = nullptr, *frame_blank = nullptr;               // engine option "frame_blank_logprobs": scratch [U * W] and a ring [U][FRAME_CAP] (T <= 2048 < FRAME_CAP)
-    std::vector<std::vector<float>> frame_blank_lps;               // ... of the last call, by utterance: [T] (nasr_engine_offline_frame_blank_logprobs)
-    std::vector<std::vector<float>> logprobs;                      // ... of the last call, by utterance (nasr_engine_offline_token_logprobs)
+    // greedy decode: one slot per utterance of a sub-batch, OFF_DEC_WIN rows per slot (nasr_decode_set.h; allocated with the row buffers for the
+    // engine's decode options, which the first offline call freezes); win = the encoder projection of the window being decoded
+    DecodeSet dec;
+    float *win = nullptr; RowDesc *drows = nullptr; int4 *dwin = nullptr;
+    bool no_boost = false, no_lm = false;                          // NASR_FLAG_NO_BOOST, NASR_FLAG_NO_LM of the call in progress
+    std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // "token_alternatives" of the last call, by utterance: [tokens][K] each
+    std::vector<std::vector<float>> frame_blank_lps;               // "frame_blank_logprobs" of the last call, by utterance: [T] (nasr_engine_offline_frame_blank_logprobs)
+    std::vector<std::vector<float>> logprobs;                      // "token_logprobs" of the last call, by utterance (nasr_engine_offline_token_logprobs)
     // forced alignment (nasr_engine_align*): the prediction-network rows g, the lattice of the sub-batch in flight (two values and one
     // back-pointer byte per cell), its descriptors and its results
     OffBuf al_g, al_lpb, al_lpt, al_tlp, al_bp, al_tiles, al_tok, al_frames;

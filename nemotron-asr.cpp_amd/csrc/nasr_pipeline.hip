@@ -57,7 +57,7 @@ int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t 
         launch_decode_begin(dp, st);
         int it = 0;
         enqueue_decode_iters(e, dp, B, decode_blind_iterations(T * G), it);
-        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, st, g_meta, g_meta + B, B, e->ctrl, e->tok_ring, e->collect_dev, COLLECT_STRIDE, e->n_active);
+        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, st, g_meta, g_meta + B, B, e->dec.ctrl, e->dec.tok_ring, e->collect_dev, COLLECT_STRIDE, e->dec.n_active);
         HIPCHK(hipMemcpyAsync(e->gh_collect, e->collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         return 0;
     }, st, "");
@@ -116,7 +116,7 @@ int capture_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipStream_t
         dp.encproj = P.encproj;
         launch_decode_begin(dp, cs);
         for (int k = 0; k < iters; k++) launch_decode_iter(dp, cs);
-        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->ctrl, e->tok_ring, P.collect_dev, COLLECT_STRIDE, e->n_active);
+        hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->dec.ctrl, e->dec.tok_ring, P.collect_dev, COLLECT_STRIDE, e->dec.n_active);
         HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));
         return 0;
     }, cs, what);
@@ -125,7 +125,7 @@ int capture_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipStream_t
 int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int iters, int round, bool fallback, bool recollect) {
     int *gh_active = d.gh_collect + (size_t)d.B * (1 + COLLECT_STRIDE);      // k_collect appends n_active to its records
     if (*gh_active < 0) {          // reported once: the flag is cleared so that the steps after this one are judged on their own (advisor, round 5: it was sticky)
-        hipMemsetAsync(e->n_active + 3, 0, sizeof(int), e->st);
+        hipMemsetAsync(e->dec.n_active + 3, 0, sizeof(int), e->st);
         return fail("a chained GEMM launch gave up waiting for its head workgroups (GemmParams::chain): results of this step are invalid");
     }
     if (*gh_active == 0 || !fallback) return 0;
@@ -136,7 +136,7 @@ int finish_step_decode(nasr_engine *e, const StepDecode &d, hipStream_t st, int 
     e->decode_fallbacks++;
     if (decode_until_idle(e, dp, d.B, st, gh_active, iters, round, d.T * d.G, &e->decode_fallback_rounds)) return -1;
     if (recollect) {
-        hipLaunchKernelGGL(k_collect, dim3(d.B), dim3(64), 0, st, d.g_dmeta, d.g_dmeta + d.B, d.B, e->ctrl, e->tok_ring, d.collect_dev, COLLECT_STRIDE, e->n_active);
+        hipLaunchKernelGGL(k_collect, dim3(d.B), dim3(64), 0, st, d.g_dmeta, d.g_dmeta + d.B, d.B, e->dec.ctrl, e->dec.tok_ring, d.collect_dev, COLLECT_STRIDE, e->dec.n_active);
         HIPCHK(hipMemcpyAsync(d.gh_collect, d.collect_dev, ((size_t)d.B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }

@@ -45,7 +45,10 @@ def test_setters_refuse_null_handles_and_word_their_errors_like_boosting():
     assert L.nasr_stream_set_lm(None, 1) < 0 and b"null stream" in L.nasr_last_error()
     abi = (PKG / "csrc" / "nasr_abi.hip").read_text()
     assert abi.count('engine option \\"lm_fusion\\" is off (set it to 1 before the first step or offline call)') == 2
-    assert 'lm_fusion must be set before the first step or offline call (the decode kernels are already chosen)' in abi
+    # the refusal of a late change exists once, for every decode option, and "lm_fusion" is one of the options routed to it
+    assert abi.count('"%s must be set before the first step or offline call (the decode kernels are already chosen)", key') == 1
+    routed = re.search(r"DECODE_OPTIONS\[\] = \{([^}]*)\};", abi).group(1)
+    assert '"lm_fusion"' in routed and "else if (is_decode_option(key)) { ApiGuard api_guard; if (set_decode_option(e, key, value)) return -1; }" in abi
     assert "NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm" in abi
     rules = (PKG / "csrc" / "nasr_lm.h").read_text()
     for name in ("struct Greedy", "NASR_LP_HD float lmbias", "NASR_LP_HD int32_t greedy_start", "STATE_DISABLED = -1", "ROW_COLS = 1040"):
