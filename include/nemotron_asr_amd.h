@@ -234,6 +234,43 @@ int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams, int B,
 int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams, int B,
                          int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens);
 
+/* ---- stream fork and tail preview (the reference has neither: a nemo_stream_context has one future) ----
+ * nasr_stream_fork: *out = a new stream in the lowest free slot whose state is src's at this moment.  One device launch copies the live
+ * part of src's slot (per layer the 70 K/V window rows and the conv cache, the buffered mel frames and samples, the decoder's per-slot
+ * buffers: 8.6 MB of the 38 MB a slot of a 24-layer bf16 engine owns) into the free slot.
+ *  - What the fork inherits.  Like nasr_stream_reset the call first completes the pipelined steps in flight.  The fork takes src's
+ *    right_context, prompt, audio format and converter plan, boost / LM enable flags, every host-mirror counter (samples_in, chunks,
+ *    cache_valid_len, ...) and the tokens decoded but not yet handed over (they come out of BOTH streams' next step / collect / finalize).
+ *  - Identical twin.  Any sequence of calls made on both afterwards gives the same tokens, frames and read-outs (token frames, log-
+ *    probabilities, alternatives, per-frame blank log-probabilities).  The read-outs are counted from src's create / reset: token index i
+ *    and frame t mean the same on both.  (Stepped in one call of their own each they are equal bit for bit; two rows of one call may differ
+ *    in the last bits of a log-probability, like any two rows.)
+ *  - Isolation.  src is not changed in any bit, and the two streams are independent from then on: destroy, reset, set_boost, set_lm,
+ *    set_prompt on one do not reach the other.
+ *  - Failures.  Fails -- with a message, *out = NULL and the engine usable -- on a null stream, on a pointer that is no live stream (destroyed, or its engine destroyed: the library keeps the set of
+ *    live streams and does not read the pointer) and on an exhausted pool
+ *    ("stream pool exhausted (max_streams=%d)").
+ *  - Options and graphs.  It allocates nothing on the device, captures no step graph and invalidates none (step graphs take the slot from
+ *    their row descriptors).  Debug taps are not copied: a fork's taps (mel, PCM16, subsampled, layer and encoder outputs) are empty
+ *    until its own first call. */
+int nasr_stream_fork(nasr_stream *src, nasr_stream **out);
+/* nasr_engine_preview: the tokens nasr_engine_finalize would add for each stream if it were called now; the streams are not changed.
+ *  - Mechanism.  Every stream is forked into a free slot, the forks take the nasr_engine_finalize path as ONE batch (the converter's tail
+ *    of streams with an audio format of their own included), their new tokens are read and the slots are released.
+ *  - Outputs.  n_tokens[b] (required) = the number of tail tokens; tokens the source produced before, delivered or still queued, are not
+ *    among them.  The first min(n_tokens[b], tokens_cap[b]) are written to tokens_out[b]; the rest are dropped -- they are a preview, and
+ *    nothing is queued anywhere.  frames_out (may be NULL, as may frames_out[b]) receives their absolute encoder frames.
+ *  - Needs.  B free slots: fewer is an error that names how many are missing (max_streams is the caller's to size with headroom).  The
+ *    rules of every batched call apply (one engine, one right_context, no stream twice).
+ *  - Effects.  It completes steps in flight and runs eagerly, and synchronises.  Neither the sources nor their debug taps change (on a
+ *    debug engine the per-call staging of NASR_TAP_MEL / NASR_TAP_PCM16 is set aside and put back; only NASR_TAP_ENCODER_OUT WITHOUT debug
+ *    mode, which reads the engine's workspace and is valid "until the next chunk step of this engine", ends with a preview).  A stream with
+ *    nothing to flush (at most 9 mel frames buffered) gives 0 tokens.
+ * Engine counters "stream_forks" (fork launches: nasr_stream_fork calls and every fork of a preview) and "stream_previews". */
+int nasr_engine_preview(nasr_engine *e, nasr_stream *const *streams, int B,
+                        int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens,
+                        int32_t *const *frames_out);
+
 /* with NASR_FLAG_NO_SYNC: wait for outstanding work and fetch the tokens produced since the
  * last collect (replaces nemo_stream_get_tokens, src/nemo-stream.cpp:1301-1305, as a delta) */
 int nasr_engine_collect(nasr_engine *e, nasr_stream *const *streams, int B,
@@ -302,6 +339,8 @@ enum {
  * nasr_engine_lend_stream).
  * "audio_lds_table" (1 default / 0): nasr_engine_step_audio's kernel reads the coefficients of the 8 / 24 / 32 / 48 kHz tables from a copy in LDS
  * (0: from global memory like the larger tables; same bits; A/B switch, profiles/audio_input.md).
+ * "fork_piece_kb" (0 default = 256; 1 .. 1024): KiB one workgroup of nasr_stream_fork's copy launch moves at most, i.e. its grid; the same
+ * bytes are copied at every value (measurement only: A/B runs of profiles/stream_fork.md).
  * "token_logprobs" (0 default / 1): a capability, not a kernel A/B switch -- with 1 the device decode also keeps, for every emitted token,
  * the natural-log softmax probability of that token over the 1025 joint outputs (blank included) at the frame and decoder state where it
  * was emitted (nasr_stream_get_token_logprobs, nasr_engine_offline_token_logprobs).  Tokens, frames, iteration counts and decoder state
@@ -345,7 +384,7 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * pushes, streams that complete different chunk counts), "pipelined_steps", "grouped_steps", "lanes" (HIP streams the engine found
  * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
- * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls), "cut_drains" (pipelined calls that first completed the steps in flight because
  * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);

@@ -46,6 +46,7 @@ EXPORTS = [
     "nasr_engine_set_lm", "nasr_engine_set_lm_weights", "nasr_engine_beam_hypothesis_lm",
     "nasr_engine_beam_hypothesis_boost",
     "nasr_engine_set_greedy_lm_weights", "nasr_stream_set_lm",
+    "nasr_stream_fork", "nasr_engine_preview",
 ]
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
@@ -138,6 +139,8 @@ def lib():
         L.nasr_engine_step_mel.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_finalize.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, ip]
         L.nasr_engine_collect.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, ip]
+        L.nasr_stream_fork.argtypes = [vp, C.POINTER(vp)]
+        L.nasr_engine_preview.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp)]
         L.nasr_engine_set_debug.argtypes = [vp, C.c_int]
         L.nasr_engine_set_option.argtypes = [vp, C.c_char_p, C.c_int]
         L.nasr_stream_get_tap.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64]
@@ -226,12 +229,21 @@ def default_hparams(n_layers=24, kernel_size=9, num_prompts=0) -> HParams:
 
 
 class Stream:
-    def __init__(self, engine: "Engine", right_context=0, prompt_index=-1):
+    def __init__(self, engine: "Engine", right_context=0, prompt_index=-1, _fork_of: "Stream" = None):
         self.engine = engine
         h = C.c_void_p()
-        _chk(lib().nasr_stream_create(engine.h, right_context, prompt_index, C.byref(h)))
+        if _fork_of is None:
+            _chk(lib().nasr_stream_create(engine.h, right_context, prompt_index, C.byref(h)))
+        else:
+            _chk(lib().nasr_stream_fork(_fork_of.h, C.byref(h)))
+            self.fmt = _fork_of.fmt
         self.h = h
         self.R, self.T = right_context, 1 + right_context
+
+    def fork(self) -> "Stream":
+        """a new stream in the lowest free slot whose state is this one's at this moment (one device launch); the two are independent
+        from then on and, given the same calls, give the same tokens, frames and read-outs"""
+        return Stream(self.engine, self.R, _fork_of=self)
 
     def reset(self, reference=False):
         """reference=True: nemo_stream_reset as the reference codes it (stale conv cache / preprocessor carry survive)"""
@@ -572,6 +584,16 @@ class Engine:
         bufs, tptrs, caps, n = self._tok_bufs(B, 256)
         _chk(lib().nasr_engine_finalize(self.h, self._handles(streams), B, tptrs, caps, n))
         return self._gather(streams, bufs, tptrs, caps, n, 256)
+
+    def preview(self, streams, frames=False, cap=256):
+        """the tokens finalize would add for each stream if it were called now, as a list of token lists (frames=True: a list of
+        (tokens, absolute encoder frames)); the streams are not changed.  Needs len(streams) free slots"""
+        B = len(streams)
+        bufs, tptrs, caps, n = self._tok_bufs(B, cap)
+        fbufs, fptrs, _, _ = self._tok_bufs(B, cap)
+        _chk(lib().nasr_engine_preview(self.h, self._handles(streams), B, tptrs, caps, n, fptrs if frames else None))
+        toks = [bufs[b][:min(n[b], cap)].tolist() for b in range(B)]
+        return [(toks[b], fbufs[b][:len(toks[b])].tolist()) for b in range(B)] if frames else toks
 
     def collect(self, streams, cap=4096):
         B = len(streams)

@@ -171,6 +171,33 @@ void launch_stream_reset(const StreamResetParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_stream_reset, dim3(p.n_layers + 1), dim3(256), 0, st, p);
 }
 
+// ---- stream fork in ONE launch: slot B becomes the twin of slot A (nasr_fork_plan.h) --------------------------------------------
+// The host cuts the live part of the source slot (70 K/V window rows and the conv cache of every layer, the buffered mel frames, the waiting
+// samples, the decoder's per-slot buffers) into disjoint pieces of at most 256 KiB (nasr_fork::PIECE_BYTES: measured, larger grids are
+// a little slower); workgroup i moves piece i: four 16-byte loads in flight per thread, then their stores.  The few pieces that are no whole 16-byte vectors (last_sample, the boost and LM state, the converter's history) move as
+// 4-byte words.  No workgroup reads what another writes: no atomics, no flags, nothing waits.
+__global__ __launch_bounds__(256) void k_stream_fork(StreamForkParams p) {
+    if ((int)blockIdx.x >= p.n_pieces) return;
+    const StreamForkPiece pc = p.pieces[blockIdx.x];
+    if (((uintptr_t)pc.src | (uintptr_t)pc.dst | (uintptr_t)pc.bytes) & 15) {
+        for (uint32_t i = threadIdx.x; i < pc.bytes / 4; i += 256) ((uint32_t *)pc.dst)[i] = ((const uint32_t *)pc.src)[i];
+        return;
+    }
+    const float4 *src = (const float4 *)pc.src;
+    float4 *dst = (float4 *)pc.dst;
+    const uint32_t n = pc.bytes / 16;
+    for (uint32_t i = threadIdx.x; i < n; i += 4 * 256) {
+        float4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (i + k * 256 < n) v[k] = src[i + k * 256];
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (i + k * 256 < n) dst[i + k * 256] = v[k];
+    }
+}
+void launch_stream_fork(const StreamForkParams &p, hipStream_t st) {
+    if (p.n_pieces > 0) hipLaunchKernelGGL(k_stream_fork, dim3(p.n_pieces), dim3(256), 0, st, p);
+}
+
 // ---- conv0 + the first depthwise conv (nasr_conv0_dw.h) on a chunk of a stream's mel ring ----------------
 // One workgroup per (output position, chunk); the mel patch addresses are workgroup-uniform (scalar loads).  out [B][H2][W2][256].
 template <bool OUT_BF16>

@@ -250,6 +250,7 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
     else if (!strcmp(key, "offline_rows")) { if (value < 1) return fail("offline_rows must be >= 1"); e->opt_offline_rows = value; }
     else if (!strcmp(key, "align_cells")) { if (value < nasr_align::MIN_CELLS) return fail("align_cells must be >= %d", nasr_align::MIN_CELLS); e->opt_align_cells = value; }
     else if (!strcmp(key, "audio_lds_table")) e->opt_audio_lds_table = value != 0;      // A/B switch of k_audio_convert (same bits)
+    else if (!strcmp(key, "fork_piece_kb")) { if (value < 0 || value > 1024) return fail("fork_piece_kb must be 0 .. 1024"); e->opt_fork_piece_kb = value; }      // measurement only: the grid of k_stream_fork (same bytes)
     else if (!strcmp(key, "ablate")) e->opt_ablate = value;          // measurement only (see the header); before the first step
     else if (!strcmp(key, "f32_mfma")) e->opt_f32_mfma = value != 0;      // 0: f32 GEMMs above four rows on the FMA tile kernel (round 3's path); like "fused", set before the first step
     else if (!strcmp(key, "pipeline")) {
@@ -781,12 +782,8 @@ extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams,
     return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens);
 }
 
-extern "C" int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *const *tokens_out,
-                                    const int32_t *tokens_cap, int32_t *n_tokens) {
-    ApiGuard api_guard;
-    if (validate_batch(e, streams, B)) return -1;
-    HIPCHK(hipSetDevice(e->device));
-    if (pipe_drain(e)) return -1;
+namespace nasr_eng {
+int finalize_flush(nasr_engine *e, nasr_stream *const *streams, int B) {
     if (audio_flush(e, streams, B)) return -1;          // streams with an audio format of their own: the converter's tail goes through the front end first
     // src/nemo-stream.cpp:1234-1258: frames > 9 -> n_valid = (frames-9)/8 outputs of one zero-padded step
     std::vector<nasr_stream *> rows;
@@ -818,7 +815,86 @@ extern "C" int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams,
         launch_mel_zero(dpd, (int)pd.size(), max_pad, e->mel_ring, e->st);
     }
     if (!rows.empty() && run_chunk(e, rows, nd)) return -1;
+    return 0;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *const *tokens_out,
+                                    const int32_t *tokens_cap, int32_t *n_tokens) {
+    ApiGuard api_guard;
+    if (validate_batch(e, streams, B)) return -1;
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    if (finalize_flush(e, streams, B)) return -1;
     return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens);
+}
+
+// the steps in flight are completed, every stream is forked into a free slot, the forks take the finalize path as one batch, their new tokens
+// are read and their slots released: the streams themselves (device state, host mirror, queued tokens) are not touched
+extern "C" int nasr_engine_preview(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *const *tokens_out, const int32_t *tokens_cap,
+                                   int32_t *n_tokens, int32_t *const *frames_out) {
+    ApiGuard api_guard;
+    if (validate_batch(e, streams, B)) return -1;
+    if (!n_tokens) return fail("nasr_engine_preview: null n_tokens");
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    int n_free = 0;
+    for (int i = 0; i < e->max_streams; i++) n_free += e->slots[i] == nullptr;
+    if (n_free < B) return fail("nasr_engine_preview: %d free slot(s) missing: %d stream(s) need as many, %d of max_streams=%d are free", B - n_free, B, n_free, e->max_streams);
+    std::vector<nasr_stream *> forks;
+    // a debug engine stages NASR_TAP_MEL (by batch row) and NASR_TAP_PCM16 per call: what the sources' last call left there is set aside and
+    // put back, so that their taps read after the preview what they read before it (debug only: two allocations and four copies)
+    struct TapSave { void *mel = nullptr, *pcm = nullptr; size_t mel_bytes = 0, pcm_bytes = 0; std::vector<int> frames, row; std::vector<int64_t> off, n; } taps;
+    if (e->debug && e->tap_mel) {
+        taps.mel_bytes = (size_t)B * e->tap_mel_cap * NMEL * 4; taps.pcm_bytes = e->tap_pcm_cap * 2;
+        taps.frames = e->tap_mel_frames; taps.row = e->tap_mel_row; taps.off = e->tap_pcm_off; taps.n = e->tap_pcm_n;
+        HIPCHK(hipStreamSynchronize(e->st));
+        HIPCHK(hipMalloc(&taps.mel, taps.mel_bytes));
+        if (hipMemcpy(taps.mel, e->tap_mel, taps.mel_bytes, hipMemcpyDeviceToDevice) != hipSuccess) { hipFree(taps.mel); return fail("nasr_engine_preview: saving the mel tap failed"); }
+        if (taps.pcm_bytes && (hipMalloc(&taps.pcm, taps.pcm_bytes) != hipSuccess || hipMemcpy(taps.pcm, e->tap_pcm, taps.pcm_bytes, hipMemcpyDeviceToDevice) != hipSuccess)) {
+            hipFree(taps.mel); if (taps.pcm) hipFree(taps.pcm);
+            return fail("nasr_engine_preview: saving the PCM16 tap failed");
+        }
+    }
+    const auto release = [&](int rc) {
+        if (rc) pipe_drain(e);                             // a failed call: nothing in flight may still name a fork
+        hipStreamSynchronize(e->st);
+        for (nasr_stream *f : forks) { e->slots[f->slot] = nullptr; stream_unregister(f); delete f; }
+        if (taps.mel) {                                    // tap_pcm only ever grows: the saved bytes fit
+            hipMemcpy(e->tap_mel, taps.mel, taps.mel_bytes, hipMemcpyDeviceToDevice);
+            if (taps.pcm) hipMemcpy(e->tap_pcm, taps.pcm, taps.pcm_bytes, hipMemcpyDeviceToDevice);
+            e->tap_mel_frames = taps.frames; e->tap_mel_row = taps.row; e->tap_pcm_off = taps.off; e->tap_pcm_n = taps.n;
+            hipFree(taps.mel); if (taps.pcm) hipFree(taps.pcm);
+        }
+        return rc;
+    };
+    for (int b = 0; b < B; b++) {
+        nasr_stream *f = nullptr;
+        if (stream_fork(streams[b], &f)) return release(-1);
+        forks.push_back(f);
+    }
+    // what the sources had decoded before (queued on the host, or still on the device behind a NO_SYNC step) is not part of the tail
+    if (collect_tokens(e, forks.data(), B, nullptr, nullptr, nullptr)) return release(-1);
+    if (finalize_flush(e, forks.data(), B)) return release(-1);
+    std::vector<std::vector<int32_t>> toks((size_t)B, std::vector<int32_t>(TOK_CAP));
+    std::vector<int32_t *> tptr((size_t)B);
+    std::vector<int32_t> tcap((size_t)B, TOK_CAP), tn((size_t)B, 0);
+    for (int b = 0; b < B; b++) tptr[b] = toks[b].data();
+    if (collect_tokens(e, forks.data(), B, tptr.data(), tcap.data(), tn.data())) return release(-1);      // synchronises the engine's stream
+    for (int b = 0; b < B; b++) {
+        n_tokens[b] = tn[b];
+        const int n_out = tokens_cap ? std::min(tn[b], std::max(tokens_cap[b], 0)) : 0;
+        if (tokens_out && tokens_out[b]) for (int i = 0; i < n_out; i++) tokens_out[b][i] = toks[b][(size_t)i];
+        if (!frames_out || !frames_out[b] || n_out <= 0) continue;
+        // only the tail's entries of the fork's frame ring: one copy, two where they wrap (tok_read = the fork's token count once its tail is collected)
+        const int *ring = e->dec.tok_frame + (size_t)forks[b]->slot * TOK_CAP;
+        const int first = (forks[b]->tok_read - tn[b]) & (TOK_CAP - 1), n1 = std::min(n_out, TOK_CAP - first);
+        if (hipMemcpy(frames_out[b], ring + first, (size_t)n1 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            (n_out > n1 && hipMemcpy(frames_out[b] + n1, ring, (size_t)(n_out - n1) * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+            return release(fail("nasr_engine_preview: reading the token frames failed"));
+    }
+    e->stream_previews++;
+    return release(0);
 }
 
 extern "C" int nasr_engine_collect(nasr_engine *e, nasr_stream *const *streams, int B, int32_t *const *tokens_out,
@@ -938,6 +1014,8 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "eager_steps")) *value = e->eager_steps;
     else if (!strcmp(name, "pipelined_steps")) *value = e->pipe_steps;
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;
+    else if (!strcmp(name, "stream_forks")) *value = e->stream_forks;                       // k_stream_fork launches: nasr_stream_fork calls and the forks of every preview
+    else if (!strcmp(name, "stream_previews")) *value = e->stream_previews;                 // nasr_engine_preview calls that succeeded
     else if (!strcmp(name, "cut_drains")) *value = e->cut_drains;                           // pipelined steps that first completed the steps in flight: cut differently (piece count, family)
     else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)

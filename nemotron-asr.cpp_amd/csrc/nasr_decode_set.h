@@ -1,5 +1,5 @@
 // nasr_decode_set.h -- the working set of the device greedy decode: the options in force (DecFeatures), every per-slot and per-row buffer
-// its launches touch (DecodeSet), each buffer's size and the option that needs it (dec_set_layout), the allocation of what is missing
+// its launches touch (DecodeSet), each buffer's size and the option that needs it (dec_set_layout; dec_set_slot_layout: what one slot owns of them), the allocation of what is missing
 // (dec_set_ensure) and the DecParams of a launch sequence (dec_set_bind).  The live engine holds one set, the offline path another; a new
 // decode option is added here.  Pure host code (tests/test_decode_set.py compiles it with the host compiler); include it after
 // nasr_internal.h.  The beam search has a working set of its own (OfflineState::bm_*, BeamParams).
@@ -79,6 +79,21 @@ inline void dec_set_layout(DecodeSet &d, const DecFeatures &f, int slots, int ro
     buf("lm_state",    d.lm_state,      f.lm_fusion,            S);
     buf("lm_row",      d.lm_row,        f.lm_fusion,            S * nasr_lm::ROW_COLS);
     buf("lm_next",     d.lm_next,       f.lm_fusion,            S * nasr_lm::ROW_COLS);
+}
+
+// The per-slot part of THE layout: buf(name, pointer, needed, elements_per_slot) once for every buffer whose size grows with the slots and
+// whose option is in force under f -- what one slot owns of the set (a stream fork copies it, nasr_fork_plan.h).  Read off dec_set_layout
+// itself (its sizes at two slots against one), so a buffer added there is here without being named again; [row] buffers are not listed
+template <class Visit>
+inline void dec_set_slot_layout(DecodeSet &d, const DecFeatures &f, Visit &&buf) {
+    size_t one[64];
+    int n = 0, i = 0;
+    dec_set_layout(d, f, 1, 1, [&](const char *, auto *&, bool, size_t elems) { if (n < 64) one[n++] = elems; });
+    dec_set_layout(d, f, 2, 1, [&](const char *name, auto *&p, bool needed, size_t elems) {
+        const size_t per_slot = i < n ? elems - one[i] : 0;
+        i++;
+        if (needed && per_slot) buf(name, p, needed, per_slot);
+    });
 }
 
 // Allocates every buffer that f needs and the set does not have yet; never frees or moves one.  alloc(name, &pointer, bytes) returns 0 or

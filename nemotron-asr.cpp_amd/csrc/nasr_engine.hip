@@ -625,7 +625,7 @@ void engine_destroy_impl(nasr_engine *e) {
     offline_destroy(e);
     delete e->lm;
     if (e->lm_dev) hipFree(e->lm_dev);
-    for (auto *s : e->slots) delete s;
+    for (auto *s : e->slots) { if (s) stream_unregister(s); delete s; }
     for (void *p : e->allocs) hipFree(p);
     for (auto &kv : e->graphs) hipGraphExecDestroy(kv.second);
     for (auto &per_slot : e->gp_graphs) for (auto &m : per_slot) for (auto &kv : m) if (kv.second) hipGraphExecDestroy(kv.second);
@@ -713,7 +713,73 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     return 0;
 }
 
+// the streams that exist, of every engine of the process: nasr_stream_fork is handed a pointer and must be able to refuse a destroyed one
+// without reading it (create, fork and destroy are rare; the step path never looks here)
+static std::mutex g_streams_mtx;
+static std::set<const nasr_stream *> g_streams;
+void stream_register(const nasr_stream *s) { std::lock_guard<std::mutex> lk(g_streams_mtx); g_streams.insert(s); }
+void stream_unregister(const nasr_stream *s) { std::lock_guard<std::mutex> lk(g_streams_mtx); g_streams.erase(s); }
+bool stream_is_live(const nasr_stream *s) { std::lock_guard<std::mutex> lk(g_streams_mtx); return g_streams.count(s) != 0; }
+
+// ---- stream fork: slot B becomes the twin of slot A in ONE launch (nasr_fork_plan.h, k_stream_fork) ----------------------------
+// Everything a stream is lives in its slot of the pools and in its host mirror, and the step graphs take the slot from their RowDesc: a
+// fork is a copy of the mirror with another slot number, and a copy of the LIVE part of the slot (at bf16 and 24 layers 8.6 MB of the
+// slot's 38 MB).  Nothing is allocated (the piece table goes through the descriptor arena), no graph is captured or invalidated.
+int stream_fork(nasr_stream *src, nasr_stream **out) {
+    nasr_engine *e = src->e;
+    int slot = -1;
+    for (int i = 0; i < e->max_streams; i++)
+        if (!e->slots[i]) { slot = i; break; }
+    if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
+    const nasr_fork::Source live = {src->kv_head, src->mel_start, src->mel_count, src->abuf_cnt, src->abuf_par};
+    const std::vector<nasr_fork::Seg> segs = nasr_fork::fork_plan(live, src->slot, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e));
+    if (const char *what = nasr_fork::plan_fault(segs, src->slot, slot)) return fail("nasr_stream_fork: bad copy plan (%s)", what);
+    const int64_t piece_bytes = e->opt_fork_piece_kb > 0 ? (int64_t)e->opt_fork_piece_kb * 1024 : nasr_fork::PIECE_BYTES;
+    std::vector<StreamForkPiece> pieces;
+    for (const nasr_fork::Seg &s : segs) {
+        char *base = s.base;
+        switch (s.buf) {
+        case nasr_fork::BUF_KV: base = (char *)e->kv_pool[s.layer]; break;
+        case nasr_fork::BUF_CC: base = (char *)e->cc_pool[s.layer]; break;
+        case nasr_fork::BUF_MEL: base = (char *)e->mel_ring; break;
+        case nasr_fork::BUF_ABUF: base = (char *)e->abuf; break;
+        case nasr_fork::BUF_LAST_SAMPLE: base = (char *)e->last_sample; break;
+        case nasr_fork::BUF_AUD_HIST: base = (char *)e->aud_hist; break;
+        default: break;
+        }
+        if (!base) return fail("nasr_stream_fork: buffer '%s' is not allocated", s.name);
+        nasr_fork::cut_pieces(pieces, s, base, piece_bytes);
+    }
+    const StreamForkPiece *dpieces;
+    if (stage_desc(e, pieces, &dpieces)) return -1;
+    {
+        ProfScope ps(e, "k_stream_fork", 2.0 * (double)nasr_fork::plan_bytes(segs));
+        launch_stream_fork(StreamForkParams{dpieces, (int)pieces.size()}, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    nasr_stream *f = new nasr_stream(*src);          // right_context, prompt, audio format and plan, boost / LM flags, every counter, the queued tokens
+    f->slot = slot;
+    f->last_T = 0;                                   // the taps show what a call left for its own slots and rows: a fork has taken part in none
+    e->slots[slot] = f;
+    stream_register(f);
+    if (e->debug) { e->tap_mel_frames[slot] = 0; e->tap_pcm_n[slot] = 0; }
+    e->stream_forks++;
+    *out = f;
+    return 0;
+}
+
 }  // namespace nasr_eng
+extern "C" int nasr_stream_fork(nasr_stream *src, nasr_stream **out) {
+    ApiGuard api_guard;
+    if (!src || !out) return fail("nasr_stream_fork: null argument");
+    *out = nullptr;
+    if (!stream_is_live(src)) return fail("nasr_stream_fork: not a live stream (it has been destroyed, or its engine has)");
+    nasr_engine *e = src->e;
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    return stream_fork(src, out);
+}
+
 extern "C" int nasr_stream_create(nasr_engine *e, int right_context, int prompt_index, nasr_stream **out) {
     ApiGuard api_guard;
     if (!e || !out) return fail("nasr_stream_create: null argument");
@@ -732,6 +798,7 @@ extern "C" int nasr_stream_create(nasr_engine *e, int right_context, int prompt_
     s->alive = true;
     e->slots[slot] = s;
     if (stream_zero_state(s)) { e->slots[slot] = nullptr; delete s; return -1; }
+    stream_register(s);
     *out = s;
     return 0;
 }
@@ -757,6 +824,7 @@ extern "C" int nasr_stream_destroy(nasr_stream *s) {
     pipe_drain(e);
     hipStreamSynchronize(e->st);
     e->slots[s->slot] = nullptr;
+    stream_unregister(s);
     delete s;
     return 0;
 }

@@ -10,6 +10,7 @@
 #include "nasr_internal.h"
 #include "nasr_decode_set.h"
 #include "nasr_step_plan.h"
+#include "nasr_fork_plan.h"
 #include "nemotron_asr_amd.h"
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <set>
 #include <shared_mutex>
 #include <string>
 #include <vector>
@@ -155,6 +157,8 @@ struct nasr_engine {
     int opt_graph_cache = 16;        // option "graph_cache": step shapes (B, T, G, E) whose hipGraphs are kept, per slot; least recently used goes first
     std::map<int64_t, int64_t> graph_used;   // shape key -> tick of its last use
     int64_t graph_tick = 0, graph_evictions = 0;
+    int64_t stream_forks = 0, stream_previews = 0;   // k_stream_fork launches (nasr_stream_fork and the forks of a preview) / nasr_engine_preview calls (counters of the same names)
+    int opt_fork_piece_kb = 0;       // option "fork_piece_kb" (MEASUREMENT ONLY): KiB one workgroup of k_stream_fork moves at most; 0 = nasr_fork::PIECE_BYTES
     // hipGraph replay of the steady-state step: fixed descriptor buffers + one exec per (B, T)
     std::map<int64_t, hipGraphExec_t> graphs;
     int w_rows = 0;                  // workspace rows = max(max_streams x TMAX, MAXNEW)
@@ -345,6 +349,14 @@ int alloc_ws(nasr_engine *e, nasr_engine::WS &w);
 void use_ws(nasr_engine *e, const nasr_engine::WS &w);
 void engine_destroy_impl(nasr_engine *e);
 int stream_zero_state(nasr_stream *s, bool keep_reference_state = false);
+// a new stream in the lowest free slot whose device state and host mirror are src's (one k_stream_fork launch on the engine's stream); the
+// caller holds an ApiGuard and has completed the steps in flight (pipe_drain)
+int stream_fork(nasr_stream *src, nasr_stream **out);
+void stream_register(const nasr_stream *s);      // the process-wide set of streams that exist (nasr_stream_fork refuses any other pointer)
+void stream_unregister(const nasr_stream *s);
+bool stream_is_live(const nasr_stream *s);
+// what nasr_engine_finalize does between pipe_drain and its collect: the converter's tail, then one zero-padded step of what is buffered
+int finalize_flush(nasr_engine *e, nasr_stream *const *streams, int B);
 double gemm_bytes(const nasr_engine *e, int M, int N, int K, int wesz);
 // out = A [M][K] (row stride lda) . W^T in one K slice, every other field zero: the caller sets the epilogue
 inline GemmParams gemm_desc(const void *A, int lda, const void *W, int M, int N, int K) {

@@ -157,6 +157,11 @@ struct StreamResetParams {      // one launch per stream start / reset (kernels_
     float *aud_hist;            // [slot][2][nasr_rs::HIST_MAX] input history of the audio converter: cleared in both modes
 };
 void launch_stream_reset(const StreamResetParams &p, hipStream_t st);
+// one launch per stream fork (kernels_front.hip: k_stream_fork): workgroup i moves piece i of the copy plan (nasr_fork_plan.h).  A piece whose
+// addresses and length are multiples of 16 moves as 16-byte vectors, any other as 4-byte words; the pieces of a launch are disjoint
+struct StreamForkPiece { const char *src; char *dst; uint32_t bytes, pad; };
+struct StreamForkParams { const StreamForkPiece *pieces; int n_pieces; };
+void launch_stream_fork(const StreamForkParams &p, hipStream_t st);
 
 // audio input conversion (kernels_audio.hip, nasr_resample.h): one per stream of a launch
 struct AudioDesc {

@@ -658,6 +658,29 @@ std::string nemo_stream_finalize(nemo_stream_context *sctx) {
     return text;
 }
 
+nemo_stream_context *nemo_stream_fork(nemo_stream_context *sctx) {
+    if (!sctx) return nullptr;
+    nemo_stream_context *f = new nemo_stream_context(*sctx);      // config, prompt, audio format, transcript, tokens, endpoint detector state and events, timing
+    f->stream = nullptr;
+    if (nasr_stream_fork(sctx->stream, &f->stream) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        delete f;
+        return nullptr;
+    }
+    return f;
+}
+
+std::string nemo_stream_preview(nemo_stream_context *sctx) {
+    if (!sctx) return "";
+    int32_t tok[256], cap = 256, cnt = 0;
+    int32_t *tp = tok;
+    if (nasr_engine_preview(sctx->nctx->engine, &sctx->stream, 1, &tp, &cap, &cnt, nullptr) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return "";
+    }
+    return tokens_to_text(std::vector<int>(tok, tok + std::min(cnt, cap)), sctx->nctx->vocab);      // tentative: neither the transcript nor the tokens change
+}
+
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx) { return sctx ? sctx->transcript : ""; }
 
 const std::vector<int> &nemo_stream_get_tokens(nemo_stream_context *sctx) {

@@ -160,6 +160,13 @@ std::string nemo_stream_process_incremental(nemo_stream_context *sctx, const int
 bool nemo_stream_set_audio_format(nemo_stream_context *sctx, int sample_rate, int encoding, int channels, int channel);
 std::string nemo_stream_process_audio(nemo_stream_context *sctx, const void *audio, int n_frames);
 std::string nemo_stream_finalize(nemo_stream_context *sctx);
+// MI355X extension: a second stream that continues from where sctx is now (nasr_stream_fork: one device launch into a free slot of the
+// engine); the mirror's own transcript, tokens and endpoint detector state are copied too, and the two are independent from then on.
+// nullptr on failure (no free slot; the reason on stderr).  Free it with nemo_stream_free
+nemo_stream_context *nemo_stream_fork(nemo_stream_context *sctx);
+// MI355X extension: the text nemo_stream_finalize would add if it were called now -- the tentative tail of a caption at a long right
+// context -- without ending or changing the stream (nasr_engine_preview; it needs one free slot).  "" when nothing is buffered or on failure
+std::string nemo_stream_preview(nemo_stream_context *sctx);
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx);
 const std::vector<int> &nemo_stream_get_tokens(nemo_stream_context *sctx);
 void nemo_stream_reset(nemo_stream_context *sctx);

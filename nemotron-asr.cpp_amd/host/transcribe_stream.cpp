@@ -25,7 +25,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--preview] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
             "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
@@ -46,6 +46,11 @@ static void usage(const char *prog) {
             "                   open utterance at the end of the audio (only if it has tokens).  A frame (80 ms) is silent if it emitted no token and\n"
             "                   P(blank) >= --endpoint-blank-prob P (default 0: every token-less frame).  --endpoint-silence S (rule 2, default 1.2 s),\n"
             "                   --endpoint-idle S (rule 1, default 2.4 s), --endpoint-max S (rule 3, default 20 s); 0 disables a rule\n"
+            "  --preview:       after every read one extra line, `~ ` followed by the tentative text of the tail: what the audio still waiting for its right\n"
+            "                   context (up to 1.12 s at right_context 13) would add if the stream ended now (a flush on a fork of the stream; the stream goes\n"
+            "                   on untouched).  NOTE: the committed transcript is held back and printed when the audio ends, so that every line which does\n"
+            "                   not start with `~ ` is the output without the flag; until then only the `~ ` lines appear.  A live caption shows\n"
+            "                   committed text + tail: nemo_stream_get_transcript() + nemo_stream_preview() of host/nemo_amd.h\n"
             "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
             "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
             "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
@@ -68,7 +73,7 @@ int main(int argc, char **argv) {
     bool print_tokens = false, timestamps = false, confidence = false;
     const char *boost_file = nullptr;
     int alternatives = 0;
-    bool endpoints = false;
+    bool endpoints = false, preview = false;
     nasr_endpoint::Config ep_cfg;
     float boost_bonus = 4.0f;
     const char *lm_path = nullptr;
@@ -90,6 +95,7 @@ int main(int argc, char **argv) {
         else if (a == "--confidence") confidence = true;
         else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
         else if (a == "--endpoints") endpoints = true;
+        else if (a == "--preview") preview = true;
         else if (a == "--endpoint-silence" && i + 1 < argc) ep_cfg.silence_frames_after_speech = (int)std::lround(atof(argv[++i]) / 0.08);
         else if (a == "--endpoint-idle" && i + 1 < argc) ep_cfg.silence_frames_idle = (int)std::lround(atof(argv[++i]) / 0.08);
         else if (a == "--endpoint-max" && i + 1 < argc) ep_cfg.max_utterance_frames = (int)std::lround(atof(argv[++i]) / 0.08);
@@ -135,7 +141,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Configuration:\n  Model:          %s\n  Audio:          %s\n  Chunk size:     %d ms\n  Right context:  %d\n\n",
             model_path, from_stdin ? "stdin" : audio_path, chunk_ms, right_context);
 
-    nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
+    if (preview && !diarize_gguf.empty()) { fprintf(stderr, "--preview does not go with --diarize\n"); return 1; }
+    nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, preview ? 2 : 1);      // a preview flushes a fork of the stream: one slot of headroom
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
     if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
@@ -172,8 +179,10 @@ int main(int argc, char **argv) {
         if (!dp) { fprintf(stderr, "Failed to init diarization pipeline\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
     }
     FILE *json_file = json_path.empty() || json_path == "-" ? nullptr : fopen(json_path.c_str(), "w");
+    std::string held;
     auto handle_text = [&](const std::string &text, size_t samples_so_far) {     // reference :196-224
-        if (!text.empty()) { fputs(text.c_str(), stdout); fflush(stdout); }
+        if (!text.empty() && preview) held += text;       // --preview: the `~ ` lines come first, the transcript's line stays whole
+        else if (!text.empty()) { fputs(text.c_str(), stdout); fflush(stdout); }
         if (!dp || text.empty()) return;
         diarize_pipeline_push_text(dp, text, (double)samples_so_far / 16000.0);
         if (!json_path.empty()) {
@@ -243,6 +252,7 @@ int main(int argc, char **argv) {
         total += got;
         // handle_text's sample count feeds the diarization pipeline only, which runs on the default format: there frames are 16 kHz samples
         handle_text(own_format ? nemo_stream_process_audio(sctx, buf, (int)got) : nemo_stream_process_incremental(sctx, (const int16_t *)buf, (int)got), total);
+        if (preview) { printf("~ %s\n", nemo_stream_preview(sctx).c_str()); fflush(stdout); }
         if (dp) {
             f32.resize(got);
             for (size_t k = 0; k < got; k++) f32[k] = (float)((const int16_t *)buf)[k] / 32768.0f;
@@ -251,6 +261,7 @@ int main(int argc, char **argv) {
         if (have < want || data_left == 0) break;
     }
     handle_text(nemo_stream_finalize(sctx), total);
+    fputs(held.c_str(), stdout);
     printf("\n");
     if (!from_stdin) fclose(in);
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
