@@ -271,6 +271,44 @@ int nasr_engine_preview(nasr_engine *e, nasr_stream *const *streams, int B,
                         int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens,
                         int32_t *const *frames_out);
 
+/* ---- stream snapshots in host memory: save, restore, move between engines (the reference has none) ----
+ * nasr_stream_save: writes everything stream s is into buf as one self-describing blob (little-endian, format version 1:
+ * csrc/nasr_snapshot.h) and its exact size into *bytes_out.  nasr_stream_restore: *out = a new stream in the lowest free slot of e that
+ * continues exactly as the saved one would have.  nasr_engine_snapshot_bound: *bytes_out = the largest blob any stream of e can produce
+ * under the decode options now in force (a buffer of that size always suffices).
+ *  - What travels.  The live part of the slot -- what nasr_stream_fork copies: per layer the 70 K/V window rows and the conv cache, the
+ *    buffered mel frames and samples, the converter's history, the decoder's per-slot buffers (8.55 MB at 24 layers bf16) -- gathered by one
+ *    device launch and one device-to-host copy, and the host mirror: right_context, prompt, every counter (samples_in, chunks,
+ *    cache_valid_len, ...), the boost / LM enable flags, the audio format, and the tokens decoded but not yet handed over.  Those tokens stay
+ *    queued in s AND are in the blob: they come out of the restored stream's next step / collect / finalize.  Ring rows are stored in
+ *    logical order with the ring positions in the mirror, so a blob does not depend on the slot it came from; it holds no pointer.
+ *  - Identical twin.  The contract of nasr_stream_fork: any sequence of calls made on s and on the restored stream afterwards gives the
+ *    same tokens, frames and read-outs, bit for bit when each is stepped in calls of its own; read-outs are counted from the original's
+ *    create / reset.  e may be the engine that saved, another engine of the process, an engine on another device or of a later process, as
+ *    long as it agrees with the blob: dtype, n_layers, kernel_size, the layout constants, the decode options (token_logprobs,
+ *    token_alternatives, frame_blank_logprobs, phrase_boost, lm_fusion) and three fingerprints -- of the weight set (names, types, shapes
+ *    and a bounded sample of every tensor's bytes, taken at nasr_engine_create), of the boost set in force and of the language model in
+ *    force with its greedy weights (0 when none).  A caller who wants to restore under another boost set or model sets the same one
+ *    first; there is no mode that resets the bias state.
+ *  - Isolation.  nasr_stream_save completes the pipelined steps in flight, like nasr_stream_fork; s is not changed in any bit and goes on
+ *    living.  The restored stream is independent of s and of the blob, which may be restored any number of times.
+ *  - Failures.  Save: buf == NULL or cap too small is an error whose message names the size needed, and *bytes_out is still set (so a
+ *    call with buf == NULL asks for the size); a null stream, a pointer that is no live stream.  Restore refuses, before any device work and
+ *    with one message per cause: bad magic or version, a truncated blob or trailing bytes, a corrupted header / mirror checksum, every
+ *    mismatch with the engine (the message names the field and both values), every mirror field out of its range, a device section whose
+ *    size is not what the plan for this mirror says (no offset or length inside the blob is trusted), an exhausted pool
+ *    ("stream pool exhausted (max_streams=%d)").  The device section's checksum is computed by the unpack launch itself and compared with the header
+ *    afterwards; then the decoder fields a kernel uses as an index are range-checked.  On any failure *out = NULL, a message is set, no
+ *    slot is held and the engine stays usable.  The format is integrity-checked, not authenticated: the checksums catch corruption in
+ *    transit or on disk; a forged blob with matching checksums is outside the promise.
+ *  - Options and graphs.  Neither call captures a step graph or invalidates one, and a step that never saves or restores launches what it
+ *    always did.  The first save or restore allocates a device staging buffer of the size of the bound (grown when an option raises it,
+ *    freed with the engine) and a pinned block.  Debug taps are empty until the restored stream's own first call, as after a fork.
+ * Engine counters "stream_saves" and "stream_restores". */
+int nasr_engine_snapshot_bound(nasr_engine *e, int64_t *bytes_out);
+int nasr_stream_save(nasr_stream *s, void *buf, int64_t cap, int64_t *bytes_out);
+int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t bytes, nasr_stream **out);
+
 /* with NASR_FLAG_NO_SYNC: wait for outstanding work and fetch the tokens produced since the
  * last collect (replaces nemo_stream_get_tokens, src/nemo-stream.cpp:1301-1305, as a delta) */
 int nasr_engine_collect(nasr_engine *e, nasr_stream *const *streams, int B,
@@ -384,7 +422,8 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * pushes, streams that complete different chunk counts), "pipelined_steps", "grouped_steps", "lanes" (HIP streams the engine found
  * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
- * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls),
+ * "stream_saves" / "stream_restores" (nasr_stream_save calls that wrote a blob / nasr_stream_restore calls that made a stream; refused calls are not counted), "cut_drains" (pipelined calls that first completed the steps in flight because
  * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 from pathlib import Path
 
 import numpy as np
@@ -47,7 +48,9 @@ EXPORTS = [
     "nasr_engine_beam_hypothesis_boost",
     "nasr_engine_set_greedy_lm_weights", "nasr_stream_set_lm",
     "nasr_stream_fork", "nasr_engine_preview",
+    "nasr_engine_snapshot_bound", "nasr_stream_save", "nasr_stream_restore",
 ]
+SNAPSHOT_HEADER_BYTES = 144          # csrc/nasr_snapshot.h: the mirror section follows (R first, the audio format at +60)
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
 LM_MAX_ORDER, LM_BOS, LM_EOS = 5, 1025, 1026
@@ -141,6 +144,9 @@ def lib():
         L.nasr_engine_collect.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, ip]
         L.nasr_stream_fork.argtypes = [vp, C.POINTER(vp)]
         L.nasr_engine_preview.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, ip, C.POINTER(vp)]
+        L.nasr_engine_snapshot_bound.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.nasr_stream_save.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.nasr_stream_restore.argtypes = [vp, vp, C.c_int64, C.POINTER(vp)]
         L.nasr_engine_set_debug.argtypes = [vp, C.c_int]
         L.nasr_engine_set_option.argtypes = [vp, C.c_char_p, C.c_int]
         L.nasr_stream_get_tap.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64]
@@ -229,10 +235,18 @@ def default_hparams(n_layers=24, kernel_size=9, num_prompts=0) -> HParams:
 
 
 class Stream:
-    def __init__(self, engine: "Engine", right_context=0, prompt_index=-1, _fork_of: "Stream" = None):
+    def __init__(self, engine: "Engine", right_context=0, prompt_index=-1, _fork_of: "Stream" = None, _blob: bytes = None):
         self.engine = engine
         h = C.c_void_p()
-        if _fork_of is None:
+        if _blob is not None:
+            buf = (C.c_char * len(_blob)).from_buffer_copy(_blob) if len(_blob) else None
+            _chk(lib().nasr_stream_restore(engine.h, C.cast(buf, C.c_void_p), len(_blob), C.byref(h)))
+            # accepted: the mirror's right_context and audio format are in their ranges
+            right_context, = struct.unpack_from("<i", _blob, SNAPSHOT_HEADER_BYTES)
+            fmt = AudioFormat(*struct.unpack_from("<4i", _blob, SNAPSHOT_HEADER_BYTES + 60))
+            if (fmt.sample_rate, fmt.encoding, fmt.channels, fmt.channel) != (16000, AUDIO_S16, 1, 0):
+                self.fmt = fmt
+        elif _fork_of is None:
             _chk(lib().nasr_stream_create(engine.h, right_context, prompt_index, C.byref(h)))
         else:
             _chk(lib().nasr_stream_fork(_fork_of.h, C.byref(h)))
@@ -244,6 +258,17 @@ class Stream:
         """a new stream in the lowest free slot whose state is this one's at this moment (one device launch); the two are independent
         from then on and, given the same calls, give the same tokens, frames and read-outs"""
         return Stream(self.engine, self.R, _fork_of=self)
+
+    def save(self) -> bytes:
+        """the stream as one blob in host memory (nasr_stream_save: one device launch and one copy); the stream goes on living unchanged.
+        Engine.restore(blob) -- of this engine, another one, another device's or a later process's -- makes its identical twin"""
+        need = C.c_int64()
+        lib().nasr_stream_save(self.h, None, 0, C.byref(need))          # buf == NULL: an error by contract that names the size and sets it
+        if need.value <= 0:
+            raise NasrError(lib().nasr_last_error().decode())
+        buf = C.create_string_buffer(need.value)
+        _chk(lib().nasr_stream_save(self.h, C.cast(buf, C.c_void_p), need.value, C.byref(need)))
+        return buf.raw[:need.value]
 
     def reset(self, reference=False):
         """reference=True: nemo_stream_reset as the reference codes it (stale conv cache / preprocessor carry survive)"""
@@ -481,6 +506,16 @@ class Engine:
 
     def stream(self, right_context=0, prompt_index=-1) -> Stream:
         return Stream(self, right_context, prompt_index)
+
+    def restore(self, blob: bytes) -> Stream:
+        """a new stream in the lowest free slot that continues exactly as the stream Stream.save() was called on would have"""
+        return Stream(self, _blob=bytes(blob))
+
+    def snapshot_bound(self) -> int:
+        """the largest blob any stream of this engine can produce under the decode options now in force"""
+        n = C.c_int64()
+        _chk(lib().nasr_engine_snapshot_bound(self.h, C.byref(n)))
+        return n.value
 
     token_alternatives = 0          # K of option "token_alternatives": the width of the rows the two alternatives getters return
 

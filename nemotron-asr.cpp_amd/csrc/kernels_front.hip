@@ -7,6 +7,9 @@
 // to the x86-64 reference build; logf differs by <= 1-2 ulp.
 #include "nasr_internal.h"
 #include "nasr_conv0_dw.h"
+#include "nasr_decode_set.h"
+#include "nasr_fork_plan.h"
+#include "nasr_snapshot.h"
 
 namespace nasr {
 
@@ -196,6 +199,65 @@ __global__ __launch_bounds__(256) void k_stream_fork(StreamForkParams p) {
 }
 void launch_stream_fork(const StreamForkParams &p, hipStream_t st) {
     if (p.n_pieces > 0) hipLaunchKernelGGL(k_stream_fork, dim3(p.n_pieces), dim3(256), 0, st, p);
+}
+
+// ---- stream snapshot: the live part of a slot <-> the device section of a blob, in ONE launch each way (nasr_snapshot.h) -------------
+// k_stream_pack gathers the pieces of the snapshot plan from the slot into a contiguous staging buffer, k_stream_unpack scatters them from
+// staging into a free slot; the data moves as in k_stream_fork (16-byte vectors, four loads in flight per thread; the word items as 4-byte
+// words).  Workgroup i also sums nasr_snap::word_term over the words of piece i as they stand in the section (StreamForkPiece::pad = the
+// section index of the piece's first word): per thread in a register, per wave by shuffles, across the four waves through LDS, and writes
+// the 64-bit partial to sums[i], its own entry of the table behind the payload -- no atomics, nothing waits; the host adds the partials.
+// A word item's piece is padded to 16 bytes in the section: pack writes the padding as zeros, unpack leaves it out of the slot, both sum it.
+template <bool UNPACK>
+__device__ __forceinline__ void snapshot_piece(const StreamPackParams &p) {
+    __shared__ unsigned long long wave_part[4];
+    if ((int)blockIdx.x >= p.n_pieces) return;
+    const StreamForkPiece pc = p.pieces[blockIdx.x];
+    const uint32_t word0 = pc.pad;
+    unsigned long long acc = 0ull;
+    if (((uintptr_t)pc.src | (uintptr_t)pc.dst | (uintptr_t)pc.bytes) & 15) {
+        const uint32_t n = pc.bytes / 4, n_padded = (pc.bytes + 15) / 16 * 4;
+        for (uint32_t i = threadIdx.x; i < n_padded; i += 256) {
+            uint32_t w;
+            if (UNPACK) {
+                w = ((const uint32_t *)pc.src)[i];
+                if (i < n) ((uint32_t *)pc.dst)[i] = w;
+            } else {
+                w = i < n ? ((const uint32_t *)pc.src)[i] : 0u;
+                ((uint32_t *)pc.dst)[i] = w;
+            }
+            acc += nasr_snap::word_term(w, word0 + i);
+        }
+    } else {
+        const uint4 *src = (const uint4 *)pc.src;
+        uint4 *dst = (uint4 *)pc.dst;
+        const uint32_t n = pc.bytes / 16;
+        for (uint32_t i = threadIdx.x; i < n; i += 4 * 256) {
+            uint4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (i + k * 256 < n) v[k] = src[i + k * 256];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (i + k * 256 < n) {
+                    dst[i + k * 256] = v[k];
+                    const uint32_t at = word0 + 4 * (i + k * 256);
+                    acc += nasr_snap::word_term(v[k].x, at) + nasr_snap::word_term(v[k].y, at + 1) + nasr_snap::word_term(v[k].z, at + 2) + nasr_snap::word_term(v[k].w, at + 3);
+                }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) p.sums[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+__global__ __launch_bounds__(256) void k_stream_pack(StreamPackParams p) { snapshot_piece<false>(p); }
+__global__ __launch_bounds__(256) void k_stream_unpack(StreamPackParams p) { snapshot_piece<true>(p); }
+void launch_stream_pack(const StreamPackParams &p, hipStream_t st) {
+    if (p.n_pieces > 0) hipLaunchKernelGGL(k_stream_pack, dim3(p.n_pieces), dim3(256), 0, st, p);
+}
+void launch_stream_unpack(const StreamPackParams &p, hipStream_t st) {
+    if (p.n_pieces > 0) hipLaunchKernelGGL(k_stream_unpack, dim3(p.n_pieces), dim3(256), 0, st, p);
 }
 
 // ---- conv0 + the first depthwise conv (nasr_conv0_dw.h) on a chunk of a stream's mel ring ----------------

@@ -20,6 +20,7 @@ static int upload_boost_set(nasr_engine *e, int n_phrases, const int32_t *const 
     for (int i = 0; i < e->max_streams; i++) if (e->slots[i] && !e->slots[i]->boost_enabled) st[(size_t)i] = nasr_boost::STATE_OFF;
     HIPCHK(hipMemcpy(e->dec.boost_state, st.data(), st.size() * sizeof(int), hipMemcpyHostToDevice));
     e->boost_states = a.n_states;
+    e->boost_fp = nasr_snap::hash_bytes(nasr_snap::hash_bytes((uint64_t)a.n_states, a.bonus.data(), n * sizeof(float)), a.next.data(), n * sizeof(int32_t));   // a snapshot's boost_state means a row of THESE tables
     e->boost_host = std::move(a);
     return 0;
 }
@@ -49,6 +50,8 @@ static int upload_lm(nasr_engine *e, const nasr_lm_desc *d) {
     delete e->lm;
     if (e->lm_dev) hipFree(e->lm_dev);
     e->lm = m; e->lm_dev = dev; e->lm_generation++;
+    e->lm_fp = nasr_snap::hash_bytes(nasr_snap::hash_bytes(nasr_snap::hash_bytes(((uint64_t)(uint32_t)m->order << 32) | (uint32_t)m->start, m->states.data(), m->states.size() * sizeof(nasr_lm::State)),
+                                                           m->uni.data(), m->uni.size() * sizeof(nasr_lm::Uni)), m->arcs.data(), b_arcs);      // a snapshot's lm_state and bias rows mean THIS model
     e->lm_view = m->view();
     e->lm_view.arcs = (const nasr_lm::Arc *)dev; e->lm_view.uni = (const nasr_lm::Uni *)(dev + b_arcs); e->lm_view.states = (const nasr_lm::State *)(dev + b_arcs + b_uni);
     e->lm_weight = d->weight; e->lm_bonus = d->token_bonus;
@@ -1016,7 +1019,9 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "grouped_steps")) *value = e->gp_steps;
     else if (!strcmp(name, "stream_forks")) *value = e->stream_forks;                       // k_stream_fork launches: nasr_stream_fork calls and the forks of every preview
     else if (!strcmp(name, "stream_previews")) *value = e->stream_previews;                 // nasr_engine_preview calls that succeeded
-    else if (!strcmp(name, "cut_drains")) *value = e->cut_drains;                           // pipelined steps that first completed the steps in flight: cut differently (piece count, family)
+    else if (!strcmp(name, "stream_saves")) *value = e->stream_saves;                       // nasr_stream_save calls that wrote a blob (one k_stream_pack launch each)
+    else if (!strcmp(name, "stream_restores")) *value = e->stream_restores;                 // nasr_stream_restore calls that made a stream (refused ones are not counted)
+    else if (!strcmp(name, "cut_drains")) *value = e->cut_drains;                          // pipelined steps that first completed the steps in flight: cut differently (piece count, family)
     else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)
     else if (!strcmp(name, "lm_states")) *value = e->lm ? (int64_t)e->lm->states.size() : 0;

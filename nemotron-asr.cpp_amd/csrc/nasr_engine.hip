@@ -493,6 +493,12 @@ extern "C" int nasr_engine_create_ex(nasr_engine **out, int device_id, int dtype
     if (!g_stamp_buf) { hipMalloc((void **)&g_stamp_buf, (size_t)STAMP_SLOTS * STAMP_PER_SLOT * 32 * 8); hipMemset(g_stamp_buf, 0, (size_t)STAMP_SLOTS * STAMP_PER_SLOT * 32 * 8); }
 #endif
     if (load_weights(e, weights, n_weights)) { engine_destroy_impl(e); return -1; }
+    for (int i = 0; i < n_weights; i++) {            // the weight set's fingerprint (a stream snapshot names the set it was decoded with)
+        const nasr_weight_desc &w = weights[i];
+        const int64_t n = desc_numel(w);
+        const int64_t bytes = w.type == NASR_TYPE_F32 ? n * 4 : w.type == NASR_TYPE_F16 ? n * 2 : w.type == NASR_TYPE_Q8_0 ? n / 32 * 34 : w.type == NASR_TYPE_Q4_0 ? n / 32 * 18 : 0;
+        e->fp_weights += nasr_snap::tensor_fingerprint(w.name, w.type, w.n_dims, w.ne, w.data, bytes > 0 ? (size_t)bytes : 0);
+    }
 
     const size_t S = (size_t)max_streams, Lr = (size_t)hp->n_layers, ks1 = (size_t)hp->kernel_size - 1;
     e->w_rows = std::max(std::max(max_streams * TMAX, MAXNEW), workspace_rows);      // workspace_rows: room for several chunks of every stream in ONE launch sequence (a server's backlog)
@@ -656,6 +662,9 @@ void engine_destroy_impl(nasr_engine *e) {
     if (e->pcm_stage) hipFree(e->pcm_stage);
     if (e->mel_stage) hipFree(e->mel_stage);
     if (e->raw_stage) hipFree(e->raw_stage);
+    if (e->snap_stage) hipFree(e->snap_stage);
+    if (e->snap_pin.p) hipHostFree(e->snap_pin.p);
+    if (e->snap_pin.copied) hipEventDestroy(e->snap_pin.copied);
     for (auto *ring : {e->pcm_pin, e->raw_pin})
         for (int i = 0; i < 4; i++) { if (ring[i].p) hipHostFree(ring[i].p); if (ring[i].copied) hipEventDestroy(ring[i].copied); }
     if (e->tap_pcm) hipFree(e->tap_pcm);
@@ -778,6 +787,188 @@ extern "C" int nasr_stream_fork(nasr_stream *src, nasr_stream **out) {
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
     return stream_fork(src, out);
+}
+
+// ---- stream snapshots in host memory (nasr_snapshot.h, k_stream_pack / k_stream_unpack) -----------------------------------
+// save = the fork plan's segments gathered into a staging buffer by ONE launch that also leaves the checksum partials, ONE device-to-host
+// copy of payload + partials into a pinned block, and header + mirror written by the host; restore = the parser and every host check, ONE
+// host-to-device copy, ONE launch that scatters into the lowest free slot and leaves the same partials.  A step that never saves or restores
+// launches what it always did: nothing here touches a step graph, and the staging buffer is allocated by the first save or restore.
+namespace nasr_eng {
+static nasr_snap::Config snapshot_config(const nasr_engine *e) {
+    const DecFeatures f = dec_features(e);
+    uint64_t fp_lm = 0;
+    if (f.lm_fusion && e->lm) {                      // the bias rows hold weight * lp + bonus: the greedy weights belong to "the LM in force"
+        uint32_t w, b;
+        memcpy(&w, &e->glm_weight, 4); memcpy(&b, &e->glm_bonus, 4);
+        fp_lm = nasr_snap::mix64(e->lm_fp ^ ((uint64_t)w << 32 | b));
+        if (!fp_lm) fp_lm = 1;                       // 0 means "none"
+    }
+    return nasr_snap::make_config(e->dtype, e->esz, e->hp.n_layers, e->hp.kernel_size, f, e->fp_weights, f.phrase_boost ? e->boost_fp : 0, fp_lm);
+}
+static nasr_snap::Mirror snapshot_mirror(const nasr_stream *s) {
+    nasr_snap::Mirror m;
+    m.R = s->R; m.prompt = s->prompt; m.abuf_cnt = s->abuf_cnt; m.abuf_par = s->abuf_par; m.mel_start = s->mel_start; m.mel_count = s->mel_count;
+    m.valid_len = s->valid_len; m.kv_head = s->kv_head; m.cc_par = s->cc_par; m.chunks = s->chunks; m.tok_read = s->tok_read; m.samples_in = s->samples_in;
+    m.boost_enabled = s->boost_enabled ? 1 : 0; m.lm_enabled = s->lm_enabled ? 1 : 0;
+    m.sample_rate = s->fmt.sample_rate; m.encoding = s->fmt.encoding; m.channels = s->fmt.channels; m.channel = s->fmt.channel;
+    m.aud_in = s->aud_in; m.aud_out = s->aud_out; m.aud_par = s->aud_par;
+    m.tok_queue = s->tok_queue;
+    return m;
+}
+// the pieces of a pack / unpack launch between slot and staging, through the descriptor arena
+static int snapshot_pieces(nasr_engine *e, const std::vector<nasr_fork::Seg> &segs, bool unpack, const StreamForkPiece **dev, int *n) {
+    std::vector<StreamForkPiece> pieces;
+    for (const nasr_fork::Seg &s : segs) {
+        char *base = s.base;
+        switch (s.buf) {
+        case nasr_fork::BUF_KV: base = (char *)e->kv_pool[s.layer]; break;
+        case nasr_fork::BUF_CC: base = (char *)e->cc_pool[s.layer]; break;
+        case nasr_fork::BUF_MEL: base = (char *)e->mel_ring; break;
+        case nasr_fork::BUF_ABUF: base = (char *)e->abuf; break;
+        case nasr_fork::BUF_LAST_SAMPLE: base = (char *)e->last_sample; break;
+        case nasr_fork::BUF_AUD_HIST: base = (char *)e->aud_hist; break;
+        default: break;
+        }
+        if (!base) return fail("stream snapshot: buffer '%s' is not allocated", s.name);
+        nasr_snap::cut_snapshot_pieces(pieces, s, base, e->snap_stage, nasr_fork::PIECE_BYTES, unpack);
+    }
+    *n = (int)pieces.size();
+    return stage_desc(e, pieces, dev);
+}
+// the largest device section a stream of this engine can have under the options in force, and the pieces it is cut into
+static void snapshot_bound(nasr_engine *e, int64_t *section, int64_t *n_pieces) {
+    const std::vector<nasr_fork::Seg> segs = nasr_snap::snapshot_plan(nasr_snap::largest_mirror(), 0, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e), section);
+    *n_pieces = 0;
+    for (const nasr_fork::Seg &s : segs) *n_pieces += (s.bytes + nasr_fork::PIECE_BYTES - 1) / nasr_fork::PIECE_BYTES;
+}
+// staging: payload + one 64-bit partial per piece, sized by the bound (a decode option that raises it makes the next call grow it)
+static int ensure_snapshot_stage(nasr_engine *e) {
+    int64_t section, n_pieces;
+    snapshot_bound(e, &section, &n_pieces);
+    return grow_device(e, &e->snap_stage, &e->snap_stage_cap, (size_t)(section + 8 * n_pieces), 0);
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_engine_snapshot_bound(nasr_engine *e, int64_t *bytes_out) {
+    ApiGuard api_guard;
+    if (!e || !bytes_out) return fail("nasr_engine_snapshot_bound: null argument");
+    int64_t section, n_pieces;
+    snapshot_bound(e, &section, &n_pieces);
+    *bytes_out = nasr_snap::HEADER_BYTES + nasr_snap::mirror_bytes((size_t)TOK_CAP) + section;
+    return 0;
+}
+
+extern "C" int nasr_stream_save(nasr_stream *s, void *buf, int64_t cap, int64_t *bytes_out) {
+    ApiGuard api_guard;
+    if (!s || !bytes_out) return fail("nasr_stream_save: null argument");
+    *bytes_out = 0;
+    if (!stream_is_live(s)) return fail("nasr_stream_save: not a live stream (it has been destroyed, or its engine has)");
+    nasr_engine *e = s->e;
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    const nasr_snap::Mirror m = snapshot_mirror(s);
+    int64_t section = 0;
+    const std::vector<nasr_fork::Seg> segs = nasr_snap::snapshot_plan(m, s->slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e), &section);
+    if (const char *what = nasr_snap::snapshot_plan_fault(segs, s->slot, section)) return fail("nasr_stream_save: bad copy plan (%s)", what);
+    const int64_t head = nasr_snap::HEADER_BYTES + nasr_snap::mirror_bytes(m.tok_queue.size()), total = head + section;
+    *bytes_out = total;
+    if (!buf || cap < total) return fail("nasr_stream_save: the snapshot needs %lld bytes, the buffer has %lld", (long long)total, (long long)(buf ? cap : 0));
+    if (ensure_snapshot_stage(e)) return -1;
+    const StreamForkPiece *dpieces;
+    int n_pieces = 0;
+    if (snapshot_pieces(e, segs, false, &dpieces, &n_pieces)) return -1;
+    const size_t moved = (size_t)section + 8 * (size_t)n_pieces;
+    if (moved > e->snap_stage_cap) return fail("nasr_stream_save: the plan exceeds the snapshot bound");
+    if (e->snap_pin.acquire(moved, 0, e->st)) return -1;
+    {
+        ProfScope ps(e, "k_stream_pack", 2.0 * (double)section);
+        launch_stream_pack(StreamPackParams{dpieces, n_pieces, (unsigned long long *)(e->snap_stage + section)}, e->st);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(e, "snapshot_d2h", (double)moved);
+        HIPCHK(hipMemcpyAsync(e->snap_pin.p, e->snap_stage, moved, hipMemcpyDeviceToHost, e->st));       // payload and partials: one copy
+    }
+    HIPCHK(hipStreamSynchronize(e->st));
+    nasr_snap::Header h;
+    h.cfg = snapshot_config(e);
+    h.device_bytes = (uint64_t)section;
+    for (int i = 0; i < n_pieces; i++) { uint64_t part; memcpy(&part, e->snap_pin.p + section + 8 * (size_t)i, 8); h.device_sum += part; }
+    std::vector<uint8_t> front;
+    nasr_snap::write_head(h, m, front);
+    if ((int64_t)front.size() != head) return fail("nasr_stream_save: header and mirror took %lld bytes, not %lld", (long long)front.size(), (long long)head);
+    memcpy(buf, front.data(), front.size());
+    memcpy((char *)buf + head, e->snap_pin.p, (size_t)section);
+    e->stream_saves++;
+    return 0;
+}
+
+extern "C" int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t bytes, nasr_stream **out) {
+    ApiGuard api_guard;
+    if (out) *out = nullptr;
+    if (!e || !buf || !out) return fail("nasr_stream_restore: null argument");
+    // everything the host can know, before any device work
+    nasr_snap::Header h;
+    nasr_snap::Mirror m;
+    std::string err;
+    if (!nasr_snap::parse((const uint8_t *)buf, bytes, h, m, err)) return fail("nasr_stream_restore: %s", err.c_str());
+    if (nasr_snap::config_mismatch(h.cfg, snapshot_config(e), err)) return fail("nasr_stream_restore: %s", err.c_str());
+    if (nasr_snap::mirror_fault(m, e->hp.num_prompts, err)) return fail("nasr_stream_restore: %s", err.c_str());
+    HIPCHK(hipSetDevice(e->device));
+    if (pipe_drain(e)) return -1;
+    int slot = -1;
+    for (int i = 0; i < e->max_streams; i++)
+        if (!e->slots[i]) { slot = i; break; }
+    if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
+    int64_t section = 0;
+    const std::vector<nasr_fork::Seg> segs = nasr_snap::snapshot_plan(m, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e), &section);
+    if ((uint64_t)section != h.device_bytes) return fail("nasr_stream_restore: device section of %lld bytes, the plan for this mirror says %lld", (long long)h.device_bytes, (long long)section);
+    if (const char *what = nasr_snap::snapshot_plan_fault(segs, slot, section)) return fail("nasr_stream_restore: bad copy plan (%s)", what);
+    const uint8_t *payload = (const uint8_t *)buf + nasr_snap::HEADER_BYTES + h.mirror_bytes;
+    if (ensure_posproj(e, 1 + m.R)) return -1;
+    nasr_stream *f = new nasr_stream();
+    f->fmt = nasr_audio_format{m.sample_rate, m.encoding, m.channels, m.channel};
+    if (!f->default_format()) {                      // plan and table from the format, as nasr_stream_set_audio_format makes them
+        nasr_rs::make_plan(f->fmt.sample_rate, &f->aud_plan);
+        if (ensure_audio_table(e, f->aud_plan, &f->aud_table)) { delete f; return -1; }
+    }
+    const auto give_up = [f](int rc) { delete f; return rc; };          // the slot was never taken: a free slot with foreign bytes in it is what every create and fork start from
+    if (ensure_snapshot_stage(e)) return give_up(-1);
+    const StreamForkPiece *dpieces;
+    int n_pieces = 0;
+    if (snapshot_pieces(e, segs, true, &dpieces, &n_pieces)) return give_up(-1);
+    const size_t table = 8 * (size_t)n_pieces;
+    if ((size_t)section + table > e->snap_stage_cap) return give_up(fail("nasr_stream_restore: the plan exceeds the snapshot bound"));
+    if (e->snap_pin.acquire((size_t)section + table, 0, e->st)) return give_up(-1);
+    memcpy(e->snap_pin.p, payload, (size_t)section);
+    if (e->snap_pin.copy_to(e->snap_stage, (size_t)section, e->st)) return give_up(-1);
+    {
+        ProfScope ps(e, "k_stream_unpack", 2.0 * (double)section);
+        launch_stream_unpack(StreamPackParams{dpieces, n_pieces, (unsigned long long *)(e->snap_stage + section)}, e->st);
+        if (hipGetLastError() != hipSuccess) return give_up(fail("nasr_stream_restore: the unpack launch failed"));
+    }
+    if (hipMemcpyAsync(e->snap_pin.p + section, e->snap_stage + section, table, hipMemcpyDeviceToHost, e->st) != hipSuccess ||
+        hipStreamSynchronize(e->st) != hipSuccess) return give_up(fail("nasr_stream_restore: reading the checksum partials failed"));
+    uint64_t sum = 0;
+    for (int i = 0; i < n_pieces; i++) { uint64_t part; memcpy(&part, e->snap_pin.p + section + 8 * (size_t)i, 8); sum += part; }
+    if (sum != h.device_sum) return give_up(fail("nasr_stream_restore: device section checksum mismatch (the snapshot is corrupted): %016llx, the header says %016llx",
+                                                 (unsigned long long)sum, (unsigned long long)h.device_sum));
+    if (nasr_snap::device_fault(payload, segs, m, e->opt_phrase_boost ? e->boost_states : 0, err)) return give_up(fail("nasr_stream_restore: %s", err.c_str()));
+    f->e = e; f->slot = slot; f->R = m.R; f->T = 1 + m.R; f->prompt = m.prompt;
+    f->abuf_cnt = m.abuf_cnt; f->abuf_par = m.abuf_par; f->mel_start = m.mel_start; f->mel_count = m.mel_count;
+    f->valid_len = m.valid_len; f->kv_head = m.kv_head; f->cc_par = m.cc_par; f->chunks = m.chunks; f->tok_read = m.tok_read; f->samples_in = m.samples_in;
+    f->last_T = 0; f->last_row = 0; f->last_ws = 0;  // the taps show what a call left: a restored stream has taken part in none
+    f->alive = true;
+    f->boost_enabled = m.boost_enabled != 0; f->lm_enabled = m.lm_enabled != 0;
+    f->tok_queue = m.tok_queue;
+    f->aud_in = m.aud_in; f->aud_out = m.aud_out; f->aud_par = m.aud_par;
+    e->slots[slot] = f;
+    stream_register(f);
+    if (e->debug) { e->tap_mel_frames[slot] = 0; e->tap_pcm_n[slot] = 0; }
+    e->stream_restores++;
+    *out = f;
+    return 0;
 }
 
 extern "C" int nasr_stream_create(nasr_engine *e, int right_context, int prompt_index, nasr_stream **out) {

@@ -11,6 +11,7 @@
 #include "nasr_decode_set.h"
 #include "nasr_step_plan.h"
 #include "nasr_fork_plan.h"
+#include "nasr_snapshot.h"
 #include "nemotron_asr_amd.h"
 
 #include <algorithm>
@@ -158,6 +159,13 @@ struct nasr_engine {
     std::map<int64_t, int64_t> graph_used;   // shape key -> tick of its last use
     int64_t graph_tick = 0, graph_evictions = 0;
     int64_t stream_forks = 0, stream_previews = 0;   // k_stream_fork launches (nasr_stream_fork and the forks of a preview) / nasr_engine_preview calls (counters of the same names)
+    // stream snapshots (nasr_snapshot.h): the device staging buffer of k_stream_pack / k_stream_unpack (payload + checksum partials; allocated
+    // by the first save or restore, sized by the snapshot bound) and the pinned block it crosses PCIe through; the fingerprints a blob carries
+    char *snap_stage = nullptr; size_t snap_stage_cap = 0;
+    PinBlock snap_pin;
+    int64_t stream_saves = 0, stream_restores = 0;   // counters of the same names
+    uint64_t fp_weights = 0;         // of the weight set, taken at nasr_engine_create (names, types, shapes, a bounded sample of the bytes)
+    uint64_t boost_fp = 0, lm_fp = 0;   // of the boost set's tables (every nasr_engine_set_boost_phrases) / the n-gram model's tables (nasr_engine_set_lm)
     int opt_fork_piece_kb = 0;       // option "fork_piece_kb" (MEASUREMENT ONLY): KiB one workgroup of k_stream_fork moves at most; 0 = nasr_fork::PIECE_BYTES
     // hipGraph replay of the steady-state step: fixed descriptor buffers + one exec per (B, T)
     std::map<int64_t, hipGraphExec_t> graphs;

@@ -15,8 +15,9 @@ enum Buf { BUF_KV = 0, BUF_CC, BUF_MEL, BUF_ABUF, BUF_LAST_SAMPLE, BUF_AUD_HIST,
 // the source stream's host mirror, as far as it says what is live (nasr_stream)
 struct Source { int kv_head, mel_start, mel_count, abuf_cnt, abuf_par; };
 
-// bytes [src, src + bytes) -> [dst, dst + bytes) of one buffer, offsets from the buffer's base; slot_bytes: what one slot owns of it
-struct Seg { int buf, layer; const char *name; char *base; int64_t src, dst, bytes, slot_bytes; };
+// bytes [src, src + bytes) -> [dst, dst + bytes) of one buffer, offsets from the buffer's base; slot_bytes: what one slot owns of it.
+// blob: the segment's offset in the device section of a snapshot (nasr_snapshot.h; a fork leaves it 0)
+struct Seg { int buf, layer; const char *name; char *base; int64_t src, dst, bytes, slot_bytes, blob = 0; };
 
 // Segments move as 16-byte vectors; the buffers below hold one 4-byte value per slot, or (aud_hist: 2 x 193 floats) slots that are no multiple
 // of 16 bytes, and move as 4-byte words
@@ -73,13 +74,18 @@ inline int64_t plan_bytes(const std::vector<Seg> &segs) {
 
 // What the engine checks before it launches: every segment lies inside its own slot's part of its buffer on both sides, and is made of
 // 16-byte vectors unless it is a word item (then of 4-byte words).  nullptr, or what is wrong
+// one side of one segment: [at, at + bytes) inside slot's part of the buffer, in whole vectors (words)
+inline const char *seg_fault(const Seg &s, int64_t at, int slot, const char *leaves) {
+    if (s.bytes <= 0 || s.slot_bytes <= 0) return "empty segment";
+    if (at < slot * s.slot_bytes || at + s.bytes > (slot + 1) * s.slot_bytes) return leaves;
+    if ((at | s.bytes) & (word_item(s.name) ? 3 : 15)) return "misaligned segment";
+    return nullptr;
+}
 inline const char *plan_fault(const std::vector<Seg> &segs, int src_slot, int dst_slot) {
     if (src_slot == dst_slot || src_slot < 0 || dst_slot < 0) return "source and destination slot must differ";
     for (const Seg &s : segs) {
-        if (s.bytes <= 0 || s.slot_bytes <= 0) return "empty segment";
-        if (s.src < src_slot * s.slot_bytes || s.src + s.bytes > (src_slot + 1) * s.slot_bytes) return "source range leaves its slot";
-        if (s.dst < dst_slot * s.slot_bytes || s.dst + s.bytes > (dst_slot + 1) * s.slot_bytes) return "destination range leaves its slot";
-        if ((s.src | s.dst | s.bytes) & (word_item(s.name) ? 3 : 15)) return "misaligned segment";
+        if (const char *what = seg_fault(s, s.src, src_slot, "source range leaves its slot")) return what;
+        if (const char *what = seg_fault(s, s.dst, dst_slot, "destination range leaves its slot")) return what;
     }
     return nullptr;
 }

@@ -162,6 +162,11 @@ void launch_stream_reset(const StreamResetParams &p, hipStream_t st);
 struct StreamForkPiece { const char *src; char *dst; uint32_t bytes, pad; };
 struct StreamForkParams { const StreamForkPiece *pieces; int n_pieces; };
 void launch_stream_fork(const StreamForkParams &p, hipStream_t st);
+// k_stream_pack / k_stream_unpack (nasr_snapshot.h): the pieces as above with pad = the index of the piece's first word in the device section;
+// sums[i] = the checksum partial of piece i
+struct StreamPackParams { const StreamForkPiece *pieces; int n_pieces; unsigned long long *sums; };
+void launch_stream_pack(const StreamPackParams &p, hipStream_t st);
+void launch_stream_unpack(const StreamPackParams &p, hipStream_t st);
 
 // audio input conversion (kernels_audio.hip, nasr_resample.h): one per stream of a launch
 struct AudioDesc {

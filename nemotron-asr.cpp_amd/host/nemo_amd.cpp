@@ -10,6 +10,7 @@
 #include "gguf_reader.h"
 #include "lm_arpa.h"
 #include "nemotron_asr_amd.h"
+#include "stream_envelope.h"
 
 using nasr_host::GgufFile;
 using nasr_host::GgufValue;
@@ -668,6 +669,69 @@ nemo_stream_context *nemo_stream_fork(nemo_stream_context *sctx) {
         return nullptr;
     }
     return f;
+}
+
+bool nemo_stream_save(nemo_stream_context *sctx, std::vector<uint8_t> &out) {
+    out.clear();
+    if (!sctx) return false;
+    nemo_env::Envelope env;
+    int64_t need = 0;
+    nasr_stream_save(sctx->stream, nullptr, 0, &need);          // the size of THIS stream's blob (an error by contract, with the size set)
+    if (need <= 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return false; }
+    env.engine_blob.resize((size_t)need);
+    if (nasr_stream_save(sctx->stream, env.engine_blob.data(), need, &need) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    env.engine_blob.resize((size_t)need);
+    env.transcript = sctx->transcript;
+    env.tokens.assign(sctx->tokens.begin(), sctx->tokens.end());
+    env.right_context = sctx->config.att_right_context; env.prompt_index = sctx->prompt_index;
+    env.audio_rate = sctx->audio_rate; env.audio_encoding = sctx->audio_encoding; env.audio_channels = sctx->audio_channels; env.audio_channel = sctx->audio_channel;
+    env.ep_on = sctx->ep_on ? 1 : 0;
+    memcpy(&env.ep_min_blank_bits, &sctx->ep_cfg.min_blank_logprob, 4);
+    env.ep_idle = sctx->ep_cfg.silence_frames_idle; env.ep_after_speech = sctx->ep_cfg.silence_frames_after_speech; env.ep_max_utterance = sctx->ep_cfg.max_utterance_frames;
+    env.ep_utt_start = sctx->ep_state.utt_start; env.ep_state_tokens = sctx->ep_state.tokens; env.ep_trailing = sctx->ep_state.trailing;
+    env.ep_frames = sctx->ep_frames; env.ep_tokens = sctx->ep_tokens;
+    for (const nasr_endpoint::Event &ev : sctx->ep_events) env.ep_events.push_back(nemo_env::Event{ev.frame, ev.utt_start, ev.rule, ev.tokens});
+    memcpy(&env.audio_seconds_bits, &sctx->total_audio_seconds, 8);
+    env.chunks_processed = sctx->total_chunks_processed;
+    nemo_env::write(env, out);
+    return true;
+}
+
+nemo_stream_context *nemo_stream_restore(nemo_context *ctx, const uint8_t *data, size_t size) {
+    if (!ctx || !data) return nullptr;
+    nemo_env::Envelope env;
+    std::string err;
+    if (!nemo_env::parse(data, (int64_t)size, env, err)) {
+        fprintf(stderr, "%s: %s\n", __func__, err.c_str());
+        return nullptr;
+    }
+    nemo_stream_context *s = new nemo_stream_context();
+    s->nctx = ctx;
+    if (nasr_stream_restore(ctx->engine, env.engine_blob.data(), (int64_t)env.engine_blob.size(), &s->stream) < 0) {      // the engine checks everything the blob says, right_context and prompt included
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        delete s;
+        return nullptr;
+    }
+    s->config.att_right_context = env.right_context;
+    s->config.att_left_context = ctx->hparams.att_left_context;
+    s->config.subsampling_factor = ctx->hparams.subsampling_factor;
+    s->config.n_mels = ctx->hparams.n_mels;
+    s->prompt_index = env.prompt_index;
+    s->audio_rate = env.audio_rate; s->audio_encoding = env.audio_encoding; s->audio_channels = env.audio_channels; s->audio_channel = env.audio_channel;
+    s->transcript = env.transcript;
+    s->tokens.assign(env.tokens.begin(), env.tokens.end());
+    s->ep_on = env.ep_on != 0;
+    memcpy(&s->ep_cfg.min_blank_logprob, &env.ep_min_blank_bits, 4);
+    s->ep_cfg.silence_frames_idle = env.ep_idle; s->ep_cfg.silence_frames_after_speech = env.ep_after_speech; s->ep_cfg.max_utterance_frames = env.ep_max_utterance;
+    s->ep_state.utt_start = env.ep_utt_start; s->ep_state.tokens = env.ep_state_tokens; s->ep_state.trailing = env.ep_trailing;
+    s->ep_frames = env.ep_frames; s->ep_tokens = env.ep_tokens;
+    for (const nemo_env::Event &ev : env.ep_events) { nasr_endpoint::Event o; o.frame = ev.frame; o.utt_start = ev.utt_start; o.rule = ev.rule; o.tokens = ev.tokens; s->ep_events.push_back(o); }
+    memcpy(&s->total_audio_seconds, &env.audio_seconds_bits, 8);
+    s->total_chunks_processed = env.chunks_processed;
+    return s;
 }
 
 std::string nemo_stream_preview(nemo_stream_context *sctx) {

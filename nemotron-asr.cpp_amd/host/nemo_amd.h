@@ -164,6 +164,14 @@ std::string nemo_stream_finalize(nemo_stream_context *sctx);
 // engine); the mirror's own transcript, tokens and endpoint detector state are copied too, and the two are independent from then on.
 // nullptr on failure (no free slot; the reason on stderr).  Free it with nemo_stream_free
 nemo_stream_context *nemo_stream_fork(nemo_stream_context *sctx);
+// MI355X extension: the stream as bytes in host memory, and a stream made from such bytes (nasr_stream_save / nasr_stream_restore: the live
+// part of the slot and the engine's mirror, checksummed) -- to park an idle stream and give its slot away, to move it to another context or
+// device, to resume it in a later process.  Around the engine's blob goes what nemo_stream_fork carries beside the engine stream:
+// transcript, tokens, language prompt, audio format, endpoint detector state and events (stream_envelope.h).  save leaves sctx as it is;
+// restore needs a context with the same model, dtype and decode options (boost set and language model included) and a free slot, and
+// returns nullptr on failure (the reason on stderr).  Free the result with nemo_stream_free
+bool nemo_stream_save(nemo_stream_context *sctx, std::vector<uint8_t> &out);
+nemo_stream_context *nemo_stream_restore(nemo_context *ctx, const uint8_t *data, size_t size);
 // MI355X extension: the text nemo_stream_finalize would add if it were called now -- the tentative tail of a caption at a long right
 // context -- without ending or changing the stream (nasr_engine_preview; it needs one free slot).  "" when nothing is buffered or on failure
 std::string nemo_stream_preview(nemo_stream_context *sctx);

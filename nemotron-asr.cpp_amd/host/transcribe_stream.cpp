@@ -25,7 +25,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--preview] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--preview] [--save-state FILE] [--load-state FILE] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
             "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
@@ -51,6 +51,13 @@ static void usage(const char *prog) {
             "                   on untouched).  NOTE: the committed transcript is held back and printed when the audio ends, so that every line which does\n"
             "                   not start with `~ ` is the output without the flag; until then only the `~ ` lines appear.  A live caption shows\n"
             "                   committed text + tail: nemo_stream_get_transcript() + nemo_stream_preview() of host/nemo_amd.h\n"
+            "  --save-state F:  at the end of the audio do NOT flush the stream: write it to F as a snapshot (nemo_stream_save: the engine's state and the\n"
+            "                   transcript so far) and print what has been transcribed so far.  --load-state F: start from such a snapshot instead of a fresh\n"
+            "                   stream, with the same model, --f32 or not, and the same --confidence / --alternatives / --endpoints / --boost-file / --lm\n"
+            "                   flags; right_context and the input format come from the snapshot.  Two runs over the two halves of a file, the first cut at a\n"
+            "                   multiple of the read size, print what one run over the whole file prints, by this rule: the FIRST line of run 1 without its\n"
+            "                   newline, followed by the first line of run 2, is the first line of the whole run; every later line of run 2 (--print-tokens,\n"
+            "                   --timestamps, --confidence, --alternatives, --endpoints) covers the whole stream and is the whole run's; run 1's later lines do not count\n"
             "  --boost-file F:  phrase boosting: one phrase per line, `phrase<TAB>bonus` (bonus optional, natural-log units added to the logits of the\n"
             "                   phrase's next token).  Words are cut into vocabulary pieces by greedy longest match; `ids:12,55,9` gives token ids literally\n"
             "  --boost-bonus X: the bonus of lines that give none (default 4.0)\n"
@@ -71,7 +78,7 @@ int main(int argc, char **argv) {
     int chunk_ms = 80, right_context = 0, device = 0, dtype = 1, positional = 0;
     const char *lang = nullptr;
     bool print_tokens = false, timestamps = false, confidence = false;
-    const char *boost_file = nullptr;
+    const char *boost_file = nullptr, *save_state = nullptr, *load_state = nullptr;
     int alternatives = 0;
     bool endpoints = false, preview = false;
     nasr_endpoint::Config ep_cfg;
@@ -96,6 +103,8 @@ int main(int argc, char **argv) {
         else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
         else if (a == "--endpoints") endpoints = true;
         else if (a == "--preview") preview = true;
+        else if (a == "--save-state" && i + 1 < argc) save_state = argv[++i];
+        else if (a == "--load-state" && i + 1 < argc) load_state = argv[++i];
         else if (a == "--endpoint-silence" && i + 1 < argc) ep_cfg.silence_frames_after_speech = (int)std::lround(atof(argv[++i]) / 0.08);
         else if (a == "--endpoint-idle" && i + 1 < argc) ep_cfg.silence_frames_idle = (int)std::lround(atof(argv[++i]) / 0.08);
         else if (a == "--endpoint-max" && i + 1 < argc) ep_cfg.max_utterance_frames = (int)std::lround(atof(argv[++i]) / 0.08);
@@ -142,6 +151,7 @@ int main(int argc, char **argv) {
             model_path, from_stdin ? "stdin" : audio_path, chunk_ms, right_context);
 
     if (preview && !diarize_gguf.empty()) { fprintf(stderr, "--preview does not go with --diarize\n"); return 1; }
+    if ((save_state || load_state) && !diarize_gguf.empty()) { fprintf(stderr, "--save-state / --load-state do not go with --diarize\n"); return 1; }
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, preview ? 2 : 1);      // a preview flushes a fork of the stream: one slot of headroom
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
@@ -157,10 +167,23 @@ int main(int argc, char **argv) {
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     nemo_cache_config cfg = nemo_cache_config::default_config();
     cfg.att_right_context = right_context;
-    nemo_stream_context *sctx = nemo_stream_init(ctx, &cfg);
+    nemo_stream_context *sctx = nullptr;
+    if (load_state) {                                  // the stream of an earlier run: its right_context, format and endpoint detector come with it
+        std::vector<uint8_t> blob;
+        FILE *sf = fopen(load_state, "rb");
+        if (!sf) { fprintf(stderr, "Failed to open the snapshot: %s\n", load_state); nemo_free(ctx); return 1; }
+        uint8_t part[65536];
+        for (size_t k; (k = fread(part, 1, sizeof(part), sf)) > 0;) blob.insert(blob.end(), part, part + k);
+        fclose(sf);
+        sctx = nemo_stream_restore(ctx, blob.data(), blob.size());
+        if (!sctx) { fprintf(stderr, "Failed to restore the stream from '%s'\n", load_state); nemo_free(ctx); return 1; }
+        if (positional >= 2 && right_context != sctx->config.att_right_context) fprintf(stderr, "note: right_context %d comes from the snapshot\n", sctx->config.att_right_context);
+        right_context = sctx->config.att_right_context;
+        cfg.att_right_context = right_context;
+    } else sctx = nemo_stream_init(ctx, &cfg);
     if (!sctx) { fprintf(stderr, "Failed to create streaming context\n"); nemo_free(ctx); return 1; }
 
-    if (endpoints && !nemo_stream_set_endpointing(sctx, &ep_cfg)) { fprintf(stderr, "Failed to enable endpointing\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
+    if (endpoints && !load_state && !nemo_stream_set_endpointing(sctx, &ep_cfg)) { fprintf(stderr, "Failed to enable endpointing\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
 
     diarize_pipeline *dp = nullptr;
     if (!diarize_gguf.empty()) {                       // reference :146-170
@@ -227,7 +250,13 @@ int main(int argc, char **argv) {
     }
     if (in_channel == -2) in_channel = in_channels > 1 ? -1 : 0;
     const bool own_format = !(in_rate == 16000 && in_enc == NASR_AUDIO_S16 && in_channels == 1 && in_channel == 0);
-    if (own_format) {
+    if (load_state) {
+        if (in_rate != sctx->audio_rate || in_enc != sctx->audio_encoding || in_channels != sctx->audio_channels || in_channel != sctx->audio_channel) {
+            fprintf(stderr, "The snapshot's stream takes %d Hz, encoding %d, %d channel(s), channel %d: give the same --input-* flags\n", sctx->audio_rate, sctx->audio_encoding, sctx->audio_channels, sctx->audio_channel);
+            nemo_stream_free(sctx); nemo_free(ctx);
+            return 1;
+        }
+    } else if (own_format) {
         if (dp) { fprintf(stderr, "--diarize takes s16le 16 kHz mono audio\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
         if (!nemo_stream_set_audio_format(sctx, in_rate, in_enc, in_channels, in_channel)) { fprintf(stderr, "Unsupported input format\n"); nemo_stream_free(sctx); nemo_free(ctx); return 1; }
         fprintf(stderr, "  Input:          %d Hz, encoding %d, %d channel(s), channel %d (converted on the GPU)\n\n", in_rate, in_enc, in_channels, in_channel);
@@ -260,7 +289,16 @@ int main(int argc, char **argv) {
         }
         if (have < want || data_left == 0) break;
     }
-    handle_text(nemo_stream_finalize(sctx), total);
+    if (save_state) {                                  // no flush: the stream goes on in a later run
+        std::vector<uint8_t> blob;
+        FILE *sf = nemo_stream_save(sctx, blob) ? fopen(save_state, "wb") : nullptr;
+        if (!sf || fwrite(blob.data(), 1, blob.size(), sf) != blob.size() || fclose(sf) != 0) {
+            fprintf(stderr, "Failed to write the snapshot: %s\n", save_state);
+            nemo_stream_free(sctx); nemo_free(ctx);
+            return 1;
+        }
+        fprintf(stderr, "Wrote snapshot: %s (%zu bytes)\n", save_state, blob.size());
+    } else handle_text(nemo_stream_finalize(sctx), total);
     fputs(held.c_str(), stdout);
     printf("\n");
     if (!from_stdin) fclose(in);

@@ -39,6 +39,16 @@ def max_over_ranks(dist, value: float, device="cpu") -> float:
     return float(t.item())
 
 
+def migrate(stream, dst_engine):
+    """Moves a live stream (capi.Stream) to another engine -- on this device or another -- and returns the stream that continues there:
+    save, restore into dst_engine, destroy the source.  The placement rule above says where a stream STARTS; this is how it is rebalanced or
+    a device drained.  dst_engine must agree with the source's engine (weights, dtype, decode options, boost set, language model).  If the
+    restore fails (no free slot, a mismatch) the error is raised and the source stream is still alive and unchanged."""
+    moved = dst_engine.restore(stream.save())
+    stream.destroy()
+    return moved
+
+
 def aggregate_rtfx(world: int, audio_s_per_rank: float, elapsed_max: float) -> float:
     """Whole-job audio seconds per wall second (weak scaling: every rank processes its own audio)."""
     return world * audio_s_per_rank / elapsed_max
