@@ -58,6 +58,15 @@ static int upload_lm(nasr_engine *e, const nasr_lm_desc *d) {
     return 0;
 }
 
+// engine option "lm_fusion": the bias rows (LM term + phrase bonus) of slots slot0 .. slot0 + n - 1 recomputed from their states, and waited for
+static int refresh_lm_rows(nasr_engine *e, int slot0, int n) {
+    launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->dec.boost_state : nullptr,
+                   slot0, n, e->st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->st));
+    return 0;
+}
+
 // engine option "lm_fusion": rewrites the block the decode kernels read from the engine's model and greedy weights and recomputes the bias rows
 // of every slot in one launch -- after the states were put back to the model's start (restart: a new or detached model) or with the states
 // kept (new weights, a new phrase set: the automaton states were reset by their own setter).  The caller has completed the steps in flight
@@ -73,11 +82,7 @@ static int refresh_greedy_lm(nasr_engine *e, bool restart) {
         for (int i = 0; i < e->max_streams; i++) st[(size_t)i] = nasr_lm::greedy_start(g, !e->slots[i] || e->slots[i]->lm_enabled);
         HIPCHK(hipMemcpy(e->dec.lm_state, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->dec.boost_state : nullptr,
-                   0, e->max_streams, e->st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->st));
-    return 0;
+    return refresh_lm_rows(e, 0, e->max_streams);
 }
 }  // namespace nasr_eng
 
@@ -122,11 +127,7 @@ extern "C" int nasr_stream_set_lm(nasr_stream *s, int enable) {
     const int32_t state = nasr_lm::greedy_start(g, enable != 0);      // either way an empty history
     HIPCHK(hipMemcpy(e->dec.lm_state + s->slot, &state, sizeof(state), hipMemcpyHostToDevice));
     s->lm_enabled = enable != 0;
-    launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->opt_phrase_boost ? e->boost_bonus : nullptr, e->opt_phrase_boost ? e->dec.boost_state : nullptr,
-                   s->slot, 1, e->st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->st));
-    return 0;
+    return refresh_lm_rows(e, s->slot, 1);
 }
 
 extern "C" int nasr_engine_set_lm_weights(nasr_engine *e, float weight, float token_bonus) {
@@ -159,12 +160,7 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
     const int state = enable ? nasr_boost::STATE_ROOT : nasr_boost::STATE_OFF;      // either way an empty history
     HIPCHK(hipMemcpy(e->dec.boost_state + s->slot, &state, sizeof(int), hipMemcpyHostToDevice));
     s->boost_enabled = enable != 0;
-    if (e->opt_lm_fusion) {                                    // the slot's bias row carries the phrase bonus
-        launch_lm_rows(e->lm_blk, e->dec.lm_state, e->dec.lm_row, e->dec.lm_next, e->boost_bonus, e->dec.boost_state, s->slot, 1, e->st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(e->st));
-    }
-    return 0;
+    return e->opt_lm_fusion ? refresh_lm_rows(e, s->slot, 1) : 0;      // the slot's bias row carries the phrase bonus
 }
 
 // The decode options.  Each picks the decode launches that get captured into the step graphs and adds what they read to e->dec (or, engine-wide: the
@@ -562,7 +558,7 @@ int audio_flush(nasr_engine *e, nasr_stream *const *streams, int B) {
     double flops = 0;
     for (int b = 0; b < B; b++) {
         nasr_stream *s = streams[b];
-        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt, s->aud_table);
+        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt(), s->aud_table);
         const long long n = s->default_format() ? 0 : nasr_rs::out_total(s->aud_plan, s->aud_in) - s->aud_out;
         descs[b].hist = e->aud_hist + (size_t)s->slot * 2 * nasr_rs::HIST_MAX; descs[b].par = s->aud_par;
         descs[b].n_before = s->aud_in; descs[b].n_push = 0; descs[b].out_first = s->aud_out; descs[b].n_out = n > 0 ? n : 0;
@@ -574,19 +570,25 @@ int audio_flush(nasr_engine *e, nasr_stream *const *streams, int B) {
     return step_tail(e, streams, B, base.data(), n16.data(), nullptr, nullptr, nullptr, NASR_FLAG_NO_SYNC);
 }
 
+// the flags a step entry does not take
+static int refuse_offline_flags(uint32_t flags) {
+    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
+    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
+    return 0;
+}
+
 }  // namespace nasr_eng
 extern "C" int nasr_engine_step(nasr_engine *e, nasr_stream *const *streams, int B, const int16_t *const *pcm,
                                 const int32_t *n_samples, int32_t *const *tokens_out, const int32_t *tokens_cap,
                                 int32_t *n_tokens, uint32_t flags) {
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
-    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
-    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
+    if (refuse_offline_flags(flags)) return -1;
     if (!pcm || !n_samples) return fail("null pcm / n_samples");
     for (int b = 0; b < B; b++)
         if (!streams[b]->default_format())
             return fail("stream %d has an audio format of its own (%d Hz, encoding %d, %d channel(s)): push it with nasr_engine_step_audio", b,
-                        streams[b]->fmt.sample_rate, streams[b]->fmt.encoding, streams[b]->fmt.channels);
+                        streams[b]->sample_rate, streams[b]->encoding, streams[b]->channels);
     HIPCHK(hipSetDevice(e->device));
     return step_s16(e, streams, B, pcm, n_samples, tokens_out, tokens_cap, n_tokens, flags);
 }
@@ -628,7 +630,8 @@ extern "C" int nasr_stream_set_audio_format(nasr_stream *s, const nasr_audio_for
     nasr_rs::make_plan(f->sample_rate, &p);
     const float *table = nullptr;
     if (ensure_audio_table(e, p, &table)) return -1;
-    s->fmt = *f; s->aud_plan = p; s->aud_table = table;
+    s->sample_rate = f->sample_rate; s->encoding = f->encoding; s->channels = f->channels; s->channel = f->channel;
+    s->aud_plan = p; s->aud_table = table;
     return 0;
 }
 
@@ -637,8 +640,7 @@ extern "C" int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *stream
                                       int32_t *n_tokens, uint32_t flags) {
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
-    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
-    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
+    if (refuse_offline_flags(flags)) return -1;
     if (!audio || !n_frames) return fail("null audio / n_frames");
     HIPCHK(hipSetDevice(e->device));
     bool all_default = true;
@@ -652,15 +654,15 @@ extern "C" int nasr_engine_step_audio(nasr_engine *e, nasr_stream *const *stream
         nasr_stream *s = streams[b];
         if (n_frames[b] < 0) return fail("negative n_frames");
         if (n_frames[b] > 0 && !audio[b]) return fail("null audio for stream %d", b);
-        if ((flags & NASR_FLAG_PCM_DEVICE) && ((uintptr_t)audio[b] % (size_t)nasr_rs::bytes_per_sample(s->fmt.encoding)))
+        if ((flags & NASR_FLAG_PCM_DEVICE) && ((uintptr_t)audio[b] % (size_t)nasr_rs::bytes_per_sample(s->encoding)))
             return fail("stream %d: device audio must be naturally aligned (2 bytes for s16, 4 for f32)", b);
         if (!s->aud_table && ensure_audio_table(e, s->aud_plan, &s->aud_table)) return -1;      // a default-format stream beside the others
         const long long n_out = std::max<long long>(0, nasr_rs::out_ready(s->aud_plan, s->aud_in + n_frames[b]) - s->aud_out);
         if (n_out > INT32_MAX) return fail("stream %d: the push completes more than 2^31 samples", b);
-        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt, s->aud_table);
+        fill_audio_desc(e, descs[b], s->aud_plan, s->fmt(), s->aud_table);
         descs[b].hist = e->aud_hist + (size_t)s->slot * 2 * nasr_rs::HIST_MAX; descs[b].par = s->aud_par;
         descs[b].n_before = s->aud_in; descs[b].n_push = n_frames[b]; descs[b].out_first = s->aud_out; descs[b].n_out = n_out;
-        raw_bytes[b] = (size_t)n_frames[b] * s->fmt.channels * nasr_rs::bytes_per_sample(s->fmt.encoding);
+        raw_bytes[b] = (size_t)n_frames[b] * s->channels * nasr_rs::bytes_per_sample(s->encoding);
         raw_off[b] = raw_total;
         raw_total += (raw_bytes[b] + 15) & ~(size_t)15;
         flops += audio_flops(s->aud_plan, (double)n_out);
@@ -740,8 +742,7 @@ extern "C" int nasr_engine_step_mel(nasr_engine *e, nasr_stream *const *streams,
                                     int32_t *n_tokens, uint32_t flags) {
     ApiGuard api_guard;
     if (validate_batch(e, streams, B)) return -1;
-    if (flags & NASR_FLAG_NO_BOOST) return fail("NASR_FLAG_NO_BOOST belongs to the offline entries; a stream is switched with nasr_stream_set_boost");
-    if (flags & NASR_FLAG_NO_LM) return fail("NASR_FLAG_NO_LM belongs to the offline entries; a stream is switched with nasr_stream_set_lm");
+    if (refuse_offline_flags(flags)) return -1;
     if (!mel || !n_frames) return fail("null mel / n_frames");
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
@@ -908,92 +909,78 @@ extern "C" int nasr_engine_collect(nasr_engine *e, nasr_stream *const *streams, 
     return collect_tokens(e, streams, B, tokens_out, tokens_cap, n_tokens);
 }
 
-extern "C" int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t count, int32_t *frames_out) {
-    ApiGuard api_guard;
-    if (!s || (count > 0 && !frames_out)) return fail("null argument");
-    if (first < 0 || count < 0) return fail("negative token range");
+// ---- the read-out rings of the device decode: token frames, token log-probabilities, per-frame blank log-probabilities, top-K alternatives.
+// One read for the four getters: the steps in flight completed and the slot's DecCtrl fetched (ring_ctrl), the range clamped to what the
+// device has produced or found older than the ring (nasr_step::ring_window), the slot's ring copied and un-wrapped (ring_copy).  The getters
+// keep what differs: the option that gates them, what counts as produced, and what "older than the ring" returns
+namespace nasr_eng {
+static int ring_ctrl(const nasr_stream *s, DecCtrl &c) {
     nasr_engine *e = s->e;
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
     HIPCHK(hipStreamSynchronize(e->st));
-    DecCtrl c;
     HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
-    if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
-    if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
+    return 0;
+}
+// items first .. first + count - 1 of the slot's ring of cap items (a power of two) of `stride` elements each -> out; returns count
+template <typename Tp>
+static int ring_copy(const nasr_stream *s, const Tp *rings, int cap, int stride, int64_t first, int count, Tp *out) {
     if (count <= 0) return 0;
-    std::vector<int> ring(TOK_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->dec.tok_frame + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(int), hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; i++) frames_out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
+    std::vector<Tp> ring((size_t)cap * stride);
+    HIPCHK(hipMemcpy(ring.data(), rings + (size_t)s->slot * ring.size(), ring.size() * sizeof(Tp), hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; i++) memcpy(out + (size_t)i * stride, ring.data() + (size_t)((first + i) & (cap - 1)) * stride, (size_t)stride * sizeof(Tp));
     return count;
+}
+// the clamped range of a per-token ring, or the refusal of one whose first token has left it
+static int token_window(const DecCtrl &c, int64_t first, int count) {
+    count = ring_window(first, count, c.n_tok, TOK_CAP);
+    return count == RING_TOO_OLD ? fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP) : count;
+}
+}  // namespace nasr_eng
+
+extern "C" int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t count, int32_t *frames_out) {
+    ApiGuard api_guard;
+    if (!s || (count > 0 && !frames_out)) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative token range");
+    DecCtrl c;
+    if (ring_ctrl(s, c) || (count = token_window(c, first, count)) < 0) return -1;
+    return ring_copy(s, s->e->dec.tok_frame, TOK_CAP, 1, first, count, frames_out);
 }
 
 extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out) {
     ApiGuard api_guard;
     if (!s || (count > 0 && !out)) return fail("null argument");
     if (first < 0 || count < 0) return fail("negative token range");
-    nasr_engine *e = s->e;
-    if (!e->opt_token_logprobs) return fail("no token log-probabilities: engine option \"token_logprobs\" is off (set it to 1 before the first step)");
-    HIPCHK(hipSetDevice(e->device));
-    if (pipe_drain(e)) return -1;
-    HIPCHK(hipStreamSynchronize(e->st));
+    if (!s->e->opt_token_logprobs) return fail("no token log-probabilities: engine option \"token_logprobs\" is off (set it to 1 before the first step)");
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
-    if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
-    if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
-    if (count <= 0) return 0;
-    std::vector<float> ring(TOK_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->dec.tok_logprob + (size_t)s->slot * TOK_CAP, TOK_CAP * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (TOK_CAP - 1))];
-    return count;
+    if (ring_ctrl(s, c) || (count = token_window(c, first, count)) < 0) return -1;
+    return ring_copy(s, s->e->dec.tok_logprob, TOK_CAP, 1, first, count, out);
 }
 
 extern "C" int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out) {
     ApiGuard api_guard;
     if (!s) return fail("null argument");
     if (first < 0 || count < 0) return fail("negative frame range");
-    nasr_engine *e = s->e;
-    if (!e->opt_frame_blank) return fail("no per-frame blank log-probabilities: engine option \"frame_blank_logprobs\" is off (set it to 1 before the first step)");
-    HIPCHK(hipSetDevice(e->device));
-    if (pipe_drain(e)) return -1;
-    HIPCHK(hipStreamSynchronize(e->st));
+    if (!s->e->opt_frame_blank) return fail("no per-frame blank log-probabilities: engine option \"frame_blank_logprobs\" is off (set it to 1 before the first step)");
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    if (ring_ctrl(s, c)) return -1;
     const int64_t n_frames = (int64_t)c.frame0 + c.t;          // frames the decode has left since create / reset
     if (!out) return (int)n_frames;
-    if (first + count > n_frames) count = first < n_frames ? (int32_t)(n_frames - first) : 0;
-    if (n_frames - first > FRAME_CAP) return 0;               // the range starts before the most recent FRAME_CAP frames: nothing of it can be written from its first frame on
-    if (count <= 0) return 0;
-    std::vector<float> ring(FRAME_CAP);
-    HIPCHK(hipMemcpy(ring.data(), e->dec.frame_blank + (size_t)s->slot * FRAME_CAP, FRAME_CAP * sizeof(float), hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; i++) out[i] = ring[(size_t)((first + i) & (FRAME_CAP - 1))];
-    return count;
+    count = ring_window(first, count, n_frames, FRAME_CAP);
+    if (count == RING_TOO_OLD) return 0;                       // the range starts before the most recent FRAME_CAP frames: nothing of it can be written from its first frame on
+    return ring_copy(s, s->e->dec.frame_blank, FRAME_CAP, 1, first, count, out);
 }
 
 extern "C" int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t first, int32_t count, int32_t *ids_out, float *logprobs_out) {
     ApiGuard api_guard;
     if (!s || (count > 0 && (!ids_out || !logprobs_out))) return fail("null argument");
     if (first < 0 || count < 0) return fail("negative token range");
-    nasr_engine *e = s->e;
-    const int K = e->opt_token_alt;
+    const int K = s->e->opt_token_alt;
     if (!K) return fail("no token alternatives: engine option \"token_alternatives\" is off (set it to K = 1 .. 8 before the first step)");
-    HIPCHK(hipSetDevice(e->device));
-    if (pipe_drain(e)) return -1;
-    HIPCHK(hipStreamSynchronize(e->st));
     DecCtrl c;
-    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
-    if (first + count > c.n_tok) count = first < c.n_tok ? (int32_t)(c.n_tok - first) : 0;
-    if (count > 0 && c.n_tok - first > TOK_CAP) return fail("token %lld is older than the %d-token device ring", (long long)first, TOK_CAP);
-    if (count <= 0) return 0;
-    std::vector<int32_t> ids((size_t)TOK_CAP * K);
-    std::vector<float> lps((size_t)TOK_CAP * K);
-    HIPCHK(hipMemcpy(ids.data(), e->dec.alt_id + (size_t)s->slot * TOK_CAP * K, ids.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lps.data(), e->dec.alt_lp + (size_t)s->slot * TOK_CAP * K, lps.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; i++) {
-        const size_t at = (size_t)((first + i) & (TOK_CAP - 1)) * K;
-        memcpy(ids_out + (size_t)i * K, ids.data() + at, (size_t)K * 4);
-        memcpy(logprobs_out + (size_t)i * K, lps.data() + at, (size_t)K * 4);
-    }
-    return count;
+    if (ring_ctrl(s, c) || (count = token_window(c, first, count)) < 0) return -1;
+    if (ring_copy(s, s->e->dec.alt_id, TOK_CAP, K, first, count, ids_out) < 0) return -1;
+    return ring_copy(s, s->e->dec.alt_lp, TOK_CAP, K, first, count, logprobs_out);
 }
 
 // host-side counters.  Walks the graph caches without a lock: call it from the thread that steps the engine (as every entry point that

@@ -703,23 +703,16 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     rp.aud_hist = e->aud_hist;
     launch_stream_reset(rp, e->st);
     HIPCHK(hipGetLastError());
-    if (!keep_reference_state) {
-        s->abuf_cnt = NFFT / 2;                // 256 zero samples pre-seeded, src/preprocessor.cpp:220-221
-        s->abuf_par = 0;
-        s->kv_head = 0;
-        s->cc_par = 0;
-    }
-    s->mel_start = 0;
-    s->mel_count = PRE_CACHE;                  // 9 literal-zero frames, src/nemo-stream.cpp:73-74 (reset: :100-102)
-    s->valid_len = 0;                          // :81 (reset: :112)
-    s->chunks = 0;
-    s->tok_read = 0;
-    s->samples_in = 0;
-    s->aud_in = s->aud_out = 0;                // the audio converter starts over in both modes; the format stays
-    s->aud_par = 0;
+    nasr_snap::reset_state(*s, keep_reference_state);      // the host's half: the rules are the record's
     s->last_T = 0;
     s->last_ws = 0;
     return 0;
+}
+
+static int free_slot(const nasr_engine *e) {       // the lowest one, -1: the pool is full
+    for (int i = 0; i < e->max_streams; i++)
+        if (!e->slots[i]) return i;
+    return -1;
 }
 
 // the streams that exist, of every engine of the process: nasr_stream_fork is handed a pointer and must be able to refuse a destroyed one
@@ -734,28 +727,35 @@ bool stream_is_live(const nasr_stream *s) { std::lock_guard<std::mutex> lk(g_str
 // Everything a stream is lives in its slot of the pools and in its host mirror, and the step graphs take the slot from their RowDesc: a
 // fork is a copy of the mirror with another slot number, and a copy of the LIVE part of the slot (at bf16 and 24 layers 8.6 MB of the
 // slot's 38 MB).  Nothing is allocated (the piece table goes through the descriptor arena), no graph is captured or invalidated.
+// the base address a plan segment's offsets count from: the engine's pools, or the DecodeSet buffer the plan named itself (nullptr: not allocated)
+static char *seg_base(const nasr_engine *e, const nasr_fork::Seg &s) {
+    switch (s.buf) {
+    case nasr_fork::BUF_KV: return (char *)e->kv_pool[s.layer];
+    case nasr_fork::BUF_CC: return (char *)e->cc_pool[s.layer];
+    case nasr_fork::BUF_MEL: return (char *)e->mel_ring;
+    case nasr_fork::BUF_ABUF: return (char *)e->abuf;
+    case nasr_fork::BUF_LAST_SAMPLE: return (char *)e->last_sample;
+    case nasr_fork::BUF_AUD_HIST: return (char *)e->aud_hist;
+    default: return s.base;
+    }
+}
+// a stream made by a fork or a restore becomes visible: its slot, the registry; the taps show what a call left, and it has taken part in none
+static void publish_stream(nasr_engine *e, nasr_stream *f, int slot) {
+    e->slots[slot] = f;
+    stream_register(f);
+    if (e->debug) { e->tap_mel_frames[slot] = 0; e->tap_pcm_n[slot] = 0; }
+}
+
 int stream_fork(nasr_stream *src, nasr_stream **out) {
     nasr_engine *e = src->e;
-    int slot = -1;
-    for (int i = 0; i < e->max_streams; i++)
-        if (!e->slots[i]) { slot = i; break; }
+    const int slot = free_slot(e);
     if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
-    const nasr_fork::Source live = {src->kv_head, src->mel_start, src->mel_count, src->abuf_cnt, src->abuf_par};
-    const std::vector<nasr_fork::Seg> segs = nasr_fork::fork_plan(live, src->slot, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e));
+    const std::vector<nasr_fork::Seg> segs = nasr_fork::fork_plan(nasr_snap::live_part(*src), src->slot, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e));
     if (const char *what = nasr_fork::plan_fault(segs, src->slot, slot)) return fail("nasr_stream_fork: bad copy plan (%s)", what);
     const int64_t piece_bytes = e->opt_fork_piece_kb > 0 ? (int64_t)e->opt_fork_piece_kb * 1024 : nasr_fork::PIECE_BYTES;
     std::vector<StreamForkPiece> pieces;
     for (const nasr_fork::Seg &s : segs) {
-        char *base = s.base;
-        switch (s.buf) {
-        case nasr_fork::BUF_KV: base = (char *)e->kv_pool[s.layer]; break;
-        case nasr_fork::BUF_CC: base = (char *)e->cc_pool[s.layer]; break;
-        case nasr_fork::BUF_MEL: base = (char *)e->mel_ring; break;
-        case nasr_fork::BUF_ABUF: base = (char *)e->abuf; break;
-        case nasr_fork::BUF_LAST_SAMPLE: base = (char *)e->last_sample; break;
-        case nasr_fork::BUF_AUD_HIST: base = (char *)e->aud_hist; break;
-        default: break;
-        }
+        char *base = seg_base(e, s);
         if (!base) return fail("nasr_stream_fork: buffer '%s' is not allocated", s.name);
         nasr_fork::cut_pieces(pieces, s, base, piece_bytes);
     }
@@ -766,12 +766,10 @@ int stream_fork(nasr_stream *src, nasr_stream **out) {
         launch_stream_fork(StreamForkParams{dpieces, (int)pieces.size()}, e->st);
         HIPCHK(hipGetLastError());
     }
-    nasr_stream *f = new nasr_stream(*src);          // right_context, prompt, audio format and plan, boost / LM flags, every counter, the queued tokens
+    nasr_stream *f = new nasr_stream(*src);          // the whole record (the queued tokens with it), the audio plan and table
     f->slot = slot;
     f->last_T = 0;                                   // the taps show what a call left for its own slots and rows: a fork has taken part in none
-    e->slots[slot] = f;
-    stream_register(f);
-    if (e->debug) { e->tap_mel_frames[slot] = 0; e->tap_pcm_n[slot] = 0; }
+    publish_stream(e, f, slot);
     e->stream_forks++;
     *out = f;
     return 0;
@@ -806,30 +804,11 @@ static nasr_snap::Config snapshot_config(const nasr_engine *e) {
     }
     return nasr_snap::make_config(e->dtype, e->esz, e->hp.n_layers, e->hp.kernel_size, f, e->fp_weights, f.phrase_boost ? e->boost_fp : 0, fp_lm);
 }
-static nasr_snap::Mirror snapshot_mirror(const nasr_stream *s) {
-    nasr_snap::Mirror m;
-    m.R = s->R; m.prompt = s->prompt; m.abuf_cnt = s->abuf_cnt; m.abuf_par = s->abuf_par; m.mel_start = s->mel_start; m.mel_count = s->mel_count;
-    m.valid_len = s->valid_len; m.kv_head = s->kv_head; m.cc_par = s->cc_par; m.chunks = s->chunks; m.tok_read = s->tok_read; m.samples_in = s->samples_in;
-    m.boost_enabled = s->boost_enabled ? 1 : 0; m.lm_enabled = s->lm_enabled ? 1 : 0;
-    m.sample_rate = s->fmt.sample_rate; m.encoding = s->fmt.encoding; m.channels = s->fmt.channels; m.channel = s->fmt.channel;
-    m.aud_in = s->aud_in; m.aud_out = s->aud_out; m.aud_par = s->aud_par;
-    m.tok_queue = s->tok_queue;
-    return m;
-}
 // the pieces of a pack / unpack launch between slot and staging, through the descriptor arena
 static int snapshot_pieces(nasr_engine *e, const std::vector<nasr_fork::Seg> &segs, bool unpack, const StreamForkPiece **dev, int *n) {
     std::vector<StreamForkPiece> pieces;
     for (const nasr_fork::Seg &s : segs) {
-        char *base = s.base;
-        switch (s.buf) {
-        case nasr_fork::BUF_KV: base = (char *)e->kv_pool[s.layer]; break;
-        case nasr_fork::BUF_CC: base = (char *)e->cc_pool[s.layer]; break;
-        case nasr_fork::BUF_MEL: base = (char *)e->mel_ring; break;
-        case nasr_fork::BUF_ABUF: base = (char *)e->abuf; break;
-        case nasr_fork::BUF_LAST_SAMPLE: base = (char *)e->last_sample; break;
-        case nasr_fork::BUF_AUD_HIST: base = (char *)e->aud_hist; break;
-        default: break;
-        }
+        char *base = seg_base(e, s);
         if (!base) return fail("stream snapshot: buffer '%s' is not allocated", s.name);
         nasr_snap::cut_snapshot_pieces(pieces, s, base, e->snap_stage, nasr_fork::PIECE_BYTES, unpack);
     }
@@ -867,7 +846,7 @@ extern "C" int nasr_stream_save(nasr_stream *s, void *buf, int64_t cap, int64_t 
     nasr_engine *e = s->e;
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
-    const nasr_snap::Mirror m = snapshot_mirror(s);
+    const nasr_snap::Mirror &m = *s;                 // the stream is the record
     int64_t section = 0;
     const std::vector<nasr_fork::Seg> segs = nasr_snap::snapshot_plan(m, s->slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e), &section);
     if (const char *what = nasr_snap::snapshot_plan_fault(segs, s->slot, section)) return fail("nasr_stream_save: bad copy plan (%s)", what);
@@ -917,9 +896,7 @@ extern "C" int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t byte
     if (nasr_snap::mirror_fault(m, e->hp.num_prompts, err)) return fail("nasr_stream_restore: %s", err.c_str());
     HIPCHK(hipSetDevice(e->device));
     if (pipe_drain(e)) return -1;
-    int slot = -1;
-    for (int i = 0; i < e->max_streams; i++)
-        if (!e->slots[i]) { slot = i; break; }
+    const int slot = free_slot(e);
     if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
     int64_t section = 0;
     const std::vector<nasr_fork::Seg> segs = nasr_snap::snapshot_plan(m, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e), &section);
@@ -927,10 +904,11 @@ extern "C" int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t byte
     if (const char *what = nasr_snap::snapshot_plan_fault(segs, slot, section)) return fail("nasr_stream_restore: bad copy plan (%s)", what);
     const uint8_t *payload = (const uint8_t *)buf + nasr_snap::HEADER_BYTES + h.mirror_bytes;
     if (ensure_posproj(e, 1 + m.R)) return -1;
-    nasr_stream *f = new nasr_stream();
-    f->fmt = nasr_audio_format{m.sample_rate, m.encoding, m.channels, m.channel};
+    nasr_stream *f = new nasr_stream();              // the taps show what a call left: a restored stream has taken part in none (last_* = 0)
+    static_cast<nasr_snap::Mirror &>(*f) = m;        // the record, in one assignment; then what is not state
+    f->e = e; f->slot = slot; f->T = 1 + m.R; f->alive = true;
     if (!f->default_format()) {                      // plan and table from the format, as nasr_stream_set_audio_format makes them
-        nasr_rs::make_plan(f->fmt.sample_rate, &f->aud_plan);
+        nasr_rs::make_plan(f->sample_rate, &f->aud_plan);
         if (ensure_audio_table(e, f->aud_plan, &f->aud_table)) { delete f; return -1; }
     }
     const auto give_up = [f](int rc) { delete f; return rc; };          // the slot was never taken: a free slot with foreign bytes in it is what every create and fork start from
@@ -955,17 +933,7 @@ extern "C" int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t byte
     if (sum != h.device_sum) return give_up(fail("nasr_stream_restore: device section checksum mismatch (the snapshot is corrupted): %016llx, the header says %016llx",
                                                  (unsigned long long)sum, (unsigned long long)h.device_sum));
     if (nasr_snap::device_fault(payload, segs, m, e->opt_phrase_boost ? e->boost_states : 0, err)) return give_up(fail("nasr_stream_restore: %s", err.c_str()));
-    f->e = e; f->slot = slot; f->R = m.R; f->T = 1 + m.R; f->prompt = m.prompt;
-    f->abuf_cnt = m.abuf_cnt; f->abuf_par = m.abuf_par; f->mel_start = m.mel_start; f->mel_count = m.mel_count;
-    f->valid_len = m.valid_len; f->kv_head = m.kv_head; f->cc_par = m.cc_par; f->chunks = m.chunks; f->tok_read = m.tok_read; f->samples_in = m.samples_in;
-    f->last_T = 0; f->last_row = 0; f->last_ws = 0;  // the taps show what a call left: a restored stream has taken part in none
-    f->alive = true;
-    f->boost_enabled = m.boost_enabled != 0; f->lm_enabled = m.lm_enabled != 0;
-    f->tok_queue = m.tok_queue;
-    f->aud_in = m.aud_in; f->aud_out = m.aud_out; f->aud_par = m.aud_par;
-    e->slots[slot] = f;
-    stream_register(f);
-    if (e->debug) { e->tap_mel_frames[slot] = 0; e->tap_pcm_n[slot] = 0; }
+    publish_stream(e, f, slot);
     e->stream_restores++;
     *out = f;
     return 0;
@@ -978,12 +946,10 @@ extern "C" int nasr_stream_create(nasr_engine *e, int right_context, int prompt_
     if (right_context != 0 && right_context != 1 && right_context != 6 && right_context != 13)
         return fail("right_context must be 0, 1, 6 or 13 (src/nemo-stream.h:15-20), got %d", right_context);
     HIPCHK(hipSetDevice(e->device));
-    int slot = -1;
-    for (int i = 0; i < e->max_streams; i++)
-        if (!e->slots[i]) { slot = i; break; }
+    const int slot = free_slot(e);
     if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
     if (ensure_posproj(e, 1 + right_context)) return -1;
-    nasr_stream *s = new nasr_stream();
+    nasr_stream *s = new nasr_stream();              // a default record; stream_zero_state puts it through the fresh reset
     s->e = e; s->slot = slot; s->R = right_context; s->T = 1 + right_context;
     s->prompt = e->hp.num_prompts > 0 ? prompt_index : -1;
     s->alive = true;
@@ -1000,7 +966,6 @@ extern "C" int nasr_stream_reset_ex(nasr_stream *s, int mode) {
     if (mode != NASR_RESET_FRESH && mode != NASR_RESET_REFERENCE) return fail("unknown reset mode %d", mode);
     HIPCHK(hipSetDevice(s->e->device));
     if (pipe_drain(s->e)) return -1;
-    s->tok_queue.clear();
     return stream_zero_state(s, mode == NASR_RESET_REFERENCE);
 }
 

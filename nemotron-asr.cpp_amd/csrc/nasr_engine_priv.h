@@ -99,28 +99,19 @@ struct Prof {
     }
 };
 
-struct nasr_stream {
-    nasr_engine *e;
-    int slot, R, T, prompt;
-    // host mirror of the stream manager state (reference nemo_stream_context)
-    int abuf_cnt, abuf_par;          // samples waiting in the audio buffer (pre-seeded 256 zeros)
-    int mel_start, mel_count;        // mel ring window
-    int valid_len, kv_head, cc_par;  // cache_valid_len, K/V ring head, conv-cache parity
-    int chunks, tok_read;
-    int64_t samples_in;
-    int last_T, last_row, last_ws;   // rows of the last chunk and the workspace set they are in (for taps)
-    bool alive;
-    bool boost_enabled = true;       // nasr_stream_set_boost (engine option "phrase_boost")
-    bool lm_enabled = true;          // nasr_stream_set_lm (engine option "lm_fusion")
-    std::vector<int32_t> tok_queue;  // tokens gathered from the device, not yet handed to the caller
-    // audio input conversion (nasr_stream_set_audio_format, nasr_resample.h): the format survives a reset, the counters and the parity do not
-    nasr_audio_format fmt = {16000, NASR_AUDIO_S16, 1, 0};
+// A stream is the record of what it is (nasr_snap::Mirror: the host mirror of the stream manager state, reference nemo_stream_context --
+// the one declaration create, reset, fork, save and restore share) plus what is not state
+struct nasr_stream : nasr_snap::Mirror {
+    nasr_engine *e = nullptr;
+    int slot = 0, T = 1;                           // T = 1 + R
+    int last_T = 0, last_row = 0, last_ws = 0;     // rows of the last chunk and the workspace set they are in (for taps)
+    bool alive = false;
+    // audio input conversion (nasr_resample.h): recomputed from the record's format by nasr_stream_set_audio_format and a restore
     nasr_rs::Plan aud_plan = {16000, 1, 1, 0, 1};
-    const float *aud_table = nullptr;      // device coefficients of fmt.sample_rate (the engine's cache owns them)
-    int64_t aud_in = 0, aud_out = 0;       // input frames taken / 16 kHz samples produced since create or reset
-    int aud_par = 0;                       // parity of the history buffer that holds the frames before the next push
-    bool default_format() const { return fmt.sample_rate == 16000 && fmt.encoding == NASR_AUDIO_S16 && fmt.channels == 1 && fmt.channel == 0; }
+    const float *aud_table = nullptr;              // device coefficients of sample_rate (the engine's cache owns them)
+    nasr_audio_format fmt() const { return {sample_rate, encoding, channels, channel}; }
 };
+static_assert(NASR_AUDIO_S16 == 0, "Mirror::default_format");
 
 // A rotating pinned block of a host hand-over: the streams' buffers are gathered into it and cross PCIe as ONE asynchronous copy.  A block
 // is reused four calls later, so its last copy must have been executed by then (the grouped pipeline keeps eight calls in flight and

@@ -8,7 +8,8 @@
 //                       LCTX, MEL_RING, NMEL, ABUF_CAP, the converter's HIST_MAX, TOK_CAP, the five DecFeatures values); the fingerprints
 //                       of the weight set, the boost set and the LM in force; the sizes of the two sections; the checksum of the device
 //                       section; 8 reserved bytes (zero); the checksum of header and mirror
-//   mirror              the fields of nasr_stream that say what the stream is, one by one (struct Mirror), then the queued tokens, zero-padded to 16 bytes
+//   mirror              the record of what the stream is (struct Mirror: nasr_stream derives from it, so the stream IS the record and nothing
+//                       copies it field by field), its fixed fields in wire order (visit_fields), then the queued tokens, zero-padded to 16 bytes
 //   device              the segments of the fork plan for this mirror (nasr_fork::fork_plan) in plan order, each zero-padded to 16 bytes.
 //                       Ring rows come in logical order (ring_rows), so the bytes do not depend on the slot; they do name the ring
 //                       positions (kv_head, mel_start), which restore keeps
@@ -110,17 +111,67 @@ inline DecFeatures features_of(const Config &c) {
 }
 struct Header { Config cfg; uint64_t total_bytes = 0, mirror_bytes = 0, device_bytes = 0, device_sum = 0, head_sum = 0; };
 
-// nasr_stream, as far as it says what the stream is.  Not stored: the slot, the engine, aud_plan and aud_table (recomputed from the format
-// the way nasr_stream_set_audio_format does), T (1 + R) and the tap fields
+// THE record of what a stream is on the host: struct nasr_stream (nasr_engine_priv.h) derives from it and adds only what is not state -- the
+// engine and the slot, T (1 + R), the tap fields, aud_plan and aud_table (recomputed from the format the way nasr_stream_set_audio_format
+// does).  Create, reset, fork, save and restore all go through this one declaration.  The two enable flags are words, not bools: parse must
+// be able to hold a 7 in order to refuse it.  The audio format is nasr_audio_format's four integers (encoding 0 = NASR_AUDIO_S16)
 struct Mirror {
-    int32_t R = 0, prompt = -1, abuf_cnt = 0, abuf_par = 0, mel_start = 0, mel_count = 0, valid_len = 0, kv_head = 0, cc_par = 0, chunks = 0, tok_read = 0;
+    int32_t R = 0, prompt = -1;
+    int32_t abuf_cnt = 0, abuf_par = 0;            // samples waiting in the audio buffer (pre-seeded 256 zeros), and its parity
+    int32_t mel_start = 0, mel_count = 0;          // mel ring window
+    int32_t valid_len = 0, kv_head = 0, cc_par = 0;    // cache_valid_len, K/V ring head, conv-cache parity
+    int32_t chunks = 0, tok_read = 0;
     int64_t samples_in = 0;
-    uint32_t boost_enabled = 1, lm_enabled = 1;
-    int32_t sample_rate = 16000, encoding = 0, channels = 1, channel = 0;
-    int64_t aud_in = 0, aud_out = 0;
-    int32_t aud_par = 0;
-    std::vector<int32_t> tok_queue;
+    uint32_t boost_enabled = 1, lm_enabled = 1;    // nasr_stream_set_boost / nasr_stream_set_lm (engine options "phrase_boost" / "lm_fusion")
+    int32_t sample_rate = 16000, encoding = 0, channels = 1, channel = 0;      // nasr_stream_set_audio_format: survives a reset, the counters below do not
+    int64_t aud_in = 0, aud_out = 0;               // input frames taken / 16 kHz samples produced since create or reset
+    int32_t aud_par = 0;                           // parity of the history buffer that holds the frames before the next push
+    std::vector<int32_t> tok_queue;                // tokens gathered from the device, not yet handed to the caller
+    bool default_format() const { return sample_rate == 16000 && encoding == 0 && channels == 1 && channel == 0; }
 };
+
+// THE field table: f(name, field, lo, hi) for every fixed field in wire order, [lo, hi] its inclusive range.  write_head, parse and
+// mirror_fault are written over it.  Three ranges say less than the rule: R is one of 0, 1, 6, 13, prompt ends at the restoring engine's
+// num_prompts - 1, and the four format fields are judged together (audio_format_fault) -- mirror_fault keeps those explicit
+template <class M, class F>
+inline void visit_fields(M &m, F &&f) {
+    f("R", m.R, 0, 13); f("prompt", m.prompt, -1, INT32_MAX);
+    f("abuf_cnt", m.abuf_cnt, 0, ABUF_CAP); f("abuf_par", m.abuf_par, 0, 1);
+    f("mel_start", m.mel_start, 0, MEL_RING - 1); f("mel_count", m.mel_count, 0, MEL_RING);
+    f("valid_len", m.valid_len, 0, LCTX); f("kv_head", m.kv_head, 0, KVC - 1); f("cc_par", m.cc_par, 0, 1);
+    f("chunks", m.chunks, 0, INT32_MAX); f("tok_read", m.tok_read, 0, INT32_MAX);
+    f("samples_in", m.samples_in, 0, INT64_MAX);
+    f("boost_enabled", m.boost_enabled, 0, 1); f("lm_enabled", m.lm_enabled, 0, 1);
+    f("sample_rate", m.sample_rate, INT32_MIN, INT32_MAX); f("encoding", m.encoding, INT32_MIN, INT32_MAX);
+    f("channels", m.channels, INT32_MIN, INT32_MAX); f("channel", m.channel, INT32_MIN, INT32_MAX);
+    f("aud_in", m.aud_in, 0, INT64_MAX); f("aud_out", m.aud_out, 0, INT64_MAX);
+    f("aud_par", m.aud_par, 0, 1);
+}
+
+// What a reset leaves of the record (k_stream_reset is the device's half).  Both modes start the mel window, the validity mask, the
+// counters, the audio converter and the token queue over; only a fresh reset also forgets the preprocessor's carry and the ring positions
+// (keep_reference_state: what the reference's nemo_stream_context::reset() leaves behind, see stream_zero_state).  R, prompt, the audio
+// format and the two enable flags survive both.  A default record through the fresh reset is a new stream
+inline void reset_state(Mirror &m, bool keep_reference_state) {
+    if (!keep_reference_state) {
+        m.abuf_cnt = NFFT / 2;                     // 256 zero samples pre-seeded, src/preprocessor.cpp:220-221
+        m.abuf_par = 0;
+        m.kv_head = 0;
+        m.cc_par = 0;
+    }
+    m.mel_start = 0;
+    m.mel_count = PRE_CACHE;                       // 9 literal-zero frames, src/nemo-stream.cpp:73-74 (reset: :100-102)
+    m.valid_len = 0;                               // :81 (reset: :112)
+    m.chunks = 0;
+    m.tok_read = 0;
+    m.samples_in = 0;
+    m.aud_in = m.aud_out = 0;                      // the audio converter starts over in both modes; the format stays
+    m.aud_par = 0;
+    m.tok_queue.clear();
+}
+
+// the record, as far as it says what of the slot is live (the fork plan's input)
+inline nasr_fork::Source live_part(const Mirror &m) { return {m.kv_head, m.mel_start, m.mel_count, m.abuf_cnt, m.abuf_par}; }
 
 inline int64_t pad16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 inline int64_t mirror_bytes(size_t n_queue) { return pad16(MIRROR_FIXED + 4 * (int64_t)n_queue); }
@@ -129,11 +180,13 @@ struct Writer {
     std::vector<uint8_t> &out;
     void u32(uint32_t v) { for (int i = 0; i < 4; i++) out.push_back((uint8_t)(v >> (8 * i))); }
     void u64(uint64_t v) { for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i))); }
+    template <class V> void field(V v) { if (sizeof(V) == 8) u64((uint64_t)v); else u32((uint32_t)v); }       // a 32- or 64-bit field of the mirror
 };
 struct Reader {
     const uint8_t *p;
     uint32_t u32() { uint32_t v = 0; for (int i = 0; i < 4; i++) v |= (uint32_t)p[i] << (8 * i); p += 4; return v; }
     uint64_t u64() { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)p[i] << (8 * i); p += 8; return v; }
+    template <class V> void field(V &v) { v = sizeof(V) == 8 ? (V)u64() : (V)u32(); }
 };
 
 // header + mirror (HEADER_BYTES + mirror_bytes bytes) into out, with the sizes and the head checksum filled in; device_bytes and device_sum are the caller's
@@ -150,12 +203,7 @@ inline void write_head(Header h, const Mirror &m, std::vector<uint8_t> &out) {
     w.u64(h.mirror_bytes); w.u64(h.device_bytes); w.u64(h.device_sum);
     w.u64(0);                                                  // reserved
     w.u64(0);                                                  // the head checksum, below
-    for (int32_t v : {m.R, m.prompt, m.abuf_cnt, m.abuf_par, m.mel_start, m.mel_count, m.valid_len, m.kv_head, m.cc_par, m.chunks, m.tok_read}) w.u32((uint32_t)v);
-    w.u64((uint64_t)m.samples_in);
-    w.u32(m.boost_enabled); w.u32(m.lm_enabled);
-    for (int32_t v : {m.sample_rate, m.encoding, m.channels, m.channel}) w.u32((uint32_t)v);
-    w.u64((uint64_t)m.aud_in); w.u64((uint64_t)m.aud_out);
-    w.u32((uint32_t)m.aud_par);
+    visit_fields(m, [&](const char *, auto v, long long, long long) { w.field(v); });
     w.u32((uint32_t)m.tok_queue.size());
     for (int32_t t : m.tok_queue) w.u32((uint32_t)t);
     out.resize((size_t)(HEADER_BYTES + (int64_t)h.mirror_bytes), 0);
@@ -196,12 +244,7 @@ inline bool parse(const uint8_t *p, int64_t n, Header &h, Mirror &m, std::string
     const uint64_t sum = checksum(p, HEAD_SUM_AT, 0) + checksum(p + HEADER_BYTES, (int64_t)h.mirror_bytes, (uint32_t)(HEADER_BYTES / 4));
     if (sum != h.head_sum) return refuse(err, "header / mirror checksum mismatch (the snapshot is corrupted)");
     r.p = p + HEADER_BYTES;
-    for (int32_t *v : {&m.R, &m.prompt, &m.abuf_cnt, &m.abuf_par, &m.mel_start, &m.mel_count, &m.valid_len, &m.kv_head, &m.cc_par, &m.chunks, &m.tok_read}) *v = (int32_t)r.u32();
-    m.samples_in = (int64_t)r.u64();
-    m.boost_enabled = r.u32(); m.lm_enabled = r.u32();
-    for (int32_t *v : {&m.sample_rate, &m.encoding, &m.channels, &m.channel}) *v = (int32_t)r.u32();
-    m.aud_in = (int64_t)r.u64(); m.aud_out = (int64_t)r.u64();
-    m.aud_par = (int32_t)r.u32();
+    visit_fields(m, [&](const char *, auto &v, long long, long long) { r.field(v); });
     const uint32_t n_queue = r.u32();
     if (n_queue > (uint32_t)TOK_CAP) return refuse(err, "tok_queue of %lld tokens is longer than the token ring (%lld)", n_queue, TOK_CAP);
     if ((uint64_t)mirror_bytes(n_queue) != h.mirror_bytes) return refuse(err, "tok_queue of %lld tokens does not fill a mirror section of %lld bytes", n_queue, (long long)h.mirror_bytes);
@@ -250,12 +293,9 @@ inline bool mirror_fault(const Mirror &m, int num_prompts, std::string &err) {
     };
     if (m.R != 0 && m.R != 1 && m.R != 6 && m.R != 13) { refuse(err, "mirror field R = %lld is none of 0, 1, 6, 13", m.R); return true; }
     if (out("prompt", m.prompt, -1, num_prompts > 0 ? num_prompts - 1 : -1)) return true;
-    if (out("abuf_cnt", m.abuf_cnt, 0, ABUF_CAP) || out("abuf_par", m.abuf_par, 0, 1) || out("mel_start", m.mel_start, 0, MEL_RING - 1) ||
-        out("mel_count", m.mel_count, 0, MEL_RING) || out("valid_len", m.valid_len, 0, LCTX) || out("kv_head", m.kv_head, 0, KVC - 1) ||
-        out("cc_par", m.cc_par, 0, 1) || out("chunks", m.chunks, 0, INT32_MAX) || out("tok_read", m.tok_read, 0, INT32_MAX) ||
-        out("samples_in", m.samples_in, 0, INT64_MAX) || out("boost_enabled", m.boost_enabled, 0, 1) || out("lm_enabled", m.lm_enabled, 0, 1) ||
-        out("aud_in", m.aud_in, 0, INT64_MAX) || out("aud_out", m.aud_out, 0, INT64_MAX) || out("aud_par", m.aud_par, 0, 1))
-        return true;
+    bool bad = false;                              // the first field outside its range, in wire order
+    visit_fields(m, [&](const char *name, auto v, long long lo, long long hi) { bad = bad || out(name, (long long)v, lo, hi); });
+    if (bad) return true;
     if (const char *what = audio_format_fault(m.sample_rate, m.encoding, m.channels, m.channel)) {
         err = std::string("mirror audio format: unsupported ") + what;
         return true;
@@ -269,8 +309,7 @@ inline bool mirror_fault(const Mirror &m, int num_prompts, std::string &err) {
 // through dec_set_slot_layout as it does in a fork), each with its offset in the device section (Seg::blob): dense, in plan order, every
 // segment padded to 16 bytes.  SAVE copies [src, src + bytes) of the slot to blob; RESTORE copies blob to [dst, dst + bytes).
 inline std::vector<Seg> snapshot_plan(const Mirror &m, int slot, int esz, int n_layers, int kernel_size, DecodeSet &d, const DecFeatures &f, int64_t *section_bytes) {
-    const nasr_fork::Source live = {m.kv_head, m.mel_start, m.mel_count, m.abuf_cnt, m.abuf_par};
-    std::vector<Seg> segs = nasr_fork::fork_plan(live, slot, slot, esz, n_layers, kernel_size, d, f);
+    std::vector<Seg> segs = nasr_fork::fork_plan(live_part(m), slot, slot, esz, n_layers, kernel_size, d, f);
     int64_t at = 0;
     for (Seg &s : segs) { s.blob = at; at += pad16(s.bytes); }
     if (section_bytes) *section_bytes = at;

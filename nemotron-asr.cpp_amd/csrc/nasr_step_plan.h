@@ -124,4 +124,14 @@ inline bool valid_cut4(const int *cut4, int L) {
     return prev < 8 * L;
 }
 
+// ---- the read-out rings (token frames, log-probabilities, alternatives, per-frame blank): item i of the `have` the device has produced
+// lives at i & (cap - 1), so the last `cap` are there.  Of the items first .. first + count - 1 (first, count >= 0: the getters refuse
+// negatives) the caller gets those that exist: their number, or RING_TOO_OLD when there are some but the first of them has been overwritten
+constexpr int RING_TOO_OLD = -1;
+inline int ring_window(int64_t first, int count, int64_t have, int cap) {
+    if (first >= have || count <= 0) return 0;
+    if (count > have - first) count = (int)(have - first);
+    return have - first > cap ? RING_TOO_OLD : count;
+}
+
 }  // namespace nasr_step

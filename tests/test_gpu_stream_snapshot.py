@@ -155,6 +155,87 @@ def test_blob_identities_and_the_kernel_checksum(trios, dtype, R, point):
             s.destroy()
 
 
+# ---- a reset stream against a new one --------------------------------------------------------------------------------------------------
+MIRROR_NAMES = ("R", "prompt", "abuf_cnt", "abuf_par", "mel_start", "mel_count", "valid_len", "kv_head", "cc_par", "chunks", "tok_read", "samples_in", "boost_enabled", "lm_enabled",
+                "sample_rate", "encoding", "channels", "channel", "aud_in", "aud_out", "aud_par", "n_queue")
+MIRROR_FMT = "<11iqII4iqqiI"         # the mirror's fixed fields in wire order (tests/test_snapshot_format.py restates the whole format)
+FRESH = dict(abuf_cnt=256, abuf_par=0, mel_start=0, mel_count=9, valid_len=0, kv_head=0, cc_par=0, chunks=0, tok_read=0, samples_in=0, aud_in=0, aud_out=0, aud_par=0, n_queue=0)
+
+
+def _mirror(blob):
+    return dict(zip(MIRROR_NAMES, struct.unpack_from(MIRROR_FMT, blob, HEADER_BYTES)))
+
+
+def _segments(mirror, esz, n_layers=2, ks=9):
+    """(name, bytes in the device section) of the fork plan's segments under OPTS for a mirror whose K/V and mel windows do not wrap (csrc/nasr_fork_plan.h
+    and the per-slot buffers of csrc/nasr_decode_set.h restated)"""
+    pad = lambda n: -(-n // 16) * 16
+    assert mirror["kv_head"] + 70 <= KVC and mirror["mel_start"] + mirror["mel_count"] <= 4096
+    segs = []
+    for layer in range(n_layers):
+        segs += [(f"kv[{layer}].K", 70 * 1024 * esz), (f"kv[{layer}].V", 70 * 1024 * esz), (f"cc[{layer}]", 2 * (ks - 1) * 1024 * 4)]
+    segs += [("mel", mirror["mel_count"] * 128 * 4), ("abuf", pad(mirror["abuf_cnt"] * 4)), ("last_sample", 16), ("aud_hist", pad(2 * 193 * 4))]
+    segs += [("ctrl", 48), ("h", 4 * 640 * 4), ("c", 4 * 640 * 4), ("predg", 640 * 4), ("tok_ring", 4096 * 4), ("tok_frame", 4096 * 4), ("tok_logprob", 4096 * 4),
+             ("alt_id", 4096 * 3 * 4), ("alt_lp", 4096 * 3 * 4), ("frame_blank", 4096 * 4)]
+    return [(name, n) for name, n in segs if n]
+
+
+# what k_stream_reset leaves as it finds it, because the decode writes it before it reads it: the LSTM candidate (DecCtrl::dirty = 1) and the
+# read-out rings (clipped to n_tok and frame0 + t, which it zeroes)
+NOT_RESET = {"predg", "tok_ring", "tok_frame", "tok_logprob", "alt_id", "alt_lp", "frame_blank"}
+
+
+def _differing(payload_a, payload_b, mirror, esz):
+    """names of the device-section segments in which two payloads of the same plan differ"""
+    at, out = 0, []
+    for name, n in _segments(mirror, esz):
+        if payload_a[at:at + n] != payload_b[at:at + n]:
+            out.append(name)
+        at += n
+    assert at == len(payload_a) == len(payload_b)
+    return out
+
+
+@pytest.mark.parametrize("reference", [False, True])
+def test_a_reset_stream_saves_what_a_new_stream_saves(trios, reference):
+    """one engine, right_context 0: a stream that has decoded two chunks and more and is reset saves the header and mirror bytes of a stream just
+    created with the same right_context and prompt (create and reset go through one function on the record), and every segment of the device
+    section that k_stream_reset writes.  The device sections as a whole are NOT equal, before the record existed or since: the segments of
+    NOT_RESET hold what the slot's earlier life left (all seven differed on the MI355X), so the device checksum and the head checksum over it
+    are left out of the header comparison.
+    reset(reference=True): abuf_cnt, abuf_par, kv_head and cc_par in the mirror are those from before the reset, the rest of it is a new
+    stream's, and the device section has the size the fork plan gives that mirror"""
+    eng, _, _ = trios(capi.DTYPE_BF16)
+    R, n = 0, synth.shift_samples(0)
+    used, new = eng.stream(R), None
+    try:
+        eng.step([used], [synth.make_pcm(17, (3 * n + 77) / 16000 + 0.01)[:3 * n + 77]])
+        before = _mirror(used.save())
+        assert before["chunks"] >= 2 and before["kv_head"] == before["chunks"] and before["samples_in"] == 3 * n + 77 and before["abuf_cnt"] != 256
+        used.reset(reference=reference)
+        blob_used = used.save()
+        new = eng.stream(R)
+        blob_new = new.save()
+    finally:
+        used.destroy()
+        if new:
+            new.destroy()
+    got, fresh = _mirror(blob_used), _mirror(blob_new)
+    assert fresh == dict(before, **FRESH) and _sections(blob_new)[0] == 112
+    if reference:
+        kept = {k: before[k] for k in ("abuf_cnt", "abuf_par", "kv_head", "cc_par")}
+        assert got == dict(fresh, **kept), (got, fresh)
+        pad = lambda v: -(-v // 16) * 16
+        assert _sections(blob_used)[1] == _sections(blob_new)[1] - pad(256 * 4) + pad(kept["abuf_cnt"] * 4)
+        return
+    head = HEADER_BYTES + 112
+    diff = _differing(blob_used[head:], blob_new[head:], fresh, 2)
+    print(f"reset against create: device segments that differ: {diff or 'none'}")
+    assert got == fresh
+    assert blob_used[:120] == blob_new[:120] and blob_used[128:136] == blob_new[128:136] and blob_used[HEADER_BYTES:head] == blob_new[HEADER_BYTES:head]
+    assert set(diff) <= NOT_RESET, diff
+
+
 # ---- carried decoder state ----------------------------------------------------------------------------------------------------------------
 def test_boost_and_lm_state_travel(W2):
     """tests/test_gpu_stream_fork.py::test_boost_and_lm_state_travel with a save on one engine and a restore on another that carries the

@@ -48,6 +48,10 @@ using nasr_fork::Seg;
 //   C                                    the checksum's properties: "<pieces ok> <flips that did not change the sum of 2048>"
 //   F seed count                         count deterministic mutations of the base blob (bit flips, truncations, splices, with and without the checksums put right): "<refused> <accepted same> <accepted DIFFERENT>"
 //   E seed count                         the same for an envelope around the head of the base blob
+//   R keep <the 22 mirror values of S>   the record (n_queue tokens queued) after reset_state(keep): "<its 22 values>"
+//   D                                    a default record after the fresh reset: "<its 22 values>"
+//   M <the 22 mirror values of S>        the field table: "<bytes of the visitor's fields, 4 per 32-bit and 8 per 64-bit one, plus the queue-length word> <fields visited>
+//                                        <1: write, parse, write gave the same bytes and parse gave the same fields> <hex of header and mirror>"
 struct Base {
     std::vector<uint8_t> blob;
     nasr_snap::Config cfg;
@@ -94,6 +98,19 @@ static std::string validate(const std::vector<uint8_t> &b, const nasr_snap::Conf
     *same = again.size() == (size_t)(nasr_snap::HEADER_BYTES + h.mirror_bytes) && !memcmp(again.data(), b.data(), again.size());
     return "";
 }
+static bool read_mirror(nasr_snap::Mirror &m) {
+    long long si, ai, ao;
+    unsigned be, le, nq;
+    if (scanf("%d %d %d %d %d %d %d %d %d %d %d %lld %u %u %d %d %d %d %lld %lld %d %u", &m.R, &m.prompt, &m.abuf_cnt, &m.abuf_par, &m.mel_start, &m.mel_count, &m.valid_len, &m.kv_head,
+              &m.cc_par, &m.chunks, &m.tok_read, &si, &be, &le, &m.sample_rate, &m.encoding, &m.channels, &m.channel, &ai, &ao, &m.aud_par, &nq) != 22) return false;
+    m.samples_in = si; m.aud_in = ai; m.aud_out = ao; m.boost_enabled = be; m.lm_enabled = le;
+    for (unsigned i = 0; i < nq; i++) m.tok_queue.push_back((int32_t)(i * 7 % 1024));
+    return true;
+}
+static void print_mirror(const nasr_snap::Mirror &m) {
+    printf("%d %d %d %d %d %d %d %d %d %d %d %lld %u %u %d %d %d %d %lld %lld %d %zu\n", m.R, m.prompt, m.abuf_cnt, m.abuf_par, m.mel_start, m.mel_count, m.valid_len, m.kv_head, m.cc_par, m.chunks,
+           m.tok_read, (long long)m.samples_in, m.boost_enabled, m.lm_enabled, m.sample_rate, m.encoding, m.channels, m.channel, (long long)m.aud_in, (long long)m.aud_out, m.aud_par, m.tok_queue.size());
+}
 static nasr_snap::Config bumped(nasr_snap::Config c, int field, int delta) {
     uint32_t *f32[] = {&c.dtype, &c.esz, &c.n_layers, &c.kernel_size, &c.kvc, &c.lctx, &c.mel_ring, &c.nmel, &c.abuf_cap, &c.hist_max, &c.tok_cap,
                        &c.token_logprobs, &c.alt_k, &c.frame_blank, &c.phrase_boost, &c.lm_fusion};
@@ -138,15 +155,10 @@ int main() {
             printf("| %s | %lld %lld %lld %lld %lld %s\n", fault ? fault : "ok", (long long)section, n_pack, total, largest, odd, short_fault ? "refused" : "ok");
         } else if (op == 'S') {
             nasr_snap::Mirror m;
-            long long si, ai, ao;
-            unsigned be, le, nq;
             int dtype, esz, n_layers, ks;
             DecFeatures f;
-            if (scanf("%d %d %d %d %d %d %d %d %d %d %d %lld %u %u %d %d %d %d %lld %lld %d %u", &m.R, &m.prompt, &m.abuf_cnt, &m.abuf_par, &m.mel_start, &m.mel_count, &m.valid_len, &m.kv_head,
-                      &m.cc_par, &m.chunks, &m.tok_read, &si, &be, &le, &m.sample_rate, &m.encoding, &m.channels, &m.channel, &ai, &ao, &m.aud_par, &nq) != 22) return 2;
+            if (!read_mirror(m)) return 2;
             if (scanf("%d %d %d %d", &dtype, &esz, &n_layers, &ks) != 4 || !read_features(f) || scanf("%d %d", &g.num_prompts, &g.boost_states) != 2) return 2;
-            m.samples_in = si; m.aud_in = ai; m.aud_out = ao; m.boost_enabled = be; m.lm_enabled = le;
-            for (unsigned i = 0; i < nq; i++) m.tok_queue.push_back((int32_t)(i * 7 % 1024));
             g.cfg = nasr_snap::make_config(dtype, esz, n_layers, ks, f, 0x1111222233334444ull, f.phrase_boost ? 0x5555666677778888ull : 0, f.lm_fusion ? 0x9999aaaabbbbccccull : 0);
             DecodeSet d;
             int64_t section = 0;
@@ -257,6 +269,31 @@ int main() {
                 if (!err.empty()) refused++; else if (same) accepted++; else different++;
             }
             printf("%d %d %d\n", refused, accepted, different);
+        } else if (op == 'R' || op == 'D') {
+            nasr_snap::Mirror m;
+            int keep = 0;
+            if (op == 'R' && (scanf("%d", &keep) != 1 || !read_mirror(m))) return 2;
+            nasr_snap::reset_state(m, keep != 0);
+            print_mirror(m);
+        } else if (op == 'M') {
+            nasr_snap::Mirror m, back;
+            if (!read_mirror(m)) return 2;
+            long long bytes = 4, fields = 0;                    // the queue-length word
+            nasr_snap::visit_fields(m, [&](const char *, auto &v, long long, long long) { static_assert(sizeof(v) == 4 || sizeof(v) == 8, "a 32- or 64-bit field"); bytes += sizeof(v); fields++; });
+            nasr_snap::Header h, h2;
+            std::vector<uint8_t> first, again;
+            std::string err;
+            nasr_snap::write_head(h, m, first);
+            int same = nasr_snap::parse(first.data(), (int64_t)first.size(), h2, back, err) ? 1 : 0;
+            std::vector<long long> a, b;
+            nasr_snap::visit_fields(m, [&](const char *, auto &v, long long, long long) { a.push_back((long long)v); });
+            nasr_snap::visit_fields(back, [&](const char *, auto &v, long long, long long) { b.push_back((long long)v); });
+            h2.device_bytes = 0; h2.device_sum = 0;
+            nasr_snap::write_head(h2, back, again);
+            if (a != b || back.tok_queue != m.tok_queue || again != first) same = 0;
+            printf("%lld %lld %d ", bytes, fields, same);
+            for (uint8_t v : first) printf("%02x", v);
+            printf("\n");
         } else return 2;
     }
     return 0;
@@ -399,6 +436,49 @@ def test_checksum_is_order_free_position_sensitive_and_sees_every_bit(snap):
     piece with its global word offset; two different words exchanged change it; every one of the 2 048 single-bit flips of a 256-byte buffer changes it"""
     assert snap([("C",)]) == ["1 0"]
     assert checksum(b"\x00" * 8) == fmix32(0) + fmix32(0x9E3779B1) and checksum(b"\x01\x00\x00\x00", 2) == fmix32(1 ^ (2 * 0x9E3779B1 & 0xFFFFFFFF))
+
+
+# ---- the field table and the reset rules ---------------------------------------------------------------------------------------------------
+def mirror_case(op, mirror, *front):
+    return (op,) + front + tuple(mirror[k] for k in MIRROR_NAMES)
+
+
+def test_field_table_is_the_wire_format(snap):
+    """the visitor's fields take MIRROR_FIXED = 100 bytes with the queue-length word (17 of 32 bits, 4 of 64); a record with every field at its
+    maximum (the ranges of test_every_mirror_field_is_range_checked_at_both_ends, R 13, the largest format, a full token queue) is written as
+    the format restated above says, and parse followed by write gives the same bytes"""
+    big = 2 ** 31 - 1
+    top = dict(R=13, prompt=7, abuf_cnt=ABUF_CAP, abuf_par=1, mel_start=MEL_RING - 1, mel_count=MEL_RING, valid_len=LCTX, kv_head=KVC - 1, cc_par=1, chunks=big, tok_read=big,
+               samples_in=2 ** 63 - 1, boost_enabled=1, lm_enabled=1, sample_rate=48000, encoding=3, channels=8, channel=7, aud_in=2 ** 63 - 1, aud_out=2 ** 63 - 1, aud_par=1, n_queue=TOK_CAP)
+    for mirror in (top, BASE_MIRROR, dict(BASE_MIRROR, n_queue=0)):
+        nbytes, fields, same, head = snap([mirror_case("M", mirror)])[0].split()
+        assert (int(nbytes), int(fields), int(same)) == (100, 21, 1)
+        assert struct.calcsize(MIRROR_FMT) == 100 and len(MIRROR_NAMES) == 22
+        head = bytes.fromhex(head)
+        want = struct.pack(MIRROR_FMT, *(mirror[k] for k in MIRROR_NAMES)) + struct.pack("<%di" % mirror["n_queue"], *(i * 7 % 1024 for i in range(mirror["n_queue"])))
+        assert head[HEADER_BYTES:] == want + bytes(-len(want) % 16)
+
+
+# what a reset leaves, restated (not read from the header): both modes start these over ...
+RESET_BOTH = dict(mel_start=0, mel_count=9, valid_len=0, chunks=0, tok_read=0, samples_in=0, aud_in=0, aud_out=0, aud_par=0, n_queue=0)
+# ... only a fresh reset these; R, prompt, the audio format and the two enable flags survive both
+RESET_FRESH_ONLY = dict(abuf_cnt=256, abuf_par=0, kv_head=0, cc_par=0)
+
+
+def test_reset_rules(snap):
+    """a record with every field at a distinct non-default value and five queued tokens, after a fresh and after a reference reset, field by field;
+    a default record through the fresh reset is what nasr_stream_create makes: 256 waiting samples, 9 mel frames, everything else 0 / default"""
+    used = dict(R=6, prompt=2, abuf_cnt=301, abuf_par=1, mel_start=33, mel_count=44, valid_len=55, kv_head=66, cc_par=1, chunks=77, tok_read=88, samples_in=99, boost_enabled=0, lm_enabled=0,
+                sample_rate=8000, encoding=1, channels=3, channel=-1, aud_in=111, aud_out=122, aud_par=1, n_queue=5)
+    default = dict(R=0, prompt=-1, abuf_cnt=0, abuf_par=0, mel_start=0, mel_count=0, valid_len=0, kv_head=0, cc_par=0, chunks=0, tok_read=0, samples_in=0, boost_enabled=1, lm_enabled=1,
+                   sample_rate=16000, encoding=0, channels=1, channel=0, aud_in=0, aud_out=0, aud_par=0, n_queue=0)
+    values = [used[k] for k in MIRROR_NAMES if k not in ("abuf_par", "cc_par", "aud_par", "boost_enabled", "lm_enabled")]
+    assert len(set(values)) == len(values) and all(used[k] != default[k] for k in MIRROR_NAMES)
+    assert set(RESET_BOTH) | set(RESET_FRESH_ONLY) | {"R", "prompt", "boost_enabled", "lm_enabled", "sample_rate", "encoding", "channels", "channel"} == set(MIRROR_NAMES)
+    fresh, reference, created = ([int(v) for v in ln.split()] for ln in snap([mirror_case("R", used, 0), mirror_case("R", used, 1), ("D",)]))
+    assert dict(zip(MIRROR_NAMES, fresh)) == dict(used, **RESET_BOTH, **RESET_FRESH_ONLY)
+    assert dict(zip(MIRROR_NAMES, reference)) == dict(used, **RESET_BOTH)
+    assert dict(zip(MIRROR_NAMES, created)) == dict(default, **RESET_BOTH, **RESET_FRESH_ONLY) == dict(default, abuf_cnt=256, mel_count=9)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------------

@@ -54,6 +54,7 @@ static_assert(nasr::NFFT == 512 && nasr::HOP == 160 && nasr::PRE_CACHE == 9 && n
 //   C mel_count T                      -> chunks_completed
 //   G T B w_rows multichunk (cnt mel n) x B -> graph_step_chunks
 //   S T B w_rows                       -> piece_samples
+//   W first count have cap             -> ring_window (cap 0: nasr::TOK_CAP)
 int main() {
     char op;
     while (scanf(" %c", &op) == 1) {
@@ -86,6 +87,11 @@ int main() {
             int T, B, w_rows;
             if (scanf("%d %d %d", &T, &B, &w_rows) != 3) return 2;
             printf("%lld\n", (long long)nasr_step::piece_samples(T, B, w_rows));
+        } else if (op == 'W') {
+            long long first, have;
+            int count, cap;
+            if (scanf("%lld %d %lld %d", &first, &count, &have, &cap) != 4) return 2;
+            printf("%d\n", nasr_step::ring_window(first, count, have, cap ? cap : nasr::TOK_CAP));
         } else return 2;
     }
     return 0;
@@ -258,3 +264,34 @@ def test_piece_samples(plan):
     got = plan([("S",) + k for k, _ in table])
     assert got == [[g * 8 * k[0] * HOP] for k, g in table]
     assert all(v[0] <= MAX_PUSH for v in got)
+
+
+def ring_model(first, count, have, cap):
+    """brute force: the device has written items 0 .. have - 1, item i to place i % cap; of the items asked for, those that exist are handed over,
+    each read from its place -- and the answer is "too old" (-1) when there are some and the place of the first of them holds a later item"""
+    ring = {}
+    for i in range(have):
+        ring[i % cap] = i
+    asked = [i for i in range(first, first + count) if i < have]
+    if asked and ring[asked[0] % cap] != asked[0]:
+        return -1
+    assert all(ring[i % cap] == i for i in asked)                      # the first is there: so are the rest
+    return len(asked)
+
+
+@pytest.mark.parametrize("cap,label", [(8, 8), (4096, 0)])
+def test_ring_window_against_a_brute_force_ring(plan, cap, label):
+    """the range the four read-out getters of nasr_abi.hip hand over (nasr_step::ring_window): first in {0, 1, have - cap - 1, have - cap,
+    have - cap + 1, have - 1, have, have + 1}, count in {0, 1, cap, cap + 1}, have in {0, 1, cap - 1, cap, cap + 1, 3 cap + 5}, at cap = 8 and at
+    TOK_CAP.  A negative first (have - cap - 1 and its neighbours while have <= cap) is no case: every getter refuses it before it gets here"""
+    assert plan([("W", 0, 1, 1, 0)]) == [[1]] and plan([("W", 0, 4097, 5000, 0)]) == [[-1]] and plan([("W", 904, 4097, 5000, 0)]) == [[4096]]      # cap 0 is TOK_CAP = 4096
+    cases, want = [], []
+    for have in (0, 1, cap - 1, cap, cap + 1, 3 * cap + 5):
+        for first in sorted({0, 1, have - cap - 1, have - cap, have - cap + 1, have - 1, have, have + 1}):
+            for count in (0, 1, cap, cap + 1):
+                if first < 0:
+                    continue
+                cases.append(("W", first, count, have, label))
+                want.append([ring_model(first, count, have, cap)])
+    assert len(cases) >= 100 and [-1] in want and [cap] in want and [0] in want
+    assert plan(cases) == want
