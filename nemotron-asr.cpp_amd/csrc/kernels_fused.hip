@@ -123,7 +123,9 @@ __device__ __forceinline__ float dot32(const float *qs, const void *row) {   // 
 // to FUSED_GROUP problems per launch, blockIdx.z = problem: the same layer type of several steps in flight, each with its own
 // weights, activations and state -- round 3, tests/micro/dual_probe.hip: two chains of 4-problem launches stream 4.1 TB/s where
 // four chains of 1-problem launches stream 2.45).  Same code per problem: results are bit-identical whichever entry runs it.
-template <int PRO, int MMAX>
+// NPART (PRO_LN at M <= 2 only): the number of split-K partials the prologue loads, a compile-time value so that its loads are
+// straight-line code; a launch has part_splits == NPART or part_splits == 0 (launch_fused_m).
+template <int PRO, int MMAX, int NPART = 0>
 __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams &g = p.g;
@@ -143,7 +145,11 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
 
     // The weight stream does not depend on the prologue: this wave's tiles (<= 8 KiB) are requested at the top of
     // the kernel so that their 2.2-2.4 us run under the prologue -- but AFTER the prologue's own first loads: the
-    // memory pipeline serves a wave's requests in order, and the prologue inputs are the critical path.
+    // memory pipeline serves a wave's requests in order, and the prologue inputs are the critical path.  What the
+    // binary does with this is written down per instantiation in profiles/fused_ln_load_order.md; for the M <= 2
+    // forms of PRO_LN tests/test_fused_load_order.py holds it to that: no wait on the vector-memory counter stands
+    // between the prologue loads and the weight loads, and every wait before the panel barrier leaves the U weight
+    // loads in flight.  (PRO_ATTN has two round trips by design; the generic-ks loop of PRO_DWCONV waits per tap.)
     constexpr int U = (PRO == PRO_DWCONV && MMAX == 1) ? 2 : 8;   // k-tiles per wave (pw2 at split-K 4: 2; the launcher checks)
     const int nts = t1 - t0;
     const int w0 = t0 + nts * wave / 4, w1 = t0 + nts * (wave + 1) / 4;   // host guarantees w1 - w0 <= U
@@ -175,32 +181,40 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
     if (!((PRO == PRO_LN && SMALL) || PRO == PRO_ATTN || PRO == PRO_PLAIN || (PRO == PRO_DWCONV && SMALL))) issue_weights();
     STAMP(1);
 
-    if (PRO == PRO_LN && SMALL) {
-        // block-per-row: every global load of the prologue is issued up front (one memory round trip)
+    if constexpr (PRO == PRO_LN && SMALL) {
+        // block-per-row.  Every global load of the prologue is issued up front, the weight stream right behind it, and
+        // nothing waits in between (tests/test_fused_load_order.py).  The partial loads are unconditional: a per-partial
+        // `sI < part_splits ? load : zero` made hipcc branch around each load and drain the vector-memory counter at the
+        // first join -- a wait for the previous launch's output, with the weight stream not yet requested.  A launch without
+        // partials (layer 0; a group mixes it with the others) reads row m of x_in in their place and does not add them.
+        // The scheduling barriers pin the order of the three groups; the compiler's own counted waits then fit it.
+        static_assert(NPART == 4 || NPART == 8, "the partial counts of run_layers_fused");
         const int c4 = threadIdx.x * 4;
+        const bool live = p.part_splits > 0;
+        const float *pbase = live ? p.part : p.x_in;
+        const size_t pstride = live ? (size_t)M * D : 0;
         const float4 lw = *(const float4 *)(p.ln_w + c4), lb = *(const float4 *)(p.ln_b + c4);
         float4 ow = make_float4(0.f, 0.f, 0.f, 0.f), ob = ow;
         if (p.lno_w) { ow = *(const float4 *)(p.lno_w + c4); ob = *(const float4 *)(p.lno_b + c4); }
-        float4 xv[MR], t[MR][8];
+        float4 xv[MR], t[MR][NPART];
 #pragma unroll
         for (int m = 0; m < MR; m++) {
-            if (m < M) {
-                xv[m] = *(const float4 *)(p.x_in + (size_t)m * D + c4);
+            const int mc = m < M ? m : M - 1;                              // M = 1 in the two-row form: row 0 again, unused
+            xv[m] = *(const float4 *)(p.x_in + (size_t)mc * D + c4);
 #pragma unroll
-                for (int sI = 0; sI < 8; sI++)
-                    t[m][sI] = sI < p.part_splits ? *(const float4 *)(p.part + ((size_t)sI * M + m) * D + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            for (int sI = 0; sI < NPART; sI++) t[m][sI] = *(const float4 *)(pbase + sI * pstride + (size_t)mc * D + c4);
         }
+        __builtin_amdgcn_sched_barrier(0);
         issue_weights();
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < MR; m++) {
             if (m < M) {
                 float4 v = xv[m];
-                if (p.part_splits > 0) {
+                if (live) {
                     float4 o = t[m][0];
 #pragma unroll
-                    for (int sI = 1; sI < 8; sI++)
-                        if (sI < p.part_splits) { o.x += t[m][sI].x; o.y += t[m][sI].y; o.z += t[m][sI].z; o.w += t[m][sI].w; }
+                    for (int sI = 1; sI < NPART; sI++) { o.x += t[m][sI].x; o.y += t[m][sI].y; o.z += t[m][sI].z; o.w += t[m][sI].w; }
                     v.x += p.scale * o.x; v.y += p.scale * o.y; v.z += p.scale * o.z; v.w += p.scale * o.w;
                 }
                 STAMP(2);
@@ -671,15 +685,15 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
     STAMP(7);
 }
 
-template <int PRO, int MMAX>
+template <int PRO, int MMAX, int NPART = 0>
 __global__ __launch_bounds__(256, (MMAX == 1 && PRO != PRO_ATTN) ? 4 : 1) void k_fused_skinny(FusedParams p) {
-    fused_skinny_body<PRO, MMAX>(p);
+    fused_skinny_body<PRO, MMAX, NPART>(p);
 }
-template <int PRO, int MMAX>
+template <int PRO, int MMAX, int NPART = 0>
 __global__ __launch_bounds__(256, (MMAX == 1 && PRO != PRO_ATTN) ? GRP_OCC : 1) void k_fused_skinny_grp(FusedParamsGroup pp) {
     const FusedParams &p = pp.p[blockIdx.z];
     if (p.g.M <= 0) return;                       // a stage of the pipeline that holds no step (fill / drain)
-    fused_skinny_body<PRO, MMAX>(p);
+    fused_skinny_body<PRO, MMAX, NPART>(p);
 }
 
 void init_fused_kernel_attributes() {   // LN / dwconv row staging can exceed the 64 KiB default dynamic-LDS limit at M = 16
@@ -687,12 +701,23 @@ void init_fused_kernel_attributes() {   // LN / dwconv row staging can exceed th
     hipFuncSetAttribute((const void *)k_fused_skinny<PRO_DWCONV, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 + 32768 + 16 * D * 4);
 }
 
+// The M <= 2 forms of PRO_LN are built for the partial counts of run_layers_fused: 4 and 8 (no partials: the 4 form, which
+// then skips them).  -1: any other count, which only the row-staging form takes.
+static int ln_npart(const FusedParams &p) { return p.part_splits == 0 || p.part_splits == 4 ? 4 : p.part_splits == 8 ? 8 : -1; }
+
 template <int MMAX>
 static void launch_fused_m(const FusedParams &p, hipStream_t st, size_t lds) {
     const GemmParams &g = p.g;
     dim3 grid(g.N / 16, g.splits);
     switch (p.pro) {
-    case PRO_LN: hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX>), grid, dim3(256), lds, st, p); break;
+    case PRO_LN:
+        if constexpr (MMAX <= 2) {
+            if (ln_npart(p) == 8) hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 8>), grid, dim3(256), lds, st, p);
+            else hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 4>), grid, dim3(256), lds, st, p);
+        } else {
+            hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX>), grid, dim3(256), lds, st, p);
+        }
+        break;
     case PRO_PLAIN: hipLaunchKernelGGL((k_fused_skinny<PRO_PLAIN, MMAX>), grid, dim3(256), 4096, st, p); break;
     case PRO_ATTN: hipLaunchKernelGGL((k_fused_skinny<PRO_ATTN, MMAX>), dim3(g.N / 128, g.splits), dim3(256), lds, st, p); break;   // (column group, head)
     case PRO_DWCONV: hipLaunchKernelGGL((k_fused_skinny<PRO_DWCONV, MMAX>), grid, dim3(256), lds, st, p); break;
@@ -704,7 +729,10 @@ static void launch_fused_grp_m(const FusedParamsGroup &pp, const FusedParams &p,
     const GemmParams &g = p.g;
     dim3 grid(g.N / 16, g.splits, n);
     switch (p.pro) {
-    case PRO_LN: hipLaunchKernelGGL((k_fused_skinny_grp<PRO_LN, MMAX>), grid, dim3(256), lds, st, pp); break;
+    case PRO_LN:
+        if (ln_npart(p) == 8) hipLaunchKernelGGL((k_fused_skinny_grp<PRO_LN, MMAX, 8>), grid, dim3(256), lds, st, pp);
+        else hipLaunchKernelGGL((k_fused_skinny_grp<PRO_LN, MMAX, 4>), grid, dim3(256), lds, st, pp);
+        break;
     case PRO_PLAIN: hipLaunchKernelGGL((k_fused_skinny_grp<PRO_PLAIN, MMAX>), grid, dim3(256), 4096, st, pp); break;
     case PRO_ATTN: hipLaunchKernelGGL((k_fused_skinny_grp<PRO_ATTN, MMAX>), dim3(g.N / 128, g.splits, n), dim3(256), lds, st, pp); break;
     case PRO_DWCONV: hipLaunchKernelGGL((k_fused_skinny_grp<PRO_DWCONV, MMAX>), grid, dim3(256), lds, st, pp); break;
@@ -717,6 +745,21 @@ void launch_fused_skinny_group(const FusedParamsGroup &pp, int n, hipStream_t st
     for (int i = 0; i < n; i++)
         if (pp.p[i].g.M > 0) { first = i; break; }
     if (first < 0) return;
+    if (pp.p[first].pro == PRO_LN) {
+        // one kernel loads one number of partials: the problems that have partials must agree on it (the stages of a step do:
+        // the same launch of different layers).  The problem the launch is described by is one with partials, if there is one.
+        bool same = true;
+        for (int i = 0; i < n; i++) {
+            if (pp.p[i].g.M <= 0 || pp.p[i].part_splits == 0) continue;
+            if (pp.p[first].part_splits == 0) first = i;
+            same = same && ln_npart(pp.p[i]) > 0 && pp.p[i].part_splits == pp.p[first].part_splits;
+        }
+        if (!same) {                              // never the engine's: one launch each, the same arithmetic
+            for (int i = 0; i < n; i++)
+                if (pp.p[i].g.M > 0) launch_fused_skinny(pp.p[i], st);
+            return;
+        }
+    }
     const FusedParams &p = pp.p[first];
     const GemmParams &g = p.g;
     const int KP = (g.K / g.splits);
@@ -732,11 +775,12 @@ void launch_fused_skinny(const FusedParams &p, hipStream_t st) {
     const int KP = (g.K / g.splits);
     size_t lds = 4096 + (size_t)16 * KP * 2;
     if (p.pro == PRO_ATTN) lds += (size_t)(2 * 16 * DH + 16 * KVC) * 4;
-    if ((p.pro == PRO_LN || p.pro == PRO_DWCONV) && g.M > 2) lds += (size_t)g.M * D * 4;   // f32 row staging
+    const bool staged = g.M > 2 || (p.pro == PRO_LN && ln_npart(p) < 0);   // PRO_LN: also a partial count the M <= 2 forms are not built for
+    if ((p.pro == PRO_LN || p.pro == PRO_DWCONV) && staged) lds += (size_t)g.M * D * 4;   // f32 row staging
     const bool fits_u2 = p.pro != PRO_DWCONV || (g.K / 32 / g.splits + 3) / 4 <= 2;   // the one-row dwconv form holds 2 k-tiles per wave
-    if (g.M == 1 && fits_u2) launch_fused_m<1>(p, st, lds);
+    if (staged) launch_fused_m<16>(p, st, lds);
+    else if (g.M == 1 && fits_u2) launch_fused_m<1>(p, st, lds);
     else if (g.M <= 2) launch_fused_m<2>(p, st, lds);      // also one row whose k-slice does not fit the one-row form: the SMALL forms need no row staging
-    else launch_fused_m<16>(p, st, lds);
 }
 
 }  // namespace nasr
