@@ -102,14 +102,55 @@ __device__ __forceinline__ float dot32(const float *qs, const void *row) {   // 
 // diagnostic build (never shipped): wave 0 of the first and of the last workgroup stamp the 100 MHz real-time counter
 #define STAMP(i)                                                                                                         \
     do {                                                                                                                 \
-        if (p.stamps && threadIdx.x == 0 && blockIdx.y == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))          \
-            p.stamps[(blockIdx.x == 0 ? 0 : 16) + (i)] = __builtin_amdgcn_s_memrealtime();                                \
+        if (l.stamps && threadIdx.x == 0 && blockIdx.y == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))          \
+            l.stamps[(blockIdx.x == 0 ? 0 : 16) + (i)] = __builtin_amdgcn_s_memrealtime();                                \
     } while (0)
 #else
 #define STAMP(i)
 #endif
 
 #define PIN_SGPR(x) asm volatile("" ::"s"(x))
+
+// What a launch needs before its first vector load: the pointers its prologue and its weight stream read through, and the
+// shape words their addresses are formed from.  The one-problem kernel takes these as its LEADING, scalar kernel arguments
+// (the Makefile builds this file with -amdgpu-kernarg-preload-count): gfx950's command processor then writes them into user
+// SGPRs before the first wave starts, and no load of the launch waits for a scalar fetch from the kernel-argument segment --
+// which every dispatch's acquire has just thrown out of the scalar cache and the L2 (profiles/kernarg_preload.md).  14 dwords
+// is what the hardware preloads beside the segment pointer: five pointers, two ints, a sixth pointer.  Everything else stays
+// in FusedParams; its scalar loads run under the vector loads.  The group kernel cannot be preloaded (its problem is picked
+// by blockIdx.z) and fills the same record from its problem's FusedParams: one body, the same bits.
+//   kind        a[0]    a[1]                            a[2]     a[3]    a[4]  a[5]    x
+//   PRO_LN      x_in    part (x_in without partials)    ln_w     ln_b    W     lno_w   part_splits
+//   PRO_PLAIN   A       -                               -        -       W     -       lda
+//   PRO_ATTN    rows    q                               posproj  bias_u  W     bias_v  T
+//   PRO_DWCONV  rows    dw                              ln_w     ln_b    W     glu     ks
+struct FusedLead {
+#ifdef NASR_STAMPS
+    unsigned long long *stamps;   // diagnostic build: a leading argument too (STAMP(0) must not wait for a scalar load); a[5] then is not preloaded
+#endif
+    const void *a[6];
+    int shape;                    // K / 32 | splits << 12 | M << 20
+    int x;
+};
+template <int PRO>
+__host__ __device__ __forceinline__ FusedLead fused_lead(const FusedParams &p) {
+    FusedLead l;
+#ifdef NASR_STAMPS
+    l.stamps = p.stamps;
+#endif
+    l.shape = (p.g.K >> 5) | (p.g.splits << 12) | (p.g.M << 20);
+    l.a[4] = p.g.W;
+    if (PRO == PRO_LN) {
+        l.a[0] = p.x_in; l.a[1] = p.part_splits > 0 ? p.part : p.x_in; l.a[2] = p.ln_w; l.a[3] = p.ln_b; l.a[5] = p.lno_w; l.x = p.part_splits;
+    } else if (PRO == PRO_PLAIN) {
+        l.a[0] = p.g.A; l.a[1] = l.a[2] = l.a[3] = l.a[5] = nullptr; l.x = p.g.lda;
+    } else if (PRO == PRO_ATTN) {
+        l.a[0] = p.at.rows; l.a[1] = p.at.q; l.a[2] = p.at.posproj; l.a[3] = p.at.bias_u; l.a[5] = p.at.bias_v; l.x = p.at.T;
+    } else {
+        l.a[0] = p.cv.rows; l.a[1] = p.cv.dw; l.a[2] = p.cv.ln_w; l.a[3] = p.cv.ln_b; l.a[5] = p.cv.glu; l.x = p.cv.ks;
+    }
+    return l;
+}
 
 // MMAX = compile-time bound of M: 1 (one row: the chunk-by-chunk single stream), 2, or 16 (any M the small-M path takes).
 // The M <= 2 forms keep every prologue input in registers at once; giving them their own instantiation keeps the
@@ -125,20 +166,25 @@ __device__ __forceinline__ float dot32(const float *qs, const void *row) {   // 
 // four chains of 1-problem launches stream 2.45).  Same code per problem: results are bit-identical whichever entry runs it.
 // NPART (PRO_LN at M <= 2 only): the number of split-K partials the prologue loads, a compile-time value so that its loads are
 // straight-line code; a launch has part_splits == NPART or part_splits == 0 (launch_fused_m).
-template <int PRO, int MMAX, int NPART = 0>
-__device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
+// LEADING: the record came in preloaded registers (the one-problem kernel).  The three places where the body is arranged around that -- the
+// norm_out pair behind the partials, the pins of late fields, the attention's scheduling barrier -- are left as they were in the group form,
+// whose record is read from its problem like everything else: its code, and what the grouped pipeline measures, stay what they were.
+template <int PRO, int MMAX, int NPART = 0, bool LEADING = false>
+__device__ __forceinline__ void fused_skinny_body(const FusedLead &l, const FusedParams &p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemmParams &g = p.g;
     const int nt = blockIdx.x, split = blockIdx.y;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
-    const int KT = g.K >> 5;
-    const int t0 = (int)((long)KT * split / g.splits), t1 = (int)((long)KT * (split + 1) / g.splits);
+    const int KT = l.shape & 0xfff, nsplit = (l.shape >> 12) & 0xff;
+    // KT < 4096 and split < 256: 32 bits hold the products (the 64-bit division stood in front of the first load)
+    const int t0 = (int)((unsigned)(KT * split) / (unsigned)nsplit), t1 = (int)((unsigned)(KT * (split + 1)) / (unsigned)nsplit);
     const int KP = (t1 - t0) * 32;                 // K range of this workgroup
     float *red = (float *)smem;                    // [4][64][4] floats = 4 KiB
     char *panel = smem + 4096;                     // [16][KP] bf16
     const bool writer = blockIdx.x == 0 && blockIdx.y == 0;
-    const int M = MMAX == 1 ? 1 : g.M;
+    const int M = MMAX == 1 ? 1 : l.shape >> 20;
+    const void *const gW = l.a[4];
     constexpr bool SMALL = MMAX <= 2;              // M <= 2: block-per-row prologues
     constexpr int MR = MMAX == 1 ? 1 : 2;
     STAMP(0);
@@ -153,7 +199,7 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
     constexpr int U = (PRO == PRO_DWCONV && MMAX == 1) ? 2 : 8;   // k-tiles per wave (pw2 at split-K 4: 2; the launcher checks)
     const int nts = t1 - t0;
     const int w0 = t0 + nts * wave / 4, w1 = t0 + nts * (wave + 1) / 4;   // host guarantees w1 - w0 <= U
-    const u32x4 *wp = (const u32x4 *)g.W + (size_t)nt * KT * 64 + lane;
+    const u32x4 *wp = (const u32x4 *)gW + (size_t)nt * KT * 64 + lane;
     u32x4 wv[U];
     auto issue_weights = [&]() {
         if (PRO == PRO_ATTN) {
@@ -163,7 +209,7 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int ntile = blockIdx.x * 8 + wave * 2 + (u >> 2), kt = t0 + (u & 3);
-                wv[u] = __builtin_nontemporal_load((const u32x4 *)g.W + ((size_t)ntile * KT + kt) * 64 + lane);
+                wv[u] = __builtin_nontemporal_load((const u32x4 *)gW + ((size_t)ntile * KT + kt) * 64 + lane);
             }
         } else {
 #pragma unroll
@@ -189,23 +235,30 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
         // partials (layer 0; a group mixes it with the others) reads row m of x_in in their place and does not add them.
         // The scheduling barriers pin the order of the three groups; the compiler's own counted waits then fit it.
         static_assert(NPART == 4 || NPART == 8, "the partial counts of run_layers_fused");
+        // One-problem kernel: the previous layer's norm_out pair goes last of the group -- lno_b is the one pointer of this prologue
+        // that does not fit the leading arguments, and the wait for its scalar load must not stand in front of x_in and the partials.
         const int c4 = threadIdx.x * 4;
-        const bool live = p.part_splits > 0;
-        const float *pbase = live ? p.part : p.x_in;
+        const float *x_in = (const float *)l.a[0], *pbase = (const float *)l.a[1], *lno_w = (const float *)l.a[5];
+        const bool live = l.x > 0;
         const size_t pstride = live ? (size_t)M * D : 0;
-        const float4 lw = *(const float4 *)(p.ln_w + c4), lb = *(const float4 *)(p.ln_b + c4);
+        const float4 lw = *(const float4 *)((const float *)l.a[2] + c4), lb = *(const float4 *)((const float *)l.a[3] + c4);
         float4 ow = make_float4(0.f, 0.f, 0.f, 0.f), ob = ow;
-        if (p.lno_w) { ow = *(const float4 *)(p.lno_w + c4); ob = *(const float4 *)(p.lno_b + c4); }
+        if (!LEADING && lno_w) { ow = *(const float4 *)(lno_w + c4); ob = *(const float4 *)(p.lno_b + c4); }
         float4 xv[MR], t[MR][NPART];
 #pragma unroll
         for (int m = 0; m < MR; m++) {
             const int mc = m < M ? m : M - 1;                              // M = 1 in the two-row form: row 0 again, unused
-            xv[m] = *(const float4 *)(p.x_in + (size_t)mc * D + c4);
+            xv[m] = *(const float4 *)(x_in + (size_t)mc * D + c4);
 #pragma unroll
             for (int sI = 0; sI < NPART; sI++) t[m][sI] = *(const float4 *)(pbase + sI * pstride + (size_t)mc * D + c4);
         }
+        if (LEADING) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (lno_w) { ow = *(const float4 *)(lno_w + c4); ob = *(const float4 *)(p.lno_b + c4); }
+        }
         __builtin_amdgcn_sched_barrier(0);
         issue_weights();
+        if (LEADING) { PIN_SGPR(p.scale); PIN_SGPR(p.x_out); }                          // used between the loads and the panel barrier: requested with the rest
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < MR; m++) {
@@ -218,7 +271,7 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
                     v.x += p.scale * o.x; v.y += p.scale * o.y; v.z += p.scale * o.z; v.w += p.scale * o.w;
                 }
                 STAMP(2);
-                if (p.lno_w) v = block_ln(v, ow, ob, red);                 // previous layer's norm_out (:687)
+                if (lno_w) v = block_ln(v, ow, ob, red);                   // previous layer's norm_out (:687)
                 if (writer && p.x_out) *(float4 *)(p.x_out + (size_t)m * D + c4) = v;
                 v = block_ln(v, lw, lb, red);
                 STAMP(3);
@@ -231,30 +284,32 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
         // loads independent) and parks it in LDS; B: one wave per row does the LayerNorm(s) out of LDS.
         float *xs = (float *)(panel + 16 * KP * 2);            // [M][1024] f32
         const int c4 = threadIdx.x * 4;
+        const float *x_in = (const float *)l.a[0], *ln_w = (const float *)l.a[2], *ln_b = (const float *)l.a[3], *lno_w = (const float *)l.a[5];
+        const int part_splits = l.x;
         for (int m0 = 0; m0 < M; m0 += 4) {                    // 4 rows per round: all their loads in flight together
             float4 xv[4], t[4][8];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int m = m0 + u < M ? m0 + u : M - 1;
-                xv[u] = *(const float4 *)(p.x_in + (size_t)m * D + c4);
+                xv[u] = *(const float4 *)(x_in + (size_t)m * D + c4);
 #pragma unroll
                 for (int sI = 0; sI < 8; sI++)
-                    t[u][sI] = sI < p.part_splits ? *(const float4 *)(p.part + ((size_t)sI * M + m) * D + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    t[u][sI] = sI < part_splits ? *(const float4 *)((const float *)l.a[1] + ((size_t)sI * M + m) * D + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int m = m0 + u;
                 if (m < M) {
                     float4 v = xv[u];
-                    if (p.part_splits > 0) {
+                    if (part_splits > 0) {
                         float4 o = t[u][0];
 #pragma unroll
                         for (int sI = 1; sI < 8; sI++)
-                            if (sI < p.part_splits) { o.x += t[u][sI].x; o.y += t[u][sI].y; o.z += t[u][sI].z; o.w += t[u][sI].w; }
+                            if (sI < part_splits) { o.x += t[u][sI].x; o.y += t[u][sI].y; o.z += t[u][sI].z; o.w += t[u][sI].w; }
                         v.x += p.scale * o.x; v.y += p.scale * o.y; v.z += p.scale * o.z; v.w += p.scale * o.w;
                     }
                     *(float4 *)(xs + (size_t)m * D + c4) = v;
-                    if (writer && p.x_out && !p.lno_w) *(float4 *)(p.x_out + (size_t)m * D + c4) = v;
+                    if (writer && p.x_out && !lno_w) *(float4 *)(p.x_out + (size_t)m * D + c4) = v;
                 }
             }
         }
@@ -263,14 +318,14 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
             float4 v[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) v[i] = *(const float4 *)(xs + (size_t)m * D + lane * 4 + 256 * i);
-            if (p.lno_w) {
-                wave_ln(v, p.lno_w, p.lno_b, lane);                // previous layer's norm_out (:687)
+            if (lno_w) {
+                wave_ln(v, lno_w, p.lno_b, lane);                // previous layer's norm_out (:687)
                 if (writer && p.x_out) {
 #pragma unroll
                     for (int i = 0; i < 4; i++) *(float4 *)(p.x_out + (size_t)m * D + lane * 4 + 256 * i) = v[i];
                 }
             }
-            wave_ln(v, p.ln_w, p.ln_b, lane);
+            wave_ln(v, ln_w, ln_b, lane);
 #pragma unroll
             for (int i = 0; i < 4; i++) store4_panel(panel, m, lane * 4 + 256 * i, KP, v[i].x, v[i].y, v[i].z, v[i].w);
         }
@@ -282,7 +337,10 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
         // relative-position rows; (b) once the descriptors are in, the K and V ring rows.  A second row (M = 2) is
         // handled by a second pass that loads as it goes (keeps the kernel under the register limit).
         const AttnParams &a = p.at;
-        const int h = split, T = a.T, KV = LCTX + T, TS = a.TS > 0 ? a.TS : a.T;
+        const RowDesc *a_rows = (const RowDesc *)l.a[0];
+        const float *a_q = (const float *)l.a[1], *a_bias_u = (const float *)l.a[3], *a_bias_v = (const float *)l.a[5];
+        const void *a_posproj = l.a[2];
+        const int h = split, T = l.x, KV = LCTX + T, TS = a.TS > 0 ? a.TS : T;
         float *qu = (float *)(panel + 16 * KP * 2);                  // [2][128]
         float *qv = qu + 16 * DH;                                    // [2][128]
         float *sc = qv + 16 * DH;                                    // [2][KVC]
@@ -292,17 +350,17 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
         float qq = 0.f, bu = 0.f, bv = 0.f;
         if ((int)threadIdx.x < M * DH) {
             const int m = threadIdx.x >> 7, d = threadIdx.x & 127;
-            qq = a.q[(size_t)m * D + h * DH + d]; bu = a.bias_u[h * DH + d]; bv = a.bias_v[h * DH + d];
+            qq = a_q[(size_t)m * D + h * DH + d]; bu = a_bias_u[h * DH + d]; bv = a_bias_v[h * DH + d];
         }
         RowDesc rds[2];
-        rds[0] = a.rows[0];
-        rds[1] = a.rows[(M - 1) / TS];                               // stream of row 1 (= stream 0 unless B = 2)
+        rds[0] = a_rows[0];
+        rds[1] = a_rows[(M - 1) / TS];                               // stream of row 1 (= stream 0 unless B = 2)
         auto pair_rows = [&](int pr, int &m, int &j, const bf16_t *&prow) {
             const bool ok = pr < npair;
             m = ok ? pr / KV : 0;
             j = ok ? pr - m * KV : 0;
             const int il = m - (m / TS) * TS, gch = il / T, i = il - gch * T;
-            prow = (const bf16_t *)a.posproj + (size_t)(j + T - 1 - i) * D + h * DH + sub * 64;
+            prow = (const bf16_t *)a_posproj + (size_t)(j + T - 1 - i) * D + h * DH + sub * 64;
             return ok;
         };
         auto key_row = [&](int m, int j) {
@@ -367,8 +425,8 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
             for (int m = 0; m < M; m++) {
             const RowDesc rd = m == 0 ? rds[0] : rds[1];
             float *scm = sc + m * KVC;
-            const float4 *qp = (const float4 *)(a.q + (size_t)m * D + h * DH + c * 8);
-            const float4 *up = (const float4 *)(a.bias_u + h * DH + c * 8), *vp = (const float4 *)(a.bias_v + h * DH + c * 8);
+            const float4 *qp = (const float4 *)(a_q + (size_t)m * D + h * DH + c * 8);
+            const float4 *up = (const float4 *)(a_bias_u + h * DH + c * 8), *vp = (const float4 *)(a_bias_v + h * DH + c * 8);
             const float4 q0 = qp[0], q1 = qp[1], u0 = up[0], u1 = up[1], b0 = vp[0], b1 = vp[1];
             uint4 kk[5], pp[5], vr[5];
             int jk[5];
@@ -376,9 +434,10 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
             for (int t = 0; t < 5; t++) {
                 jk[t] = t * 16 + wave * 4 + sr;
                 const int jc = jk[t] < KV ? jk[t] : 0;
-                pp[t] = *(const uint4 *)((const bf16_t *)a.posproj + (size_t)(jc + T - 1) * D + h * DH + c * 8);
+                pp[t] = *(const uint4 *)((const bf16_t *)a_posproj + (size_t)(jc + T - 1) * D + h * DH + c * 8);
             }
             if (m == 0) issue_weights();
+            if (LEADING) __builtin_amdgcn_sched_barrier(0);              // the ring addresses wait for the row descriptor: behind the weight loads, not in front
 #pragma unroll
             for (int t = 0; t < 5; t++) {
                 const int jc = jk[t] < KV ? jk[t] : 0;
@@ -513,28 +572,31 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
         __syncthreads();
     } else if (PRO == PRO_DWCONV) {
         const ConvParams &c = p.cv;
-        const int T = c.T, ks1 = c.ks - 1;
+        const RowDesc *c_rows = (const RowDesc *)l.a[0];
+        const float *c_dw = (const float *)l.a[1], *c_ln_w = (const float *)l.a[2], *c_ln_b = (const float *)l.a[3], *c_glu = (const float *)l.a[5];
+        const int T = c.T, ks = l.x, ks1 = ks - 1;
         const int k0 = t0 * 32;
         if (SMALL) {
             // block-per-row, 4 channels per thread; taps unrolled so all loads are in flight together
             const int c4 = threadIdx.x * 4;
-            const float4 lw = *(const float4 *)(c.ln_w + c4), lb = *(const float4 *)(c.ln_b + c4);
-            const RowDesc rd_first = c.rows[0];             // the cache rows below depend on it: request it first,
+            const float4 lw = *(const float4 *)(c_ln_w + c4), lb = *(const float4 *)(c_ln_b + c4);
+            const RowDesc rd_first = c_rows[0];             // the cache rows below depend on it: request it first,
             float4 w[9];                                    // then what does not (taps weights, the GEMM weight stream)
-            if (c.ks == 9) {
+            if (ks == 9) {
 #pragma unroll
-                for (int k = 0; k < 9; k++) w[k] = *(const float4 *)(c.dw + (size_t)k * D + c4);
+                for (int k = 0; k < 9; k++) w[k] = *(const float4 *)(c_dw + (size_t)k * D + c4);
             }
             issue_weights();
+            if (LEADING) PIN_SGPR(T);
             for (int m = 0; m < M; m++) {
                 const int b = m / T, i = m - b * T;
-                const RowDesc rd = b == 0 ? rd_first : c.rows[b];
+                const RowDesc rd = b == 0 ? rd_first : c_rows[b];
                 const float *cc_in = c.cc_pool + (size_t)rd.slot * c.cc_slot_stride + (size_t)rd.cc_par * ks1 * D;
                 float *cc_out = c.cc_pool + (size_t)rd.slot * c.cc_slot_stride + (size_t)(rd.cc_par ^ 1) * ks1 * D;
-                const float *gl = c.glu + (size_t)b * T * D;
+                const float *gl = c_glu + (size_t)b * T * D;
                 float4 acc;
                 bool cache_written = false;
-                if (c.ks == 9) {
+                if (ks == 9) {
                     float4 z[9];
 #pragma unroll
                     for (int k = 0; k < 9; k++) {
@@ -551,10 +613,10 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
                     }
                 } else {
                     acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    for (int k = 0; k < c.ks; k++) {
+                    for (int k = 0; k < ks; k++) {
                         const int rr = i + k;
                         const float4 z = rr < ks1 ? *(const float4 *)(cc_in + (size_t)rr * D + c4) : *(const float4 *)(gl + (size_t)(rr - ks1) * D + c4);
-                        const float4 w = *(const float4 *)(c.dw + (size_t)k * D + c4);
+                        const float4 w = *(const float4 *)(c_dw + (size_t)k * D + c4);
                         if (k == 0) acc = make_float4(z.x * w.x, z.y * w.y, z.z * w.z, z.w * w.w);
                         else { acc.x += z.x * w.x; acc.y += z.y * w.y; acc.z += z.z * w.z; acc.w += z.w * w.w; }
                     }
@@ -580,28 +642,28 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
             const int c4 = threadIdx.x * 4;
             for (int m = 0; m < M; m++) {
                 const int b = m / T, i = m - b * T;
-                const RowDesc rd = c.rows[b];
+                const RowDesc rd = c_rows[b];
                 const float *cc_in = c.cc_pool + (size_t)rd.slot * c.cc_slot_stride + (size_t)rd.cc_par * ks1 * D;
                 float *cc_out = c.cc_pool + (size_t)rd.slot * c.cc_slot_stride + (size_t)(rd.cc_par ^ 1) * ks1 * D;
-                const float *gl = c.glu + (size_t)b * T * D;
+                const float *gl = c_glu + (size_t)b * T * D;
                 float4 acc;
-                if (c.ks == 9) {
+                if (ks == 9) {
                     float4 z[9], w[9];
 #pragma unroll
                     for (int k = 0; k < 9; k++) {
                         const int rr = i + k;
                         z[k] = rr < 8 ? *(const float4 *)(cc_in + (size_t)rr * D + c4) : *(const float4 *)(gl + (size_t)(rr - 8) * D + c4);
-                        w[k] = *(const float4 *)(c.dw + (size_t)k * D + c4);
+                        w[k] = *(const float4 *)(c_dw + (size_t)k * D + c4);
                     }
                     acc = make_float4(z[0].x * w[0].x, z[0].y * w[0].y, z[0].z * w[0].z, z[0].w * w[0].w);
 #pragma unroll
                     for (int k = 1; k < 9; k++) { acc.x += z[k].x * w[k].x; acc.y += z[k].y * w[k].y; acc.z += z[k].z * w[k].z; acc.w += z[k].w * w[k].w; }
                 } else {
                     acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    for (int k = 0; k < c.ks; k++) {
+                    for (int k = 0; k < ks; k++) {
                         const int rr = i + k;
                         const float4 z = rr < ks1 ? *(const float4 *)(cc_in + (size_t)rr * D + c4) : *(const float4 *)(gl + (size_t)(rr - ks1) * D + c4);
-                        const float4 w = *(const float4 *)(c.dw + (size_t)k * D + c4);
+                        const float4 w = *(const float4 *)(c_dw + (size_t)k * D + c4);
                         if (k == 0) acc = make_float4(z.x * w.x, z.y * w.y, z.z * w.z, z.w * w.w);
                         else { acc.x += z.x * w.x; acc.y += z.y * w.y; acc.z += z.z * w.z; acc.w += z.w * w.w; }
                     }
@@ -620,7 +682,7 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
                 float4 v[4];
 #pragma unroll
                 for (int ii = 0; ii < 4; ii++) v[ii] = *(const float4 *)(cs + (size_t)m * D + lane * 4 + 256 * ii);
-                wave_ln(v, c.ln_w, c.ln_b, lane);
+                wave_ln(v, c_ln_w, c_ln_b, lane);
 #pragma unroll
                 for (int ii = 0; ii < 4; ii++) {
                     const int e = lane * 4 + 256 * ii;
@@ -640,7 +702,7 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
     // ---- GEMM over this workgroup's k-tiles (weights already in registers) -------------------------
     uint4 avp[U];
     if (PRO == PRO_PLAIN) {       // activations (written by the previous kernel) first, then the weight stream
-        const char *arow = (const char *)g.A + ((size_t)(r < M ? r : M - 1) * g.lda) * 2 + q * 16;
+        const char *arow = (const char *)l.a[0] + ((size_t)(r < M ? r : M - 1) * l.x) * 2 + q * 16;
 #pragma unroll
         for (int u = 0; u < U; u++) avp[u] = *(const uint4 *)(arow + (size_t)(w0 + u < w1 ? w0 + u : w1 - 1) * 64);
         issue_weights();
@@ -686,14 +748,23 @@ __device__ __forceinline__ void fused_skinny_body(const FusedParams &p) {
 }
 
 template <int PRO, int MMAX, int NPART = 0>
-__global__ __launch_bounds__(256, (MMAX == 1 && PRO != PRO_ATTN) ? 4 : 1) void k_fused_skinny(FusedParams p) {
-    fused_skinny_body<PRO, MMAX, NPART>(p);
+__global__ __launch_bounds__(256, (MMAX == 1 && PRO != PRO_ATTN) ? 4 : 1) void k_fused_skinny(
+#ifdef NASR_STAMPS
+    unsigned long long *stamps,
+#endif
+    const void *a0, const void *a1, const void *a2, const void *a3, const void *a4, int shape, int x, const void *a5, FusedParams p) {
+    FusedLead l;
+#ifdef NASR_STAMPS
+    l.stamps = stamps;
+#endif
+    l.a[0] = a0; l.a[1] = a1; l.a[2] = a2; l.a[3] = a3; l.a[4] = a4; l.a[5] = a5; l.shape = shape; l.x = x;
+    fused_skinny_body<PRO, MMAX, NPART, true>(l, p);
 }
 template <int PRO, int MMAX, int NPART = 0>
 __global__ __launch_bounds__(256, (MMAX == 1 && PRO != PRO_ATTN) ? GRP_OCC : 1) void k_fused_skinny_grp(FusedParamsGroup pp) {
     const FusedParams &p = pp.p[blockIdx.z];
     if (p.g.M <= 0) return;                       // a stage of the pipeline that holds no step (fill / drain)
-    fused_skinny_body<PRO, MMAX, NPART>(p);
+    fused_skinny_body<PRO, MMAX, NPART>(fused_lead<PRO>(p), p);
 }
 
 void init_fused_kernel_attributes() {   // LN / dwconv row staging can exceed the 64 KiB default dynamic-LDS limit at M = 16
@@ -705,22 +776,31 @@ void init_fused_kernel_attributes() {   // LN / dwconv row staging can exceed th
 // then skips them).  -1: any other count, which only the row-staging form takes.
 static int ln_npart(const FusedParams &p) { return p.part_splits == 0 || p.part_splits == 4 ? 4 : p.part_splits == 8 ? 8 : -1; }
 
+// the leading arguments of k_fused_skinny, in the kernel's order
+#ifdef NASR_STAMPS
+#define LEAD_ARGS(l) (l).stamps, (l).a[0], (l).a[1], (l).a[2], (l).a[3], (l).a[4], (l).shape, (l).x, (l).a[5]
+#else
+#define LEAD_ARGS(l) (l).a[0], (l).a[1], (l).a[2], (l).a[3], (l).a[4], (l).shape, (l).x, (l).a[5]
+#endif
+
 template <int MMAX>
 static void launch_fused_m(const FusedParams &p, hipStream_t st, size_t lds) {
     const GemmParams &g = p.g;
     dim3 grid(g.N / 16, g.splits);
     switch (p.pro) {
-    case PRO_LN:
+    case PRO_LN: {
+        const FusedLead l = fused_lead<PRO_LN>(p);
         if constexpr (MMAX <= 2) {
-            if (ln_npart(p) == 8) hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 8>), grid, dim3(256), lds, st, p);
-            else hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 4>), grid, dim3(256), lds, st, p);
+            if (ln_npart(p) == 8) hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 8>), grid, dim3(256), lds, st, LEAD_ARGS(l), p);
+            else hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX, 4>), grid, dim3(256), lds, st, LEAD_ARGS(l), p);
         } else {
-            hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX>), grid, dim3(256), lds, st, p);
+            hipLaunchKernelGGL((k_fused_skinny<PRO_LN, MMAX>), grid, dim3(256), lds, st, LEAD_ARGS(l), p);
         }
         break;
-    case PRO_PLAIN: hipLaunchKernelGGL((k_fused_skinny<PRO_PLAIN, MMAX>), grid, dim3(256), 4096, st, p); break;
-    case PRO_ATTN: hipLaunchKernelGGL((k_fused_skinny<PRO_ATTN, MMAX>), dim3(g.N / 128, g.splits), dim3(256), lds, st, p); break;   // (column group, head)
-    case PRO_DWCONV: hipLaunchKernelGGL((k_fused_skinny<PRO_DWCONV, MMAX>), grid, dim3(256), lds, st, p); break;
+    }
+    case PRO_PLAIN: { const FusedLead l = fused_lead<PRO_PLAIN>(p); hipLaunchKernelGGL((k_fused_skinny<PRO_PLAIN, MMAX>), grid, dim3(256), 4096, st, LEAD_ARGS(l), p); break; }
+    case PRO_ATTN: { const FusedLead l = fused_lead<PRO_ATTN>(p); hipLaunchKernelGGL((k_fused_skinny<PRO_ATTN, MMAX>), dim3(g.N / 128, g.splits), dim3(256), lds, st, LEAD_ARGS(l), p); break; }   // (column group, head)
+    case PRO_DWCONV: { const FusedLead l = fused_lead<PRO_DWCONV>(p); hipLaunchKernelGGL((k_fused_skinny<PRO_DWCONV, MMAX>), grid, dim3(256), lds, st, LEAD_ARGS(l), p); break; }
     }
 }
 
