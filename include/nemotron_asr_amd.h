@@ -252,7 +252,9 @@ int nasr_engine_finalize(nasr_engine *e, nasr_stream *const *streams, int B,
  *    ("stream pool exhausted (max_streams=%d)").
  *  - Options and graphs.  It allocates nothing on the device, captures no step graph and invalidates none (step graphs take the slot from
  *    their row descriptors).  Debug taps are not copied: a fork's taps (mel, PCM16, subsampled, layer and encoder outputs) are empty
- *    until its own first call. */
+ *    until its own first call.  The frame history (engine option "frame_history") is not copied either: a fork starts with an empty
+ *    history at the frames src has decoded (nasr_stream_history_range gives (done, 0)) and keeps its own frames from there; src's history
+ *    is untouched.  The copy plan is the same with the option on or off. */
 int nasr_stream_fork(nasr_stream *src, nasr_stream **out);
 /* nasr_engine_preview: the tokens nasr_engine_finalize would add for each stream if it were called now; the streams are not changed.
  *  - Mechanism.  Every stream is forked into a free slot, the forks take the nasr_engine_finalize path as ONE batch (the converter's tail
@@ -304,6 +306,9 @@ int nasr_engine_preview(nasr_engine *e, nasr_stream *const *streams, int B,
  *  - Options and graphs.  Neither call captures a step graph or invalidates one, and a step that never saves or restores launches what it
  *    always did.  The first save or restore allocates a device staging buffer of the size of the bound (grown when an option raises it,
  *    freed with the engine) and a pinned block.  Debug taps are empty until the restored stream's own first call, as after a fork.
+ *    The frame history (engine option "frame_history") does not travel: the blob has the same bytes, size and header with the option on or
+ *    off, the option is not among the ones that must agree, and a restored stream starts with an empty history at the frames the saved
+ *    stream had decoded, as a fork does.
  * Engine counters "stream_saves" and "stream_restores". */
 int nasr_engine_snapshot_bound(nasr_engine *e, int64_t *bytes_out);
 int nasr_stream_save(nasr_stream *s, void *buf, int64_t cap, int64_t *bytes_out);
@@ -409,7 +414,18 @@ enum {
  * endpoint detector needs (csrc/nasr_endpoint.h).  Under "phrase_boost" the value stays the model's.  Tokens, frames, iteration counts, decoder
  * state and the values of "token_logprobs" / "token_alternatives" are bit-identical to 0.  It selects the decode kernels that are captured
  * into the step graphs (those of "token_logprobs" plus one small launch per iteration) and allocates a ring per stream, so it is REJECTED
- * after the first step or offline call. */
+ * after the first step or offline call.
+ * "frame_history" (0 default; N = 64 .. 2048 in multiples of 64, other values are refused): a capability like "frame_blank_logprobs" -- with
+ * N every live stream keeps the joint's encoder-projection rows ([640] f32, prompt fused in) of the last N encoder frames it decoded, in a
+ * device ring filled by one more small launch at the head of every step's decode (csrc/nasr_history.h), so that the offline modes can run
+ * over a window of them without audio and without an encoder run: nasr_stream_history_range, nasr_stream_get_history,
+ * nasr_engine_history_transcribe / _beam / _align.  HBM: max_streams x N x 2 560 bytes -- 5.2 MB per slot at N = 2048, 2.7 GB at 512 streams.
+ * Tokens, frames, decoder state and every other read-out are bit-identical to 0; with 0 no launch is added and nothing is allocated.  Cost
+ * at 24 layers bf16 (profiles/frame_history.md): the headline shape (1 stream, "pipeline" = 4) and 64 streams x right_context 13 stay inside
+ * their run-to-run spread; a synchronous one-stream step, one dependent chain, gains about 0.005 ms (0.8685 -> 0.873 .. 0.875 ms, 0.5 .. 0.75 %).  The
+ * launch is captured into the step graphs and the rings are allocated by this call, so it is REJECTED after the first step or offline call;
+ * until then another N replaces the rings and 0 frees them.  "history_append_rows" (MEASUREMENT ONLY; 0 default = 1, or 4): rows one
+ * workgroup of the append launch moves, i.e. its grid; the same bytes (profiles/frame_history.md).  Before the first step. */
 int nasr_engine_set_option(nasr_engine *e, const char *key, int value);
 /* replaces the engine's boost set (engine option "phrase_boost" = N): phrase i = tokens[i][0 .. lens[i]), 1 .. 32 non-blank token ids
  * (0 .. 1023), with bonus[i], finite, 0 < bonus <= 1e4, in natural-log units (added to the joint's logits).  n_phrases = 0 clears the set.
@@ -423,7 +439,8 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * to overlap; 0 before the first pipelined step), "boost_states" (automaton states of the current boost set, the two fixed ones included:
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
  * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls),
- * "stream_saves" / "stream_restores" (nasr_stream_save calls that wrote a blob / nasr_stream_restore calls that made a stream; refused calls are not counted), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * "stream_saves" / "stream_restores" (nasr_stream_save calls that wrote a blob / nasr_stream_restore calls that made a stream; refused calls are not counted),
+ * "history_calls" / "history_frames" (nasr_engine_history_* calls that succeeded / the frames they gathered out of the streams' rings), "cut_drains" (pipelined calls that first completed the steps in flight because
  * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);
@@ -642,6 +659,49 @@ int nasr_stream_set_lm(nasr_stream *s, int enable);
  * pointer may be NULL. */
 int nasr_engine_beam_hypothesis_boost(nasr_engine *e, int u, int rank, double *boost_out, double *total_out, float *token_bonus_out,
                                       int32_t cap);
+
+/* ---- frame history of a live stream: second-pass greedy / beam / alignment over frames the stream has already encoded (engine option
+ * "frame_history" = N; the reference has none: its offline entries take audio and run their own encoder).  With the option every step
+ * appends the joint's encoder-projection rows of the frames it decodes to a ring of N rows in the stream's slot (csrc/nasr_history.h).
+ * Frames are numbered from create / reset as by nasr_stream_get_token_frames; `done` = the frames decoded so far, what
+ * nasr_stream_get_frame_blank_logprobs(s, 0, 0, NULL) returns.  A stream keeps frames [max(valid_from, done - N), done): valid_from is 0 after
+ * nasr_stream_create and both reset modes, and `done` of the source after nasr_stream_fork / nasr_stream_restore (the history does not
+ * travel).  The ring is never cleared and every read is checked against that range, so what a recycled slot or an earlier life of the stream
+ * left in it is never visible.
+ * nasr_stream_history_range: frames [*first_out, *first_out + *count_out) of s are kept.  Completes steps in flight.  Fails -- with a message,
+ * the engine usable -- on a null argument and when the option is off. */
+int nasr_stream_history_range(const nasr_stream *s, int64_t *first_out, int32_t *count_out);
+/* parity read-out: the kept rows of frames [first, first + count) of s -> out [count][640] f32.  Returns the number of frames written
+ * (= count), 0 for a range that is not wholly kept (and for count = 0), < 0 on error: a null stream, a null out with count > 0, a negative
+ * range, the option off.  Completes steps in flight; changes nothing. */
+int nasr_stream_get_history(const nasr_stream *s, int64_t first, int32_t count, float *out);
+/* The three offline modes over window [first[b], first[b] + count[b]) of streams[b], b = 0 .. B - 1: nasr_engine_history_transcribe is
+ * nasr_engine_transcribe, nasr_engine_history_beam is nasr_engine_transcribe_beam, nasr_engine_history_align is nasr_engine_align, each with
+ * its twin's remaining arguments, outputs and failures -- but no front end and no encoder runs: a gather launch copies the windows' kept rows
+ * into the packed rows the mode reads, then the mode runs unchanged (the same sub-batches under "offline_rows").
+ *  - A fresh decode of the window.  The decoder starts from the zero state and blank, with an empty boost history and the LM's start state,
+ *    exactly as an offline utterance starts: the window is meant to be an utterance between two endpoints, and the result is NOT the
+ *    continuation of the stream's own decode at `first`.  Frames in every output are relative to first[b]; the caller adds it.  The prompt
+ *    is the one the stream had when the frames were encoded (it is fused into the rows); there is no prompt_index.
+ *  - Windows.  A window that is not wholly kept fails the call with a message that names the stream's index, the window and the kept range;
+ *    so does count[b] > NASR_OFFLINE_MAX_FRAMES (never kept: N <= 2048).  count[b] = 0 gives what T = 0 gives in the offline entries.  The
+ *    same stream may appear in several rows, and the streams need not share right_context.
+ *  - Call contract.  The calls complete steps in flight, run eagerly and synchronise; they change no stream in any bit (K/V, caches,
+ *    decoder state, token rings, the history itself), capture no graph and invalidate none.  They reject NASR_FLAG_NO_SYNC and accept the
+ *    flags of their twins: NASR_FLAG_NO_BOOST and NASR_FLAG_NO_LM (transcribe), NASR_FLAG_BEAM_BOOST (beam).  Like every offline call each
+ *    one forgets the read-outs of the call before; they fail with a message, the engine usable, when the option is off, on null streams /
+ *    first / count and on a stream of another engine.
+ *  - Results are read with the offline read-outs, which behave as after the twin: nasr_engine_beam_hypothesis, _lm and _boost,
+ *    nasr_engine_offline_token_logprobs, _token_alternatives and _frame_blank_logprobs, nasr_engine_align_lattice.  The encoder taps of
+ *    nasr_engine_offline_tap are empty after such a call.  Results of a window are bit-identical whatever else is in the batch.
+ * Engine counters "history_calls" and "history_frames". */
+int nasr_engine_history_transcribe(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                                   int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags);
+int nasr_engine_history_beam(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                             const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags);
+int nasr_engine_history_align(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                              const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                              int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags);
 
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =

@@ -49,7 +49,10 @@ EXPORTS = [
     "nasr_engine_set_greedy_lm_weights", "nasr_stream_set_lm",
     "nasr_stream_fork", "nasr_engine_preview",
     "nasr_engine_snapshot_bound", "nasr_stream_save", "nasr_stream_restore",
+    "nasr_stream_history_range", "nasr_stream_get_history",
+    "nasr_engine_history_transcribe", "nasr_engine_history_beam", "nasr_engine_history_align",
 ]
+HISTORY_ROW = 640                    # csrc/nasr_history.h: f32 values of one kept frame (the joint's encoder projection)
 SNAPSHOT_HEADER_BYTES = 144          # csrc/nasr_snapshot.h: the mirror section follows (R first, the audio format at +60)
 ALIGN_MAX_TOKENS = 1024
 BEAM_MAX, BEAM_MAX_SYMBOLS, BEAM_DEFAULT_SYMBOLS = 8, 10, 4
@@ -188,6 +191,12 @@ def lib():
         L.nasr_stream_set_lm.argtypes = [vp, C.c_int]
         L.nasr_engine_beam_hypothesis_lm.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
         L.nasr_engine_beam_hypothesis_boost.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_float), C.c_int32]
+        lp = C.POINTER(C.c_int64)
+        L.nasr_stream_history_range.argtypes = [vp, lp, ip]
+        L.nasr_stream_get_history.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
+        L.nasr_engine_history_transcribe.argtypes = [vp, C.POINTER(vp), C.c_int, lp, ip, C.POINTER(vp), ip, ip, C.POINTER(vp), C.c_uint32]
+        L.nasr_engine_history_beam.argtypes = [vp, C.POINTER(vp), C.c_int, lp, ip, C.POINTER(BeamParams), ip, C.c_uint32]
+        L.nasr_engine_history_align.argtypes = [vp, C.POINTER(vp), C.c_int, lp, ip, C.POINTER(vp), ip, dp, dp, C.POINTER(vp), C.POINTER(vp), C.c_uint32]
         L.nasr_stream_set_audio_format.argtypes = [vp, C.POINTER(AudioFormat)]
         L.nasr_engine_step_audio.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_convert_audio.argtypes = [vp, C.POINTER(AudioFormat), vp, C.c_int64, vp, C.c_int64, C.c_uint32]
@@ -341,6 +350,23 @@ class Stream:
             count = max(_chk(lib().nasr_stream_get_frame_blank_logprobs(self.h, 0, 0, None)) - first, 0)
         out = np.zeros(max(count, 1), np.float32)
         n = _chk(lib().nasr_stream_get_frame_blank_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:n].copy()
+
+    def history_range(self):
+        """(first, count): encoder frames [first, first + count) since create/reset whose encoder-projection rows this stream keeps
+        (engine option "frame_history" = N, set before the first step)"""
+        first, count = C.c_int64(0), C.c_int32(0)
+        _chk(lib().nasr_stream_history_range(self.h, C.byref(first), C.byref(count)))
+        return int(first.value), int(count.value)
+
+    def history(self, first=0, count=None) -> np.ndarray:
+        """the kept rows of frames [first, first + count), [count][640] f32 (count None: up to the last frame kept); no rows when the range
+        is not wholly kept"""
+        if count is None:
+            f0, n = self.history_range()
+            count = max(f0 + n - first, 0)
+        out = np.zeros((max(count, 1), HISTORY_ROW), np.float32)
+        n = _chk(lib().nasr_stream_get_history(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:n].copy()
 
     def set_boost(self, enable=True):
@@ -847,6 +873,37 @@ class Engine:
             ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
             ns = [a.size for a in arrs]
         return self._beam(lib().nasr_engine_transcribe_beam, ptrs, ns, beam, nbest, max_symbols, prompts, flags, lm, boost)
+
+    # ---- second pass over live streams' frame history (engine option "frame_history") -------------------
+    def _history_fn(self, fn, streams, windows):
+        """fn with the argument order of its offline twin: (engine, B, -, count[], -, ...) -> fn(engine, streams, B, first[], count[], ...)"""
+        if len(windows) != len(streams):
+            raise ValueError("one (first, count) window per stream")
+        handles = self._handles(streams)
+        firsts = (C.c_int64 * len(streams))(*[int(f) for f, _ in windows])
+        return lambda h, B, _ptrs, counts, _prompts, *rest: fn(h, handles, B, firsts, counts, *rest)
+
+    def history_transcribe(self, streams, windows, tok_cap=None, flags=0):
+        """greedy second pass: a fresh decode of window (first, count) of each stream's kept frames, as transcribe() decodes an utterance.
+        Returns (tokens, frames), frames relative to the window's first frame.  The same stream may appear several times."""
+        if len(streams) == 0:
+            return [], []
+        fn = self._history_fn(lib().nasr_engine_history_transcribe, streams, windows)
+        return self._offline(fn, None, [c for _, c in windows], 1, None, tok_cap, flags)
+
+    def history_beam(self, streams, windows, beam=4, nbest=0, max_symbols=0, flags=0, lm=False, boost=False):
+        """beam second pass over the windows: what transcribe_beam() returns, frames relative to each window's first frame"""
+        if len(streams) == 0:
+            return []
+        fn = self._history_fn(lib().nasr_engine_history_beam, streams, windows)
+        return self._beam(fn, None, [c for _, c in windows], beam, nbest, max_symbols, None, flags, lm, boost)
+
+    def history_align(self, streams, windows, tokens, flags=0):
+        """forced alignment / scoring of one transcript per window: what align() returns, frames relative to each window's first frame"""
+        if len(streams) == 0:
+            return []
+        fn = self._history_fn(lib().nasr_engine_history_align, streams, windows)
+        return self._align(fn, None, [c for _, c in windows], tokens, None, flags)
 
     def set_boost_phrases(self, phrases, bonus=None):
         """replace the engine's boost set (engine option "phrase_boost" = state capacity): phrases = sequences of 1 .. 32 non-blank token

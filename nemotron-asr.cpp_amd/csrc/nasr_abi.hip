@@ -2,6 +2,7 @@
 // include/nemotron_asr_amd.h that are not life cycle: options, step / finalize / collect, counters, taps, profiling, device helpers.
 // Which path a push takes and how it is cut is nasr_step_plan.h; the staging areas grow through grow_device, host buffers cross in PinBlocks.
 #include "nasr_engine_priv.h"
+#include "nasr_offline_plan.h"
 
 namespace nasr_eng {
 // builds the automaton on the host (nasr_boost.h) and, only if that succeeds, replaces the tables' content and puts every stream's history
@@ -201,6 +202,24 @@ static int set_decode_option(nasr_engine *e, const char *key, int value) {      
     return 0;
 }
 
+// "frame_history" = N: a capability like the decode options -- the append is captured into the step graphs with the rings' address -- so it is
+// taken until the first decode has been enqueued or the first offline call has run.  Until then no launch knows the rings: another N replaces
+// them and 0 frees them
+static int set_history_option(nasr_engine *e, int value) {          // the caller holds an ApiGuard
+    if (!nasr_hist::valid_frames(value))
+        return fail("frame_history must be 0 or the frames kept per stream, %d .. %d in multiples of %d", nasr_hist::MIN_FRAMES, nasr_hist::MAX_FRAMES, nasr_hist::MIN_FRAMES);
+    if (e->dec_started || e->off) return fail("frame_history must be set before the first step or offline call (the step's launches are already chosen)");
+    HIPCHK(hipSetDevice(e->device));
+    if (value != e->opt_frame_history) {
+        float *ring = nullptr;
+        if (value) HIPCHK(hipMalloc((void **)&ring, (size_t)nasr_hist::ring_bytes(e->max_streams, value)));
+        if (e->hist_ring) hipFree(e->hist_ring);
+        e->hist_ring = ring;
+        e->opt_frame_history = value;
+    }
+    return 0;
+}
+
 extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value) {
     if (!e || !key) return fail("null argument");
     if (!strcmp(key, "fused")) {
@@ -237,6 +256,12 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         e->opt_decode_lane = value != 0;
     }
     else if (is_decode_option(key)) { ApiGuard api_guard; if (set_decode_option(e, key, value)) return -1; }
+    else if (!strcmp(key, "history_append_rows")) {          // measurement only: the grid of k_history_append (same bytes); before the first step
+        if (value != 0 && value != 1 && value != 4) return fail("history_append_rows must be 0, 1 or 4");
+        if (e->dec_started) return fail("history_append_rows must be set before the first step");
+        e->opt_history_append_rows = value == 4 ? 4 : 0;
+    }
+    else if (!strcmp(key, "frame_history")) { ApiGuard api_guard; if (set_history_option(e, value)) return -1; }
     else if (!strcmp(key, "wide_min_tiles")) e->opt_wide_min_tiles = value;
     else if (!strcmp(key, "large_step_rows")) e->opt_large_step_rows = value;
     else if (!strcmp(key, "wide_min_rows")) e->opt_wide_min_rows = value;
@@ -971,6 +996,36 @@ extern "C" int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_
     return ring_copy(s, s->e->dec.frame_blank, FRAME_CAP, 1, first, count, out);
 }
 
+// ---- engine option "frame_history" (nasr_history.h): the kept range of a stream and the parity read-out of its rows
+extern "C" int nasr_stream_history_range(const nasr_stream *s, int64_t *first_out, int32_t *count_out) {
+    ApiGuard api_guard;
+    if (!s || !first_out || !count_out) return fail("null argument");
+    if (!s->e->opt_frame_history) return fail("%s", HISTORY_OFF);
+    DecCtrl c;
+    if (ring_ctrl(s, c)) return -1;
+    const nasr_hist::Range r = nasr_hist::retained(s->hist_valid_from, (int64_t)c.frame0 + c.t, s->e->opt_frame_history);
+    *first_out = r.first; *count_out = r.count;
+    return 0;
+}
+
+extern "C" int nasr_stream_get_history(const nasr_stream *s, int64_t first, int32_t count, float *out) {
+    ApiGuard api_guard;
+    if (!s || (count > 0 && !out)) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative frame range");
+    nasr_engine *e = s->e;
+    const int N = e->opt_frame_history;
+    if (!N) return fail("%s", HISTORY_OFF);
+    DecCtrl c;
+    if (ring_ctrl(s, c)) return -1;
+    if (count == 0 || !nasr_hist::window_kept(nasr_hist::retained(s->hist_valid_from, (int64_t)c.frame0 + c.t, N), first, count)) return 0;
+    // the window's runs in the slot's ring: one copy, two where it crosses the wrap
+    const nasr_hist::Runs r = nasr_hist::ring_runs(first, count, N);
+    const float *ring = e->hist_ring + (size_t)s->slot * N * nasr_hist::ROW_FLOATS;
+    HIPCHK(hipMemcpy(out, ring + (size_t)r.row0 * nasr_hist::ROW_FLOATS, (size_t)r.n0 * nasr_hist::ROW_BYTES, hipMemcpyDeviceToHost));
+    if (r.n1 > 0) HIPCHK(hipMemcpy(out + (size_t)r.n0 * nasr_hist::ROW_FLOATS, ring, (size_t)r.n1 * nasr_hist::ROW_BYTES, hipMemcpyDeviceToHost));
+    return count;
+}
+
 extern "C" int nasr_stream_get_token_alternatives(const nasr_stream *s, int64_t first, int32_t count, int32_t *ids_out, float *logprobs_out) {
     ApiGuard api_guard;
     if (!s || (count > 0 && (!ids_out || !logprobs_out))) return fail("null argument");
@@ -1008,6 +1063,8 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "stream_previews")) *value = e->stream_previews;                 // nasr_engine_preview calls that succeeded
     else if (!strcmp(name, "stream_saves")) *value = e->stream_saves;                       // nasr_stream_save calls that wrote a blob (one k_stream_pack launch each)
     else if (!strcmp(name, "stream_restores")) *value = e->stream_restores;                 // nasr_stream_restore calls that made a stream (refused ones are not counted)
+    else if (!strcmp(name, "history_calls")) *value = e->history_calls;                     // nasr_engine_history_* calls that succeeded
+    else if (!strcmp(name, "history_frames")) *value = e->history_frames;                   // frames those calls gathered out of the rings
     else if (!strcmp(name, "cut_drains")) *value = e->cut_drains;                          // pipelined steps that first completed the steps in flight: cut differently (piece count, family)
     else if (!strcmp(name, "boost_states")) *value = e->opt_phrase_boost ? e->boost_states : 0;      // automaton states of the current boost set
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)

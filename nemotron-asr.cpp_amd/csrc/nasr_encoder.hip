@@ -466,6 +466,27 @@ void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParam
     e->dec_started = true;                     // the decode kernels are chosen from here on: "token_logprobs", "phrase_boost", "token_alternatives", "frame_blank_logprobs" and "lm_fusion" are no longer taken
 }
 
+// k_dec_begin has advanced DecCtrl::frame0 to this step's first frame, and dp.encproj (a pipelined step: its slot's own buffer) lives until the
+// decode is done: the append belongs here, not behind k_encproj, whose step may still be waiting for the decode of the step before
+void enqueue_decode_begin(nasr_engine *e, const DecParams &dp, hipStream_t st) {
+    launch_decode_begin(dp, st);
+    if (!e->opt_frame_history) return;
+    const HistAppendParams hp = {dp.rows, dp.B, dp.T, dp.ctrl, dp.encproj, e->hist_ring, e->opt_frame_history, e->max_streams, e->opt_history_append_rows};
+    if (st == e->st) {
+        ProfScope ps(e, "k_history_append", 2.0 * dp.B * dp.T * nasr_hist::ROW_BYTES);
+        launch_history_append(hp, st);
+    } else launch_history_append(hp, st);
+}
+
+int stream_frames_done(const nasr_stream *s, int64_t *done) {
+    nasr_engine *e = s->e;
+    DecCtrl c;
+    HIPCHK(hipStreamSynchronize(e->st));
+    HIPCHK(hipMemcpy(&c, e->dec.ctrl + s->slot, sizeof(c), hipMemcpyDeviceToHost));
+    *done = (int64_t)c.frame0 + c.t;
+    return 0;
+}
+
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st) {
     ProfScope ps(e, "k_dec_iter", (double)n * (4.0 * 4 * HID * HID * 4 + (double)JNT * HID * 4 + (double)VOCAB * JNT * 4),
                  (double)n * 2.0 * B * (4.0 * 4 * HID * HID + JNT * HID + VOCAB * JNT));
@@ -520,7 +541,7 @@ int run_chunk(nasr_engine *e, const std::vector<nasr_stream *> &rows_s, const st
     // ---- a-12..a-14 greedy decode, device resident -----------------------------------------------
     DecParams dp;
     make_dec_params(e, rows, B, T, dp);
-    launch_decode_begin(dp, st);
+    enqueue_decode_begin(e, dp, st);
     int max_dec = 0;
     for (int b = 0; b < B; b++) max_dec = std::max(max_dec, n_dec[b]);
     // the landing word: the first 256 bytes of the pinned arena are reserved for it

@@ -663,6 +663,7 @@ void engine_destroy_impl(nasr_engine *e) {
     if (e->mel_stage) hipFree(e->mel_stage);
     if (e->raw_stage) hipFree(e->raw_stage);
     if (e->snap_stage) hipFree(e->snap_stage);
+    if (e->hist_ring) hipFree(e->hist_ring);
     if (e->snap_pin.p) hipHostFree(e->snap_pin.p);
     if (e->snap_pin.copied) hipEventDestroy(e->snap_pin.copied);
     for (auto *ring : {e->pcm_pin, e->raw_pin})
@@ -706,6 +707,7 @@ int stream_zero_state(nasr_stream *s, bool keep_reference_state) {
     nasr_snap::reset_state(*s, keep_reference_state);      // the host's half: the rules are the record's
     s->last_T = 0;
     s->last_ws = 0;
+    s->hist_valid_from = 0;                                // "frame_history": the frame count starts over, and with it what the stream may show of its ring
     return 0;
 }
 
@@ -750,6 +752,10 @@ int stream_fork(nasr_stream *src, nasr_stream **out) {
     nasr_engine *e = src->e;
     const int slot = free_slot(e);
     if (slot < 0) return fail("stream pool exhausted (max_streams=%d)", e->max_streams);
+    // "frame_history": the history does not travel -- the fork starts with an empty one at the frames its source has decoded, read before
+    // anything is launched or made
+    int64_t hist_from = 0;
+    if (e->opt_frame_history && stream_frames_done(src, &hist_from)) return -1;
     const std::vector<nasr_fork::Seg> segs = nasr_fork::fork_plan(nasr_snap::live_part(*src), src->slot, slot, e->esz, e->hp.n_layers, e->hp.kernel_size, e->dec, dec_features(e));
     if (const char *what = nasr_fork::plan_fault(segs, src->slot, slot)) return fail("nasr_stream_fork: bad copy plan (%s)", what);
     const int64_t piece_bytes = e->opt_fork_piece_kb > 0 ? (int64_t)e->opt_fork_piece_kb * 1024 : nasr_fork::PIECE_BYTES;
@@ -769,6 +775,7 @@ int stream_fork(nasr_stream *src, nasr_stream **out) {
     nasr_stream *f = new nasr_stream(*src);          // the whole record (the queued tokens with it), the audio plan and table
     f->slot = slot;
     f->last_T = 0;                                   // the taps show what a call left for its own slots and rows: a fork has taken part in none
+    f->hist_valid_from = hist_from;
     publish_stream(e, f, slot);
     e->stream_forks++;
     *out = f;
@@ -933,6 +940,7 @@ extern "C" int nasr_stream_restore(nasr_engine *e, const void *buf, int64_t byte
     if (sum != h.device_sum) return give_up(fail("nasr_stream_restore: device section checksum mismatch (the snapshot is corrupted): %016llx, the header says %016llx",
                                                  (unsigned long long)sum, (unsigned long long)h.device_sum));
     if (nasr_snap::device_fault(payload, segs, m, e->opt_phrase_boost ? e->boost_states : 0, err)) return give_up(fail("nasr_stream_restore: %s", err.c_str()));
+    if (e->opt_frame_history && stream_frames_done(f, &f->hist_valid_from)) return give_up(-1);      // the history does not travel: empty, from the frames the saved stream had decoded
     publish_stream(e, f, slot);
     e->stream_restores++;
     *out = f;

@@ -106,6 +106,10 @@ struct nasr_stream : nasr_snap::Mirror {
     int slot = 0, T = 1;                           // T = 1 + R
     int last_T = 0, last_row = 0, last_ws = 0;     // rows of the last chunk and the workspace set they are in (for taps)
     bool alive = false;
+    // engine option "frame_history": the first frame this stream may show of its slot's ring (nasr_hist::retained).  0 from create and both
+    // resets; a fork and a restored stream start at the frames their source had decoded -- the history does not travel, so it is not part
+    // of the record above
+    int64_t hist_valid_from = 0;
     // audio input conversion (nasr_resample.h): recomputed from the record's format by nasr_stream_set_audio_format and a restore
     nasr_rs::Plan aud_plan = {16000, 1, 1, 0, 1};
     const float *aud_table = nullptr;              // device coefficients of sample_rate (the engine's cache owns them)
@@ -269,7 +273,14 @@ struct nasr_engine {
     // option "frame_blank_logprobs": ln P(blank) at the last joint evaluation of every frame the decode has left.  Taken like "token_alternatives"
     // (LP kernels, so lp_part / tok_logprob come with it; the ring's life: DecodeSet::frame_blank)
     bool opt_frame_blank = false;
-    int *collect_dev;                // [B][1+COLLECT_STRIDE]
+    // option "frame_history" = N (0: off; nasr_history.h): every step appends its encoder-projection rows to their slots' rings
+    // [max_streams][N][640] f32, an engine buffer of its own -- not part of `dec`, so the fork plan and the snapshot format do not know it.  Taken
+    // like "frame_blank_logprobs": it adds a launch that is captured into the step graphs
+    int opt_frame_history = 0;
+    float *hist_ring = nullptr;                        // the rings for opt_frame_history frames (set_history_option allocates and frees them; freed with the engine)
+    int opt_history_append_rows = 0;                   // option "history_append_rows" (MEASUREMENT ONLY): 4 = k_history_append with four rows per workgroup; 0 = one (same bytes)
+    int64_t history_calls = 0, history_frames = 0;     // counters of the same names: nasr_engine_history_* calls / frames they gathered
+    int *collect_dev;               // [B][1+COLLECT_STRIDE]
     // descriptor staging
     char *pin = nullptr; size_t pin_cap = 0, pin_off = 0;
     char *ddesc = nullptr; size_t ddesc_cap = 0, ddesc_off = 0;
@@ -306,6 +317,8 @@ struct nasr_engine {
 };
 
 constexpr int COLLECT_STRIDE = 256;
+// what every frame-history entry answers on an engine without the option
+constexpr const char *HISTORY_OFF = "no frame history: engine option \"frame_history\" is off (set it to the frames kept per stream before the first step or offline call)";
 
 
 struct ProfScope {
@@ -398,6 +411,10 @@ DecFeatures dec_features(const nasr_engine *e);                 // the decode op
 void bind_decode(const nasr_engine *e, const DecodeSet &set, const DecFeatures &f, DecParams &dp);     // dec_set_bind with the engine's tables + bind_dec_weights; rows, B, T, encproj: the caller's
 int ensure_decode_set(nasr_engine *e);                          // dec_set_ensure of e->dec for dec_features(e), through dalloc
 void make_dec_params(nasr_engine *e, const RowDesc *rows, int B, int T, DecParams &dp);
+// the head of every live step's decode sequence on st: launch_decode_begin, then -- option "frame_history" -- the step's rows into their rings
+void enqueue_decode_begin(nasr_engine *e, const DecParams &dp, hipStream_t st);
+// frames the stream's decode has left since create / reset, read from its slot (the caller has completed the steps in flight and holds an ApiGuard)
+int stream_frames_done(const nasr_stream *s, int64_t *done);
 void enqueue_decode_iters(nasr_engine *e, const DecParams &dp, int B, int n, int &it, hipStream_t st = nullptr);
 // Rounds of decode iterations on st until no stream is active: `round` iterations, dp.n_active read into *landing, the round doubled (32 at
 // most).  `it` = iterations enqueued so far; more than frames * MAX_SYMBOLS + 64 is the error "<what> did not terminate".  rounds: counted if given

@@ -9,6 +9,7 @@
 #include "nasr_align.h"
 #include "nasr_beam.h"
 #include "nasr_resample.h"
+#include "nasr_history.h"
 
 namespace nasr {
 
@@ -265,6 +266,20 @@ int decode_blind_iterations(int frames);
 void launch_encproj(const float *x, const float *wpk, const float *bias, float *out, int M, int K, int N, hipStream_t st);
 // the LSTM candidate and g = joint.pred(h1') + b_pred of the rows in p.dlist (*p.n_dirty of them): the first three launches of launch_decode_iter
 void launch_decode_candidates(const DecParams &p, hipStream_t st);
+
+// ---- engine option "frame_history" (kernels_history.hip, nasr_history.h) ------------------------------------------------------------
+// the append: one launch at the head of a step's decode sequence, right behind launch_decode_begin (DecCtrl::frame0 of the step is in force)
+struct HistAppendParams {
+    const RowDesc *rows; int B; int T;   // the decode's own descriptors: row (b, t) is encproj row b * T + t, valid while t < rows[b].n_dec
+    const DecCtrl *ctrl;         // [slot]
+    const float *encproj;        // [B * T][640]
+    float *ring; int N; int slots;   // [slots][N][640]
+    int wg_rows;                 // 0: the rule (one row per workgroup); 4: four rows per workgroup (measurement only, same bytes)
+};
+void launch_history_append(const HistAppendParams &p, hipStream_t st);
+// the gather: frames [first, first + count) of slot's ring -> packed rows [out_row, out_row + count) (count <= N, the window kept: the host's check)
+struct HistWindow { long long first; int slot, count, out_row, pad; };
+void launch_history_gather(const HistWindow *win, int n, int max_count, const float *ring, int N, float *out, hipStream_t st);
 
 // ---- forced alignment / transcript scoring on the RNN-T lattice (kernels_align.hip, nasr_align.h) ------------------------------
 struct AlignPredParams {         // teacher forcing, step u: decoder slot k = utterance k of the sub-batch

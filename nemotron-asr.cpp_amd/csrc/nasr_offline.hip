@@ -58,6 +58,20 @@ static int ensure_offline_pos(nasr_engine *e, OfflineState *o) {
     return 0;
 }
 
+// the decode slots of a sub-batch and what the greedy decode's windows need, once per engine
+static int ensure_dec_slots(nasr_engine *e, OfflineState *o) {
+    if (o->dec.ctrl) return 0;
+    const size_t U = nasr_plan::OFFLINE_MAX_UTTS, W = OFF_DEC_WIN;
+    int rc = dec_set_ensure(o->dec, dec_features(e), (int)U, (int)(U * W), [o](const char *, void **p, size_t bytes) { return off_alloc(o, p, bytes); }, fail);
+    rc |= off_alloc(o, (void **)&o->win, U * W * JNT * 4);
+    rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
+    rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
+    rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
+    if (rc) return -1;
+    HIPCHK(hipMemset(o->dec.n_active, 0, 16));
+    return 0;
+}
+
 // row buffers for `rows` packed rows (grown, never shrunk) and the decode slots
 static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
     if (rows <= o->rows_cap) return 0;
@@ -76,17 +90,7 @@ static int ensure_rows(nasr_engine *e, OfflineState *o, int rows) {
         if (off_alloc(o, (void **)&o->zero_bias, 3 * D * 4)) return -1;
         HIPCHK(hipMemset(o->zero_bias, 0, 3 * D * 4));
     }
-    if (!o->dec.ctrl) {
-        const size_t U = nasr_plan::OFFLINE_MAX_UTTS, W = OFF_DEC_WIN;
-        rc |= dec_set_ensure(o->dec, dec_features(e), (int)U, (int)(U * W), [o](const char *, void **p, size_t bytes) { return off_alloc(o, p, bytes); }, fail);
-        rc |= off_alloc(o, (void **)&o->win, U * W * JNT * 4);
-        rc |= off_alloc(o, (void **)&o->drows, U * sizeof(RowDesc));
-        rc |= off_alloc(o, (void **)&o->dwin, U * sizeof(int4));
-        rc |= off_alloc(o, (void **)&o->sdesc, U * sizeof(OffSubDesc));
-        if (rc) return -1;
-        HIPCHK(hipMemset(o->dec.n_active, 0, 16));
-    }
-    return 0;
+    return ensure_dec_slots(e, o);
 }
 
 int grow(nasr_engine *e, OfflineState *o, OffBuf &b, size_t bytes) {
@@ -444,6 +448,72 @@ static int fail_over_limit(const OffInput &in, const int32_t *n_mel, int bad, bo
     return fail("offline plan rejected the call");
 }
 
+// ---- the third input kind: windows of live streams' frame history (engine option "frame_history", nasr_history.h) -----------------------------
+// what can be said of the arguments before anything is completed or forgotten
+static int history_check(nasr_engine *e, int B, const OffInput &in, const char *who) {
+    if (!e->opt_frame_history) return fail("%s: %s", who, HISTORY_OFF);
+    if (!in.streams || !in.first || !in.n) return fail("%s: null streams / first / count", who);
+    for (int b = 0; b < B; b++) {
+        if (!in.streams[b] || in.streams[b]->e != e) return fail("%s: streams[%d] does not belong to this engine", who, b);
+        if (in.first[b] < 0 || in.n[b] < 0) return fail("%s: negative frame window [%lld, %lld + %d) of streams[%d]", who, (long long)in.first[b], (long long)in.first[b], in.n[b], b);
+    }
+    return 0;
+}
+// behind begin_call (the steps in flight are complete): every window against what its stream keeps, the one plan over the windows' frame
+// counts, and per sub-batch the gather into o->encproj in place of front end, encoder and position tables; then the mode's batch step as ever.
+// No stream is written: the gather reads the rings, the modes decode in the offline path's own slots
+static int history_call(nasr_engine *e, OfflineState *o, int B, const OffInput &in, const OffMode &m) {
+    const int N = e->opt_frame_history;
+    std::map<const nasr_stream *, int64_t> done_of;               // the same stream may appear in several rows
+    for (int b = 0; b < B; b++) {
+        const nasr_stream *s = in.streams[b];
+        if (!done_of.count(s) && stream_frames_done(s, &done_of[s])) return -1;
+        const nasr_hist::Range kept = nasr_hist::retained(s->hist_valid_from, done_of[s], N);
+        if (!nasr_hist::window_kept(kept, in.first[b], in.n[b]))
+            return fail("%s: window [%lld, %lld) of streams[%d] is not wholly kept: the stream keeps frames [%lld, %lld) (engine option \"frame_history\" = %d)", m.who,
+                        (long long)in.first[b], (long long)in.first[b] + in.n[b], b, (long long)kept.first, (long long)kept.first + kept.count, N);
+    }
+    std::vector<int> T;
+    std::vector<nasr_plan::Batch> batches;
+    int bad = -1;
+    if (nasr_plan::plan_offline(in.n, B, e->opt_offline_rows, nasr_plan::OFFLINE_MAX_UTTS, T, batches, &bad, true))
+        return fail("%s: window %d has %d frames, more than NASR_OFFLINE_MAX_FRAMES = %d", m.who, bad, bad >= 0 ? in.n[bad] : -1, NASR_OFFLINE_MAX_FRAMES);
+    int64_t frames = 0;
+    auto run = [&]() -> int {
+        if (e->debug) { o->tap_mel.assign(B, {}); o->tap_sub.assign(B, {}); o->tap_enc.assign(B, {}); o->tap_lay.assign(B, {}); }      // no encoder ran: its taps are empty
+        if (m.setup(o, B)) return -1;
+        for (const auto &bt : batches) {
+            OffBatch ob;
+            ob.first = bt.first; ob.n = bt.count;
+            ob.off.assign(bt.count, 0); ob.T.assign(bt.count, 0);
+            std::vector<HistWindow> win(bt.count);
+            for (int k = 0; k < bt.count; k++) {
+                const int b = bt.first + k;
+                ob.T[k] = T[b]; ob.off[k] = ob.M; ob.maxT = std::max(ob.maxT, T[b]);
+                win[k] = HistWindow{(long long)in.first[b], in.streams[b]->slot, T[b], ob.M, 0};
+                ob.M += T[b];
+            }
+            if (ob.M > 0) {
+                if (ensure_dec_slots(e, o) || grow(e, o, o->encproj, (size_t)std::max(ob.M, 64) * JNT * 4)) return -1;
+                const HistWindow *dwin;                              // through the pinned descriptor arena, like every step descriptor
+                if (stage_desc(e, win, &dwin)) return -1;
+                ProfScope ps(e, "k_history_gather", 2.0 * ob.M * nasr_hist::ROW_BYTES);
+                launch_history_gather(dwin, bt.count, ob.maxT, e->hist_ring, N, o->encproj.as<float>(), e->st);
+                frames += ob.M;
+            }
+            if (m.batch(o, ob)) return -1;
+        }
+        return 0;
+    };
+    if (run()) {
+        if (m.failed) m.failed(o);
+        return -1;
+    }
+    e->history_calls++;
+    e->history_frames += frames;
+    return m.finish(o, B);
+}
+
 // An offline call from the ABI's arguments to the caller's results.  The order is the contract of all six entries: a mode's early checks hold
 // for B == 0 too; begin_call forgets the call before, so whatever fails behind it leaves no read-out of an earlier call; the limit is checked
 // by the one plan before any device work; the mode's batch step also sees the sub-batches without a frame (ob.M == 0)
@@ -453,7 +523,9 @@ int offline_call(nasr_engine *e, int B, const OffInput &in, const int32_t *promp
     if (m.early && m.early()) return -1;
     if ((flags & NASR_FLAG_NO_LM) && !m.greedy) return fail("NASR_FLAG_NO_LM belongs to nasr_engine_transcribe / _transcribe_mel; the beam search is fused by nasr_engine_set_lm alone and alignment never is");
     if (B == 0) return 0;
-    if (in.is_pcm) {
+    if (in.is_history) {
+        if (history_check(e, B, in, m.who)) return -1;
+    } else if (in.is_pcm) {
         if (!in.pcm || !in.n) return fail("null pcm / n_samples");
         for (int b = 0; b < B; b++)
             if (in.n[b] < 0 || (in.n[b] > 0 && !in.pcm[b])) return fail("bad pcm input for utterance %d", b);
@@ -465,6 +537,7 @@ int offline_call(nasr_engine *e, int B, const OffInput &in, const int32_t *promp
     if (begin_call(e, B, prompt_index, m.counts, flags, m.who)) return -1;
     OfflineState *o = e->off;
     if (m.check && m.check(B)) return -1;
+    if (in.is_history) return history_call(e, o, B, in, m);
     std::vector<int32_t> pcm_mel(in.is_pcm ? B : 0);
     for (int b = 0; b < (int)pcm_mel.size(); b++) pcm_mel[b] = nasr_plan::mel_frames(in.n[b]);
     const int32_t *n_mel = in.is_pcm ? pcm_mel.data() : in.n;
@@ -533,6 +606,13 @@ extern "C" int nasr_engine_transcribe(nasr_engine *e, int B, const int16_t *cons
     ApiGuard api_guard;
     return offline_call(e, B, pcm_input(pcm, n_samples), prompt_index, flags,
                         greedy_mode(e, "nasr_engine_transcribe", tokens_out, tokens_cap, n_tokens, frames_out));
+}
+
+extern "C" int nasr_engine_history_transcribe(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                                              int32_t *const *tokens_out, const int32_t *tokens_cap, int32_t *n_tokens, int32_t *const *frames_out, uint32_t flags) {
+    ApiGuard api_guard;
+    return offline_call(e, B, history_input(streams, first, count), nullptr, flags,
+                        greedy_mode(e, "nasr_engine_history_transcribe", tokens_out, tokens_cap, n_tokens, frames_out));
 }
 
 extern "C" int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, float *out, int64_t cap) {

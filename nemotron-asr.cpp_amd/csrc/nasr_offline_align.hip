@@ -169,6 +169,14 @@ extern "C" int nasr_engine_align(nasr_engine *e, int B, const int16_t *const *pc
                         align_mode(e, "nasr_engine_align", tokens, n_tokens, loglik_out, best_out, frames_out, token_logprobs_out));
 }
 
+extern "C" int nasr_engine_history_align(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                                         const int32_t *const *tokens, const int32_t *n_tokens, double *loglik_out, double *best_out,
+                                         int32_t *const *frames_out, float *const *token_logprobs_out, uint32_t flags) {
+    ApiGuard api_guard;
+    return offline_call(e, B, history_input(streams, first, count), nullptr, flags,
+                        align_mode(e, "nasr_engine_history_align", tokens, n_tokens, loglik_out, best_out, frames_out, token_logprobs_out));
+}
+
 extern "C" int64_t nasr_engine_align_lattice(nasr_engine *e, int u, float *lp_blank_out, float *lp_token_out, int64_t cap) {
     ApiGuard api_guard;
     if (!e) return fail("null engine");

@@ -215,6 +215,12 @@ extern "C" int nasr_engine_transcribe_beam(nasr_engine *e, int B, const int16_t 
     return offline_call(e, B, pcm_input(pcm, n_samples), prompt_index, flags, beam_mode(e, "nasr_engine_transcribe_beam", params, n_hyps, flags));
 }
 
+extern "C" int nasr_engine_history_beam(nasr_engine *e, nasr_stream *const *streams, int B, const int64_t *first, const int32_t *count,
+                                        const nasr_beam_params *params, int32_t *n_hyps, uint32_t flags) {
+    ApiGuard api_guard;
+    return offline_call(e, B, history_input(streams, first, count), nullptr, flags, beam_mode(e, "nasr_engine_history_beam", params, n_hyps, flags));
+}
+
 extern "C" int nasr_engine_beam_hypothesis(nasr_engine *e, int u, int rank, int32_t *tokens_out, int32_t *frames_out, float *token_logprobs_out,
                                            int32_t cap, double *score_out) {
     ApiGuard api_guard;

@@ -31,14 +31,16 @@ struct Batch { int first, count, rows; };
 
 // Returns 0, or -1 with *bad = the first utterance over the limit (or with a negative frame count).  T[b] and the sub-batches
 // are filled on success.
-inline int plan_offline(const int32_t *n_mel, int B, int row_budget, int max_utts, std::vector<int> &T, std::vector<Batch> &batches, int *bad) {
+// frames_given: n_mel[b] is already the encoder frame count of utterance b (a window of a stream's frame history), not its mel frames
+inline int plan_offline(const int32_t *n_mel, int B, int row_budget, int max_utts, std::vector<int> &T, std::vector<Batch> &batches, int *bad,
+                        bool frames_given = false) {
     T.assign(B > 0 ? B : 0, 0);
     batches.clear();
     if (bad) *bad = -1;
     if (B < 0 || row_budget < 1 || max_utts < 1) return -1;
     for (int b = 0; b < B; b++) {
         if (n_mel[b] < 0) { if (bad) *bad = b; return -1; }
-        T[b] = enc_frames(n_mel[b]);
+        T[b] = frames_given ? n_mel[b] : enc_frames(n_mel[b]);
         if (T[b] > OFFLINE_MAX_FRAMES) { if (bad) *bad = b; return -1; }
     }
     int b = 0;

@@ -64,9 +64,13 @@ int grow(nasr_engine *e, OfflineState *o, OffBuf &b, size_t bytes);   // room fo
 struct OffBatch { int first = 0, n = 0, M = 0, maxT = 0; std::vector<int> off, T; };
 
 // the input of an offline call: the log-mel of every utterance in host memory, or its 16 kHz s16 samples (host, or device with NASR_FLAG_PCM_DEVICE)
-struct OffInput { bool is_pcm; const float *const *mel; const int16_t *const *pcm; const int32_t *n; };
+// ... or, engine option "frame_history", windows of live streams' kept encoder-projection rows: frames [first[b], first[b] + n[b]) of streams[b].
+// Such a call runs no front end and no encoder: o->encproj is filled by the gather (k_history_gather), then the mode's batch step runs unchanged
+struct OffInput { bool is_pcm; const float *const *mel; const int16_t *const *pcm; const int32_t *n;
+                  bool is_history = false; nasr_stream *const *streams = nullptr; const int64_t *first = nullptr; };
 inline OffInput mel_input(const float *const *mel, const int32_t *n_frames) { return {false, mel, nullptr, n_frames}; }
 inline OffInput pcm_input(const int16_t *const *pcm, const int32_t *n_samples) { return {true, nullptr, pcm, n_samples}; }
+inline OffInput history_input(nasr_stream *const *streams, const int64_t *first, const int32_t *count) { return {false, nullptr, nullptr, count, true, streams, first}; }
 
 // What a mode (greedy, align, beam) supplies to offline_call, in the order it is called.  early and check may be empty
 struct OffMode {

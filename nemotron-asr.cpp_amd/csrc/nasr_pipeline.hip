@@ -54,7 +54,7 @@ int build_step_graph(nasr_engine *e, int B, int T, int R, int G, hipGraphExec_t 
         if (enqueue_encoder(e, g_rows, G > 1 ? g_vrows : g_rows, nullptr, B, T, R, G)) return -1;
         DecParams dp;
         make_dec_params(e, g_rows, B, T * G, dp);
-        launch_decode_begin(dp, st);
+        enqueue_decode_begin(e, dp, st);
         int it = 0;
         enqueue_decode_iters(e, dp, B, decode_blind_iterations(T * G), it);
         hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, st, g_meta, g_meta + B, B, e->dec.ctrl, e->dec.tok_ring, e->collect_dev, COLLECT_STRIDE, e->dec.n_active);
@@ -114,7 +114,7 @@ int capture_decode_graph(nasr_engine *e, int p, int B, int T, int G, hipStream_t
         DecParams dp;
         make_dec_params(e, (const RowDesc *)(P.g_desc + graph_desc_layout(B, G).rows), B, T * G, dp);
         dp.encproj = P.encproj;
-        launch_decode_begin(dp, cs);
+        enqueue_decode_begin(e, dp, cs);
         for (int k = 0; k < iters; k++) launch_decode_iter(dp, cs);
         hipLaunchKernelGGL(k_collect, dim3(B), dim3(64), 0, cs, P.g_dmeta, P.g_dmeta + B, B, e->dec.ctrl, e->dec.tok_ring, P.collect_dev, COLLECT_STRIDE, e->dec.n_active);
         HIPCHK(hipMemcpyAsync(P.gh_collect, P.collect_dev, ((size_t)B * (1 + COLLECT_STRIDE) + 1) * sizeof(int), hipMemcpyDeviceToHost, cs));

@@ -413,6 +413,38 @@ nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_s
     return out;
 }
 
+// the hypotheses of utterance 0 of the beam call that has just returned n_hyps (an offline call or a second pass), with the LM and boost sides
+// where the context has them; empty on failure
+static std::vector<nemo_hypothesis> read_beam_hypotheses(nemo_context *ctx, int n_hyps, const char *who) {
+    std::vector<nemo_hypothesis> out;
+    for (int r = 0; r < n_hyps; r++) {
+        nemo_hypothesis h;
+        const int n = nasr_engine_beam_hypothesis(ctx->engine, 0, r, nullptr, nullptr, nullptr, 0, nullptr);
+        if (n < 0) { fprintf(stderr, "%s: %s\n", who, nasr_last_error()); out.clear(); return out; }
+        h.tokens.assign((size_t)n, 0); h.frames.assign((size_t)n, 0); h.logprobs.assign((size_t)n, 0.0f);
+        nasr_engine_beam_hypothesis(ctx->engine, 0, r, h.tokens.data(), h.frames.data(), h.logprobs.data(), n, &h.score);
+        if (ctx->lm_attached) {
+            if (nasr_engine_beam_hypothesis_lm(ctx->engine, 0, r, &h.lm_logprob, &h.total, nullptr, 0) < 0) {
+                fprintf(stderr, "%s: %s\n", who, nasr_last_error());
+                out.clear();
+                return out;
+            }
+            h.has_lm = true;
+        }
+        if (ctx->beam_boost) {
+            h.token_bonuses.assign((size_t)n, 0.0f);
+            if (nasr_engine_beam_hypothesis_boost(ctx->engine, 0, r, &h.boost, &h.total, h.token_bonuses.data(), n) < 0) {
+                fprintf(stderr, "%s: %s\n", who, nasr_last_error());
+                out.clear();
+                return out;
+            }
+            h.has_boost = true;
+        }
+        out.push_back(h);
+    }
+    return out;
+}
+
 std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest, int max_symbols) {
     std::vector<nemo_hypothesis> out;
     if (!ctx || !ctx->engine || n_samples < 0 || (n_samples > 0 && !audio)) return out;
@@ -439,32 +471,7 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return out;
     }
-    for (int r = 0; r < n_hyps; r++) {
-        nemo_hypothesis h;
-        const int n = nasr_engine_beam_hypothesis(ctx->engine, 0, r, nullptr, nullptr, nullptr, 0, nullptr);
-        if (n < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); out.clear(); return out; }
-        h.tokens.assign((size_t)n, 0); h.frames.assign((size_t)n, 0); h.logprobs.assign((size_t)n, 0.0f);
-        nasr_engine_beam_hypothesis(ctx->engine, 0, r, h.tokens.data(), h.frames.data(), h.logprobs.data(), n, &h.score);
-        if (ctx->lm_attached) {
-            if (nasr_engine_beam_hypothesis_lm(ctx->engine, 0, r, &h.lm_logprob, &h.total, nullptr, 0) < 0) {
-                fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
-                out.clear();
-                return out;
-            }
-            h.has_lm = true;
-        }
-        if (ctx->beam_boost) {
-            h.token_bonuses.assign((size_t)n, 0.0f);
-            if (nasr_engine_beam_hypothesis_boost(ctx->engine, 0, r, &h.boost, &h.total, h.token_bonuses.data(), n) < 0) {
-                fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
-                out.clear();
-                return out;
-            }
-            h.has_boost = true;
-        }
-        out.push_back(h);
-    }
-    return out;
+    return read_beam_hypotheses(ctx, n_hyps, __func__);
 }
 
 bool nemo_set_language(nemo_context *ctx, const char *lang) {
@@ -743,6 +750,68 @@ std::string nemo_stream_preview(nemo_stream_context *sctx) {
         return "";
     }
     return tokens_to_text(std::vector<int>(tok, tok + std::min(cnt, cap)), sctx->nctx->vocab);      // tentative: neither the transcript nor the tokens change
+}
+
+std::string beam_hypothesis_line(size_t rank, const nemo_hypothesis &h, const std::vector<std::string> &vocab) {
+    const std::string text = tokens_to_text(std::vector<int>(h.tokens.begin(), h.tokens.end()), vocab);
+    char head[160];
+    if (h.has_boost && h.has_lm) snprintf(head, sizeof(head), "%zu %.6f %.6f %.6f %.6f ", rank, h.score, h.lm_logprob, h.boost, h.total);
+    else if (h.has_boost) snprintf(head, sizeof(head), "%zu %.6f %.6f %.6f ", rank, h.score, h.boost, h.total);
+    else if (h.has_lm) snprintf(head, sizeof(head), "%zu %.6f %.6f %.6f ", rank, h.score, h.lm_logprob, h.total);
+    else snprintf(head, sizeof(head), "%zu %.6f ", rank, h.score);
+    return head + text;
+}
+
+bool nemo_set_frame_history(nemo_context *ctx, int frames) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "frame_history", frames) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool nemo_stream_history_range(nemo_stream_context *sctx, int64_t *first, int *count) {
+    int32_t n = 0;
+    if (!sctx || !first || !count) return false;
+    if (nasr_stream_history_range(sctx->stream, first, &n) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    *count = n;
+    return true;
+}
+
+std::vector<nemo_hypothesis> nemo_stream_second_pass_beam(nemo_stream_context *sctx, int64_t first, int count, int beam, int nbest, int max_symbols) {
+    std::vector<nemo_hypothesis> out;
+    if (!sctx || !sctx->nctx || !sctx->nctx->engine) return out;
+    nemo_context *ctx = sctx->nctx;
+    nasr_beam_params bp;
+    bp.beam = beam; bp.nbest = nbest; bp.max_symbols = max_symbols; bp.reserved = 0;
+    const int32_t cnt = count;
+    int32_t n_hyps = 0;
+    if (nasr_engine_history_beam(ctx->engine, &sctx->stream, 1, &first, &cnt, &bp, &n_hyps, ctx->beam_boost ? NASR_FLAG_BEAM_BOOST : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return out;
+    }
+    return read_beam_hypotheses(ctx, n_hyps, __func__);
+}
+
+nemo_alignment nemo_stream_second_pass_align(nemo_stream_context *sctx, int64_t first, int count, const std::vector<int32_t> &tokens) {
+    nemo_alignment out;
+    if (!sctx || !sctx->nctx || !sctx->nctx->engine) return out;
+    out.frames.assign(tokens.size(), -1);
+    out.logprobs.assign(tokens.size(), NAN);
+    const int32_t n_tok = (int32_t)tokens.size(), cnt = count;
+    const int32_t *tp = tokens.data();
+    int32_t *fp = out.frames.data();
+    float *lp = out.logprobs.data();
+    if (nasr_engine_history_align(sctx->nctx->engine, &sctx->stream, 1, &first, &cnt, &tp, &n_tok, &out.loglik, &out.best, &fp, &lp, 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return out;
+    }
+    out.ok = true;
+    return out;
 }
 
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx) { return sctx ? sctx->transcript : ""; }

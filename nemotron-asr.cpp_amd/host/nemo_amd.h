@@ -126,6 +126,8 @@ struct nemo_hypothesis {
     std::vector<float> token_bonuses;
 };
 std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16_t *audio, int n_samples, int beam, int nbest = 0, int max_symbols = 0);
+// the line both command-line tools print for hypothesis `rank` of a beam call: rank score [lm] [boost] [total] text
+std::string beam_hypothesis_line(size_t rank, const nemo_hypothesis &h, const std::vector<std::string> &vocab);
 
 // MI355X extension: shallow fusion of a back-off n-gram language model in nemo_transcribe_beam (nasr_engine_set_lm).
 // The ARPA file is over the vocabulary's pieces (lm_arpa.h: one piece or `ids:N` per word, <s>, </s>, <unk>; log10 values).  weight and
@@ -175,6 +177,18 @@ nemo_stream_context *nemo_stream_restore(nemo_context *ctx, const uint8_t *data,
 // MI355X extension: the text nemo_stream_finalize would add if it were called now -- the tentative tail of a caption at a long right
 // context -- without ending or changing the stream (nasr_engine_preview; it needs one free slot).  "" when nothing is buffered or on failure
 std::string nemo_stream_preview(nemo_stream_context *sctx);
+// MI355X extension: a second pass over frames the stream has already encoded (engine option "frame_history"): the
+// beam search of nemo_transcribe_beam, or the alignment of nemo_align_audio, over encoder frames [first, first + count) of the stream --
+// e.g. an utterance of nemo_stream_get_endpoints: first = utt_start, count = frame + 1 - utt_start -- with no audio and no encoder run.
+// nemo_set_frame_history(ctx, frames) before the first stream processes audio: frames kept per stream, 64 .. 2048 in multiples of 64 (0 =
+// off); nemo_stream_history_range: the frames the stream keeps now.  A second pass is a fresh decode of the window (zero decoder state, the
+// LM's start state, an empty boost history); frames in its results count from `first`.  The language model of nemo_load_lm_arpa and
+// nemo_set_beam_boost apply as in nemo_transcribe_beam.  The stream, its transcript and its tokens are not changed.  Empty / ok = false on
+// failure (a window that is not wholly kept, the option off: the reason on stderr)
+bool nemo_set_frame_history(nemo_context *ctx, int frames);
+bool nemo_stream_history_range(nemo_stream_context *sctx, int64_t *first, int *count);
+std::vector<nemo_hypothesis> nemo_stream_second_pass_beam(nemo_stream_context *sctx, int64_t first, int count, int beam, int nbest = 0, int max_symbols = 0);
+nemo_alignment nemo_stream_second_pass_align(nemo_stream_context *sctx, int64_t first, int count, const std::vector<int32_t> &tokens);
 std::string nemo_stream_get_transcript(nemo_stream_context *sctx);
 const std::vector<int> &nemo_stream_get_tokens(nemo_stream_context *sctx);
 void nemo_stream_reset(nemo_stream_context *sctx);

@@ -90,10 +90,7 @@ int main(int argc, char **argv) {
         const std::vector<int> toks(hyps[r].tokens.begin(), hyps[r].tokens.end());
         const std::string text = tokens_to_text(toks, ctx->vocab);
         if (beam == 0) printf("%s\n", text.c_str());
-        else if (hyps[r].has_boost && hyps[r].has_lm) printf("%zu %.6f %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].lm_logprob, hyps[r].boost, hyps[r].total, text.c_str());
-        else if (hyps[r].has_boost) printf("%zu %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].boost, hyps[r].total, text.c_str());
-        else if (hyps[r].has_lm) printf("%zu %.6f %.6f %.6f %s\n", r, hyps[r].score, hyps[r].lm_logprob, hyps[r].total, text.c_str());
-        else printf("%zu %.6f %s\n", r, hyps[r].score, text.c_str());
+        else printf("%s\n", beam_hypothesis_line(r, hyps[r], ctx->vocab).c_str());
         if (print_tokens) {
             printf("tokens");
             for (int t : toks) printf(" %d", t);

@@ -64,6 +64,13 @@ static void usage(const char *prog) {
             "  --lm FILE.arpa:  shallow fusion of a back-off n-gram model over the vocabulary's pieces (one piece or ids:N per ARPA word, <s>, </s>, <unk>;\n"
             "                   up to 5-grams) in the greedy decode: arg-max over logit + X * ln P_lm(token | tokens so far) + Y for every non-blank token,\n"
             "                   blank unbiased.  --lm-weight X (default 0.5), --token-bonus Y (default 0; it offsets the deletions an unbiased blank causes); 0 .. 100\n"
+            "  --second-pass W [--nbest N] [--max-symbols S] [--history-frames F]: a beam search (width W = 1 .. 8) over the encoder frames the stream\n"
+            "                   itself has produced (engine option frame_history = F, default 2048; no second encoder run): at the end of the input -- with\n"
+            "                   --endpoints at every endpoint, and at the end for an utterance still open -- the N best transcripts of the utterance's frames,\n"
+            "                   one line per hypothesis as nemotron-transcribe-amd --beam prints them: rank score [lm] [boost total] text.  The transcript's own\n"
+            "                   line is held until the end, as with --preview.  --lm and --boost-file then also act inside the search, as that tool's --beam\n"
+            "                   does (the model's --lm-weight / --token-bonus; hypotheses rank by total).  An utterance longer than F frames gets a notice and\n"
+            "                   its greedy text instead\n"
             "  --pipeline E:    consecutive reads overlap on the GPU, E = 0..4 (same transcript; each delta appears E reads later).\n"
             "                   1: decode of one read beside the encoder of the next; 2..4: the encoder in E pieces on E hardware queues\n"
             "                   (4 = the fastest way through a file).  --pipeline without a number = 1; --pipeline2 / --pipeline3 still work\n"
@@ -81,6 +88,7 @@ int main(int argc, char **argv) {
     const char *boost_file = nullptr, *save_state = nullptr, *load_state = nullptr;
     int alternatives = 0;
     bool endpoints = false, preview = false;
+    int second_pass = 0, sp_nbest = 0, sp_symbols = 0, history_frames = 2048;
     nasr_endpoint::Config ep_cfg;
     float boost_bonus = 4.0f;
     const char *lm_path = nullptr;
@@ -103,6 +111,10 @@ int main(int argc, char **argv) {
         else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
         else if (a == "--endpoints") endpoints = true;
         else if (a == "--preview") preview = true;
+        else if (a == "--second-pass" && i + 1 < argc) second_pass = atoi(argv[++i]);
+        else if (a == "--nbest" && i + 1 < argc) sp_nbest = atoi(argv[++i]);
+        else if (a == "--max-symbols" && i + 1 < argc) sp_symbols = atoi(argv[++i]);
+        else if (a == "--history-frames" && i + 1 < argc) history_frames = atoi(argv[++i]);
         else if (a == "--save-state" && i + 1 < argc) save_state = argv[++i];
         else if (a == "--load-state" && i + 1 < argc) load_state = argv[++i];
         else if (a == "--endpoint-silence" && i + 1 < argc) ep_cfg.silence_frames_after_speech = (int)std::lround(atof(argv[++i]) / 0.08);
@@ -146,19 +158,24 @@ int main(int argc, char **argv) {
     }
     if (read_chunks < 1 || read_chunks > 4096) { fprintf(stderr, "--read-chunks must be in 1..4096 (got %d)\n", read_chunks); return 1; }
     if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
+    if (second_pass < 0 || second_pass > 8) { fprintf(stderr, "--second-pass must be 1 .. 8 (got %d)\n", second_pass); return 1; }
+    if (!second_pass && (sp_nbest || sp_symbols || history_frames != 2048)) { fprintf(stderr, "--nbest, --max-symbols and --history-frames go with --second-pass\n"); return 1; }
     if (chunk_ms < 10) { fprintf(stderr, "chunk_ms must be >= 10 (got %d)\n", chunk_ms); return 1; }
     fprintf(stderr, "Configuration:\n  Model:          %s\n  Audio:          %s\n  Chunk size:     %d ms\n  Right context:  %d\n\n",
             model_path, from_stdin ? "stdin" : audio_path, chunk_ms, right_context);
 
+    if (second_pass && !diarize_gguf.empty()) { fprintf(stderr, "--second-pass does not go with --diarize\n"); return 1; }
+    if (second_pass && (save_state || load_state)) { fprintf(stderr, "--second-pass does not go with --save-state / --load-state (the frame history does not travel)\n"); return 1; }
     if (preview && !diarize_gguf.empty()) { fprintf(stderr, "--preview does not go with --diarize\n"); return 1; }
     if ((save_state || load_state) && !diarize_gguf.empty()) { fprintf(stderr, "--save-state / --load-state do not go with --diarize\n"); return 1; }
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, preview ? 2 : 1);      // a preview flushes a fork of the stream: one slot of headroom
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
     if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
     if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
+    if (second_pass && !nemo_set_frame_history(ctx, history_frames)) { fprintf(stderr, "Failed to enable the frame history (--history-frames 64 .. 2048 in multiples of 64)\n"); nemo_free(ctx); return 1; }
     if (endpoints && !nemo_set_frame_blank_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable per-frame blank log-probabilities\n"); nemo_free(ctx); return 1; }
-    if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
-    if (lm_path && !(nemo_set_lm_fusion(ctx, true) && nemo_load_lm_arpa(ctx, lm_path, 0.0f) && nemo_set_greedy_lm_weights(ctx, lm_weight, token_bonus))) {
+    if (boost_file && !(nemo_set_phrase_boost(ctx, 4096) && nemo_load_boost_file(ctx, boost_file, boost_bonus) && (!second_pass || nemo_set_beam_boost(ctx, true)))) { fprintf(stderr, "Failed to load boost phrases from '%s'\n", boost_file); nemo_free(ctx); return 1; }
+    if (lm_path && !(nemo_set_lm_fusion(ctx, true) && nemo_load_lm_arpa(ctx, lm_path, second_pass ? lm_weight : 0.0f, second_pass ? token_bonus : 0.0f) && nemo_set_greedy_lm_weights(ctx, lm_weight, token_bonus))) {
         fprintf(stderr, "Failed to load the language model from '%s'\n", lm_path);
         nemo_free(ctx);
         return 1;
@@ -204,7 +221,7 @@ int main(int argc, char **argv) {
     FILE *json_file = json_path.empty() || json_path == "-" ? nullptr : fopen(json_path.c_str(), "w");
     std::string held;
     auto handle_text = [&](const std::string &text, size_t samples_so_far) {     // reference :196-224
-        if (!text.empty() && preview) held += text;       // --preview: the `~ ` lines come first, the transcript's line stays whole
+        if (!text.empty() && (preview || second_pass)) held += text;       // --preview: the `~ ` lines come first, the transcript's line stays whole
         else if (!text.empty()) { fputs(text.c_str(), stdout); fflush(stdout); }
         if (!dp || text.empty()) return;
         diarize_pipeline_push_text(dp, text, (double)samples_so_far / 16000.0);
@@ -212,6 +229,30 @@ int main(int argc, char **argv) {
             const std::string j = diarize_pipeline_drain_json(dp);
             if (!j.empty()) fputs(j.c_str(), json_file ? json_file : stdout);
         }
+    };
+    // --second-pass: the N best of one utterance, frames [start, end) of the stream holding tokens [tok0, tok0 + n_tok) of its greedy decode
+    size_t sp_events = 0, sp_tok0 = 0;
+    auto second_pass_utterance = [&](int64_t start, int64_t end, size_t n_tok) {
+        const std::vector<int> &all = nemo_stream_get_tokens(sctx);
+        const size_t a = std::min(sp_tok0, all.size()), b = std::min(sp_tok0 + n_tok, all.size());
+        sp_tok0 += n_tok;
+        fprintf(stderr, "second pass: utterance %.2f .. %.2f s\n", (double)start * 0.08, (double)end * 0.08);
+        int64_t kept_first = 0;
+        int kept = 0;
+        const bool have = nemo_stream_history_range(sctx, &kept_first, &kept);
+        if (end - start > history_frames || !have || start < kept_first || end > kept_first + kept) {
+            printf("second pass: the utterance's %lld frames are not all among the %d kept; greedy:%s\n", (long long)(end - start), history_frames,
+                   tokens_to_text(std::vector<int>(all.begin() + (long)a, all.begin() + (long)b), ctx->vocab).c_str());
+            fflush(stdout);
+            return;
+        }
+        const std::vector<nemo_hypothesis> hyps = nemo_stream_second_pass_beam(sctx, start, (int)(end - start), second_pass, sp_nbest, sp_symbols);
+        for (size_t r = 0; r < hyps.size(); r++) printf("%s\n", beam_hypothesis_line(r, hyps[r], ctx->vocab).c_str());
+        fflush(stdout);
+    };
+    auto second_pass_new_endpoints = [&]() {
+        const std::vector<nasr_endpoint::Event> &evs = nemo_stream_get_endpoints(sctx);
+        for (; sp_events < evs.size(); sp_events++) second_pass_utterance(evs[sp_events].utt_start, evs[sp_events].frame + 1, (size_t)evs[sp_events].tokens);
     };
     std::vector<float> f32;
     FILE *in = from_stdin ? stdin : fopen(audio_path, "rb");
@@ -282,6 +323,7 @@ int main(int argc, char **argv) {
         // handle_text's sample count feeds the diarization pipeline only, which runs on the default format: there frames are 16 kHz samples
         handle_text(own_format ? nemo_stream_process_audio(sctx, buf, (int)got) : nemo_stream_process_incremental(sctx, (const int16_t *)buf, (int)got), total);
         if (preview) { printf("~ %s\n", nemo_stream_preview(sctx).c_str()); fflush(stdout); }
+        if (second_pass && endpoints) second_pass_new_endpoints();
         if (dp) {
             f32.resize(got);
             for (size_t k = 0; k < got; k++) f32[k] = (float)((const int16_t *)buf)[k] / 32768.0f;
@@ -299,6 +341,14 @@ int main(int argc, char **argv) {
         }
         fprintf(stderr, "Wrote snapshot: %s (%zu bytes)\n", save_state, blob.size());
     } else handle_text(nemo_stream_finalize(sctx), total);
+    if (second_pass && endpoints) {                    // the endpoints the tail produced, then the utterance still open
+        second_pass_new_endpoints();
+        if (sctx->ep_state.tokens > 0) second_pass_utterance(sctx->ep_state.utt_start, sctx->ep_frames, (size_t)sctx->ep_state.tokens);
+    } else if (second_pass) {                          // without endpointing the whole stream is one utterance
+        int64_t kept_first = 0;
+        int kept = 0;
+        if (nemo_stream_history_range(sctx, &kept_first, &kept)) second_pass_utterance(0, kept_first + kept, nemo_stream_get_tokens(sctx).size());
+    }
     fputs(held.c_str(), stdout);
     printf("\n");
     if (!from_stdin) fclose(in);
