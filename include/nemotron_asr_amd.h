@@ -156,6 +156,13 @@ int nasr_stream_get_token_frames(const nasr_stream *s, int64_t first, int32_t co
  * logits at the chosen token: a boosted token need not be the raw arg-max, so the range is then (-inf, 0] (any finite value <= 0).  Same contract as nasr_stream_get_token_frames: completes steps in flight, tokens counted from create/reset,
  * only the most recent 4096 kept, returns the number written, < 0 on error -- also when engine option "token_logprobs" is off. */
 int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out);
+/* per-token entropy (the reference has no such output; engine option "token_entropy" = round(1000 alpha)): for tokens [first, first + count)
+ * of this stream the entropy of order alpha, in nats, of the joint's softmax over all 1025 outputs at the frame and decoder state where each
+ * was emitted -- alpha = 1: -sum p ln p (Shannon), else ln(sum p^alpha) / (1 - alpha) (Renyi; Tsallis follows from it, host/token_confidence.h).
+ * f32 in [0, ln 1025].  With phrase boosting or LM fusion it stays the MODEL's (raw logits).  Same contract as
+ * nasr_stream_get_token_logprobs: completes steps in flight, tokens counted from create/reset, only the most recent 4096 kept, returns the
+ * number written, < 0 on error -- also when engine option "token_entropy" is off. */
+int nasr_stream_get_token_entropies(const nasr_stream *s, int64_t first, int32_t count, float *out);
 /* per-token alternatives (the reference has no such output; engine option "token_alternatives" = K): for tokens [first, first + count) of
  * this stream the K largest of the 1025 joint outputs (blank included: a blank among them means the model nearly emitted nothing there) at
  * the frame and decoder state where each token was emitted, as ids and ln P under the joint's softmax.  Descending logit, among equal logit
@@ -288,7 +295,7 @@ int nasr_engine_preview(nasr_engine *e, nasr_stream *const *streams, int B,
  *    same tokens, frames and read-outs, bit for bit when each is stepped in calls of its own; read-outs are counted from the original's
  *    create / reset.  e may be the engine that saved, another engine of the process, an engine on another device or of a later process, as
  *    long as it agrees with the blob: dtype, n_layers, kernel_size, the layout constants, the decode options (token_logprobs,
- *    token_alternatives, frame_blank_logprobs, phrase_boost, lm_fusion) and three fingerprints -- of the weight set (names, types, shapes
+ *    token_alternatives, frame_blank_logprobs, phrase_boost, lm_fusion, token_entropy) and three fingerprints -- of the weight set (names, types, shapes
  *    and a bounded sample of every tensor's bytes, taken at nasr_engine_create), of the boost set in force and of the language model in
  *    force with its greedy weights (0 when none).  A caller who wants to restore under another boost set or model sets the same one
  *    first; there is no mode that resets the bias state.
@@ -415,6 +422,13 @@ enum {
  * state and the values of "token_logprobs" / "token_alternatives" are bit-identical to 0.  It selects the decode kernels that are captured
  * into the step graphs (those of "token_logprobs" plus one small launch per iteration) and allocates a ring per stream, so it is REJECTED
  * after the first step or offline call.
+ * "token_entropy" (0 default / round(1000 alpha): 1000 = Shannon, 333 = the usual 1/3; accepted are 1000, 50 .. 900 and 1100 .. 4000 -- closer
+ * to 1 the order's 1 / (1 - alpha) outgrows the precision of the value -- anything else is refused): a capability like "token_logprobs" and
+ * independent of it -- the device decode also keeps, for every emitted token, the entropy of order alpha of the joint's softmax over the 1025
+ * outputs where it was emitted (nasr_stream_get_token_entropies, nasr_engine_offline_token_entropies): the input of entropy-based confidence
+ * (host/token_confidence.h).  Under "phrase_boost" / "lm_fusion" the value stays the model's.  Tokens, frames, iteration counts, decoder state
+ * and the values of the other read-outs are bit-identical to 0.  It selects the decode kernels that are captured into the step graphs and
+ * allocates a ring per stream, so it is REJECTED after the first step or offline call.
  * "frame_history" (0 default; N = 64 .. 2048 in multiples of 64, other values are refused): a capability like "frame_blank_logprobs" -- with
  * N every live stream keeps the joint's encoder-projection rows ([640] f32, prompt fused in) of the last N encoder frames it decoded, in a
  * device ring filled by one more small launch at the head of every step's decode (csrc/nasr_history.h), so that the offline modes can run
@@ -503,6 +517,10 @@ int64_t nasr_engine_offline_tap(nasr_engine *e, int which, int u, int index, flo
  * token, see nasr_stream_get_token_logprobs).  Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline
  * call forgets the values of the one before. */
 int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *out, int32_t cap);
+/* the entropy (engine option "token_entropy", see nasr_stream_get_token_entropies) at every token of utterance u of the LAST offline greedy
+ * call (nasr_engine_transcribe / _transcribe_mel / nasr_engine_history_transcribe), in token order: out[i] belongs to tokens_out[u][i].
+ * Returns the number written (<= cap), with out == NULL the number available, or < 0.  Every offline call forgets the values of the one before. */
+int nasr_engine_offline_token_entropies(nasr_engine *e, int u, float *out, int32_t cap);
 /* ln P(blank) at the last joint evaluation of every encoder frame of utterance u of the LAST offline call (either entry; engine option
  * "frame_blank_logprobs" = 1): out[t], t = 0 .. T - 1, see nasr_stream_get_frame_blank_logprobs.  Returns the number written (<= cap), with
  * out == NULL the number available (T), or < 0.  Every offline call forgets the values of the one before. */

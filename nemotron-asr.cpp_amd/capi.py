@@ -51,6 +51,7 @@ EXPORTS = [
     "nasr_engine_snapshot_bound", "nasr_stream_save", "nasr_stream_restore",
     "nasr_stream_history_range", "nasr_stream_get_history",
     "nasr_engine_history_transcribe", "nasr_engine_history_beam", "nasr_engine_history_align",
+    "nasr_stream_get_token_entropies", "nasr_engine_offline_token_entropies",
 ]
 HISTORY_ROW = 640                    # csrc/nasr_history.h: f32 values of one kept frame (the joint's encoder projection)
 SNAPSHOT_HEADER_BYTES = 144          # csrc/nasr_snapshot.h: the mirror section follows (R first, the audio format at +60)
@@ -171,6 +172,8 @@ def lib():
         L.nasr_engine_offline_tap.restype = C.c_int64
         L.nasr_stream_get_token_logprobs.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
         L.nasr_engine_offline_token_logprobs.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
+        L.nasr_stream_get_token_entropies.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_float)]
+        L.nasr_engine_offline_token_entropies.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32]
         L.nasr_engine_set_boost_phrases.argtypes = [vp, C.c_int, C.POINTER(ip), ip, C.POINTER(C.c_float)]
         L.nasr_stream_set_boost.argtypes = [vp, C.c_int]
         L.nasr_stream_get_token_alternatives.argtypes = [vp, C.c_int64, C.c_int32, ip, C.POINTER(C.c_float)]
@@ -329,6 +332,15 @@ class Stream:
             count = max(int(self.stats().tokens) - first, 0)
         out = np.zeros(max(count, 1), np.float32)
         n = _chk(lib().nasr_stream_get_token_logprobs(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out[:n].copy()
+
+    def token_entropies(self, first=0, count=None) -> np.ndarray:
+        """entropy of order alpha (nats, in [0, ln 1025]) of the joint's softmax where each of tokens [first, first + count) since
+        create/reset was emitted, f32; needs engine option "token_entropy" = round(1000 alpha) (set before the first step)"""
+        if count is None:
+            count = max(int(self.stats().tokens) - first, 0)
+        out = np.zeros(max(count, 1), np.float32)
+        n = _chk(lib().nasr_stream_get_token_entropies(self.h, first, count, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out[:n].copy()
 
     def token_alternatives(self, first=0, count=None):
@@ -938,6 +950,14 @@ class Engine:
         cap = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, None, 0))
         out = np.zeros(max(cap, 1), np.float32)
         n = _chk(L.nasr_engine_offline_token_logprobs(self.h, u, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
+        return out[:n].copy()
+
+    def offline_token_entropies(self, u) -> np.ndarray:
+        """the entropy at every token of utterance u of the last offline greedy call (engine option "token_entropy" = round(1000 alpha))"""
+        L = lib()
+        cap = _chk(L.nasr_engine_offline_token_entropies(self.h, u, None, 0))
+        out = np.zeros(max(cap, 1), np.float32)
+        n = _chk(L.nasr_engine_offline_token_entropies(self.h, u, out.ctypes.data_as(C.POINTER(C.c_float)), cap))
         return out[:n].copy()
 
     def offline_frame_blank_logprobs(self, u) -> np.ndarray:

@@ -289,6 +289,9 @@ static_assert(nasr_lp::TILE_PARTS == 65 && nasr_lp::TILE_W == 16 && nasr_lp::WG_
 // engine option "token_logprobs": the (max, sum of exp) part of a 16-entry vocab tile, lane (q, r) holding entries v0 .. v0 + 3 of row r's
 // logits: nasr_lp::tile_part_wave (nasr_logprob.h, shared with kernels_align.hip)
 __device__ __forceinline__ nasr_lp::Part lp_tile_part(float x0, float x1, float x2, float x3, int v0) { return nasr_lp::tile_part_wave(x0, x1, x2, x3, v0); }
+// a copy of v the optimiser knows nothing about: what is computed from it shares no subexpression with what is computed from v
+__device__ __forceinline__ float ent_opaque(float v) { asm volatile("" : "+v"(v)); return v; }
+template <class Tp> __device__ __forceinline__ const Tp *ent_opaque(const Tp *v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ unsigned long long kmax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
     const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
@@ -315,7 +318,13 @@ __device__ __forceinline__ void alt_tile_keys(float x0, float x1, float x2, floa
 // its raw logit in boost_raw [row][part] (one writer per element: a key names one vocabulary entry, and one lane holds it)
 // ALT (engine option "token_alternatives", nasr_topk.h; always with LP): lane group 0 also leaves the tile's alt_k largest raw-logit keys in
 // alt_key [row][part][alt_k], beside the part
-template <int MT, bool LP, bool BOOST, bool ALT, bool LMF>
+// ENT (engine option "token_entropy", nasr_entropy.h; always with LP): lane group 0 also leaves the tile's entropy term in ent_part [row][part],
+// beside the part.  The code that forms the part is the code of the form without ENT, and the term is computed AFTER it, from opaque copies of
+// the logits and behind a test of its own (ent_opaque): the compiler contracts a * b + c * d into one of two FMAs or none depending on what
+// else uses the products and on what the vectoriser pairs inside a basic block, so a term computed in one expression with the part moved the
+// part's last bit (seen on the MI355X: ln P and the blank values differed in one ulp between the option on and off).  The price is that the
+// pass repeats the part's exps
+template <int MT, bool LP, bool BOOST, bool ALT, bool LMF, bool ENT>
 __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, float (*red)[MT_MAX][64][4]) {
     const int nt = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane >> 4, r = lane & 15;
@@ -385,23 +394,30 @@ __device__ __forceinline__ void joint_pass(const DecParams &p, int i0, int nr, f
                     for (int j = 0; j < nasr_topk::KMAX; j++) if (j < p.alt_k) dst[j] = top[j];
                 }
             }
+            if (ENT) {
+                if (p.ent_part) {                      // bound whenever this form is launched: the test keeps the pass in basic blocks of its own (ent_opaque)
+                    const nasr_ent::EPart ep = nasr_ent::tile_wave(ent_opaque(lgs[0]), ent_opaque(lgs[1]), ent_opaque(lgs[2]), ent_opaque(lgs[3]), nt * 16 + q * 4, p.ent_alpha);
+                    if (row >= 0) p.ent_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), nt, nasr_lp::TILE_PARTS)] = ep.e;
+                }
+            }
         }
     }
 }
 
 // LMF (engine option "lm_fusion", always with BOOST): the lane's four bias entries come from the slot's row (phrase bonus + lmbias, k_dec_lmrows)
 // instead of the automaton's table; everything else is the boosted form
-template <bool LP, bool BOOST, bool ALT, bool LMF = false>
+template <bool LP, bool BOOST, bool ALT, bool LMF = false, bool ENT = false>
 __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
     static_assert(BOOST || !LMF, "the fused form is a form of the boosted kernel");
+    static_assert(LP || !ENT, "the entropy terms ride on the softmax parts");
     const int nr = *p.n_rows;
     if (nr == 0) return;
     __shared__ float red[4][MT_MAX][64][4];
     for (int i0 = 0; i0 < nr; i0 += 16 * MT_MAX) {
         const int tiles = nasr_lp::joint_pass_tiles(nr - i0);      // 1, 2 or 4 m-tiles: 16, 32 or more rows left
-        if (tiles == 1) joint_pass<1, LP, BOOST, ALT, LMF>(p, i0, nr, red);
-        else if (tiles == 2) joint_pass<2, LP, BOOST, ALT, LMF>(p, i0, nr, red);
-        else joint_pass<4, LP, BOOST, ALT, LMF>(p, i0, nr, red);
+        if (tiles == 1) joint_pass<1, LP, BOOST, ALT, LMF, ENT>(p, i0, nr, red);
+        else if (tiles == 2) joint_pass<2, LP, BOOST, ALT, LMF, ENT>(p, i0, nr, red);
+        else joint_pass<4, LP, BOOST, ALT, LMF, ENT>(p, i0, nr, red);
     }
 }
 
@@ -416,8 +432,10 @@ __global__ __launch_bounds__(256) void k_dec_joint(DecParams p) {
 // The per-part winner's raw logit (boost_raw) is not kept: the select kernel reads any entry's raw logit from the row
 constexpr int JT_KC = 64;                       // K per LDS chunk = 4 k-groups
 // LMF: as in k_dec_joint -- bstate holds the row's slot, and the four bias entries are one load from the slot's row
-template <bool LP, bool BOOST, bool ALT, bool BEAMB = false, bool LMF = false>
+// ENT: as in k_dec_joint -- a pass of its own behind the form without ENT leaves the workgroup's entropy term beside its part
+template <bool LP, bool BOOST, bool ALT, bool BEAMB = false, bool LMF = false, bool ENT = false>
 __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
+    static_assert(!ENT || (LP && !BEAMB), "the entropy terms ride on the softmax parts of the greedy kernel");
     static_assert(!BEAMB || (LP && BOOST && ALT), "the boosted beam form is a form of the LP + BOOST + ALT kernel");
     static_assert(!LMF || (BOOST && !BEAMB), "the fused form is a form of the boosted greedy kernel");
     const int nr = *p.n_rows;
@@ -426,6 +444,8 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
     __shared__ __attribute__((aligned(16))) float xs[2][64 * JT_KC];
     __shared__ unsigned long long bests[4][64];
     __shared__ nasr_lp::Part lps[LP ? 4 : 1][64];      // token_logprobs: the four waves' tile parts of the 64 rows
+    __shared__ nasr_lp::Part elps[ENT ? 4 : 1][64];    // token_entropy: the four waves' tile parts once more, and their entropy terms (3 KiB)
+    __shared__ float ents[ENT ? 4 : 1][64];
     __shared__ float raws[LP && BOOST && !BEAMB ? 4 : 1][64];    // ... with phrase_boost: the raw logit of each wave's winner by boosted key
     // token_alternatives: the four waves' tile lists of the 64 rows, [wave][entry][row].  They take the place of the operand staging, which nobody
     // reads after the K loop's last barrier
@@ -585,6 +605,28 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
             }
         }
     }
+    if (ENT) {
+        // the entropy terms, after everything the form without ENT does and apart from it (k_dec_joint, ent_opaque): every wave's tile parts and
+        // terms of the 64 rows once more from opaque copies of the logits, then the workgroup's four in wave order, stored beside the part
+        if (p.ent_part) {
+#pragma unroll
+            for (int mt = 0; mt < 4; mt++) {
+                const int v0 = has_tile ? nt * 16 + q * 4 : VOCAB;
+                float lg[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) lg[j] = ent_opaque(acc[mt][j]) + p.out_b[v0 + j < VOCAB ? v0 + j : 0];
+                const nasr_ent::EPart ep = nasr_ent::tile_wave(lg[0], lg[1], lg[2], lg[3], v0, p.ent_alpha);
+                if (q == 0) { elps[wave][mt * 16 + r] = ep.p; ents[wave][mt * 16 + r] = ep.e; }
+            }
+            __syncthreads();
+            const int row = nasr_lp::tiled_store_row(blockIdx.y, threadIdx.x, nr);
+            if (row >= 0) {
+                const int t = threadIdx.x;
+                const nasr_ent::EPart ep = nasr_ent::wg64({elps[0][t], ents[0][t]}, {elps[1][t], ents[1][t]}, {elps[2][t], ents[2][t]}, {elps[3][t], ents[3][t]}, p.ent_alpha);
+                p.ent_part[nasr_lp::scratch_index(nasr_lp::key_index(p.rowmap[row], p.T), blockIdx.x, nasr_lp::WG_PARTS)] = ep.e;
+            }
+        }
+    }
 }
 
 // ---- commit: walk each stream's evaluated frames up to its first non-blank -------------------------
@@ -597,9 +639,12 @@ __global__ __launch_bounds__(256) void k_dec_joint_tiled(DecParams p) {
 // (build_lists lists every frame from t to n_frames), so the value copied is that of the LAST evaluation on the frame
 // LMF (engine option "lm_fusion", always with BOOST): the slot's LM state becomes the `next` the refresh left beside the bias entry of the token;
 // the phrase automaton advances where "phrase_boost" is on too (boost_next is null otherwise)
-template <bool LP, bool BOOST, bool ALT, bool FB, bool LMF = false>
+// ENT (engine option "token_entropy", always with LP): the token's thread also finishes the entropy of the frame it commits from the parts and
+// their entropy terms (nasr_ent::finish, f64 inside, rounded once) into tok_entropy, where it writes tok_logprob
+template <bool LP, bool BOOST, bool ALT, bool FB, bool LMF = false, bool ENT = false>
 __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
     static_assert(LP || !FB, "the blank log-probabilities come from the softmax parts");
+    static_assert(LP || !ENT, "the entropy comes from the softmax parts");
     static_assert(BOOST || !LMF, "the fused form is a form of the boosted kernel");
     __shared__ int sh[4];
     if (*p.n_active == 0) return;
@@ -642,6 +687,10 @@ __global__ __launch_bounds__(256) void k_dec_commit(DecParams p) {
                 const nasr_lp::Part *parts = p.lp_part + nasr_lp::scratch_index(b * p.T + f, 0, np);
                 // phrase_boost: the key holds logit + bonus; the value stays the MODEL's probability of the token, from its raw logit
                 const float logit = BOOST ? p.boost_raw[nasr_lp::scratch_index(b * p.T + f, nasr_boost::raw_part_of(best, np), np)] : nasr_lp::key_logit(k);
+                if (ENT) {
+                    if (p.tok_entropy)                     // always bound here; the parts are read through an opaque pointer: finish shares no product with the log-probability's sum (k_dec_joint, ent_opaque)
+                        p.tok_entropy[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_ent::finish(ent_opaque(parts), p.ent_part + nasr_lp::scratch_index(b * p.T + f, 0, np), np, p.ent_alpha);
+                }
                 if (!ALT) p.tok_logprob[(size_t)slot * TOK_CAP + (n & (TOK_CAP - 1))] = nasr_lp::finish(logit, parts, np);
                 else {
                     // token_alternatives: this thread merges the frame's slice lists itself -- the streams of a step are merged side by side, one
@@ -733,19 +782,22 @@ void launch_encproj(const float *x, const float *wpk, const float *bias, float *
 void launch_decode_begin(const DecParams &p, hipStream_t st) {
     hipLaunchKernelGGL(k_dec_begin, dim3(1), dim3(256), 0, st, p);
 }
-template <bool LP, bool BOOST, bool ALT, bool LMF = false>
+template <bool LP, bool BOOST, bool ALT, bool LMF = false, bool ENT = false>
 static void launch_joint_commit(const DecParams &p, hipStream_t st) {
     static_assert(LP || !ALT, "the alternatives take their probabilities from the softmax parts");
+    if constexpr (LP && !ENT) {
+        if (p.ent_part) { launch_joint_commit<LP, BOOST, ALT, LMF, true>(p, st); return; }      // "token_entropy" (lp_part comes with it): the ENT forms of the same three kernels
+    }
     const int rows = p.B * p.T;
-    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT, LMF>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT, false, LMF>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
+    if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT, LMF, ENT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT, false, LMF, ENT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
     if constexpr (LP) {
         if (p.frame_blank) {                           // "frame_blank_logprobs": the commit variant that also fills the ring
-            hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, true, LMF>), dim3(1), dim3(256), 0, st, p);
+            hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, true, LMF, ENT>), dim3(1), dim3(256), 0, st, p);
             return;
         }
     }
-    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, false, LMF>), dim3(1), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k_dec_commit<LP, BOOST, ALT, false, LMF, ENT>), dim3(1), dim3(256), 0, st, p);
 }
 void launch_lm_rows(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus, const int *boost_state,
                     int slot0, int n, hipStream_t st) {

@@ -169,7 +169,7 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
 // valid.  A later change would be a silent no-op for the graphs that exist (and the tokens already in the ring would have no value): they are taken
 // until the first decode has been enqueued or the first offline call has run.  "lm_refresh_fold" (0 = the bias rows are refreshed by a launch of
 // their own) and "lm_commit_lookup" (1 = k_dec_commit looks the emitted token up again) are measurement only (profiles/greedy_lm.md)
-static const char *const DECODE_OPTIONS[] = {"token_logprobs", "phrase_boost", "lm_fusion", "lm_refresh_fold", "lm_commit_lookup", "token_alternatives", "frame_blank_logprobs"};
+static const char *const DECODE_OPTIONS[] = {"token_logprobs", "phrase_boost", "lm_fusion", "lm_refresh_fold", "lm_commit_lookup", "token_alternatives", "frame_blank_logprobs", "token_entropy"};
 static bool is_decode_option(const char *key) { return std::any_of(std::begin(DECODE_OPTIONS), std::end(DECODE_OPTIONS), [key](const char *k) { return !strcmp(key, k); }); }
 static int set_decode_option(nasr_engine *e, const char *key, int value) {      // key is one of DECODE_OPTIONS; the caller holds an ApiGuard
     const auto is = [key](const char *k) { return !strcmp(key, k); };
@@ -177,6 +177,9 @@ static int set_decode_option(nasr_engine *e, const char *key, int value) {      
     if (is("phrase_boost") && value != 0 && (value < nasr_boost::MIN_STATES || value > nasr_boost::MAX_STATES))
         return fail("phrase_boost must be 0 or the automaton's state capacity, %d .. %d", nasr_boost::MIN_STATES, nasr_boost::MAX_STATES);
     if (is("token_alternatives") && !nasr_topk::valid_k(value)) return fail("token_alternatives must be 0 .. %d", nasr_topk::KMAX);
+    if (is("token_entropy") && !nasr_ent::valid_milli(value))
+        return fail("token_entropy must be 0 or round(1000 alpha): %d (Shannon), or %d .. %d and %d .. %d (closer to 1 the order's 1 / (1 - alpha) outgrows the value's precision)",
+                    nasr_ent::MILLI_SHANNON, nasr_ent::MILLI_MIN, nasr_ent::BAND_LO, nasr_ent::BAND_HI, nasr_ent::MILLI_MAX);
     if (e->dec_started || e->off) return fail("%s must be set before the first step or offline call (the decode kernels are already chosen)", key);
     if (is("phrase_boost") && value && e->boost_bonus && value != e->boost_cap) return fail("phrase_boost: the capacity is already %d states", e->boost_cap);
     HIPCHK(hipSetDevice(e->device));
@@ -185,6 +188,7 @@ static int set_decode_option(nasr_engine *e, const char *key, int value) {      
     if (is("token_logprobs")) return take(e->opt_token_logprobs, value != 0);
     if (is("token_alternatives")) return take(e->opt_token_alt, value);
     if (is("frame_blank_logprobs")) return take(e->opt_frame_blank, value != 0);
+    if (is("token_entropy")) return take(e->opt_token_entropy, value);
     if (is("lm_refresh_fold")) return take(e->opt_lm_fold, value != 0 ? 1 : 0);
     if (is("lm_commit_lookup")) return take(e->opt_lm_relook, value != 0 ? 1 : 0);
     if (is("phrase_boost")) {
@@ -980,6 +984,16 @@ extern "C" int nasr_stream_get_token_logprobs(const nasr_stream *s, int64_t firs
     DecCtrl c;
     if (ring_ctrl(s, c) || (count = token_window(c, first, count)) < 0) return -1;
     return ring_copy(s, s->e->dec.tok_logprob, TOK_CAP, 1, first, count, out);
+}
+
+extern "C" int nasr_stream_get_token_entropies(const nasr_stream *s, int64_t first, int32_t count, float *out) {
+    ApiGuard api_guard;
+    if (!s || (count > 0 && !out)) return fail("null argument");
+    if (first < 0 || count < 0) return fail("negative token range");
+    if (!s->e->opt_token_entropy) return fail("no token entropies: engine option \"token_entropy\" is off (set it to round(1000 alpha) before the first step)");
+    DecCtrl c;
+    if (ring_ctrl(s, c) || (count = token_window(c, first, count)) < 0) return -1;
+    return ring_copy(s, s->e->dec.tok_entropy, TOK_CAP, 1, first, count, out);
 }
 
 extern "C" int nasr_stream_get_frame_blank_logprobs(const nasr_stream *s, int64_t first, int32_t count, float *out) {

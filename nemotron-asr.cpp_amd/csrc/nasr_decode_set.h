@@ -16,7 +16,8 @@ struct DecFeatures {
     bool phrase_boost = false;       // option "phrase_boost" (the capacity of its tables is the engine's)
     bool lm_fusion = false;          // option "lm_fusion"
     int lm_fold = 1, lm_relook = 0;  // measurement switches "lm_refresh_fold", "lm_commit_lookup"
-    bool lp_kernels() const { return token_logprobs || alt_k != 0 || frame_blank; }      // the kernels that leave the softmax parts
+    int entropy_milli = 0;           // option "token_entropy" = round(1000 alpha) (0: off), nasr_entropy.h
+    bool lp_kernels() const { return token_logprobs || alt_k != 0 || frame_blank || entropy_milli != 0; }      // the kernels that leave the softmax parts
     bool winner_raw() const { return phrase_boost || lm_fusion; }                        // the biased forms read the winner's raw logit
 };
 
@@ -49,6 +50,9 @@ struct DecodeSet {
     // "lm_fusion" (the block with the model's view and the greedy weights is the engine's), nasr_lm.h / DESIGN 17
     int32_t *lm_state = nullptr;             // [slot] LM state of the slot's emitted history
     float *lm_row = nullptr; int32_t *lm_next = nullptr;       // [slot][1040] each: the bias row (phrase bonus + lmbias), the next-state row beside it
+    // "token_entropy" = round(1000 alpha), nasr_entropy.h
+    float *ent_part = nullptr;               // scratch beside lp_part: the entropy term of every part (sum exp(alpha (x - m)), or sum exp(x - m) (x - m) at alpha = 1)
+    float *tok_entropy = nullptr;            // [slot][TOK_CAP] beside tok_ring / tok_frame / tok_logprob
 };
 
 // THE layout: buf(name, pointer, needed, elements) once for every buffer of the set, for `slots` slots and `rows` rows under features f
@@ -79,6 +83,8 @@ inline void dec_set_layout(DecodeSet &d, const DecFeatures &f, int slots, int ro
     buf("lm_state",    d.lm_state,      f.lm_fusion,            S);
     buf("lm_row",      d.lm_row,        f.lm_fusion,            S * nasr_lm::ROW_COLS);
     buf("lm_next",     d.lm_next,       f.lm_fusion,            S * nasr_lm::ROW_COLS);
+    buf("ent_part",    d.ent_part,      f.entropy_milli != 0,   parts);
+    buf("tok_entropy", d.tok_entropy,   f.entropy_milli != 0,   S * TOK_CAP);
 }
 
 // The per-slot part of THE layout: buf(name, pointer, needed, elements_per_slot) once for every buffer whose size grows with the slots and
@@ -125,6 +131,7 @@ inline void dec_set_bind(const DecodeSet &d, const DecFeatures &f, const DecTabl
     if (f.phrase_boost) { dp.boost_bonus = t.boost_bonus; dp.boost_next = t.boost_next; dp.boost_state = d.boost_state; }
     if (f.winner_raw()) dp.boost_raw = d.boost_raw;
     if (f.lm_fusion) { dp.lm_blk = t.lm_blk; dp.lm_state = d.lm_state; dp.lm_row = d.lm_row; dp.lm_next = d.lm_next; dp.lm_fold = f.lm_fold; dp.lm_relook = f.lm_relook; }
+    if (f.entropy_milli) { dp.ent_part = d.ent_part; dp.tok_entropy = d.tok_entropy; dp.ent_alpha = nasr_ent::alpha_of(f.entropy_milli); }
 }
 
 }  // namespace nasr

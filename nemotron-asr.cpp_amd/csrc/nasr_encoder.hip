@@ -453,6 +453,7 @@ DecFeatures dec_features(const nasr_engine *e) {
     DecFeatures f;
     f.token_logprobs = e->opt_token_logprobs; f.alt_k = e->opt_token_alt; f.frame_blank = e->opt_frame_blank;
     f.phrase_boost = e->opt_phrase_boost != 0; f.lm_fusion = e->opt_lm_fusion; f.lm_fold = e->opt_lm_fold; f.lm_relook = e->opt_lm_relook;
+    f.entropy_milli = e->opt_token_entropy;
     return f;
 }
 void bind_decode(const nasr_engine *e, const DecodeSet &set, const DecFeatures &f, DecParams &dp) {

@@ -273,6 +273,9 @@ struct nasr_engine {
     // option "frame_blank_logprobs": ln P(blank) at the last joint evaluation of every frame the decode has left.  Taken like "token_alternatives"
     // (LP kernels, so lp_part / tok_logprob come with it; the ring's life: DecodeSet::frame_blank)
     bool opt_frame_blank = false;
+    // option "token_entropy" = round(1000 alpha) (0: off; nasr_entropy.h): the entropy of order alpha of the joint's softmax where every token was
+    // emitted.  Taken like "frame_blank_logprobs" (the ENT forms of the LP kernels; ent_part / tok_entropy in `dec`)
+    int opt_token_entropy = 0;
     // option "frame_history" = N (0: off; nasr_history.h): every step appends its encoder-projection rows to their slots' rings
     // [max_streams][N][640] f32, an engine buffer of its own -- not part of `dec`, so the fork plan and the snapshot format do not know it.  Taken
     // like "frame_blank_logprobs": it adds a launch that is captured into the step graphs

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "nasr_constants.h"
 #include "nasr_logprob.h"
+#include "nasr_entropy.h"
 #include "nasr_boost.h"
 #include "nasr_topk.h"
 #include "nasr_align.h"
@@ -256,6 +257,10 @@ struct DecParams {
     int32_t *lm_next;            // [slot][1040] LM state after emitting that entry
     int lm_fold;                 // 1: the rows are refreshed by extra workgroups of k_dec_pred, 0: by a launch of their own
     int lm_relook;               // measurement only: 1 = k_dec_commit looks the token up again instead of reading lm_next
+    // engine option "token_entropy" (null / 0 when it is off; lp_part and the LP kernels come with it), nasr_entropy.h
+    float *ent_part;             // [B * T][n_parts] beside lp_part: the entropy term of every vocab slice of every evaluated row
+    float *tok_entropy;          // [slot][TOK_CAP] entropy of order ent_alpha (nats) of the joint's softmax where each token was emitted
+    float ent_alpha;
 };
 // the bias rows of slots slot0 .. slot0 + n - 1 from their current states (boost_bonus / boost_state null without "phrase_boost")
 void launch_lm_rows(const nasr_lm::Greedy *blk, const int32_t *lm_state, float *lm_row, int32_t *lm_next, const float *boost_bonus, const int *boost_state,

@@ -258,6 +258,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
     std::vector<int> ring((size_t)n * TOK_CAP), ringf((size_t)n * TOK_CAP);
     std::vector<float> ringl(e->opt_token_logprobs ? (size_t)n * TOK_CAP : 0);
     std::vector<float> ringb(e->opt_frame_blank ? (size_t)n * FRAME_CAP : 0);
+    std::vector<float> ringe(e->opt_token_entropy ? (size_t)n * TOK_CAP : 0);
     const int K = e->opt_token_alt;
     std::vector<int32_t> ringai((size_t)n * TOK_CAP * K);
     std::vector<float> ringal((size_t)n * TOK_CAP * K);
@@ -287,6 +288,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
         HIPCHK(hipMemcpyAsync(ringf.data(), o->dec.tok_frame, ringf.size() * 4, hipMemcpyDeviceToHost, st));
         if (!ringl.empty()) HIPCHK(hipMemcpyAsync(ringl.data(), o->dec.tok_logprob, ringl.size() * 4, hipMemcpyDeviceToHost, st));
         if (!ringb.empty()) HIPCHK(hipMemcpyAsync(ringb.data(), o->dec.frame_blank, ringb.size() * 4, hipMemcpyDeviceToHost, st));
+        if (!ringe.empty()) HIPCHK(hipMemcpyAsync(ringe.data(), o->dec.tok_entropy, ringe.size() * 4, hipMemcpyDeviceToHost, st));
         if (K) {
             HIPCHK(hipMemcpyAsync(ringai.data(), o->dec.alt_id, ringai.size() * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(ringal.data(), o->dec.alt_lp, ringal.size() * 4, hipMemcpyDeviceToHost, st));
@@ -300,6 +302,7 @@ static int run_offline_batch(nasr_engine *e, OfflineState *o, const OffBatch &ob
                 toks[first + k].push_back(ring[(size_t)k * TOK_CAP + pos]);
                 frs[first + k].push_back(ringf[(size_t)k * TOK_CAP + pos]);
                 if (!ringl.empty()) o->logprobs[first + k].push_back(ringl[(size_t)k * TOK_CAP + pos]);
+                if (!ringe.empty()) o->entropies[first + k].push_back(ringe[(size_t)k * TOK_CAP + pos]);
                 if (K) {
                     const size_t at = ((size_t)k * TOK_CAP + pos) * K;
                     o->alt_ids[first + k].insert(o->alt_ids[first + k].end(), ringai.begin() + at, ringai.begin() + at + K);
@@ -341,7 +344,7 @@ static int begin_call(nasr_engine *e, int B, const int32_t *prompt_index, const 
     if (!e->off) e->off = new OfflineState();
     OfflineState *o = e->off;
     o->tap_mel.clear(); o->tap_sub.clear(); o->tap_enc.clear(); o->tap_lay.clear();
-    o->logprobs.clear(); o->alt_ids.clear(); o->alt_lps.clear(); o->frame_blank_lps.clear();
+    o->logprobs.clear(); o->entropies.clear(); o->alt_ids.clear(); o->alt_lps.clear(); o->frame_blank_lps.clear();
     o->lat_valid = false; o->lat_b.clear(); o->lat_t.clear();
     o->beam_valid = false; o->beam_res.clear();
     o->no_boost = (flags & NASR_FLAG_NO_BOOST) != 0;
@@ -572,6 +575,7 @@ static OffMode greedy_mode(nasr_engine *e, const char *who, int32_t *const *toke
     m.who = who; m.counts = n_tokens; m.streaming_hint = true; m.greedy = true;
     m.setup = [=](OfflineState *o, int B) {
         o->logprobs.assign(e->opt_token_logprobs ? B : 0, {});
+        o->entropies.assign(e->opt_token_entropy ? B : 0, {});
         o->frame_blank_lps.assign(e->opt_frame_blank ? B : 0, {});
         o->alt_ids.assign(e->opt_token_alt ? B : 0, {}); o->alt_lps.assign(e->opt_token_alt ? B : 0, {});
         r->toks.assign(B, {}); r->frs.assign(B, {});
@@ -644,6 +648,15 @@ extern "C" int nasr_engine_offline_token_logprobs(nasr_engine *e, int u, float *
     OfflineState *o = e->off;
     if (!o || u < 0 || u >= (int)o->logprobs.size()) return fail("no offline token log-probabilities of utterance %d (they are those of the last offline call)", u);
     return (int)read_out(o->logprobs[u], out, cap);
+}
+
+extern "C" int nasr_engine_offline_token_entropies(nasr_engine *e, int u, float *out, int32_t cap) {
+    ApiGuard api_guard;
+    if (!e) return fail("null engine");
+    if (!e->opt_token_entropy) return fail("no token entropies: engine option \"token_entropy\" is off (set it to round(1000 alpha) before the first step or offline call)");
+    OfflineState *o = e->off;
+    if (!o || u < 0 || u >= (int)o->entropies.size()) return fail("no offline token entropies of utterance %d (they are those of the last offline call)", u);
+    return (int)read_out(o->entropies[u], out, cap);
 }
 
 extern "C" int nasr_engine_offline_frame_blank_logprobs(nasr_engine *e, int u, float *out, int32_t cap) {

@@ -31,6 +31,7 @@ struct OfflineState {
     bool no_boost = false, no_lm = false;                          // NASR_FLAG_NO_BOOST, NASR_FLAG_NO_LM of the call in progress
     std::vector<std::vector<int32_t>> alt_ids; std::vector<std::vector<float>> alt_lps;             // "token_alternatives" of the last call, by utterance: [tokens][K] each
     std::vector<std::vector<float>> frame_blank_lps;               // "frame_blank_logprobs" of the last call, by utterance: [T] (nasr_engine_offline_frame_blank_logprobs)
+    std::vector<std::vector<float>> entropies;                     // "token_entropy" of the last call, by utterance (nasr_engine_offline_token_entropies)
     std::vector<std::vector<float>> logprobs;                      // "token_logprobs" of the last call, by utterance (nasr_engine_offline_token_logprobs)
     // forced alignment (nasr_engine_align*): the prediction-network rows g, the lattice of the sub-batch in flight (two values and one
     // back-pointer byte per cell), its descriptors and its results

@@ -7,7 +7,9 @@
 //   header  144 bytes   magic "NASS", version, total size; what restore must agree on (dtype and element size, n_layers, kernel_size, KVC,
 //                       LCTX, MEL_RING, NMEL, ABUF_CAP, the converter's HIST_MAX, TOK_CAP, the five DecFeatures values); the fingerprints
 //                       of the weight set, the boost set and the LM in force; the sizes of the two sections; the checksum of the device
-//                       section; 8 reserved bytes (zero); the checksum of header and mirror
+//                       section; 4 reserved bytes (zero) and, in the word behind them (offset 132), the sixth DecFeatures value, option
+//                       "token_entropy" (0 = off: a blob saved with it off is byte for byte what it was before the option existed);
+//                       the checksum of header and mirror
 //   mirror              the record of what the stream is (struct Mirror: nasr_stream derives from it, so the stream IS the record and nothing
 //                       copies it field by field), its fixed fields in wire order (visit_fields), then the queued tokens, zero-padded to 16 bytes
 //   device              the segments of the fork plan for this mirror (nasr_fork::fork_plan) in plan order, each zero-padded to 16 bytes.
@@ -95,18 +97,21 @@ struct Config {
     uint32_t dtype = 0, esz = 0, n_layers = 0, kernel_size = 0;
     uint32_t kvc = KVC, lctx = LCTX, mel_ring = MEL_RING, nmel = NMEL, abuf_cap = ABUF_CAP, hist_max = nasr_rs::HIST_MAX, tok_cap = TOK_CAP;
     uint32_t token_logprobs = 0, alt_k = 0, frame_blank = 0, phrase_boost = 0, lm_fusion = 0;      // DecFeatures
+    uint32_t entropy_milli = 0;                    // ... and "token_entropy", which sits in the high word of the once reserved bytes
     uint64_t fp_weights = 0, fp_boost = 0, fp_lm = 0;
 };
 inline Config make_config(int dtype, int esz, int n_layers, int kernel_size, const DecFeatures &f, uint64_t fp_weights, uint64_t fp_boost, uint64_t fp_lm) {
     Config c;
     c.dtype = (uint32_t)dtype; c.esz = (uint32_t)esz; c.n_layers = (uint32_t)n_layers; c.kernel_size = (uint32_t)kernel_size;
     c.token_logprobs = f.token_logprobs; c.alt_k = (uint32_t)f.alt_k; c.frame_blank = f.frame_blank; c.phrase_boost = f.phrase_boost; c.lm_fusion = f.lm_fusion;
+    c.entropy_milli = (uint32_t)f.entropy_milli;
     c.fp_weights = fp_weights; c.fp_boost = fp_boost; c.fp_lm = fp_lm;
     return c;
 }
 inline DecFeatures features_of(const Config &c) {
     DecFeatures f;
     f.token_logprobs = c.token_logprobs != 0; f.alt_k = (int)c.alt_k; f.frame_blank = c.frame_blank != 0; f.phrase_boost = c.phrase_boost != 0; f.lm_fusion = c.lm_fusion != 0;
+    f.entropy_milli = (int)c.entropy_milli;
     return f;
 }
 struct Header { Config cfg; uint64_t total_bytes = 0, mirror_bytes = 0, device_bytes = 0, device_sum = 0, head_sum = 0; };
@@ -201,7 +206,8 @@ inline void write_head(Header h, const Mirror &m, std::vector<uint8_t> &out) {
                        c.token_logprobs, c.alt_k, c.frame_blank, c.phrase_boost, c.lm_fusion}) w.u32(v);
     w.u64(c.fp_weights); w.u64(c.fp_boost); w.u64(c.fp_lm);
     w.u64(h.mirror_bytes); w.u64(h.device_bytes); w.u64(h.device_sum);
-    w.u64(0);                                                  // reserved
+    w.u32(0);                                                  // reserved
+    w.u32(c.entropy_milli);
     w.u64(0);                                                  // the head checksum, below
     visit_fields(m, [&](const char *, auto v, long long, long long) { w.field(v); });
     w.u32((uint32_t)m.tok_queue.size());
@@ -232,7 +238,8 @@ inline bool parse(const uint8_t *p, int64_t n, Header &h, Mirror &m, std::string
                         &c.token_logprobs, &c.alt_k, &c.frame_blank, &c.phrase_boost, &c.lm_fusion}) *v = r.u32();
     c.fp_weights = r.u64(); c.fp_boost = r.u64(); c.fp_lm = r.u64();
     h.mirror_bytes = r.u64(); h.device_bytes = r.u64(); h.device_sum = r.u64();
-    const uint64_t reserved = r.u64();
+    const uint32_t reserved = r.u32();
+    c.entropy_milli = r.u32();
     h.head_sum = r.u64();
     if (h.total_bytes > (uint64_t)n) return refuse(err, "truncated: %lld bytes of %lld", n, (long long)h.total_bytes);
     if (h.total_bytes < (uint64_t)n) return refuse(err, "trailing bytes: %lld bytes, the snapshot ends at %lld", n, (long long)h.total_bytes);
@@ -262,7 +269,7 @@ inline bool config_mismatch(const Config &blob, const Config &eng, std::string &
         {"HIST_MAX", blob.hist_max, eng.hist_max}, {"TOK_CAP", blob.tok_cap, eng.tok_cap},
         {"option token_logprobs", blob.token_logprobs, eng.token_logprobs}, {"option token_alternatives", blob.alt_k, eng.alt_k},
         {"option frame_blank_logprobs", blob.frame_blank, eng.frame_blank}, {"option phrase_boost", blob.phrase_boost, eng.phrase_boost},
-        {"option lm_fusion", blob.lm_fusion, eng.lm_fusion}};
+        {"option lm_fusion", blob.lm_fusion, eng.lm_fusion}, {"option token_entropy", blob.entropy_milli, eng.entropy_milli}};
     for (const auto &f : f32)
         if (f.a != f.b) { refuse(err, (std::string(f.name) + " mismatch: the snapshot has %lld, the engine %lld").c_str(), f.a, f.b); return true; }
     const struct { const char *name; uint64_t a, b; } f64[] = {

@@ -76,6 +76,19 @@ std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx) {
     return out;
 }
 
+std::vector<float> nemo_stream_get_token_entropies(nemo_stream_context *sctx) {
+    std::vector<float> out;
+    if (!sctx) return out;
+    const size_t n = sctx->tokens.size();
+    std::vector<float> h(n ? n : 1);
+    const size_t first = n > 4096 ? n - 4096 : 0;       // older values have left the device ring
+    const int got = nasr_stream_get_token_entropies(sctx->stream, (int64_t)first, (int32_t)(n - first), h.data());
+    if (got < 0) { fprintf(stderr, "%s: %s\n", __func__, nasr_last_error()); return out; }
+    out.assign(first, NAN);
+    out.insert(out.end(), h.begin(), h.begin() + got);
+    return out;
+}
+
 std::vector<float> nemo_stream_get_frame_blank_logprobs(nemo_stream_context *sctx) {
     std::vector<float> out;
     if (!sctx) return out;
@@ -236,6 +249,18 @@ bool nemo_set_token_logprobs(nemo_context *ctx, bool on) {
         fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
         return false;
     }
+    ctx->token_logprobs = on;
+    return true;
+}
+
+bool nemo_set_token_entropy(nemo_context *ctx, float alpha) {
+    if (!ctx || !ctx->engine) return false;
+    const int milli = alpha >= 0.0f && alpha < 1e4f ? (int)std::lround((double)alpha * 1000.0) : -1;      // anything else: a value the engine refuses, with its message
+    if (nasr_engine_set_option(ctx->engine, "token_entropy", milli) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    ctx->token_entropy_milli = milli;
     return true;
 }
 
@@ -461,6 +486,14 @@ std::vector<nemo_hypothesis> nemo_transcribe_beam(nemo_context *ctx, const int16
         }
         h.tokens.resize((size_t)std::min(n, cap)); h.frames.resize(h.tokens.size());
         h.score = NAN;
+        const auto read = [&](int (*get)(nasr_engine *, int, float *, int32_t), std::vector<float> &v) {      // the call's per-token values, by token
+            v.assign(h.tokens.size(), NAN);
+            return h.tokens.empty() || get(ctx->engine, 0, v.data(), (int32_t)v.size()) >= 0;
+        };
+        if ((ctx->token_logprobs && !read(nasr_engine_offline_token_logprobs, h.logprobs)) || (ctx->token_entropy_milli && !read(nasr_engine_offline_token_entropies, h.entropies))) {
+            fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+            return out;
+        }
         out.push_back(h);
         return out;
     }

@@ -30,6 +30,8 @@ struct nemo_context {               // reference: nemo_context / nemo_model (src
     nasr_engine *engine = nullptr;
     int max_streams = 0;
     int token_alternatives = 0;      // K of nemo_set_token_alternatives (0: off)
+    bool token_logprobs = false;     // nemo_set_token_logprobs
+    int token_entropy_milli = 0;     // round(1000 alpha) of nemo_set_token_entropy (0: off)
     bool lm_attached = false;        // nemo_load_lm_arpa succeeded and nemo_clear_lm has not been called
     bool beam_boost = false;         // nemo_set_beam_boost: nemo_transcribe_beam applies the boost phrases inside the search
     int workspace_rows = 0;          // rows one engine call may carry (streams x chunks x (1 + right_context)); nasr_engine_create_ex
@@ -84,6 +86,10 @@ bool nemo_set_token_logprobs(nemo_context *ctx, bool on);
 // MI355X extension: per-frame blank log-probabilities (nasr_engine_set_option "frame_blank_logprobs"), the input of the endpoint detector; before
 // the first stream processes audio
 bool nemo_set_frame_blank_logprobs(nemo_context *ctx, bool on);
+// MI355X extension: per-token entropies of order alpha (nasr_engine_set_option "token_entropy" = round(1000 alpha): 1 = Shannon, 0.333 = the
+// usual 1/3, 0 = off; accepted 0.05 .. 0.9, 1 and 1.1 .. 4), the input of entropy-based confidence (token_confidence.h); before the first
+// stream processes audio
+bool nemo_set_token_entropy(nemo_context *ctx, float alpha);
 // MI355X extension: the K = 1 .. 8 most probable joint outputs at every emission (nasr_engine_set_option "token_alternatives"; 0 = off); before
 // the first stream processes audio
 bool nemo_set_token_alternatives(nemo_context *ctx, int k);
@@ -113,12 +119,14 @@ nemo_alignment nemo_align_audio(nemo_context *ctx, const int16_t *audio, int n_s
 // MI355X extension: offline transcription of one whole utterance with the frame-synchronous beam search (nasr_engine_transcribe_beam): the
 // nbest distinct transcripts, best first, each with its score (the ln P of its best-scoring lattice path), the encoder frame of every token
 // and its ln P.  beam 1 .. 8, nbest 0 = beam, max_symbols 0 = the default; beam = 0 is the greedy offline transcription
-// (nasr_engine_transcribe: one hypothesis, score NAN, no log-probabilities; it is boosted whenever phrase boosting is on).  In beam calls
+// (nasr_engine_transcribe: one hypothesis, score NAN; logprobs is filled after nemo_set_token_logprobs and entropies after
+// nemo_set_token_entropy, both empty otherwise, and a read-out that fails fails the call; it is boosted whenever phrase boosting is on).  In beam calls
 // phrase boosting is applied only after nemo_set_beam_boost(ctx, true).  Empty on failure (the reason on stderr)
 struct nemo_hypothesis {
     double score = 0.0;
     std::vector<int32_t> tokens, frames;
     std::vector<float> logprobs;
+    std::vector<float> entropies;    // beam = 0 only, after nemo_set_token_entropy: the entropy at every token (beam = 0 also fills logprobs after nemo_set_token_logprobs)
     bool has_lm = false;             // a language model was attached (nemo_load_lm_arpa): ranks are by `total`
     double lm_logprob = 0.0, total = 0.0;      // ln P_LM of the transcript (EOS term included when the model has one); score + weight * lm + bonus * tokens
     bool has_boost = false;          // the search was boosted (nemo_set_beam_boost): ranks are by `total`, which then also includes `boost`
@@ -223,6 +231,9 @@ std::vector<timed_token> nemo_stream_get_timed_tokens(nemo_stream_context *sctx)
 // ln P(token) of every token of the stream since init/reset (needs nemo_set_token_logprobs; NaN for tokens that have left the
 // engine's 4096-token ring, as their frame is -1); word confidences from them: word_confidence.h
 std::vector<float> nemo_stream_get_token_logprobs(nemo_stream_context *sctx);
+// the entropy of order alpha at every token of the stream since init/reset (needs nemo_set_token_entropy; NaN for tokens that have left the
+// engine's 4096-token ring); token and word confidences from them: token_confidence.h
+std::vector<float> nemo_stream_get_token_entropies(nemo_stream_context *sctx);
 // ln P(blank) at the last joint evaluation of every encoder frame of the stream since init/reset (needs nemo_set_frame_blank_logprobs; NaN for
 // frames that have left the engine's 4096-frame ring).  Completes steps in flight
 std::vector<float> nemo_stream_get_frame_blank_logprobs(nemo_stream_context *sctx);

@@ -22,10 +22,11 @@
 #include "nemotron_asr_amd.h"
 #include "wav_header.h"
 #include "word_confidence.h"
+#include "token_confidence.h"
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--alternatives K] [--endpoints] [--preview] [--save-state FILE] [--load-state FILE] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--confidence-method M] [--confidence-alpha A] [--confidence-norm N] [--confidence-agg G] [--alternatives K] [--endpoints] [--preview] [--save-state FILE] [--load-state FILE] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
             "  --input-encoding E: s16 (default), f32, mulaw or alaw (G.711).  --input-channels C: 1 .. 8 interleaved channels\n"
@@ -37,6 +38,11 @@ static void usage(const char *prog) {
             "  --timestamps:    print the final transcript again with {seconds} in front of every word\n"
             "  --confidence:    print the final transcript again with [0.93] behind every word: exp of the smallest log-probability among\n"
             "                   the word's tokens under the joint's softmax (with --timestamps: one line, {seconds} in front and [p] behind)\n"
+            "  --confidence-method max_prob|entropy|tsallis [--confidence-alpha A] [--confidence-norm lin|exp] [--confidence-agg min|mean|prod]:\n"
+            "                   the bracketed number becomes the chosen measure (any of these implies --confidence).  max_prob: P(token); entropy / tsallis:\n"
+            "                   the entropy of order A (default 0.333; 1 = Shannon; 0.05 .. 0.9, 1, 1.1 .. 4) of the joint's whole output distribution where\n"
+            "                   the token was emitted, mapped to [0, 1] linearly or exponentially (default exp).  A word's number is the min (default),\n"
+            "                   the mean or the product of its tokens'.  --confidence-alpha and --confidence-norm go with entropy or tsallis\n"
             "  --alternatives K: after the transcript (and the --timestamps / --confidence line) one line per emitted token, `alt <i> <id>:<p> <id>:<p> ...`\n"
             "                   with K = 1 .. 8 pairs: i = the token's index from 0, then the K most probable joint outputs at that emission (id 1024 =\n"
             "                   blank: the model nearly emitted nothing) with p = their softmax probability as %%.4f, in descending order; without\n"
@@ -85,6 +91,12 @@ int main(int argc, char **argv) {
     int chunk_ms = 80, right_context = 0, device = 0, dtype = 1, positional = 0;
     const char *lang = nullptr;
     bool print_tokens = false, timestamps = false, confidence = false;
+    bool conf_entropy_opts = false;
+    bool conf_opts = false, conf_max_prob = true;      // --confidence-*: the bracketed number becomes the chosen measure (token_confidence.h)
+    token_conf::Method conf_method = token_conf::METHOD_ENTROPY;
+    token_conf::Norm conf_norm = token_conf::NORM_EXP;
+    token_conf::Agg conf_agg = token_conf::AGG_MIN;
+    float conf_alpha = 0.333f;
     const char *boost_file = nullptr, *save_state = nullptr, *load_state = nullptr;
     int alternatives = 0;
     bool endpoints = false, preview = false;
@@ -108,6 +120,19 @@ int main(int argc, char **argv) {
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--timestamps") timestamps = true;
         else if (a == "--confidence") confidence = true;
+        else if (a == "--confidence-method" && i + 1 < argc) {
+            if (!token_conf::parse_method(argv[++i], &conf_max_prob, &conf_method)) { fprintf(stderr, "--confidence-method must be max_prob, entropy or tsallis (got %s)\n", argv[i]); return 1; }
+            confidence = conf_opts = true;
+        }
+        else if (a == "--confidence-alpha" && i + 1 < argc) { conf_alpha = strtof(argv[++i], nullptr); confidence = conf_opts = conf_entropy_opts = true; }
+        else if (a == "--confidence-norm" && i + 1 < argc) {
+            if (!token_conf::parse_norm(argv[++i], &conf_norm)) { fprintf(stderr, "--confidence-norm must be lin or exp (got %s)\n", argv[i]); return 1; }
+            confidence = conf_opts = conf_entropy_opts = true;
+        }
+        else if (a == "--confidence-agg" && i + 1 < argc) {
+            if (!token_conf::parse_agg(argv[++i], &conf_agg)) { fprintf(stderr, "--confidence-agg must be min, mean or prod (got %s)\n", argv[i]); return 1; }
+            confidence = conf_opts = true;
+        }
         else if (a == "--alternatives" && i + 1 < argc) alternatives = atoi(argv[++i]);
         else if (a == "--endpoints") endpoints = true;
         else if (a == "--preview") preview = true;
@@ -158,6 +183,7 @@ int main(int argc, char **argv) {
     }
     if (read_chunks < 1 || read_chunks > 4096) { fprintf(stderr, "--read-chunks must be in 1..4096 (got %d)\n", read_chunks); return 1; }
     if (lm_opts && !lm_path) { fprintf(stderr, "--lm-weight and --token-bonus go with --lm\n"); return 1; }
+    if (conf_entropy_opts && conf_max_prob) { fprintf(stderr, "--confidence-alpha and --confidence-norm go with --confidence-method entropy or tsallis\n"); return 1; }
     if (second_pass < 0 || second_pass > 8) { fprintf(stderr, "--second-pass must be 1 .. 8 (got %d)\n", second_pass); return 1; }
     if (!second_pass && (sp_nbest || sp_symbols || history_frames != 2048)) { fprintf(stderr, "--nbest, --max-symbols and --history-frames go with --second-pass\n"); return 1; }
     if (chunk_ms < 10) { fprintf(stderr, "chunk_ms must be >= 10 (got %d)\n", chunk_ms); return 1; }
@@ -170,7 +196,8 @@ int main(int argc, char **argv) {
     if ((save_state || load_state) && !diarize_gguf.empty()) { fprintf(stderr, "--save-state / --load-state do not go with --diarize\n"); return 1; }
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, preview ? 2 : 1);      // a preview flushes a fork of the stream: one slot of headroom
     if (!ctx) { fprintf(stderr, "Failed to load ASR model\n"); return 1; }
-    if (confidence && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
+    if (confidence && conf_max_prob && !nemo_set_token_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable token log-probabilities\n"); nemo_free(ctx); return 1; }
+    if (confidence && !conf_max_prob && !nemo_set_token_entropy(ctx, conf_alpha)) { fprintf(stderr, "Failed to enable token entropies (--confidence-alpha 0.05 .. 0.9, 1 or 1.1 .. 4)\n"); nemo_free(ctx); return 1; }
     if (alternatives && !nemo_set_token_alternatives(ctx, alternatives)) { fprintf(stderr, "Failed to enable %d token alternatives (K = 1 .. 8)\n", alternatives); nemo_free(ctx); return 1; }
     if (second_pass && !nemo_set_frame_history(ctx, history_frames)) { fprintf(stderr, "Failed to enable the frame history (--history-frames 64 .. 2048 in multiples of 64)\n"); nemo_free(ctx); return 1; }
     if (endpoints && !nemo_set_frame_blank_logprobs(ctx, true)) { fprintf(stderr, "Failed to enable per-frame blank log-probabilities\n"); nemo_free(ctx); return 1; }
@@ -358,7 +385,13 @@ int main(int argc, char **argv) {
             audio_s, wall, audio_s > 0 ? wall / audio_s : 0.0, wall > 0 ? audio_s / wall : 0.0, sctx->total_chunks_processed);
     if (timestamps && !confidence) printf("%s\n", tokens_to_text(nemo_stream_get_timed_tokens(sctx), ctx->vocab, true).c_str());
     if (confidence) {
-        const std::vector<word_conf::Word> ws = word_conf::words(nemo_stream_get_tokens(sctx), nemo_stream_get_token_logprobs(sctx), ctx->vocab);
+        // --confidence alone: exp(min ln P) as ever.  With a --confidence-* flag: the per-token confidences of the chosen measure, aggregated per word
+        const std::vector<word_conf::Word> ws =
+            !conf_opts ? word_conf::words(nemo_stream_get_tokens(sctx), nemo_stream_get_token_logprobs(sctx), ctx->vocab)
+                       : token_conf::words(nemo_stream_get_tokens(sctx),
+                                           conf_max_prob ? token_conf::max_prob_confidences(nemo_stream_get_token_logprobs(sctx))
+                                                         : token_conf::confidences(nemo_stream_get_token_entropies(sctx), (double)ctx->token_entropy_milli / 1000.0, conf_method, conf_norm),
+                                           ctx->vocab, conf_agg);
         std::vector<std::string> stamps;
         if (timestamps) {
             const std::vector<timed_token> tt = nemo_stream_get_timed_tokens(sctx);
