@@ -456,7 +456,7 @@ __device__ __forceinline__ void store_a(void *base, size_t idx, float v, int bf1
 // One thread per channel walks a tile of 16 frames with the 16 + kernel - 1 inputs it needs in registers.
 constexpr int DW_TILE = 32, DW_KMAX = 15;
 __global__ __launch_bounds__(256) void k_spk_depthwise(const float *x, int x_pitch, const float *w, int kernel, int C, int Cpad,
-                                                       const int *lens, void *a_out, int out_bf16) {
+                                                       const int *lens, float *a_out) {
     const int t0 = blockIdx.x * DW_TILE, s = blockIdx.y, L = lens[s], pad = (kernel - 1) / 2;
     const float *xs = x + (size_t)s * SPK_T * x_pitch;
     for (int c = threadIdx.x; c < Cpad; c += 256) {
@@ -479,23 +479,22 @@ __global__ __launch_bounds__(256) void k_spk_depthwise(const float *x, int x_pit
                 for (int i = 0; i < DW_KMAX; i++)
                     if (i < kernel) acc = i == 0 ? in[u + i] * wk[i] : __builtin_fmaf(in[u + i], wk[i], acc);   // explicit fma chain (what the compiler chose anyway: pinned)
             }
-            if (t < SPK_T) store_a(a_out, ((size_t)s * SPK_T + t) * Cpad + c, acc, out_bf16);
+            if (t < SPK_T) a_out[((size_t)s * SPK_T + t) * Cpad + c] = acc;
         }
     }
 }
-void launch_spk_depthwise(const float *x, int x_pitch, const float *w, int kernel, int C, int Cpad, const int *lens, void *a_out,
-                          int out_bf16, int S, hipStream_t st) {
-    hipLaunchKernelGGL(k_spk_depthwise, dim3(SPK_T / DW_TILE, S), dim3(256), 0, st, x, x_pitch, w, kernel, C, Cpad, lens, a_out, out_bf16);
+void launch_spk_depthwise(const float *x, int x_pitch, const float *w, int kernel, int C, int Cpad, const int *lens, float *a_out, int S, hipStream_t st) {
+    hipLaunchKernelGGL(k_spk_depthwise, dim3(SPK_T / DW_TILE, S), dim3(256), 0, st, x, x_pitch, w, kernel, C, Cpad, lens, a_out);
 }
 
-// masked copy into the GEMM operand type (input of the residual 1x1 conv :369-372 and of the attention conv)
-__global__ __launch_bounds__(256) void k_spk_mask_cvt(const float *x, int C, const int *lens, void *a_out, int out_bf16) {
+// masked copy into the GEMM operand (input of the residual 1x1 conv :369-372 and of the attention conv)
+__global__ __launch_bounds__(256) void k_spk_mask_cvt(const float *x, int C, const int *lens, float *a_out) {
     const int t = blockIdx.x, s = blockIdx.y, L = lens[s];
     const size_t row = ((size_t)s * SPK_T + t) * C;
-    for (int c = threadIdx.x; c < C; c += 256) store_a(a_out, row + c, t < L ? x[row + c] : 0.0f, out_bf16);
+    for (int c = threadIdx.x; c < C; c += 256) a_out[row + c] = t < L ? x[row + c] : 0.0f;
 }
-void launch_spk_mask_cvt(const float *x, int C, const int *lens, void *a_out, int out_bf16, int S, hipStream_t st) {
-    hipLaunchKernelGGL(k_spk_mask_cvt, dim3(SPK_T, S), dim3(256), 0, st, x, C, lens, a_out, out_bf16);
+void launch_spk_mask_cvt(const float *x, int C, const int *lens, float *a_out, int S, hipStream_t st) {
+    hipLaunchKernelGGL(k_spk_mask_cvt, dim3(SPK_T, S), dim3(256), 0, st, x, C, lens, a_out);
 }
 
 // squeeze-excite gate (:303-315): z = sigmoid(fc2 . relu(fc1 . masked_mean_T(y)))

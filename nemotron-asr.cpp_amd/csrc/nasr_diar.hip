@@ -5,6 +5,7 @@
 // over ALL windows (of all streams) / all sub-segments here.  Host control flow around it (onset/offset state machine,
 // sub-segment cursor, clustering, RTTM) is out of scope.
 #include "nasr_internal.h"
+#include "nasr_diar_set.h"
 #include "nemotron_asr_amd.h"
 
 #include <algorithm>
@@ -62,21 +63,18 @@ struct nasr_diar {
     float *vad_fbT = nullptr; int *vad_band = nullptr;
     VadNet vad{};
     // TitaNet-L
-    bool bf16 = true; int esz = 2;
+    bool bf16 = true;
     bool vad_bf16 = false;           // NASR_DIAR_VAD_BF16: MarbleNet on the bf16 MFMA with bf16 activation planes
     bool vad_f16 = false;            // NASR_DIAR_VAD_F16: ... on the f16 MFMA with IEEE-half planes (same kernel, 8x less rounding)
     struct SpkSub { float *dw = nullptr; void *pw = nullptr; float *bias = nullptr; int kernel = 1, cin = 0, cin_pad = 0, cout = 0; };
     struct SpkBlock { int repeat = 1; bool residual = false; SpkSub sub[3], res; float *fc1 = nullptr, *fc2 = nullptr; int cin = 0, cout = 0; };
     SpkBlock spk[5];
+    SpkSub att2;                     // the second attention conv, 128 -> 3072 (pw, bias)
     float *spk_fbT = nullptr; int *spk_band = nullptr;
-    void *a1x_w = nullptr; float *a1_w = nullptr, *a1_b = nullptr, *a_bn_s = nullptr, *a_bn_b = nullptr, *zero_bias = nullptr;
-    void *a2_w = nullptr; float *a2_b = nullptr, *e_bn_s = nullptr, *e_bn_b = nullptr, *emb_w = nullptr, *emb_b = nullptr;
-    float *s_mel = nullptr, *X0 = nullptr, *X1 = nullptr, *Y = nullptr, *R = nullptr, *se_z = nullptr, *st_mean = nullptr, *st_std = nullptr;
-    float *att_c = nullptr, *att_g = nullptr, *pool = nullptr, *emb = nullptr, *se_h = nullptr;
-    void *A = nullptr; int *s_lens = nullptr; long long *s_off = nullptr;
-    // segment-tile path (bf16 engine, kernels_spk.hip): A operands ping-pong [M][1024], block outputs [M][1024] x 2, encoder output [M][3072], all bf16
-    bf16_t *sA[2] = {nullptr, nullptr}, *sX[2] = {nullptr, nullptr}, *sX4 = nullptr;
-    float *st_ms = nullptr, *a1ms_w = nullptr, *fc_part = nullptr;      // [S][2 C] masked mean ; std, the mean / std thirds of the attention conv (pack_mfma_f32), split-K scratch
+    void *a1x_w = nullptr; float *a1_b = nullptr, *a_bn_s = nullptr, *a_bn_b = nullptr, *zero_bias = nullptr;
+    float *a1_w = nullptr, *a1ms_w = nullptr;       // the whole first attention conv (f32 engine) / its mean and std thirds in pack_mfma_f32 order (bf16 engine)
+    float *e_bn_s = nullptr, *e_bn_b = nullptr, *emb_w = nullptr, *emb_b = nullptr;
+    SpkSet set;                      // activations and scratch of an embedding call, per engine dtype (nasr_diar_set.h)
     // one hipGraph per (segments in the call, sample type): the ~45 launches of an embedding call replayed as one (the pointers inside are the
     // engine's own persistent buffers; the staged audio buffer is part of the key's validity: spk_graph_audio)
     std::map<std::pair<int, uint32_t>, hipGraphExec_t> spk_graphs;
@@ -84,7 +82,9 @@ struct nasr_diar {
     bool spk_use_graph = true;       // NASR_DIAR_NO_GRAPH=1: eager launches (A/B, debugging)
     hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // [vad / embed][begin / end] of the last call's launch sequence (nasr_diar_last_gpu_ms)
     float last_ms[2] = {0.f, 0.f};
-    // scratch
+    // grow-on-demand scratch (grow_device / grow_pinned): registered at its first allocation, freed from the registry
+    struct Grown { void **slot; bool pinned; };
+    std::vector<Grown> grown;
     char *audio = nullptr; size_t audio_cap = 0;        // staged input samples (float or s16), capacities in bytes
     char *pin_audio = nullptr; size_t pin_audio_cap = 0;
     DiarFrameDesc *fr_desc = nullptr; size_t fr_cap = 0;  // VAD: frame descriptors, frames [n][80], per-window rows / lens, results
@@ -92,7 +92,7 @@ struct nasr_diar {
     int *win_row = nullptr; size_t win_cap = 0;
     float *prob = nullptr; size_t prob_cap = 0;
     char *pin = nullptr; size_t pin_cap = 0;             // pinned staging for descriptors / results
-    GatherDesc *gather_dev = nullptr, *gather_pin = nullptr; size_t gather_cap = 0;   // device-resident inputs: (source, destination, bytes) per buffer
+    GatherDesc *gather_dev = nullptr, *gather_pin = nullptr; size_t gather_cap = 0, gather_pin_cap = 0;   // device-resident inputs: (source, destination, bytes) per buffer
 };
 
 namespace {
@@ -110,6 +110,27 @@ int upload(nasr_diar *d, const std::vector<Tp> &h, Tp **dev) {
     DCHK(hipMemcpy(*dev, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
     return 0;
 }
+// grow-on-demand scratch (the sizes depend on the call): (pointer, capacity in elements, needed, capacity to allocate when it has to grow).
+// Whatever the stream still does with the old buffer finishes before it is freed
+template <typename Tp>
+int grow(nasr_diar *d, Tp **p, size_t *cap, size_t n, size_t grown_cap, bool pinned) {
+    if (n <= *cap) return 0;
+    DCHK(hipStreamSynchronize(d->st));
+    if (*p) pinned ? hipHostFree(*p) : hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const auto same = [&](const nasr_diar::Grown &g) { return g.slot == (void **)p; };
+    if (std::none_of(d->grown.begin(), d->grown.end(), same)) d->grown.push_back({(void **)p, pinned});
+    if (pinned) DCHK(hipHostMalloc((void **)p, grown_cap * sizeof(Tp), hipHostMallocDefault));
+    else DCHK(hipMalloc((void **)p, grown_cap * sizeof(Tp)));
+    *cap = grown_cap;
+    return 0;
+}
+template <typename Tp>
+int grow_device(nasr_diar *d, Tp **p, size_t *cap, size_t n, size_t grown_cap) { return grow(d, p, cap, n, grown_cap, false); }
+template <typename Tp>
+int grow_pinned(nasr_diar *d, Tp **p, size_t *cap, size_t n, size_t grown_cap) { return grow(d, p, cap, n, grown_cap, true); }
+
 const std::vector<float> *get(nasr_diar *d, const std::string &name, size_t want) {
     auto it = d->host.find(name);
     if (it == d->host.end()) { failf("diarize weights: missing tensor '%s'", name.c_str()); return nullptr; }
@@ -286,24 +307,10 @@ int stage_audio(nasr_diar *d, const float *const *audio, const int32_t *n, int B
     size_t total = 0;
     base.resize(B);
     for (int b = 0; b < B; b++) { base[b] = (long long)total; total += ((size_t)std::max(n[b], 0) + 7) & ~(size_t)7; }     // every buffer starts on 16 bytes
-    if (total * esz > d->audio_cap) {
-        DCHK(hipStreamSynchronize(d->st));
-        if (d->audio) hipFree(d->audio);
-        d->audio = nullptr;
-        d->audio_cap = total * esz + 262144;
-        DCHK(hipMalloc((void **)&d->audio, d->audio_cap));
-    }
+    if (grow_device(d, &d->audio, &d->audio_cap, total * esz, total * esz + 262144)) return -1;
     if (on_device) {
         // one table upload + ONE gather launch (rounds 1-5: a hipMemcpyAsync per buffer)
-        if ((size_t)B > d->gather_cap) {
-            DCHK(hipStreamSynchronize(d->st));
-            if (d->gather_dev) hipFree(d->gather_dev);
-            if (d->gather_pin) hipHostFree(d->gather_pin);
-            d->gather_dev = nullptr; d->gather_pin = nullptr;
-            d->gather_cap = (size_t)B + 64;
-            DCHK(hipMalloc((void **)&d->gather_dev, d->gather_cap * sizeof(GatherDesc)));
-            DCHK(hipHostMalloc((void **)&d->gather_pin, d->gather_cap * sizeof(GatherDesc), hipHostMallocDefault));
-        }
+        if (grow_device(d, &d->gather_dev, &d->gather_cap, (size_t)B, (size_t)B + 64) || grow_pinned(d, &d->gather_pin, &d->gather_pin_cap, (size_t)B, (size_t)B + 64)) return -1;
         long long max_bytes = 0;
         for (int b = 0; b < B; b++) {                   // every entry point of this file ends with a stream synchronise: the pinned table is free again
             d->gather_pin[b].src = audio[b];
@@ -315,13 +322,7 @@ int stage_audio(nasr_diar *d, const float *const *audio, const int32_t *n, int B
         launch_gather_audio(d->gather_dev, B, max_bytes, d->audio, d->st);
     } else {
         // host hand-over: gather into one pinned block, one H2D copy (pageable sources would be staged piecewise by the runtime)
-        if (total * esz > d->pin_audio_cap) {
-            DCHK(hipStreamSynchronize(d->st));
-            if (d->pin_audio) hipHostFree(d->pin_audio);
-            d->pin_audio = nullptr;
-            d->pin_audio_cap = total * esz + 262144;
-            DCHK(hipHostMalloc((void **)&d->pin_audio, d->pin_audio_cap, hipHostMallocDefault));
-        }
+        if (grow_pinned(d, &d->pin_audio, &d->pin_audio_cap, total * esz, total * esz + 262144)) return -1;
         DCHK(hipStreamSynchronize(d->st));          // the previous call's copy out of the pinned block has finished
         for (int b = 0; b < B; b++)
             if (n[b] > 0) memcpy(d->pin_audio + (size_t)base[b] * esz, audio[b], (size_t)n[b] * esz);
@@ -345,15 +346,8 @@ static void diar_destroy_impl(nasr_diar *d) {
     for (auto &kv : d->spk_graphs) hipGraphExecDestroy(kv.second);
     for (auto &pair : d->ev) for (auto &e : pair) if (e) hipEventDestroy(e);
     for (void *p : d->allocs) hipFree(p);
-    if (d->audio) hipFree(d->audio);
-    if (d->fr_desc) hipFree(d->fr_desc);
-    if (d->fr_mel) hipFree(d->fr_mel);
-    if (d->win_row) hipFree(d->win_row);
-    if (d->prob) hipFree(d->prob);
-    if (d->pin) hipHostFree(d->pin);
-    if (d->pin_audio) hipHostFree(d->pin_audio);
-    if (d->gather_dev) hipFree(d->gather_dev);
-    if (d->gather_pin) hipHostFree(d->gather_pin);
+    for (auto &g : d->grown)
+        if (*g.slot) g.pinned ? hipHostFree(*g.slot) : hipFree(*g.slot);
     if (d->st && !d->st_borrowed) hipStreamDestroy(d->st);
     else if (d->st && d->st_lent) lent_stream_release(d->st);
     delete d;
@@ -399,7 +393,6 @@ extern "C" int nasr_diar_create(nasr_diar **out, int device_id, int dtype, const
     dtype &= ~(NASR_DIAR_VAD_BF16 | NASR_DIAR_VAD_F16);
     if (dtype != NASR_DTYPE_BF16 && dtype != NASR_DTYPE_F32) { delete d; return failf("dtype must be NASR_DTYPE_F32 or NASR_DTYPE_BF16 (optionally | NASR_DIAR_VAD_BF16 or NASR_DIAR_VAD_F16)"); }
     d->bf16 = dtype == NASR_DTYPE_BF16;      // TitaNet's pointwise convolutions; MarbleNet is f32 unless NASR_DIAR_VAD_BF16 is set
-    d->esz = d->bf16 ? 2 : 4;
     d->max_windows = std::max(max_windows, 1);
     d->max_segments = std::max(max_segments, 1);
     for (int i = 0; i < n_weights; i++) {
@@ -420,8 +413,8 @@ extern "C" int nasr_diar_create(nasr_diar **out, int device_id, int dtype, const
     init_spk_kernel_attributes();
     if (const char *ng = getenv("NASR_DIAR_NO_GRAPH")) d->spk_use_graph = !(ng[0] && ng[0] != '0');
     for (auto &pair : d->ev) for (auto &e : pair) if (hipEventCreate(&e) != hipSuccess) { diar_destroy_impl(d); return failf("hipEventCreate failed"); }
-    d->pin_cap = (size_t)(d->max_windows + d->max_segments * SPK_EMB + 4096) * 16;
-    if (hipHostMalloc((void **)&d->pin, d->pin_cap, hipHostMallocDefault) != hipSuccess) { diar_destroy_impl(d); return failf("hipHostMalloc failed"); }
+    const size_t pin_bytes = (size_t)(d->max_windows + d->max_segments * SPK_EMB + 4096) * 16;
+    if (grow_pinned(d, &d->pin, &d->pin_cap, pin_bytes, pin_bytes)) { diar_destroy_impl(d); return -1; }
     int rc = 0;
     if (d->has_vad) rc |= load_vad(d);
     if (!rc && d->has_spk) rc |= nasr_diar_load_spk(d);
@@ -432,17 +425,9 @@ extern "C" int nasr_diar_create(nasr_diar **out, int device_id, int dtype, const
     return 0;
 }
 
-// grow-on-demand device scratch (the VAD's sizes depend on the call)
+// the VAD's device scratch: half as much again, so that a slightly longer call does not reallocate
 template <typename Tp>
-static int ensure(nasr_diar *d, Tp **p, size_t *cap, size_t n) {
-    if (n <= *cap) return 0;
-    DCHK(hipStreamSynchronize(d->st));
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = n + n / 2 + 1024;
-    DCHK(hipMalloc((void **)p, *cap * sizeof(Tp)));
-    return 0;
-}
+static int ensure(nasr_diar *d, Tp **p, size_t *cap, size_t n) { return grow_device(d, p, cap, n, n + n / 2 + 1024); }
 
 // vad_session_run_batch (src/diarize_vad.cpp:490-503) for B buffers in one launch sequence: every 0.63 s window of
 // every buffer at a 10 ms shift -> P(speech).  audio[b]: n_samples[b] float samples in [-1, 1].
@@ -474,13 +459,7 @@ extern "C" int nasr_diar_vad(nasr_diar *d, int B, const float *const *audio, con
     for (int b = 0; b < B; b++) if (first[b + 1] > first[b]) n_shared += (size_t)(first[b + 1] - first[b]) + 60;
     const size_t n_frames = n_shared + 3 * (size_t)W;
     const size_t host_bytes = n_frames * sizeof(DiarFrameDesc) + (size_t)W * (2 * sizeof(int) + sizeof(float));
-    if (host_bytes > d->pin_cap) {
-        DCHK(hipStreamSynchronize(d->st));
-        if (d->pin) hipHostFree(d->pin);
-        d->pin = nullptr;
-        d->pin_cap = host_bytes + host_bytes / 2;
-        DCHK(hipHostMalloc((void **)&d->pin, d->pin_cap, hipHostMallocDefault));
-    }
+    if (grow_pinned(d, &d->pin, &d->pin_cap, host_bytes, host_bytes + host_bytes / 2)) return -1;
     DiarFrameDesc *h_fr = (DiarFrameDesc *)d->pin;
     int *h_row = (int *)(d->pin + n_frames * sizeof(DiarFrameDesc)), *h_len = h_row + W;
     float *h_prob = (float *)(h_len + W);
@@ -652,25 +631,15 @@ static int nasr_diar_load_spk(nasr_diar *d) {
     for (int a = 0; a < A; a++) memcpy(&a1x[(size_t)a * C], &(*a1w)[(size_t)a * 3 * C], (size_t)C * sizeof(float));
     std::vector<float> a1ms((size_t)A * 2 * C);                // the mean / std thirds: one [A][2 C] linear over the segments (segment-tile path)
     for (int a = 0; a < A; a++) memcpy(&a1ms[(size_t)a * 2 * C], &(*a1w)[(size_t)a * 3 * C + C], (size_t)2 * C * sizeof(float));
-    if (d->bf16 && upload(d, pack_mfma_f32(a1ms, A, 2 * C), &d->a1ms_w)) return -1;
     std::vector<float> zeros((size_t)std::max(C, 1024), 0.0f);
-    if (upload_gemm_weight(d, a1x, nullptr, A, C, C, &d->a1x_w) || upload(d, *a1w, &d->a1_w) || upload(d, *a1b, &d->a1_b) ||
+    d->att2.cin = d->att2.cin_pad = A; d->att2.cout = C;
+    if ((d->bf16 ? upload(d, pack_mfma_f32(a1ms, A, 2 * C), &d->a1ms_w) : upload(d, *a1w, &d->a1_w)) ||
+        upload_gemm_weight(d, a1x, nullptr, A, C, C, &d->a1x_w) || upload(d, *a1b, &d->a1_b) ||
         upload(d, as, &d->a_bn_s) || upload(d, ab, &d->a_bn_b) || upload(d, zeros, &d->zero_bias) ||
-        upload_gemm_weight(d, *a2w, nullptr, C, A, A, &d->a2_w) || upload(d, *a2b, &d->a2_b) || upload(d, es, &d->e_bn_s) ||
+        upload_gemm_weight(d, *a2w, nullptr, C, A, A, &d->att2.pw) || upload(d, *a2b, &d->att2.bias) || upload(d, es, &d->e_bn_s) ||
         upload(d, ebn, &d->e_bn_b) || upload(d, pack_mfma_f32(*ew, SPK_EMB, 2 * SPK_C), &d->emb_w) || upload(d, *eb, &d->emb_b))
         return -1;
-    const size_t S = (size_t)d->max_segments, M = S * SPK_T;
-    char *a = nullptr;
-    if (dalloc(d, &d->s_mel, M * 96) || dalloc(d, &d->X0, M * C) || dalloc(d, &d->X1, M * C) || dalloc(d, &d->Y, M * C) ||
-        dalloc(d, &d->R, M * 1024) || dalloc(d, &a, M * C * (size_t)d->esz) || dalloc(d, &d->se_z, 2 * S * C) || dalloc(d, &d->se_h, S * (C / 8)) ||
-        dalloc(d, &d->st_mean, S * C) || dalloc(d, &d->st_std, S * C) || dalloc(d, &d->att_c, S * A) || dalloc(d, &d->att_g, M * A) ||
-        dalloc(d, &d->pool, S * 2 * C) || dalloc(d, &d->emb, S * SPK_EMB) || dalloc(d, &d->s_lens, S) || dalloc(d, &d->s_off, S))
-        return -1;
-    d->A = a;
-    if (d->bf16 && (dalloc(d, &d->sA[0], M * 1024) || dalloc(d, &d->sA[1], M * 1024) || dalloc(d, &d->sX[0], M * 1024) || dalloc(d, &d->sX[1], M * 1024) ||
-                    dalloc(d, &d->sX4, M * C) || dalloc(d, &d->st_ms, S * 2 * C) || dalloc(d, &d->fc_part, 16 * S * 512)))
-        return -1;
-    return 0;
+    return spk_set_ensure(d->set, d->bf16, d->max_segments, [&](const char *, void **p, size_t bytes) { return dalloc(d, (char **)p, bytes); });
 }
 
 static void spk_gemm(nasr_diar *d, const void *A, int lda, const void *W, int M, int N, int K, const float *bias, bool relu, float *out) {
@@ -686,38 +655,49 @@ static void spk_gemm(nasr_diar *d, const void *A, int lda, const void *W, int M,
 
 // SE gate pre-activation (:303-315): z = fc2 . relu(fc1 . mean) over the segments (the sigmoid is applied where the gate is used)
 static int spk_se(nasr_diar *d, nasr_diar::SpkBlock &blk, const float *mean, int St) {
-    if (launch_spk_fc(mean, blk.cout, blk.fc1, d->zero_bias, d->se_h, d->fc_part, St, blk.cout, blk.cout / 8, 1, d->st) ||
-        launch_spk_fc(d->se_h, blk.cout / 8, blk.fc2, d->zero_bias, d->se_z, d->fc_part, St, blk.cout / 8, blk.cout, 0, d->st))
+    SpkSet &w = d->set;
+    if (launch_spk_fc(mean, blk.cout, blk.fc1, d->zero_bias, w.se_h, w.fc_part, St, blk.cout, blk.cout / 8, 1, d->st) ||
+        launch_spk_fc(w.se_h, blk.cout / 8, blk.fc2, d->zero_bias, w.se_z, w.fc_part, St, blk.cout / 8, blk.cout, 0, d->st))
         return failf("TitaNet-L SE gate: bad operands");
     return 0;
 }
 
-// The bf16 engine's encoder + pooling on SEGMENT TILES (round 6, kernels_spk.hip): every pointwise conv is a GEMM whose tile is one sub-segment x 256
+// a sub-block's pointwise conv as a segment GEMM: zeros + operand, weights, shape and bias; the caller adds the mode and its outputs
+static SpkGemmParams sub_gemm(const nasr_diar::SpkSub &ss, const bf16_t *A, int lda) {
+    SpkGemmParams g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.lda = lda; g.W = (const bf16_t *)ss.pw; g.N = ss.cout; g.K = ss.cin_pad; g.bias = ss.bias;
+    return g;
+}
+
+// The bf16 engine's network on SEGMENT TILES (round 6, kernels_spk.hip): every pointwise conv is a GEMM whose tile is one sub-segment x 256
 // channels, and the depthwise conv of the NEXT sub-block, the SE mean, the block's combine and the attentive pooling run in the epilogues.
-// s_mel / s_lens are set; leaves d->pool.  ~40 launches, no f32 activation in memory except each block's Y.
+// s_mel (not normalised) / s_lens are set; leaves the embeddings in set.emb.  ~40 launches, no f32 activation in memory except each block's Y.
 static int spk_embed_segment_tiles(nasr_diar *d, int St) {
-    float *mean = d->se_z + (size_t)d->max_segments * SPK_C;
+    SpkSet &w = d->set;
+    float *mean = w.se_z + (size_t)d->max_segments * SPK_C;
     int a = 0, xb = 0;                                            // sA[a]: the A operand the next GEMM reads; sX[xb]: the last block output
     auto gemm = [&](SpkGemmParams &g) -> int {
-        g.S = St; g.lens = d->s_lens;
+        g.S = St; g.lens = w.s_lens;
         if (const char *why = spk_gemm_check(g)) return failf("TitaNet-L segment GEMM (mode %d, N %d, K %d): %s", g.mode, g.N, g.K, why);
         return launch_spk_gemm(g, d->st);
     };
-    {   // block 0 (:28): depthwise k = 3 on the 80 mel channels (K padded to 128), pointwise -> Y, SE, relu(Y * gate) -> X + block 1's first depthwise conv
-        nasr_diar::SpkBlock &blk = d->spk[0];
-        nasr_diar::SpkSub &ss = blk.sub[0];
-        if (ss.kernel != 3 || ss.cin != DIAR_NMEL || launch_spk_front(d->s_mel, 96, ss.dw, d->s_lens, d->sA[a], ss.cin_pad, St, d->st))
-            return failf("TitaNet-L front kernel: block 0 is not the 80 -> 1024, k = 3 sub-block of src/diarize_spk.cpp:28");
-        SpkGemmParams g;
-        memset(&g, 0, sizeof(g));
-        g.A = d->sA[a]; g.lda = ss.cin_pad; g.W = (const bf16_t *)ss.pw; g.N = ss.cout; g.K = ss.cin_pad; g.bias = ss.bias;
-        g.mode = SG_Y; g.y_out = d->Y; g.colmean = mean;
-        if (gemm(g)) return -1;
-        if (spk_se(d, blk, mean, St)) return -1;
+    auto se_tile = [&](const nasr_diar::SpkBlock &blk, int mode, bf16_t *x_out) {      // relu(Y * gate) of a block without residual
         SpkTileParams t;
         memset(&t, 0, sizeof(t));
-        t.y_in = d->Y; t.z = d->se_z; t.lens = d->s_lens; t.S = St; t.C = blk.cout; t.mode = ST_DW; t.x_out = d->sX[xb];
-        t.dw_w = d->spk[1].sub[0].dw; t.dw_k = d->spk[1].sub[0].kernel; t.a_out = d->sA[a ^ 1]; t.lda_out = d->spk[1].sub[0].cin_pad;
+        t.y_in = w.Y; t.z = w.se_z; t.lens = w.s_lens; t.S = St; t.C = blk.cout; t.mode = mode; t.x_out = x_out;
+        return t;
+    };
+    {   // block 0 (:28): depthwise k = 3 on the 80 mel channels (K padded to 128), pointwise -> Y, SE, relu(Y * gate) -> X + block 1's first depthwise conv
+        nasr_diar::SpkBlock &blk = d->spk[0];
+        nasr_diar::SpkSub &ss = blk.sub[0], &nx = d->spk[1].sub[0];
+        if (ss.kernel != 3 || ss.cin != DIAR_NMEL || launch_spk_front(w.s_mel, 96, ss.dw, w.s_lens, w.sA[a], ss.cin_pad, St, d->st))
+            return failf("TitaNet-L front kernel: block 0 is not the 80 -> 1024, k = 3 sub-block of src/diarize_spk.cpp:28");
+        SpkGemmParams g = sub_gemm(ss, w.sA[a], ss.cin_pad);
+        g.mode = SG_Y; g.y_out = w.Y; g.colmean = mean;
+        if (gemm(g) || spk_se(d, blk, mean, St)) return -1;
+        SpkTileParams t = se_tile(blk, ST_DW, w.sX[xb]);
+        t.dw_w = nx.dw; t.dw_k = nx.kernel; t.a_out = w.sA[a ^ 1]; t.lda_out = nx.cin_pad;
         if (launch_spk_tile(t, d->st)) return failf("TitaNet-L block 0 tile kernel: bad operands");
         a ^= 1;
     }
@@ -725,167 +705,169 @@ static int spk_embed_segment_tiles(nasr_diar *d, int St) {
         nasr_diar::SpkBlock &blk = d->spk[b];
         for (int r = 0; r < blk.repeat; r++) {
             nasr_diar::SpkSub &ss = blk.sub[r];
-            SpkGemmParams g;
-            memset(&g, 0, sizeof(g));
-            g.A = d->sA[a]; g.lda = ss.cin_pad; g.W = (const bf16_t *)ss.pw; g.N = ss.cout; g.K = ss.cin_pad; g.bias = ss.bias;
+            SpkGemmParams g = sub_gemm(ss, w.sA[a], ss.cin_pad);
             if (r + 1 < blk.repeat) {
-                g.mode = SG_DW; g.dw_w = blk.sub[r + 1].dw; g.dw_k = blk.sub[r + 1].kernel; g.a_out = d->sA[a ^ 1]; g.lda_out = blk.sub[r + 1].cin_pad;
+                g.mode = SG_DW; g.dw_w = blk.sub[r + 1].dw; g.dw_k = blk.sub[r + 1].kernel; g.a_out = w.sA[a ^ 1]; g.lda_out = blk.sub[r + 1].cin_pad;
             } else {
-                g.mode = SG_Y; g.y_out = d->Y; g.colmean = mean;
+                g.mode = SG_Y; g.y_out = w.Y; g.colmean = mean;
             }
             if (gemm(g)) return -1;
             if (r + 1 < blk.repeat) a ^= 1;
         }
         if (spk_se(d, blk, mean, St)) return -1;
-        SpkGemmParams g;                                          // residual 1 x 1 conv + combine (+ the next block's first depthwise conv)
-        memset(&g, 0, sizeof(g));
-        g.A = d->sX[xb]; g.lda = blk.cin; g.W = (const bf16_t *)blk.res.pw; g.N = blk.cout; g.K = blk.cin; g.bias = blk.res.bias;
-        g.mode = SG_RES; g.y_in = d->Y; g.z = d->se_z; g.x_out = d->sX[xb ^ 1];
+        SpkGemmParams g = sub_gemm(blk.res, w.sX[xb], blk.cin);   // residual 1 x 1 conv + combine (+ the next block's first depthwise conv)
+        g.mode = SG_RES; g.y_in = w.Y; g.z = w.se_z; g.x_out = w.sX[xb ^ 1];
         nasr_diar::SpkSub &nx = d->spk[b + 1].sub[0];
-        if (nx.kernel > 1) { g.dw_w = nx.dw; g.dw_k = nx.kernel; g.a_out = d->sA[a ^ 1]; g.lda_out = nx.cin_pad; }
+        if (nx.kernel > 1) { g.dw_w = nx.dw; g.dw_k = nx.kernel; g.a_out = w.sA[a ^ 1]; g.lda_out = nx.cin_pad; }
         if (gemm(g)) return -1;
         xb ^= 1;
         if (nx.kernel > 1) a ^= 1;
     }
     {   // block 4 (:34): kernel 1 (folded into the weights at load), 1024 -> 3072, SE, relu(Y * gate) -> X4 + masked statistics (:392-410)
         nasr_diar::SpkBlock &blk = d->spk[4];
-        nasr_diar::SpkSub &ss = blk.sub[0];
-        SpkGemmParams g;
-        memset(&g, 0, sizeof(g));
-        g.A = d->sX[xb]; g.lda = ss.cin_pad; g.W = (const bf16_t *)ss.pw; g.N = ss.cout; g.K = ss.cin_pad; g.bias = ss.bias;
-        g.mode = SG_Y; g.y_out = d->Y; g.colmean = mean;
-        if (gemm(g)) return -1;
-        if (spk_se(d, blk, mean, St)) return -1;
-        SpkTileParams t;
-        memset(&t, 0, sizeof(t));
-        t.y_in = d->Y; t.z = d->se_z; t.lens = d->s_lens; t.S = St; t.C = blk.cout; t.mode = ST_STATS; t.x_out = d->sX4;
-        t.mean = d->st_ms; t.stdv = d->st_ms + SPK_C; t.stat_ld = 2 * SPK_C;
+        SpkGemmParams g = sub_gemm(blk.sub[0], w.sX[xb], blk.sub[0].cin_pad);
+        g.mode = SG_Y; g.y_out = w.Y; g.colmean = mean;
+        if (gemm(g) || spk_se(d, blk, mean, St)) return -1;
+        SpkTileParams t = se_tile(blk, ST_STATS, w.sX4);
+        t.mean = w.st_ms; t.stdv = w.st_ms + SPK_C; t.stat_ld = 2 * SPK_C;
         if (launch_spk_tile(t, d->st)) return failf("TitaNet-L block 4 tile kernel: bad operands");
     }
     // attentive statistics pooling (:384-500): the x third of the attention conv is a GEMM on X4, the second conv's logits never leave LDS
-    const int M = St * SPK_T;
-    if (launch_spk_fc(d->st_ms, 2 * SPK_C, d->a1ms_w, d->a1_b, d->att_c, d->fc_part, St, 2 * SPK_C, SPK_ATT, 0, d->st)) return failf("TitaNet-L attention constant: bad operands");
-    spk_gemm(d, d->sX4, SPK_C, d->a1x_w, M, SPK_ATT, SPK_C, d->zero_bias, false, d->att_g);
-    launch_spk_att_post(d->att_g, d->att_c, d->a_bn_s, d->a_bn_b, d->A, 1, SPK_ATT, St, d->st);
-    SpkGemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.A = (const bf16_t *)d->A; g.lda = SPK_ATT; g.W = (const bf16_t *)d->a2_w; g.N = SPK_C; g.K = SPK_ATT; g.bias = d->a2_b;
-    g.mode = SG_ASP; g.x_in = d->sX4; g.bn_s = d->e_bn_s; g.bn_b = d->e_bn_b; g.pool = d->pool;
-    return gemm(g);
+    if (launch_spk_fc(w.st_ms, 2 * SPK_C, d->a1ms_w, d->a1_b, w.att_c, w.fc_part, St, 2 * SPK_C, SPK_ATT, 0, d->st)) return failf("TitaNet-L attention constant: bad operands");
+    spk_gemm(d, w.sX4, SPK_C, d->a1x_w, St * SPK_T, SPK_ATT, SPK_C, d->zero_bias, false, w.att_g);
+    launch_spk_att_post(w.att_g, w.att_c, d->a_bn_s, d->a_bn_b, w.A16, 1, SPK_ATT, St, d->st);
+    SpkGemmParams g = sub_gemm(d->att2, w.A16, SPK_ATT);
+    g.mode = SG_ASP; g.x_in = w.sX4; g.bn_s = d->e_bn_s; g.bn_b = d->e_bn_b; g.pool = w.pool;
+    if (gemm(g)) return -1;
+    if (launch_spk_fc(w.pool, 2 * SPK_C, d->emb_w, d->emb_b, w.emb, w.fc_part, St, 2 * SPK_C, SPK_EMB, 0, d->st))      // [S][6144] x [192][6144]^T, always f32
+        return failf("TitaNet-L embedding layer: bad operands");
+    return 0;
 }
 
-// spk_session_run_chunk (src/diarize_spk.cpp:601-626) for S sub-segments in one launch sequence
+// The f32 engine's network layer by layer (kernels_diar.hip; kept for exact parity): every activation in memory as f32, the pointwise convs
+// as f32 GEMMs over all rows.  s_mel (per-feature normalised, :578) / s_lens are set; leaves the embeddings in set.emb
+static int spk_embed_layers_f32(nasr_diar *d, int St) {
+    SpkSet &w = d->set;
+    const int M = St * SPK_T;
+    const float *x = w.s_mel;
+    int x_pitch = 96;
+    float *outs[2] = {w.X0, w.X1};
+    int flip = 0;
+    for (int b = 0; b < 5; b++) {                                   // JasperBlock (:351-383)
+        nasr_diar::SpkBlock &blk = d->spk[b];
+        const float *cur = x;
+        int cur_pitch = x_pitch;
+        for (int r = 0; r < blk.repeat; r++) {
+            nasr_diar::SpkSub &ss = blk.sub[r];
+            launch_spk_depthwise(cur, cur_pitch, ss.dw, ss.kernel, ss.cin, ss.cin_pad, w.s_lens, w.A32, St, d->st);
+            spk_gemm(d, w.A32, ss.cin_pad, ss.pw, M, ss.cout, ss.cin_pad, ss.bias, r + 1 < blk.repeat, w.Y);   // ReLU between sub-convs
+            cur = w.Y;
+            cur_pitch = ss.cout;
+        }
+        {   // SE gate before the residual (:303-315, :365-368): masked mean over time, two f32 GEMMs over the segments
+            float *mean = w.se_z + (size_t)d->max_segments * SPK_C, *hid = w.se_h;
+            launch_spk_colmean(w.Y, blk.cout, w.s_lens, mean, St, d->st);
+            launch_encproj(mean, blk.fc1, d->zero_bias, hid, St, blk.cout, blk.cout / 8, d->st);
+            launch_relu(hid, (int64_t)St * (blk.cout / 8), d->st);
+            launch_encproj(hid, blk.fc2, d->zero_bias, w.se_z, St, blk.cout / 8, blk.cout, d->st);
+        }
+        const float *res = nullptr;
+        if (blk.residual) {
+            launch_spk_mask_cvt(x, blk.cin, w.s_lens, w.A32, St, d->st);
+            spk_gemm(d, w.A32, blk.cin, blk.res.pw, M, blk.cout, blk.cin, blk.res.bias, false, w.R);
+            res = w.R;
+        }
+        float *out = outs[flip];
+        flip ^= 1;
+        launch_spk_combine(w.Y, w.se_z, res, blk.cout, w.s_lens, out, St, d->st);
+        x = out;
+        x_pitch = blk.cout;
+    }
+    // attentive statistics pooling + embedding (:384-500)
+    launch_spk_stats(x, SPK_C, w.s_lens, w.st_mean, w.st_std, St, d->st);
+    launch_spk_att_const(w.st_mean, w.st_std, d->a1_w, d->a1_b, w.att_c, SPK_C, SPK_ATT, St, d->st);
+    launch_spk_mask_cvt(x, SPK_C, w.s_lens, w.A32, St, d->st);
+    spk_gemm(d, w.A32, SPK_C, d->a1x_w, M, SPK_ATT, SPK_C, d->zero_bias, false, w.att_g);
+    launch_spk_att_post(w.att_g, w.att_c, d->a_bn_s, d->a_bn_b, w.A32, 0, SPK_ATT, St, d->st);
+    spk_gemm(d, w.A32, SPK_ATT, d->att2.pw, M, SPK_C, SPK_ATT, d->att2.bias, false, w.Y);            // attention logits
+    launch_spk_asp(x, w.Y, SPK_C, w.s_lens, d->e_bn_s, d->e_bn_b, w.pool, St, d->st);
+    launch_encproj(w.pool, d->emb_w, d->emb_b, w.emb, St, 2 * SPK_C, SPK_EMB, d->st);      // [S][6144] x [192][6144]^T, always f32
+    return 0;
+}
+
+// enqueue() as one hipGraph per key = (segments in the call, sample type): captured and instantiated at first use, replayed from then on.
+// The pointers inside are the engine's own persistent buffers, except the staged audio: when that buffer moves, every graph is stale
+template <class Enqueue>
+static int spk_graph_run(nasr_diar *d, std::pair<int, uint32_t> key, Enqueue &&enqueue) {
+    if (d->spk_graph_audio != (const void *)d->audio) {
+        for (auto &kv : d->spk_graphs) hipGraphExecDestroy(kv.second);
+        d->spk_graphs.clear();
+        d->spk_graph_audio = d->audio;
+    }
+    auto it = d->spk_graphs.find(key);
+    if (it == d->spk_graphs.end()) {
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        const char *what = "hipStreamBeginCapture";
+        int rc = 0;
+        nasr_eng::api_capture_begin();
+        hipError_t e = hipStreamBeginCapture(d->st, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) { rc = enqueue(); what = "hipStreamEndCapture"; e = hipStreamEndCapture(d->st, &graph); }
+        nasr_eng::api_capture_end();
+        if (!rc && e == hipSuccess) { what = "hipGraphInstantiate"; e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); }
+        if (graph) hipGraphDestroy(graph);
+        if (rc) return -1;                                          // enqueue() has said what was wrong
+        if (e != hipSuccess) return failf("TitaNet-L graph: %s failed: %s", what, hipGetErrorString(e));
+        it = d->spk_graphs.emplace(key, exec).first;
+    }
+    DCHK(hipGraphLaunch(it->second, d->st));
+    return 0;
+}
+
+// the St segments of a tile on the device: staged audio, sample offsets and valid frames; mp = the front end's parameters for them
+static int spk_stage_segments(nasr_diar *d, int St, const float *const *audio, const int32_t *lens_samples, int s0, uint32_t flags, DiarMelParams &mp) {
+    std::vector<int32_t> n(St, SPK_SEGMENT);
+    std::vector<long long> base;
+    for (int s = 0; s < St; s++) if (!audio[s]) return failf("segment %d: null audio", s0 + s);
+    if (stage_audio(d, audio, n.data(), St, flags, base)) return -1;
+    long long *h_off = (long long *)d->pin;
+    int *h_len = (int *)(d->pin + (size_t)d->max_segments * sizeof(long long));
+    for (int s = 0; s < St; s++) {
+        h_off[s] = base[s];
+        const int lm = lens_samples[s] / HOP;                         // :613-615, :548
+        h_len[s] = lm > SPK_TVALID ? SPK_TVALID : (lm < 1 ? 1 : lm);
+    }
+    DCHK(hipMemcpyAsync(d->set.s_off, h_off, (size_t)St * sizeof(long long), hipMemcpyHostToDevice, d->st));
+    DCHK(hipMemcpyAsync(d->set.s_lens, h_len, (size_t)St * sizeof(int), hipMemcpyHostToDevice, d->st));
+    memset(&mp, 0, sizeof(mp));
+    set_audio(d, flags, mp);
+    mp.win_off = d->set.s_off; mp.n_win = SPK_SEGMENT; mp.T_pad = SPK_T; mp.t_valid = SPK_TVALID;
+    mp.cpitch = 96; mp.mel = d->set.s_mel; mp.window = d->window; mp.fbT = d->spk_fbT; mp.fb_band = d->spk_band;
+    mp.cos_t = d->cos_t; mp.sin_t = d->sin_t;
+    return 0;
+}
+
+// spk_session_run_chunk (src/diarize_spk.cpp:601-626) for S sub-segments, max_segments at a time in one launch sequence
 extern "C" int nasr_diar_embed(nasr_diar *d, int S, const float *const *audio, const int32_t *lens_samples, float *emb_out, uint32_t flags) {
     Guard g;
     if (!d || !audio || !lens_samples || !emb_out || S < 1) return failf("null argument or S < 1");
     if (!d->has_spk) return failf("this diarization engine was created without 'spk.*' tensors");
     DCHK(hipSetDevice(d->device));
     for (int s0 = 0; s0 < S; s0 += d->max_segments) {
-        const int St = std::min(d->max_segments, S - s0), M = St * SPK_T;
-        std::vector<int32_t> n(St, SPK_SEGMENT);
-        std::vector<long long> base;
-        for (int s = 0; s < St; s++) if (!audio[s0 + s]) return failf("segment %d: null audio", s0 + s);
-        if (stage_audio(d, audio + s0, n.data(), St, flags, base)) return -1;
-        long long *h_off = (long long *)d->pin;
-        int *h_len = (int *)(d->pin + (size_t)d->max_segments * sizeof(long long));
-        for (int s = 0; s < St; s++) {
-            h_off[s] = base[s];
-            int lm = lens_samples[s0 + s] / HOP;                        // :613-615, :548
-            h_len[s] = lm > SPK_TVALID ? SPK_TVALID : (lm < 1 ? 1 : lm);
-        }
-        DCHK(hipMemcpyAsync(d->s_off, h_off, (size_t)St * sizeof(long long), hipMemcpyHostToDevice, d->st));
-        DCHK(hipMemcpyAsync(d->s_lens, h_len, (size_t)St * sizeof(int), hipMemcpyHostToDevice, d->st));
+        const int St = std::min(d->max_segments, S - s0);
         DiarMelParams mp;
-        memset(&mp, 0, sizeof(mp));
-        set_audio(d, flags, mp);
-        mp.win_off = d->s_off; mp.n_win = SPK_SEGMENT; mp.T_pad = SPK_T; mp.t_valid = SPK_TVALID;
-        mp.cpitch = 96; mp.mel = d->s_mel; mp.window = d->window; mp.fbT = d->spk_fbT; mp.fb_band = d->spk_band;
-        mp.cos_t = d->cos_t; mp.sin_t = d->sin_t;
+        if (spk_stage_segments(d, St, audio + s0, lens_samples + s0, s0, flags, mp)) return -1;
+        // front end + network: the f32 engine normalises per feature here (:578), for the bf16 engine that is the first step of k_spk_front
+        auto enqueue = [&]() -> int {
+            launch_diar_logmel(mp, St, !d->bf16, d->st);
+            return d->bf16 ? spk_embed_segment_tiles(d, St) : spk_embed_layers_f32(d, St);
+        };
         DCHK(hipEventRecord(d->ev[1][0], d->st));
-        if (d->bf16) {
-            // front end + encoder + pooling + embedding layer: eager, or one graph per (St, sample type) replayed
-            auto enqueue = [&]() -> int {
-                launch_diar_logmel(mp, St, false, d->st);               // the per-feature normalisation (:578) is the first step of k_spk_front
-                if (spk_embed_segment_tiles(d, St)) return -1;
-                if (launch_spk_fc(d->pool, 2 * SPK_C, d->emb_w, d->emb_b, d->emb, d->fc_part, St, 2 * SPK_C, SPK_EMB, 0, d->st))      // [S][6144] x [192][6144]^T, always f32
-                    return failf("TitaNet-L embedding layer: bad operands");
-                return 0;
-            };
-            if (!d->spk_use_graph) {
-                if (enqueue()) return -1;
-            } else {
-                if (d->spk_graph_audio != (const void *)d->audio) {     // the staging buffer was reallocated: every captured pointer to it is stale
-                    for (auto &kv : d->spk_graphs) hipGraphExecDestroy(kv.second);
-                    d->spk_graphs.clear();
-                    d->spk_graph_audio = d->audio;
-                }
-                const std::pair<int, uint32_t> key(St, flags & NASR_FLAG_AUDIO_S16);
-                auto it = d->spk_graphs.find(key);
-                if (it == d->spk_graphs.end()) {
-                    hipGraph_t graph = nullptr;
-                    hipGraphExec_t exec = nullptr;
-                    nasr_eng::api_capture_begin();
-                    hipError_t be = hipStreamBeginCapture(d->st, hipStreamCaptureModeThreadLocal);
-                    int rc = be == hipSuccess ? enqueue() : -1;
-                    hipError_t ce = be == hipSuccess ? hipStreamEndCapture(d->st, &graph) : be;
-                    nasr_eng::api_capture_end();
-                    if (rc || ce != hipSuccess) { if (graph) hipGraphDestroy(graph); return rc ? -1 : failf("TitaNet-L graph capture failed: %s", hipGetErrorString(ce)); }
-                    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                    hipGraphDestroy(graph);
-                    if (ie != hipSuccess) return failf("hipGraphInstantiate (TitaNet-L) failed: %s", hipGetErrorString(ie));
-                    it = d->spk_graphs.emplace(key, exec).first;
-                }
-                DCHK(hipGraphLaunch(it->second, d->st));
-            }
-        } else {
-        launch_diar_logmel(mp, St, true, d->st);                        // per-feature normalisation on (:578)
-        const float *x = d->s_mel;
-        int x_pitch = 96;
-        float *outs[2] = {d->X0, d->X1};
-        int flip = 0;
-        for (int b = 0; b < 5; b++) {                                   // JasperBlock (:351-383)
-            nasr_diar::SpkBlock &blk = d->spk[b];
-            const float *cur = x;
-            int cur_pitch = x_pitch;
-            for (int r = 0; r < blk.repeat; r++) {
-                nasr_diar::SpkSub &ss = blk.sub[r];
-                launch_spk_depthwise(cur, cur_pitch, ss.dw, ss.kernel, ss.cin, ss.cin_pad, d->s_lens, d->A, d->bf16, St, d->st);
-                spk_gemm(d, d->A, ss.cin_pad, ss.pw, M, ss.cout, ss.cin_pad, ss.bias, r + 1 < blk.repeat, d->Y);   // ReLU between sub-convs
-                cur = d->Y;
-                cur_pitch = ss.cout;
-            }
-            {   // SE gate before the residual (:303-315, :365-368): masked mean over time, two f32 GEMMs over the segments
-                float *mean = d->se_z + (size_t)d->max_segments * SPK_C, *hid = d->se_h;
-                launch_spk_colmean(d->Y, blk.cout, d->s_lens, mean, St, d->st);
-                launch_encproj(mean, blk.fc1, d->zero_bias, hid, St, blk.cout, blk.cout / 8, d->st);
-                launch_relu(hid, (int64_t)St * (blk.cout / 8), d->st);
-                launch_encproj(hid, blk.fc2, d->zero_bias, d->se_z, St, blk.cout / 8, blk.cout, d->st);
-            }
-            const float *res = nullptr;
-            if (blk.residual) {
-                launch_spk_mask_cvt(x, blk.cin, d->s_lens, d->A, d->bf16, St, d->st);
-                spk_gemm(d, d->A, blk.cin, blk.res.pw, M, blk.cout, blk.cin, blk.res.bias, false, d->R);
-                res = d->R;
-            }
-            float *out = outs[flip];
-            flip ^= 1;
-            launch_spk_combine(d->Y, d->se_z, res, blk.cout, d->s_lens, out, St, d->st);
-            x = out;
-            x_pitch = blk.cout;
-        }
-        // attentive statistics pooling + embedding (:384-500)
-        launch_spk_stats(x, SPK_C, d->s_lens, d->st_mean, d->st_std, St, d->st);
-        launch_spk_att_const(d->st_mean, d->st_std, d->a1_w, d->a1_b, d->att_c, SPK_C, SPK_ATT, St, d->st);
-        launch_spk_mask_cvt(x, SPK_C, d->s_lens, d->A, d->bf16, St, d->st);
-        spk_gemm(d, d->A, SPK_C, d->a1x_w, M, SPK_ATT, SPK_C, d->zero_bias, false, d->att_g);
-        launch_spk_att_post(d->att_g, d->att_c, d->a_bn_s, d->a_bn_b, d->A, d->bf16, SPK_ATT, St, d->st);
-        spk_gemm(d, d->A, SPK_ATT, d->a2_w, M, SPK_C, SPK_ATT, d->a2_b, false, d->Y);                   // attention logits
-        launch_spk_asp(x, d->Y, SPK_C, d->s_lens, d->e_bn_s, d->e_bn_b, d->pool, St, d->st);
-        launch_encproj(d->pool, d->emb_w, d->emb_b, d->emb, St, 2 * SPK_C, SPK_EMB, d->st);      // [S][6144] x [192][6144]^T, always f32
-        }
-        float *h_emb = (float *)(d->pin + (size_t)d->max_segments * (sizeof(long long) + sizeof(int)));
+        // the bf16 engine replays its launches as one graph (NASR_DIAR_NO_GRAPH=1: eager, for A/B and debugging); the f32 engine is eager
+        if (d->bf16 && d->spk_use_graph ? spk_graph_run(d, {St, flags & NASR_FLAG_AUDIO_S16}, enqueue) : enqueue()) return -1;
         DCHK(hipEventRecord(d->ev[1][1], d->st));
-        DCHK(hipMemcpyAsync(h_emb, d->emb, (size_t)St * SPK_EMB * sizeof(float), hipMemcpyDeviceToHost, d->st));
+        float *h_emb = (float *)(d->pin + (size_t)d->max_segments * (sizeof(long long) + sizeof(int)));
+        DCHK(hipMemcpyAsync(h_emb, d->set.emb, (size_t)St * SPK_EMB * sizeof(float), hipMemcpyDeviceToHost, d->st));
         DCHK(hipStreamSynchronize(d->st));
         float tile_ms = 0.f;
         if (hipEventElapsedTime(&tile_ms, d->ev[1][0], d->ev[1][1]) != hipSuccess) tile_ms = 0.f;

@@ -468,9 +468,9 @@ int spk_fc_slices(int M, int K, int N);
 int launch_spk_fc(const float *x, int ldx, const float *wpk, const float *bias, float *out, float *part, int M, int K, int N, int relu, hipStream_t st);
 
 // TitaNet-L pieces (src/diarize_spk.cpp:320-515); activations [S * 160][C] f32, channels innermost
-void launch_spk_depthwise(const float *x, int x_pitch, const float *w, int kernel, int C, int Cpad, const int *lens, void *a_out,
-                          int out_bf16, int S, hipStream_t st);               // masked 'same' depthwise conv -> GEMM A operand
-void launch_spk_mask_cvt(const float *x, int C, const int *lens, void *a_out, int out_bf16, int S, hipStream_t st);
+void launch_spk_depthwise(const float *x, int x_pitch, const float *w, int kernel, int C, int Cpad, const int *lens, float *a_out,
+                          int S, hipStream_t st);                             // masked 'same' depthwise conv -> GEMM A operand (f32 engine)
+void launch_spk_mask_cvt(const float *x, int C, const int *lens, float *a_out, int S, hipStream_t st);
 void launch_spk_colmean(const float *y, int C, const int *lens, float *mean, int S, hipStream_t st);   // masked mean over time (SE)
 void launch_spk_combine(const float *y, const float *z, const float *r, int C, const int *lens, float *out, int S, hipStream_t st);
 void launch_spk_stats(const float *x, int C, const int *lens, float *mean, float *stdv, int S, hipStream_t st);
