@@ -724,9 +724,11 @@ int nasr_engine_history_align(nasr_engine *e, nasr_stream *const *streams, int B
 /* ---- diarization side-car (BASELINE config 5): MarbleNet VAD + TitaNet-L speaker embeddings ----------------------
  * Replaces the compute of vad_session / spk_session (src/diarize_vad.h:95-135, src/diarize_spk.h:95-120).  weights =
  * the tensors of diarize.gguf ("vad.*" and/or "spk.*", F32, layouts of scripts/convert_diarize_to_gguf.py:129-158),
- * same descriptor type as nasr_engine_create.  The onset/offset state machine, sub-segment cursor, NME-SC clustering and
- * RTTM output of src/diarize_pipeline.cpp / src/diarize_cluster.cpp are host control flow ABOVE this ABI:
- * nemotron-asr.cpp_amd/host/diarize_pipeline_amd.h, diarize_cluster_amd.h. */
+ * same descriptor type as nasr_engine_create.  The onset/offset state machine, sub-segment cursor and RTTM output of
+ * src/diarize_pipeline.cpp are host control flow ABOVE this ABI (nemotron-asr.cpp_amd/host/diarize_pipeline_amd.h).  The
+ * NME-SC clustering of src/diarize_cluster.cpp exists twice: on the host (host/diarize_cluster_amd.h, the default of the
+ * pipeline) and on the device behind nasr_diar_cluster below -- its affinity, neighbour graphs and eigen-solver as kernels,
+ * its decisions and k-means the host path's own code. */
 typedef struct nasr_diar nasr_diar;
 /* dtype: NASR_DTYPE_BF16 = TitaNet's pointwise convolutions on the bf16 MFMA (f32 accumulate), NASR_DTYPE_F32 = all f32;
  * MarbleNet is f32 (P(speech) within 2e-5 of the reference arithmetic) unless NASR_DIAR_VAD_BF16 is OR'ed in: then its pointwise
@@ -755,8 +757,43 @@ int  nasr_diar_embed(nasr_diar *d, int S, const float *const *audio, const int32
 
 /* measurement: device time (ms) of the LAST nasr_diar_vad (which = 0) / nasr_diar_embed (which = 1) call's launch sequence, from HIP events on the
  * side-car's own stream around its kernels (staging copies and the read-back excluded) -- what bench.py prices configs[4]'s roofline with.  The
- * reference has no counterpart (it times whole sessions on the host, src/diarize_pipeline.cpp). */
+ * reference has no counterpart (it times whole sessions on the host, src/diarize_pipeline.cpp).  which = 2: the last nasr_diar_cluster* /
+ * nasr_diar_sym_eigen call, the sum of its stages; which = 3 .. 7: its affinity, graph + Laplacian, tridiagonalisation, eigenvalue and
+ * eigenvector stages. */
 int  nasr_diar_last_gpu_ms(nasr_diar *d, int which, float *ms_out);
+
+/* ---- NME-SC speaker clustering on the device ------------------------------------------------------------------------
+ * nmesc_cfg (src/diarize_cluster.h:14-24) field for field, same defaults when `params` is null */
+typedef struct nasr_cluster_params {
+    int32_t  max_num_speakers;       /* 8; at most 63 here */
+    float    max_rp_threshold;       /* 0.25 */
+    int32_t  sparse_search_volume;   /* 30 */
+    int32_t  nme_mat_size;           /* 512 */
+    int32_t  min_samples_for_nmesc;  /* 6 */
+    int32_t  oracle_num_speakers;    /* -1: estimate */
+    float    fixed_thres;            /* -1; > 0: skip the NME analysis */
+    int32_t  kmeans_random_trials;   /* 1 */
+    uint64_t kmeans_seed;            /* 0 */
+} nasr_cluster_params;
+#define NASR_CLUSTER_MAX_N 8192
+/* nmesc_cluster (src/diarize_cluster.cpp:321-400) of N embeddings [N][D] (host memory): labels [N], the number of speakers, the p of
+ * the neighbour graph.  Same candidate p values, tie rule, Laplacian, gap ratio, subsampling above nme_mat_size, connectivity
+ * fallback and k-means as the host path; the eigen-pairs come from another solver, so the two agree in their decisions and in
+ * the partition, not bit for bit in the spectral embedding.  N <= min_samples_for_nmesc: the host's early return; N above
+ * NASR_CLUSTER_MAX_N: an error (the host path has no cap).  flags: 0. */
+int  nasr_diar_cluster(nasr_diar *d, const float *emb, int N, int D, const nasr_cluster_params *params, int32_t *labels,
+                       int32_t *est_num_speakers, int32_t *p_hat, uint32_t flags);
+/* its stages alone (tests, tools).  nmesc_cosine_affinity (src/diarize_cluster.cpp:40-74): out [N][N], symmetric, in [0, 1] */
+int  nasr_diar_cluster_affinity(nasr_diar *d, const float *emb, int N, int D, float *out);
+/* the p-nearest-neighbour graph of src/diarize_cluster.cpp:76-103: the p largest entries of every row of aff [N][N] (ties: lower
+ * index first), binarised, 0.5 (K + K^T) -> graph_out [N][N] */
+int  nasr_diar_cluster_graph(nasr_diar *d, const float *aff, int N, int p, float *graph_out);
+/* in place of Eigen's SelfAdjointEigenSolver (src/diarize_cluster.cpp:116-148): of each of `batch` symmetric matrices a [batch][n][n] the
+ * k_low <= min(n, 64) smallest eigenvalues (ascending, values_low [batch][k_low]) and the largest (value_max [batch]); vectors (or
+ * null): the orthonormal eigenvectors of matrix 0's k_low smallest, [n][k_low], column k with eigenvalue k.  n <= NASR_CLUSTER_MAX_N,
+ * and batch > 1 only while the matrices hold at most 512 MiB */
+int  nasr_diar_sym_eigen(nasr_diar *d, const double *a, int n, int batch, int k_low, double *values_low, double *value_max,
+                         double *vectors);
 
 /* parity tap: diarize_compute_logmel (src/diarize_audio.cpp:136-227) of one whole host buffer on the device front end,
  * which = 0: the 'vad.*' filterbank, 1: 'spk.*'.  mel_out = [80][t_padded] row-major like the reference's output

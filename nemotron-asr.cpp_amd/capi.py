@@ -36,6 +36,7 @@ EXPORTS = [
     "nasr_engine_profile_read", "nasr_engine_hip_stream", "nasr_engine_lend_stream", "nasr_device_alloc", "nasr_device_free",
     "nasr_device_upload", "nasr_engine_synchronize", "nasr_engine_get_counter", "nasr_stream_debug_fill_kv",
     "nasr_diar_create", "nasr_diar_destroy", "nasr_diar_set_stream", "nasr_diar_vad", "nasr_diar_embed", "nasr_diar_logmel", "nasr_diar_last_gpu_ms",
+    "nasr_diar_cluster", "nasr_diar_cluster_affinity", "nasr_diar_cluster_graph", "nasr_diar_sym_eigen",
     "nasr_engine_transcribe_mel", "nasr_engine_transcribe", "nasr_engine_offline_tap",
     "nasr_stream_get_token_logprobs", "nasr_engine_offline_token_logprobs",
     "nasr_engine_set_boost_phrases", "nasr_stream_set_boost",
@@ -69,6 +70,17 @@ class HParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_mels", "d_model", "n_heads", "d_head", "d_ff", "n_layers", "vocab_size", "decoder_dim",
         "joint_dim", "subsampling_factor", "att_left_context", "kernel_size", "num_prompts")]
+
+
+class ClusterParams(C.Structure):
+    """nasr_cluster_params = nmesc_cfg field for field (host/diarize_cluster_amd.h)"""
+    _fields_ = [("max_num_speakers", C.c_int32), ("max_rp_threshold", C.c_float), ("sparse_search_volume", C.c_int32),
+                ("nme_mat_size", C.c_int32), ("min_samples_for_nmesc", C.c_int32), ("oracle_num_speakers", C.c_int32),
+                ("fixed_thres", C.c_float), ("kmeans_random_trials", C.c_int32), ("kmeans_seed", C.c_uint64)]
+
+
+CLUSTER_MAX_N = 8192
+CLUSTER_STAGES = ("affinity", "graph", "tridiag", "values", "vectors")
 
 
 class BeamParams(C.Structure):
@@ -141,6 +153,11 @@ def lib():
         L.nasr_diar_embed.argtypes = [vp, C.c_int, C.POINTER(vp), ip, C.POINTER(C.c_float), C.c_uint32]
         L.nasr_diar_last_gpu_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
         L.nasr_diar_logmel.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int, C.POINTER(C.c_float), C.c_int64, ip]
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        L.nasr_diar_cluster.argtypes = [vp, fp, C.c_int, C.c_int, C.POINTER(ClusterParams), ip, ip, ip, C.c_uint32]
+        L.nasr_diar_cluster_affinity.argtypes = [vp, fp, C.c_int, C.c_int, fp]
+        L.nasr_diar_cluster_graph.argtypes = [vp, fp, C.c_int, C.c_int, fp]
+        L.nasr_diar_sym_eigen.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp, dp, dp]
         L.nasr_stream_get_token_frames.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
         L.nasr_engine_step.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
         L.nasr_engine_step_mel.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), ip, C.POINTER(vp), ip, ip, C.c_uint32]
@@ -482,10 +499,53 @@ class Diar:
         return out
 
     def last_gpu_ms(self, which: str) -> float:
-        """device time of the last vad() / embed() call's launch sequence (HIP events on the side-car's stream)"""
+        """device time of the last vad() / embed() / cluster() call's launch sequence (HIP events on the side-car's stream);
+        "cluster:<stage>" with a stage of CLUSTER_STAGES: that stage of the last cluster call"""
         ms = C.c_float(0.0)
-        _chk(lib().nasr_diar_last_gpu_ms(self.h, 0 if which == "vad" else 1, C.byref(ms)))
+        idx = 3 + CLUSTER_STAGES.index(which[8:]) if which.startswith("cluster:") else {"vad": 0, "cluster": 2}.get(which, 1)
+        _chk(lib().nasr_diar_last_gpu_ms(self.h, idx, C.byref(ms)))
         return float(ms.value)
+
+    def cluster(self, emb: np.ndarray, max_num_speakers=8, max_rp_threshold=0.25, sparse_search_volume=30, nme_mat_size=512,
+                min_samples_for_nmesc=6, oracle_num_speakers=-1, fixed_thres=-1.0, kmeans_random_trials=1, kmeans_seed=0):
+        """NME-SC on the device (cluster.nmesc_cluster is the host path) -> (labels [N] int32, est_num_speakers, p_hat)"""
+        e = np.ascontiguousarray(emb, np.float32)
+        prm = ClusterParams(max_num_speakers, max_rp_threshold, sparse_search_volume, nme_mat_size, min_samples_for_nmesc,
+                            oracle_num_speakers, fixed_thres, kmeans_random_trials, kmeans_seed)
+        labels = np.zeros(e.shape[0], np.int32)
+        est, p_hat = C.c_int32(0), C.c_int32(0)
+        _chk(lib().nasr_diar_cluster(self.h, e.ctypes.data_as(C.POINTER(C.c_float)), e.shape[0], e.shape[1], C.byref(prm),
+                                     labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(est), C.byref(p_hat), 0))
+        return labels, est.value, p_hat.value
+
+    def cluster_affinity(self, emb: np.ndarray) -> np.ndarray:
+        """cosine affinity, min-max scaled (cluster.cosine_affinity on the device) -> [N][N] float32"""
+        e = np.ascontiguousarray(emb, np.float32)
+        out = np.zeros((e.shape[0], e.shape[0]), np.float32)
+        fp = C.POINTER(C.c_float)
+        _chk(lib().nasr_diar_cluster_affinity(self.h, e.ctypes.data_as(fp), e.shape[0], e.shape[1], out.ctypes.data_as(fp)))
+        return out
+
+    def cluster_graph(self, aff: np.ndarray, p: int) -> np.ndarray:
+        """0.5 (K + K^T), K = the p largest entries of every row (ties: lower index first), binarised -> [N][N] float32"""
+        a = np.ascontiguousarray(aff, np.float32)
+        out = np.zeros_like(a)
+        fp = C.POINTER(C.c_float)
+        _chk(lib().nasr_diar_cluster_graph(self.h, a.ctypes.data_as(fp), a.shape[0], p, out.ctypes.data_as(fp)))
+        return out
+
+    def sym_eigen(self, a: np.ndarray, k_low: int, vectors=True):
+        """a: [batch][n][n] (or [n][n]) symmetric float64 -> (values_low [batch][k_low], value_max [batch], the eigenvectors
+        [n][k_low] of matrix 0's k_low smallest eigenvalues or None)"""
+        m = np.ascontiguousarray(a, np.float64)
+        m = m[None] if m.ndim == 2 else m
+        batch, n = m.shape[0], m.shape[1]
+        low, top = np.zeros((batch, k_low)), np.zeros(batch)
+        vec = np.zeros((n, k_low)) if vectors else None
+        dp = C.POINTER(C.c_double)
+        _chk(lib().nasr_diar_sym_eigen(self.h, m.ctypes.data_as(dp), n, batch, k_low, low.ctypes.data_as(dp), top.ctypes.data_as(dp),
+                                       vec.ctypes.data_as(dp) if vectors else None))
+        return low, top, vec
 
     def logmel(self, audio: np.ndarray, which: str = "vad", normalize: bool = False):
         """parity tap: diarize_compute_logmel of one buffer on the device front end -> ([80][t_padded], t_valid)"""

@@ -6,7 +6,9 @@
 // sub-segment cursor, clustering, RTTM) is out of scope.
 #include "nasr_internal.h"
 #include "nasr_diar_set.h"
+#include "nasr_diar_cluster.h"
 #include "nemotron_asr_amd.h"
+#include "../host/diarize_cluster_amd.h"
 
 #include <algorithm>
 #include <cmath>
@@ -93,6 +95,7 @@ struct nasr_diar {
     float *prob = nullptr; size_t prob_cap = 0;
     char *pin = nullptr; size_t pin_cap = 0;             // pinned staging for descriptors / results
     GatherDesc *gather_dev = nullptr, *gather_pin = nullptr; size_t gather_cap = 0, gather_pin_cap = 0;   // device-resident inputs: (source, destination, bytes) per buffer
+    ClusterState cluster;            // NME-SC on the device (nasr_diar_cluster.hip): scratch from its first call on
 };
 
 namespace {
@@ -345,6 +348,7 @@ static void diar_destroy_impl(nasr_diar *d) {
     if (d->st) hipStreamSynchronize(d->st);
     for (auto &kv : d->spk_graphs) hipGraphExecDestroy(kv.second);
     for (auto &pair : d->ev) for (auto &e : pair) if (e) hipEventDestroy(e);
+    cluster_free(d->cluster);
     for (void *p : d->allocs) hipFree(p);
     for (auto &g : d->grown)
         if (*g.slot) g.pinned ? hipHostFree(*g.slot) : hipFree(*g.slot);
@@ -506,9 +510,57 @@ extern "C" int nasr_diar_vad(nasr_diar *d, int B, const float *const *audio, con
 
 // device time of the last call's launch sequence (HIP events on the side-car's stream around its kernels; staging copies and the read-back excluded)
 extern "C" int nasr_diar_last_gpu_ms(nasr_diar *d, int which, float *ms_out) {
-    if (!d || !ms_out || (which != 0 && which != 1)) return failf("nasr_diar_last_gpu_ms: which = 0 (VAD) or 1 (embeddings)");
-    *ms_out = d->last_ms[which];
+    if (!d || !ms_out || which < 0 || which > 2 + CL_STAGES) return failf("nasr_diar_last_gpu_ms: which = 0 (VAD), 1 (embeddings), 2 (clustering) or 3 .. %d (its stages)", 2 + CL_STAGES);
+    if (which < 2) { *ms_out = d->last_ms[which]; return 0; }
+    *ms_out = 0.f;                   // clustering: the sum of its stages, or stage which - 3 (affinity, graphs, tridiagonalisation, eigenvalues, eigenvectors)
+    for (int s = 0; s < CL_STAGES; s++) if (which == 2 || which == 3 + s) *ms_out += d->cluster.ms[s];
     return 0;
+}
+
+// ---- NME-SC clustering on the device (nasr_diar_cluster.hip) ----------------------------------------------------------------------
+// nmesc_cluster (host/diarize_cluster_amd.cpp, the reference's src/diarize_cluster.cpp:321-400) with the affinity, the neighbour graphs
+// and the eigen-solver on the side-car's stream; params = null: nmesc_cfg's defaults
+extern "C" int nasr_diar_cluster(nasr_diar *d, const float *emb, int N, int D, const nasr_cluster_params *params, int32_t *labels,
+                                 int32_t *est_num_speakers, int32_t *p_hat, uint32_t flags) {
+    Guard g;
+    if (!d || !emb || !labels) return failf("nasr_diar_cluster: null argument");
+    if (flags) return failf("nasr_diar_cluster: flags must be 0");
+    DCHK(hipSetDevice(d->device));
+    nmesc_cfg cfg;
+    if (params) {
+        cfg.max_num_speakers = params->max_num_speakers; cfg.max_rp_threshold = params->max_rp_threshold;
+        cfg.sparse_search_volume = params->sparse_search_volume; cfg.nme_mat_size = params->nme_mat_size;
+        cfg.min_samples_for_nmesc = params->min_samples_for_nmesc; cfg.oracle_num_speakers = params->oracle_num_speakers;
+        cfg.fixed_thres = params->fixed_thres; cfg.kmeans_random_trials = params->kmeans_random_trials; cfg.kmeans_seed = params->kmeans_seed;
+    }
+    nmesc_result res;
+    if (cluster_run(d->cluster, d->st, emb, N, D, cfg, res)) return -1;
+    for (int i = 0; i < N; i++) labels[i] = res.labels[i];
+    if (est_num_speakers) *est_num_speakers = res.est_num_speakers;
+    if (p_hat) *p_hat = res.p_hat;
+    return 0;
+}
+// nmesc_cosine_affinity (src/diarize_cluster.cpp:40-74): out [N][N]
+extern "C" int nasr_diar_cluster_affinity(nasr_diar *d, const float *emb, int N, int D, float *out) {
+    Guard g;
+    if (!d) return failf("nasr_diar_cluster_affinity: null engine");
+    DCHK(hipSetDevice(d->device));
+    return cluster_affinity(d->cluster, d->st, emb, N, D, out);
+}
+// the p-nearest-neighbour graph 0.5 (K + K^T) of an affinity matrix (src/diarize_cluster.cpp:76-103): graph_out [N][N]
+extern "C" int nasr_diar_cluster_graph(nasr_diar *d, const float *aff, int N, int p, float *graph_out) {
+    Guard g;
+    if (!d) return failf("nasr_diar_cluster_graph: null engine");
+    DCHK(hipSetDevice(d->device));
+    return cluster_graph(d->cluster, d->st, aff, N, p, graph_out);
+}
+// the symmetric eigen-solver (the reference links Eigen's SelfAdjointEigenSolver, src/diarize_cluster.cpp:116-148), batched and partial
+extern "C" int nasr_diar_sym_eigen(nasr_diar *d, const double *a, int n, int batch, int k_low, double *values_low, double *value_max,
+                                   double *vectors) {
+    Guard g;
+    if (!d) return failf("nasr_diar_sym_eigen: null engine");
+    DCHK(hipSetDevice(d->device));
+    return cluster_sym_eigen(d->cluster, d->st, a, n, batch, k_low, values_low, value_max, vectors);
 }
 
 // parity tap: diarize_compute_logmel (src/diarize_audio.cpp:136-227) of ONE whole buffer on the device front end --

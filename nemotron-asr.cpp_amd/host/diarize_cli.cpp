@@ -1,6 +1,7 @@
 // diarize-amd -- VAD segments and speaker embeddings of a raw s16le 16 kHz file through diarize.gguf
 //   diarize-amd <diarize.gguf> <audio.pcm> [--f32] [--device N] [--onset P] [--offset P] [--sub-shift SEC]
-//               [--rttm <file> [--num-speakers K] [--push-ms MS]]   the whole pipeline: segments, sub-segments, NME-SC, RTTM
+//               [--rttm <file> [--num-speakers K] [--push-ms MS] [--cluster host|device]]   the whole pipeline: segments,
+//               sub-segments, NME-SC (on the host, the default, or on the GPU), RTTM
 // prints "SEGMENT start end" per speech segment and "EMBED start_sec e0 e1 e2 e3 ... (192 values)" per 1.5 s sub-segment
 #include <cstdio>
 #include <cstdlib>
@@ -22,7 +23,7 @@ int main(int argc, char **argv) {
     float sub_shift = 0.75f;
     std::string rttm;
     int num_speakers = -1, push_ms = 0;
-    bool have_onset = false, have_offset = false;
+    bool have_onset = false, have_offset = false, cluster_on_device = false;
     for (int i = 3; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--f32") dtype = 0;
@@ -32,6 +33,7 @@ int main(int argc, char **argv) {
         else if (a == "--rttm" && i + 1 < argc) rttm = argv[++i];
         else if (a == "--num-speakers" && i + 1 < argc) num_speakers = atoi(argv[++i]);
         else if (a == "--push-ms" && i + 1 < argc) push_ms = atoi(argv[++i]);
+        else if (a == "--cluster" && i + 1 < argc && (!strcmp(argv[i + 1], "host") || !strcmp(argv[i + 1], "device"))) cluster_on_device = !strcmp(argv[++i], "device");
         else if (a == "--sub-shift" && i + 1 < argc) sub_shift = (float)atof(argv[++i]);
         else { fprintf(stderr, "Unknown flag: %s\n", a.c_str()); return 1; }
     }
@@ -53,6 +55,7 @@ int main(int argc, char **argv) {
         pc.sub_shift_sec = sub_shift;
         pc.cluster.oracle_num_speakers = num_speakers;
         pc.cluster.min_samples_for_nmesc = 4;
+        pc.cluster_on_device = cluster_on_device;
         pc.rttm_path = rttm;
         diarize_pipeline *dp = diarize_pipeline_init_with_model(pc, m);
         if (!dp) { diarize_model_free(m); return 1; }

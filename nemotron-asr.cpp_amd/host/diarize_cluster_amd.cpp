@@ -3,17 +3,16 @@
 // eigen-gaps and the ratio g_p = (p / N) / (largest normalised gap) -> the p with the smallest ratio gives the number of
 // speakers and the graph for the spectral embedding -> k-means++.
 #include "diarize_cluster_amd.h"
+#include "diarize_cluster_shared.h"
 
 #include <algorithm>
 #include <cmath>
 #include <limits>
 #include <numeric>
 
-namespace {
+using namespace nmesc_shared;            // the constants, candidate p values, gap rule, connectivity check and k-means both paths share
 
-constexpr float  AFF_EPS = 3.5e-4f;      // src/diarize_cluster.cpp:31
-constexpr double EIG_EPS = 1e-10;        // :32
-constexpr int    MIN_P   = 2;            // :33
+namespace {
 
 // ---- symmetric eigen-solver ---------------------------------------------------------------------------------------
 // Householder reflections bring A to tridiagonal form T = Q^T A Q (Q accumulated as its transpose: row i of qt = column i
@@ -154,90 +153,16 @@ std::vector<double> laplacian(const std::vector<float> &g, int N) {
 }
 
 bool connected(const std::vector<float> &g, int N) {
-    if (N == 0) return true;
-    std::vector<char> seen(N, 0);
-    std::vector<int> stack(1, 0);
-    seen[0] = 1;
-    int reached = 1;
-    while (!stack.empty()) {
-        const int v = stack.back();
-        stack.pop_back();
+    return nmesc_shared::connected(N, [&](int v, auto &&visit) {
         for (int j = 0; j < N; j++)
-            if (!seen[j] && g[(size_t)v * N + j] > 0.0f) { seen[j] = 1; reached++; stack.push_back(j); }
-    }
-    return reached == N;
+            if (g[(size_t)v * N + j] > 0.0f) visit(j);
+    });
 }
 
-// candidate p values: `steps` points from 1 to max(2, floor(N * max_rp_threshold)), truncated to int, duplicates removed (:168-190)
-std::vector<int> candidate_p(int N, float max_rp_threshold, int sparse_search_volume) {
-    const int max_p = std::max(MIN_P, (int)std::floor((double)N * (double)max_rp_threshold));
-    const int steps = std::min(max_p, std::max(2, sparse_search_volume));
-    std::vector<int> out;
-    for (int i = 0; i < steps; i++) {
-        const int p = (int)(1.0 + (double)i * ((double)max_p - 1.0) / (double)std::max(1, steps - 1));
-        if (std::find(out.begin(), out.end(), p) == out.end()) out.push_back(p);
-    }
-    return out;
-}
-
-struct GapRatio { double g_p; int n_spk; };
 GapRatio gap_ratio(const std::vector<float> &aff, int N, int p, int max_num_speakers) {      // :199-214
     std::vector<double> L = laplacian(neighbour_graph(aff, N, p), N), lam;
     nmesc_sym_eigen(L, N, lam, nullptr);
-    const int K = std::min(N - 1, max_num_speakers);
-    int best = 0;
-    for (int i = 1; i < K; i++)
-        if (lam[i + 1] - lam[i] > lam[best + 1] - lam[best]) best = i;
-    const double gap = K > 0 ? (lam[best + 1] - lam[best]) / (lam[N - 1] + EIG_EPS) : 0.0;
-    return {((double)p / (double)N) / (gap + EIG_EPS), best + 1};
-}
-
-struct Rng {                              // splitmix64
-    uint64_t s;
-    uint64_t next() { uint64_t z = (s += 0x9E3779B97F4A7C15ull); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
-    double uniform() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); }
-};
-
-// k-means++ seeding, Lloyd iterations until the inertia moves by less than 1e-4 (:221-307)
-double kmeans(const std::vector<float> &X, int N, int D, int K, Rng &rng, std::vector<int> &labels) {
-    labels.assign(N, 0);
-    if (K <= 1) return 0.0;
-    auto dist2 = [&](const float *a, const float *b) { double s = 0.0; for (int d = 0; d < D; d++) { const double t = (double)a[d] - b[d]; s += t * t; } return s; };
-    std::vector<float> centre((size_t)K * D);
-    std::vector<double> near(N, std::numeric_limits<double>::infinity());
-    int pick = (int)(rng.next() % (uint64_t)N);
-    for (int k = 0; k < K; k++) {
-        std::copy_n(&X[(size_t)pick * D], D, &centre[(size_t)k * D]);
-        if (k + 1 == K) break;
-        double total = 0.0;
-        for (int i = 0; i < N; i++) { near[i] = std::min(near[i], dist2(&X[(size_t)i * D], &centre[(size_t)k * D])); total += near[i]; }
-        if (total <= 0.0) { pick = (int)(rng.next() % (uint64_t)N); continue; }
-        double target = rng.uniform() * total, cum = 0.0;
-        pick = N - 1;
-        for (int i = 0; i < N; i++) { cum += near[i]; if (cum >= target) { pick = i; break; } }
-    }
-    std::vector<double> sum((size_t)K * D);
-    std::vector<int> count(K);
-    double prev = std::numeric_limits<double>::infinity();
-    for (int it = 0; it < 300; it++) {
-        std::fill(sum.begin(), sum.end(), 0.0);
-        std::fill(count.begin(), count.end(), 0);
-        double inertia = 0.0;
-        for (int i = 0; i < N; i++) {
-            int best = 0;
-            double bd = std::numeric_limits<double>::infinity();
-            for (int k = 0; k < K; k++) { const double dd = dist2(&X[(size_t)i * D], &centre[(size_t)k * D]); if (dd < bd) { bd = dd; best = k; } }
-            labels[i] = best;
-            inertia += bd;
-            count[best]++;
-            for (int d = 0; d < D; d++) sum[(size_t)best * D + d] += X[(size_t)i * D + d];
-        }
-        for (int k = 0; k < K; k++)
-            if (count[k] > 0) for (int d = 0; d < D; d++) centre[(size_t)k * D + d] = (float)(sum[(size_t)k * D + d] / count[k]);
-        if (std::fabs(prev - inertia) < 1e-4) break;
-        prev = inertia;
-    }
-    return prev;
+    return gap_rule(lam.data(), lam[N - 1], N, p, max_num_speakers);
 }
 
 }  // namespace
@@ -291,15 +216,10 @@ nmesc_result nmesc_cluster(const float *emb, size_t N_, size_t D, const nmesc_cf
     nmesc_result res;
     const int N = (int)N_;
     if (N <= 0) return res;
-    if (N <= cfg.min_samples_for_nmesc) {                      // :325-331
-        res.est_num_speakers = cfg.oracle_num_speakers > 0 ? cfg.oracle_num_speakers : 1;
-        res.labels.assign(N, 0);
-        res.p_hat = N - 1;
-        return res;
-    }
+    if (early_return(N, cfg, res)) return res;                 // :325-331
     const std::vector<float> aff = nmesc_cosine_affinity(emb, N, D);
     // the NME analysis runs on every ratio-th row / column when N exceeds nme_mat_size (:150-166)
-    const int ratio = std::max(1, (int)std::ceil((double)N / (double)cfg.nme_mat_size));
+    const int ratio = subsample_ratio(N, cfg);
     std::vector<float> sub;
     int Ns = N;
     if (ratio > 1) {
@@ -311,15 +231,11 @@ nmesc_result nmesc_cluster(const float *emb, size_t N_, size_t D, const nmesc_cf
             for (int j = 0; j < Ns; j++) sub[(size_t)i * Ns + j] = aff[(size_t)rows[i] * N + rows[j]];
     }
     const std::vector<float> &ana = ratio > 1 ? sub : aff;
-    const std::vector<int> ps = cfg.fixed_thres > 0.0f
-        ? std::vector<int>(1, std::max(MIN_P, (int)std::floor((double)Ns * (double)cfg.fixed_thres)))
-        : candidate_p(Ns, cfg.max_rp_threshold, cfg.sparse_search_volume);
-    double best_g = std::numeric_limits<double>::infinity();
-    int best_p = ps[0], est = 1;
-    for (int p : ps) {
-        const GapRatio gr = gap_ratio(ana, Ns, p, cfg.max_num_speakers);
-        if (gr.g_p < best_g) { best_g = gr.g_p; best_p = p; est = gr.n_spk; }
-    }
+    const std::vector<int> ps = analysis_candidates(Ns, cfg);
+    Choice best;
+    best.p = ps[0];
+    for (int p : ps) consider(best, gap_ratio(ana, Ns, p, cfg.max_num_speakers), p);
+    const int best_p = best.p, est = best.est;
     int p_hat = ratio * best_p;
     std::vector<float> graph = neighbour_graph(aff, N, p_hat);
     if (!connected(graph, N)) {                                // grow p until the graph is connected (:367-381)
@@ -329,8 +245,7 @@ nmesc_result nmesc_cluster(const float *emb, size_t N_, size_t D, const nmesc_cf
             if (connected(graph, N)) break;
         }
     }
-    int n_clusters = cfg.oracle_num_speakers > 0 ? cfg.oracle_num_speakers : est;
-    n_clusters = std::max(1, std::min(n_clusters, cfg.max_num_speakers));
+    const int n_clusters = cluster_count(est, cfg);
     res.est_num_speakers = n_clusters;
     res.p_hat = p_hat;
     if (n_clusters == 1) { res.labels.assign(N, 0); return res; }
@@ -340,13 +255,7 @@ nmesc_result nmesc_cluster(const float *emb, size_t N_, size_t D, const nmesc_cf
     std::vector<float> se((size_t)N * n_clusters);
     for (int i = 0; i < N; i++)
         for (int k = 0; k < n_clusters; k++) se[(size_t)i * n_clusters + k] = (float)vec[(size_t)i * N + (n_clusters - 1 - k)];
-    Rng rng{cfg.kmeans_seed};
-    double best_inertia = std::numeric_limits<double>::infinity();
-    std::vector<int> labels;
-    for (int t = 0; t < std::max(1, cfg.kmeans_random_trials); t++) {
-        const double inertia = kmeans(se, N, n_clusters, n_clusters, rng, labels);
-        if (inertia < best_inertia) { best_inertia = inertia; res.labels = labels; }
-    }
+    res.labels = kmeans_trials(se, N, n_clusters, cfg);
     return res;
 }
 

@@ -271,7 +271,23 @@ std::string diarize_pipeline_finalize(diarize_pipeline *p) {             // :437
     flush_pending(*p);
     flush_word(*p);
     if (p->subs.empty()) return "";
-    const nmesc_result cl = nmesc_cluster(p->embs.data(), p->subs.size(), (size_t)EMB, p->cfg.cluster);
+    nmesc_result cl;
+    if (p->cfg.cluster_on_device && p->model && p->subs.size() <= (size_t)NASR_CLUSTER_MAX_N) {      // larger inputs: the host path has no cap
+        const nmesc_cfg &c = p->cfg.cluster;
+        const nasr_cluster_params prm = {c.max_num_speakers, c.max_rp_threshold, c.sparse_search_volume, c.nme_mat_size, c.min_samples_for_nmesc,
+                                         c.oracle_num_speakers, c.fixed_thres, c.kmeans_random_trials, c.kmeans_seed};
+        std::vector<int32_t> labels(p->subs.size());
+        int32_t est = 1, p_hat = 1;
+        if (nasr_diar_cluster(p->model->engine, p->embs.data(), (int)p->subs.size(), EMB, &prm, labels.data(), &est, &p_hat, 0) < 0) {
+            fprintf(stderr, "diarize_pipeline: nasr_diar_cluster failed: %s\n", nasr_last_error());
+            return "";
+        }
+        cl.est_num_speakers = est;
+        cl.p_hat = p_hat;
+        cl.labels.assign(labels.begin(), labels.end());
+    } else {
+        cl = nmesc_cluster(p->embs.data(), p->subs.size(), (size_t)EMB, p->cfg.cluster);
+    }
     for (size_t i = 0; i < p->subs.size(); i++) p->subs[i].speaker = cl.labels[i];
     const std::vector<Span> timeline = speaker_timeline(p->subs);
     for (Word &w : p->words) w.speaker = speaker_at(timeline, w.at_sec);

@@ -5,6 +5,7 @@
 // MI355X-first differences (results follow the reference fed sample by sample; what the reference computes is unchanged):
 //   * every VAD window a push completes goes through ONE nasr_diar_vad call (the reference runs a ggml graph per 10 ms window)
 //   * the sub-segments a push completes are embedded by ONE nasr_diar_embed call
+//   * the clustering at EOF runs on the host (diarize_cluster_amd.h) or, with cluster_on_device, on the GPU (nasr_diar_cluster)
 //   * a sub-segment is cut when the VAD frame stream has passed its end (audio through the end of the current VAD window),
 //     so the result does not depend on how the caller slices its pushes (the reference emits as far as the buffered audio
 //     reaches, src/diarize_pipeline.cpp:253-263 -- with its CLI's 89 ms reads that is the same rule)
@@ -22,6 +23,7 @@ struct diarize_pipeline_cfg {            // src/diarize_pipeline.h:27-50
     float sub_window_sec = 1.5f, sub_shift_sec = 0.75f, min_seg_sec = 0.5f;
     vad_post_cfg vad_post;
     nmesc_cfg cluster;
+    bool cluster_on_device = false;      // NME-SC through nasr_diar_cluster (inputs above its cap of 8 192 sub-segments stay on the host path)
     std::string rttm_path, speaker_text_path, json_path;
 };
 
