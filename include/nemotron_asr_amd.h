@@ -371,7 +371,11 @@ enum {
  * "t64_tiles" (default 64, per engine: the split-K GEMMs with N = 1024 take 128 x 64 tiles up to this many 128 x 128 tiles; round 3: 127),
  * "tile_bands" (-1 = the rule: above 4 row chunks the tiles of a launch are handed to the XCDs in bands of column groups, so that the panels an XCD reads stay in its L2;
  * 0 / 1 = never / always), "f32_mfma" (0: f32 GEMMs above
- * four rows on the FMA tile kernel instead of the f32 MFMA), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
+ * four rows on the FMA tile kernel instead of the f32 MFMA), "f32_split" (default 0; 1: an NASR_DTYPE_F32 engine runs its encoder GEMMs above
+ * four rows -- streaming and offline -- on the bf16 MFMA as three products of split operands, x = hi + lo with hi = bf16(x), lo = bf16(x - hi):
+ * a.w ~= a_hi.w_hi + a_hi.w_lo + a_lo.w_hi, f32 accumulation, per product an error <= 3 * 2^-16 |a||w| (bf16: 2^-8).  NOT a kernel-selection
+ * switch: results differ from the default f32 engine's in the last bits (still batch == alone); values other than 0 / 1 and calls after the
+ * first step or offline call are REJECTED; no effect on a bf16 engine, the <= 4-row kernels, the decode and the diarization side-car), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
  * fallback.  N >= 1: max(the synchronous step graph's count, min(10 frames + 1, N)).  Default 0 = auto: as 12, except that a step of ONE
  * frame and up to four rows on a bf16 engine (one to four streams at R = 0) carries 3 -- a frame of two symbols and the closing blank; its
  * decode graph runs behind the fourth encoder piece on a lane the host waits for in every call, so idle iterations there cost step time.

@@ -1404,6 +1404,9 @@ __global__ __launch_bounds__(512) void k_gemm_wide2(GemmParams p, int n_groups, 
 
 constexpr int F32M_KC = 32, F32M_NS = 3;
 template <int BM, int BN> __global__ void k_gemm_f32_mfma(GemmParams p, int n_groups, int m_chunks);      // the f32 engine's MFMA kernel, below
+// the 128 x 128 form (A/B runs only) holds a 96 KiB ring, one workgroup per CU: let it have the registers of one or two waves per SIMD (launch bounds and this on the declaration too: the attribute table below instantiates from it, and without them the kernel is compiled for 1 024 threads, 128 VGPRs)
+#define F32S_WAVES(BM, BN) __attribute__((amdgpu_waves_per_eu(1, (BM) + (BN) >= 256 ? 2 : 8)))
+template <int BM, int BN> __global__ __launch_bounds__(256) F32S_WAVES(BM, BN) void k_gemm_f32_split(GemmParams p, int n_groups, int m_chunks);     // ... and its split-bf16 form (option "f32_split"), below
 
 static int g_num_cus = 256;      // MI355X; refreshed from the device below
 // The ring depths of round 5's loops stay beside the kernels whose counted waits are written for them; the plan's table states the four sizes they give as numbers.
@@ -1420,6 +1423,9 @@ void init_gemm_kernel_attributes() {
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_num_cus = cus;
     hipFuncSetAttribute((const void *)k_gemm_f32_mfma<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 256 * 128);
     hipFuncSetAttribute((const void *)k_gemm_f32_mfma<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 128 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 256 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 192 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 128 * 128);
 }
 
 // Which instance, grid and LDS size: gemm_plan_bf16() (nasr_gemm_plan.h).  This maps the plan to a launch.
@@ -1634,6 +1640,139 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmParams p, int n_group
             }
         }
 }
+
+// ------------------------------------------------------------------------------------
+// The f32 engine above four rows on the bf16 MFMA, three products of split operands (engine option "f32_split").
+// Every f32 operand x is split in registers into hi = RNE_bf16(x) and lo = RNE_bf16(x - hi); a bf16 x bf16 product is exact in f32, so
+//   a . w  ~=  a_hi . w_hi  +  a_hi . w_lo  +  a_lo . w_hi          (dropped: a_lo . w_lo and the two residues, each <= 2^-16 |a| |w|)
+// runs as three v_mfma_f32_32x32x16_bf16 into the same f32 accumulator -- 3 instructions at 16 x the rate of v_mfma_f32_32x32x2_f32.
+//   interface, tile, wave split, ring and swizzle are k_gemm_f32_mfma's: tile BM x BN, 4 waves = 2 x 2 sub-tiles of (BM/2) x (BN/2), 32-deep
+//   f32 chunks (128 B per row) of both operands by LDS-DMA into a 3-slot ring, 16-byte columns XOR-swizzled by (row >> 1) & 7 on the
+//   source side.  A lane of the 32x32x16 instruction owns row / column l & 31 at the EIGHT consecutive k = 16 s + 8 (l >> 5) .. + 8 of
+//   k step s: logical 16-byte columns c = 4 s + 2 (l >> 5) and c + 1 of its row, two ds_read_b128.  The 32 lanes of one half wave read the
+//   same logical column of 32 consecutive rows: (row & 1) picks the 128-byte half of the 256-byte bank line and (row >> 1) & 7 the column,
+//   so any 16 consecutive lanes cover 64 banks once: conflict-free, as the bf16 kernels' activation panel.
+//   Per k step a wave splits its IM + IN fragments (4 v_cvt_pk_bf16_f32, 8 shifts / masks, 8 subtractions, 4 v_cvt_pk_bf16_f32 each)
+//   and issues 3 IM IN MFMAs; the accumulator layout is k_gemm_f32_mfma's (four consecutive n per quad -> epi_quad<false>).
+//   ORDER: per (weight block, activation block) and k step: w_hi a_hi, w_lo a_hi, w_hi a_lo; k steps ascending from a zero accumulator,
+//   no split-K.  The order is the same in every tile shape, and an output element's bits depend on its own A row and W row alone:
+//   not on M, not on the tile shape, not on the other rows of the batch ("batch == alone" holds as for the other f32 kernels).
+//   Rows >= M of the last row chunk read row M - 1 (finite data, never stored).
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN section 23.
+// ------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(8))) float f32x8;
+__device__ __forceinline__ void split_bf16x8(const float4 &x0, const float4 &x1, bf16x8 &hi, bf16x8 &lo) {
+    const f32x8 x = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    hi = __builtin_convertvector(x, bf16x8);                                   // v_cvt_pk_bf16_f32: round to nearest even
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    const u32x4 u = __builtin_bit_cast(u32x4, hi);                             // float(hi) from the packed pairs: one shift, one mask per pair
+    f32x8 r;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        r[2 * i] = x[2 * i] - __builtin_bit_cast(float, u[i] << 16);            // x - hi is exact in f32 (hi keeps x's exponent and top 8 bits)
+        r[2 * i + 1] = x[2 * i + 1] - __builtin_bit_cast(float, u[i] & 0xffff0000u);
+    }
+    lo = __builtin_convertvector(r, bf16x8);
+}
+template <int BM, int BN>
+__global__ __launch_bounds__(256) F32S_WAVES(BM, BN)
+void k_gemm_f32_split(GemmParams p, int n_groups, int m_chunks) {
+    constexpr int ROWS = BM + BN, SLOT = ROWS * 128, DMA = ROWS / 32;      // DMA instructions per wave and chunk (8 rows each)
+    constexpr int IM = BM / 64, IN = BN / 64;                              // 32 x 32 blocks per wave along m / n
+    extern __shared__ __attribute__((aligned(16))) char ring[];
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int mc = id % m_chunks, ng = id / m_chunks;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, kh = lane >> 5;
+    const int m0 = mc * BM, n0 = ng * BN, nchunks = p.K / F32M_KC;
+    // this wave fills rows [wave * ROWS / 4, + ROWS / 4) of every slot: activation rows first, weight rows behind them
+    const char *src[DMA];
+#pragma unroll
+    for (int j = 0; j < DMA; j++) {
+        const int row = wave * (ROWS / 4) + j * 8 + (lane >> 3), c4 = lane & 7;
+        const char *base;
+        if (row < BM) { int m = m0 + row; if (m >= p.M) m = p.M - 1; base = a_row_ptr(p, m, 4); }
+        else base = (const char *)p.W + (size_t)(n0 + row - BM) * p.K * 4;
+        src[j] = base + (((c4 ^ (row >> 1)) & 7) << 4);
+    }
+    const unsigned ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) char *)ring;
+    auto issue = [&](int kc, int slot) {
+        const unsigned sb = ring_base + slot * SLOT + wave * (ROWS / 4) * 128;
+#pragma unroll
+        for (int j = 0; j < DMA; j++) glds16(src[j] + (size_t)kc * 128, sb + j * 1024);
+    };
+    f32x16 acc[IN][IM];
+#pragma unroll
+    for (int a = 0; a < IN; a++)
+#pragma unroll
+        for (int b = 0; b < IM; b++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc[a][b][i] = 0.f;
+    issue(0, 0);
+    if (nchunks > 1) issue(1, 1);
+    int slot = 0;
+    for (int i = 0; i < nchunks; i++) {
+        // vmcnt counts this wave's DMA instructions alone (the fragment reads are LDS reads: lgkmcnt, the compiler's): chunks i and i + 1 are
+        // the only ones outstanding here, DMA instructions each, in order -> vmcnt(DMA) = chunk i has landed
+        if (i + 1 < nchunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();              // ... for every wave; and every wave's MFMAs have consumed the fragments of chunk i - 1
+        if (i + 2 < nchunks) issue(i + 2, slot == 0 ? 2 : slot - 1);     // into the slot chunk i - 1 has just left
+        const char *sp = ring + slot * SLOT;
+        const char *arow = sp + (wm * (BM / 2) + l31) * 128, *wrow = sp + (BM + wn * (BN / 2) + l31) * 128;
+        const int swa = ((wm * (BM / 2) + l31) >> 1) & 7, sww = ((BM + wn * (BN / 2) + l31) >> 1) & 7;     // + 32 rows: the same swizzle
+#pragma unroll
+        for (int s = 0; s < F32M_KC / 16; s++) {
+            const int c = 4 * s + 2 * kh;
+            bf16x8 ah[IM], al[IM], wh[IN], wl[IN];
+#pragma unroll
+            for (int b = 0; b < IM; b++)
+                split_bf16x8(*(const float4 *)(arow + b * 32 * 128 + ((c ^ swa) << 4)), *(const float4 *)(arow + b * 32 * 128 + (((c + 1) ^ swa) << 4)), ah[b], al[b]);
+#pragma unroll
+            for (int a = 0; a < IN; a++)
+                split_bf16x8(*(const float4 *)(wrow + a * 32 * 128 + ((c ^ sww) << 4)), *(const float4 *)(wrow + a * 32 * 128 + (((c + 1) ^ sww) << 4)), wh[a], wl[a]);
+            // term by term over the wave's blocks: consecutive MFMAs write different accumulators, every accumulator sees w_hi a_hi, w_lo a_hi, w_hi a_lo
+#pragma unroll
+            for (int t = 0; t < 3; t++)
+#pragma unroll
+                for (int a = 0; a < IN; a++)
+#pragma unroll
+                    for (int b = 0; b < IM; b++)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t == 1 ? wl[a] : wh[a], t == 2 ? al[b] : ah[b], acc[a][b], 0, 0, 0);
+        }
+        slot = slot + 1 == F32M_NS ? 0 : slot + 1;
+    }
+#pragma unroll
+    for (int a = 0; a < IN; a++)
+#pragma unroll
+        for (int b = 0; b < IM; b++) {
+            const int m = m0 + wm * (BM / 2) + b * 32 + l31;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int n = n0 + wn * (BN / 2) + a * 32 + g * 8 + kh * 4;
+                epi_quad<false>(p, 0, m, n, acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
+            }
+        }
+}
+template <int BM, int BN> static void launch_f32_split_tile(const GemmParams &p, hipStream_t st) {
+    const int n_groups = p.N / BN, m_chunks = (p.M + BM - 1) / BM;
+    hipLaunchKernelGGL((k_gemm_f32_split<BM, BN>), dim3(n_groups * m_chunks), dim3(256), F32M_NS * (BM + BN) * 128, st, p, n_groups, m_chunks);
+}
+// The split kernel's own tile rule, from measurement (profiles/f32_split.md; cold operands, us per launch).  64 (rows) x 128 beats 128 x 128 at every engine
+// shape, 7 168 rows included (W1 250 against 265, QKV 196 against 222, pw1 131 against 152): the 128 x 128 form's 96 KiB ring leaves one workgroup, four waves,
+// on a CU and nothing to hide a wave's split arithmetic behind, while three 64 x 128 workgroups fit.  64 x 64 wins while the 64 x 128 tiles would not fill the
+// chip one and a half times (896 rows: W2 64 against 86 at 112 tiles, QKV 36 against 39 at 336; W1 47 against 41 at 448): the rule takes 64 x 128 from 384
+// such tiles.  The 128 x 128 instance stays for A/B runs only: bits 4-5 of f32_fma_tile force a form (1: 128 x 128, 2: 64 x 128, 3: 64 x 64; the probe and the
+// tile-shape identity test).
+constexpr int F32S_T64W = 384;
+static void launch_gemm_f32_split(const GemmParams &p, hipStream_t st) {
+    const int force = (p.f32_fma_tile >> 4) & 3;
+    const long t64w = (long)(p.N / 128) * ((p.M + 63) / 64);
+    if (p.N % 128 == 0 && force == 1) launch_f32_split_tile<128, 128>(p, st);
+    else if (p.N % 128 == 0 && (force ? force == 2 : t64w >= F32S_T64W)) launch_f32_split_tile<64, 128>(p, st);
+    else launch_f32_split_tile<64, 64>(p, st);
+}
+
 void launch_gemm_f32(const GemmParams &p0, hipStream_t st) {
     GemmParams p = p0;
     p.splits = 1;
@@ -1641,8 +1780,10 @@ void launch_gemm_f32(const GemmParams &p0, hipStream_t st) {
         hipLaunchKernelGGL(k_gemm_f32_rows, dim3(p.N / F32R_NR), dim3(256), 0, st, p);
         return;
     }
-    if (!p.f32_fma_tile && p.M > F32R_MMAX && p.N % 64 == 0 && p.K % F32M_KC == 0 && p.lda % 4 == 0 && ((size_t)p.A & 15) == 0 && ((size_t)p.W & 15) == 0 &&
-        (p.rows_per_batch == 0 || (p.batch_stride % 4 == 0))) {
+    const bool mfma_shape = p.M > F32R_MMAX && p.N % 64 == 0 && p.K % F32M_KC == 0 && p.lda % 4 == 0 && ((size_t)p.A & 15) == 0 && ((size_t)p.W & 15) == 0 &&
+                            (p.rows_per_batch == 0 || (p.batch_stride % 4 == 0));
+    if ((p.f32_fma_tile & 15) == 2 && mfma_shape) { launch_gemm_f32_split(p, st); return; }
+    if (!p.f32_fma_tile && mfma_shape) {
         // 128 x 128 tiles when they fill the chip (or the width allows nothing else to), 64 x 64 otherwise: more, smaller workgroups, three per CU
         const long big = (long)(p.N / 128) * ((p.M + 127) / 128);
         if (p.N % 128 == 0 && big >= 192) {

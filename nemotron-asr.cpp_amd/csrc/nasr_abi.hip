@@ -281,6 +281,12 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
     else if (!strcmp(key, "fork_piece_kb")) { if (value < 0 || value > 1024) return fail("fork_piece_kb must be 0 .. 1024"); e->opt_fork_piece_kb = value; }      // measurement only: the grid of k_stream_fork (same bytes)
     else if (!strcmp(key, "ablate")) e->opt_ablate = value;          // measurement only (see the header); before the first step
     else if (!strcmp(key, "f32_mfma")) e->opt_f32_mfma = value != 0;      // 0: f32 GEMMs above four rows on the FMA tile kernel (round 3's path); like "fused", set before the first step
+    else if (!strcmp(key, "f32_split")) {
+        // read by every launch_gemm_f32 of the encoder, and by the position projections that are computed once per chunk length: one arithmetic per engine life
+        if (value != 0 && value != 1) return fail("f32_split must be 0 or 1");
+        if (e->dec_started || e->off) return fail("f32_split must be set before the first step or offline call");
+        e->opt_f32_split = value != 0;
+    }
     else if (!strcmp(key, "pipeline")) {
         ApiGuard api_guard;
         HIPCHK(hipSetDevice(e->device));

@@ -397,7 +397,7 @@ int ensure_posproj(nasr_engine *e, int T) {
         memset(&g, 0, sizeof(g));
         g.A = demb; g.W = L.wpos_f32; g.M = n_rel; g.N = D; g.K = D; g.lda = D;
         g.epi = EPI_PART_F32; g.out_f32 = dout; g.ldo = D; g.splits = 1;
-        g.f32_fma_tile = e->opt_f32_mfma ? 0 : 1;
+        g.f32_fma_tile = e->f32_gemm_kind();
         launch_gemm_f32(g, e->st);
         if (e->bf16) {
             bf16_t *pp;

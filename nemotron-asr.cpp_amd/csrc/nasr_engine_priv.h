@@ -190,6 +190,8 @@ struct nasr_engine {
     int opt_ablate = 0;              // option "ablate" (MEASUREMENT ONLY, results are invalid): bit mask of launches left out of the unfused step -- 1 k_post, 2 attention,
                                      // 4 depthwise conv, 8 decode iterations, 16 front end (mel + subsampling), 32 every encoder GEMM: what each costs a pipelined step (profiles/r5_configs2_launch_structure.md, r5_ablation_b64_R13.json)
     bool opt_f32_mfma = true;        // f32 GEMMs above four rows on v_mfma_f32_32x32x2_f32 (bit-identical to the FMA tile kernel)
+    bool opt_f32_split = false;      // option "f32_split": an f32 engine's GEMMs above four rows as three bf16 MFMA products of split operands (k_gemm_f32_split; not the f32 kernels' bits)
+    int f32_gemm_kind() const { return opt_f32_split && !bf16 ? 2 : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
     char *gh = nullptr;                                                               // pinned host block
     int *gh_collect = nullptr;       // pinned landing zone of the token gather: [B][1 + COLLECT_STRIDE] + n_active
     int64_t graph_replays = 0, eager_steps = 0, decode_fallbacks = 0, decode_fallback_rounds = 0;

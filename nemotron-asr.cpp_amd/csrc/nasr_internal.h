@@ -99,7 +99,9 @@ struct GemmParams {
     // prio >> 2 (round 5, engine option "gemm_prio"): 0 = round 5's loops (k_gemm_wide2, k_gemm_tiled3), 5 = rounds 1-4's (k_gemm_wide, k_gemm_tiled2_k32): A/B runs and the identity test
     int prio;
     // f32 GEMMs above four rows run on the f32-input MFMA (k_gemm_f32_mfma); 1 = the FMA tile kernel k_gemm_f32 instead (engine
-    // option "f32_mfma" = 0: the other side of the bit-identity test)
+    // option "f32_mfma" = 0: the other side of the bit-identity test); 2 = the split-bf16 kernel k_gemm_f32_split (engine option "f32_split":
+    // three bf16 MFMA products of hi / lo operand halves, NOT the bits of the other two) where k_gemm_f32_mfma's shape conditions hold,
+    // else as 1.  With 2, bits 4-5 force one of its tile forms (16: 128 x 128, 32: 64 x 128, 48: 64 x 64; probes and the tile-shape identity test)
     int f32_fma_tile;
     // 1 = never the persistent tile loop (k_gemm_persist), whatever the size: engine option "persistent_gemm" = 0, the other side
     // of its bit-identity test
