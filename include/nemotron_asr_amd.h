@@ -375,7 +375,12 @@ enum {
  * four rows -- streaming and offline -- on the bf16 MFMA as three products of split operands, x = hi + lo with hi = bf16(x), lo = bf16(x - hi):
  * a.w ~= a_hi.w_hi + a_hi.w_lo + a_lo.w_hi, f32 accumulation, per product an error <= 3 * 2^-16 |a||w| (bf16: 2^-8).  NOT a kernel-selection
  * switch: results differ from the default f32 engine's in the last bits (still batch == alone); values other than 0 / 1 and calls after the
- * first step or offline call are REJECTED; no effect on a bf16 engine, the <= 4-row kernels, the decode and the diarization side-car), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
+ * first step or offline call are REJECTED; no effect on a bf16 engine, the <= 4-row kernels, the decode and the diarization side-car), "f32_split_attn"
+ * (default 0; 1: an NASR_DTYPE_F32 engine runs the full-context attention of its OFFLINE calls -- transcribe, beam, align, every entry -- on the bf16 MFMA:
+ * content scores, position scores and P.V each as three products of split operands as under "f32_split", f32 online softmax, f32 context; 64 query rows per
+ * workgroup instead of 16.  Independent of "f32_split" (either alone, or both).  The STREAMING attention kernels are not touched.  Results differ from the
+ * default f32 engine's in the last bits (still batch == alone); values other than 0 / 1 and calls after the first step or offline call are REJECTED; no
+ * effect on a bf16 engine), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
  * fallback.  N >= 1: max(the synchronous step graph's count, min(10 frames + 1, N)).  Default 0 = auto: as 12, except that a step of ONE
  * frame and up to four rows on a bf16 engine (one to four streams at R = 0) carries 3 -- a frame of two symbols and the closing blank; its
  * decode graph runs behind the fourth encoder piece on a lane the host waits for in every call, so idle iterations there cost step time.

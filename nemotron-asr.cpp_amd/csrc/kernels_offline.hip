@@ -230,11 +230,12 @@ __global__ __launch_bounds__(256) void k_off_attn_f32(OffAttnParams p) {
     }
 }
 
-int off_attn_qb(int act_bf16) { return act_bf16 ? OFF_QB_BF16 : OFF_QB_F32; }
+int off_attn_qb(int act_bf16) { return act_bf16 == 2 ? OFF_QB_SPLIT : act_bf16 ? OFF_QB_BF16 : OFF_QB_F32; }
 
 void launch_off_attention(const OffAttnParams &p, int n_items, int act_bf16, hipStream_t st) {
     if (n_items <= 0) return;
-    if (act_bf16) hipLaunchKernelGGL(k_off_attn_bf16, dim3(n_items, NH), dim3(256), 0, st, p);
+    if (act_bf16 == 2) launch_off_attention_split(p, n_items, st);          // f32 operands, three bf16 MFMA products (kernels_attn_split.hip)
+    else if (act_bf16) hipLaunchKernelGGL(k_off_attn_bf16, dim3(n_items, NH), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_off_attn_f32, dim3(n_items, NH), dim3(256), 0, st, p);
 }
 

@@ -191,6 +191,8 @@ struct nasr_engine {
                                      // 4 depthwise conv, 8 decode iterations, 16 front end (mel + subsampling), 32 every encoder GEMM: what each costs a pipelined step (profiles/r5_configs2_launch_structure.md, r5_ablation_b64_R13.json)
     bool opt_f32_mfma = true;        // f32 GEMMs above four rows on v_mfma_f32_32x32x2_f32 (bit-identical to the FMA tile kernel)
     bool opt_f32_split = false;      // option "f32_split": an f32 engine's GEMMs above four rows as three bf16 MFMA products of split operands (k_gemm_f32_split; not the f32 kernels' bits)
+    bool opt_f32_split_attn = false; // option "f32_split_attn": an f32 engine's OFFLINE attention as three bf16 MFMA products of split operands (k_off_attn_f32_split; not k_off_attn_f32's bits)
+    int off_attn_kind() const { return bf16 ? 1 : opt_f32_split_attn ? 2 : 0; }                  // the integer of off_attn_qb / launch_off_attention
     int f32_gemm_kind() const { return opt_f32_split && !bf16 ? 2 : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
     char *gh = nullptr;                                                               // pinned host block
     int *gh_collect = nullptr;       // pinned landing zone of the token gather: [B][1 + COLLECT_STRIDE] + n_active

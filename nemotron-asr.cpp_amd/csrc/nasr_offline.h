@@ -9,6 +9,7 @@ constexpr int OFFLINE_MAX_T = nasr_plan::OFFLINE_MAX_FRAMES;   // 2048
 constexpr int OFFLINE_NREL = 2 * OFFLINE_MAX_T - 1;             // 4095 rows of the relative-position table, row r <-> rel = 2047 - r
 constexpr int OFF_QKV_LD = 3 * D;                               // q | k | v of a row, act dtype
 constexpr int OFF_DEC_WIN = 256;                                // encoder frames per decode window
+constexpr int OFF_QB_SPLIT = 64;                               // query rows per workgroup of k_off_attn_f32_split (kernels_attn_split.hip): 4 waves x 16
 constexpr int OFF_MIN_ROWS = 64;                                // GEMMs of the path run on at least this many rows (above the skinny kernel's 32)
 
 struct OffAttnParams {
@@ -20,8 +21,11 @@ struct OffAttnParams {
 };
 struct OffSubDesc { int mel_off, n_mel, out_row, pad; };
 
+// act_bf16: 0 = f32 (k_off_attn_f32), 1 = bf16 (k_off_attn_bf16), 2 = f32 operands on the split-bf16 MFMA kernel (k_off_attn_f32_split, engine
+// option "f32_split_attn"; NOT k_off_attn_f32's bits)
 int off_attn_qb(int act_bf16);    // query rows per attention workgroup
 void launch_off_attention(const OffAttnParams &p, int n_items, int act_bf16, hipStream_t st);
+void launch_off_attention_split(const OffAttnParams &p, int n_items, hipStream_t st);          // kernels_attn_split.hip
 void launch_off_dwconv(const float *glu, const int *tpos, int M, const float *dw, int ks, const float *ln_w, const float *ln_b,
                        void *out, int act_bf16, hipStream_t st);
 void launch_off_conv0_dw(const OffSubDesc *desc, int B, int max_h2, const float *mel_all, const float *w0t, const float *b0,

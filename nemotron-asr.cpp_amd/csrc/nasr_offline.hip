@@ -126,7 +126,8 @@ static int run_offline_encoder(nasr_engine *e, OfflineState *o, const float *con
     ob.M = M; ob.maxT = maxT;
     if (M == 0) return 0;                                    // every utterance too short for one mel frame: nothing runs
     if (ensure_rows(e, o, M)) return -1;
-    const int qb = off_attn_qb(act);
+    const int attn = e->off_attn_kind();                     // 2: f32 operands on the split-bf16 kernel (option "f32_split_attn")
+    const int qb = off_attn_qb(attn);
     std::vector<int4> items;
     std::vector<int> tpos(M);
     std::vector<RowDesc> prow(M);
@@ -198,8 +199,8 @@ static int run_offline_encoder(nasr_engine *e, OfflineState *o, const float *con
         ap.qkv = o->qkv.p; ap.pos = o->pos[l]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.items = o->items.as<int4>(); ap.ctx = o->ctx.p;
         double sq = 0;
         for (int k = 0; k < n; k++) sq += (double)T[k] * T[k];
-        ProfScope ps(e, "k_off_attention", (double)M * 4 * D * e->esz, sq * NH * DH * 6.0);
-        launch_off_attention(ap, (int)items.size(), act, st);
+        ProfScope ps(e, attn == 2 ? "k_off_attention_split" : "k_off_attention", (double)M * 4 * D * e->esz, sq * NH * DH * 6.0);
+        launch_off_attention(ap, (int)items.size(), attn, st);
     };
     r.dwconv = [&](int l) {
         const LayerW &L = e->L[l];
