@@ -380,7 +380,12 @@ enum {
  * content scores, position scores and P.V each as three products of split operands as under "f32_split", f32 online softmax, f32 context; 64 query rows per
  * workgroup instead of 16.  Independent of "f32_split" (either alone, or both).  The STREAMING attention kernels are not touched.  Results differ from the
  * default f32 engine's in the last bits (still batch == alone); values other than 0 / 1 and calls after the first step or offline call are REJECTED; no
- * effect on a bf16 engine), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
+ * effect on a bf16 engine), "f32_split_attn_stream" (default 0; 1: an NASR_DTYPE_F32 engine runs every STREAMING attention launch of its unfused steps on the
+ * bf16 MFMA (k_attention_f32_split): content scores, position scores and P.V each as three products of split operands as under "f32_split", f32 mask,
+ * softmax and context; the K / V rings, the snapshot format, the offline calls, the fused small-M path and the decode are untouched.  Independent of
+ * "f32_split" and "f32_split_attn".  Results differ from the default f32 engine's in the last bits; a stream's results depend on its own audio and on the
+ * step's chunking only (batch == alone).  Values other than 0 / 1 and calls after the first step or offline call are REJECTED; no effect on a bf16
+ * engine), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
  * fallback.  N >= 1: max(the synchronous step graph's count, min(10 frames + 1, N)).  Default 0 = auto: as 12, except that a step of ONE
  * frame and up to four rows on a bf16 engine (one to four streams at R = 0) carries 3 -- a frame of two symbols and the closing blank; its
  * decode graph runs behind the fourth encoder piece on a lane the host waits for in every call, so idle iterations there cost step time.

@@ -1,5 +1,6 @@
-// kernels_attn_split.hip -- the offline path's full-context relative-position attention for the f32 engine on the bf16 MFMA
-// (engine option "f32_split_attn"): f32 operands in HBM, f32 softmax, f32 context, and every matrix product as three
+// kernels_attn_split.hip -- the f32 engine's attention on the bf16 MFMA: k_off_attn_f32_split, the offline path's full-context relative-position
+// attention (engine option "f32_split_attn", DESIGN section 24, described first), and k_attention_f32_split, the streaming cached attention (engine
+// option "f32_split_attn_stream", DESIGN section 25, described above the kernel).  Both: f32 operands in HBM, f32 softmax, f32 context, and every matrix product as three
 // v_mfma_f32_16x16x32_bf16 of split operands,
 //   x = hi + lo + r,  hi = RNE_bf16(x),  lo = RNE_bf16(x - hi)  (x - hi is exact in f32),      a . b ~= a_hi . b_hi + a_hi . b_lo + a_lo . b_hi
 // (dropped: a_lo . b_lo and the two residues, each <= 2^-16 |a||b|).  The operation, OffAttnParams and the work items
@@ -24,6 +25,7 @@
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN section 24.
 #include "nasr_internal.h"
 #include "nasr_offline.h"
+#include "nasr_wave.h"
 
 namespace nasr {
 
@@ -240,6 +242,190 @@ __global__ __launch_bounds__(256) void k_off_attn_f32_split(OffAttnParams p) {
 
 void launch_off_attention_split(const OffAttnParams &p, int n_items, hipStream_t st) {
     if (n_items > 0) hipLaunchKernelGGL(k_off_attn_f32_split, dim3(n_items, NH), dim3(256), 0, st, p);
+}
+
+// ---- streaming: the cached relative-position attention of an f32 engine on the bf16 MFMA (engine option "f32_split_attn_stream") ----
+// The operation and AttnParams are k_attention<false>'s (kernels_layer.hip), the work split is k_attention_mfma's: one workgroup of 4 waves per
+// (head, stream, group of query rows); a group is one chunk for T >= 4 and 16 rows = 16 / T chunks for T <= 2; its keys are the SPAN of
+// 70 + (chunks in the group) T <= 86 ring rows; row (chunk g, frame i) attends the window of 70 + T keys that starts (g - g0) T rows into the span,
+// with the cache validity min(valid_len + g T, 70); every weight outside the window is exactly 0.  Every operand stays f32 in memory and every
+// product is as_mfma3 of split operands, k steps ascending from a zero accumulator:
+//   scores^T  S[j][i] = K[j] . (q_i + u), P[r][i] = Pos[r] . (q_i + v)      6 key tiles + 7 position tiles of 16 rows, dealt over the waves (tile t
+//             goes to wave t & 3; tiles that start past the span / the table are skipped).  A K or position row is the A operand of exactly one
+//             wave: its lanes load it from global memory straight into the operand layout (two float4 per lane and k step) and split it in
+//             registers.  (q + u) and (q + v) of the group's rows are split once into four swizzled bf16 images (k_attention_mfma's swizzle).
+//   softmax   f32, one wave per row, two span positions per lane; the rel-shift is the LDS gather sp[i][j + T - 1 - ic]; the f32 weights are split
+//             into a hi and a lo image that take the place of the (q + u) images
+//   context^T O[d][i] = sum_j V^T[d][j] w[i][j]     8 d tiles x 3 k steps x 3 products, wave w owns d = 32 w .. + 32.  V^T[d][8 keys] is exactly the
+//             A operand of one lane of one wave, so V does not pass through LDS: every lane loads its 48 V elements itself (16 lanes = 64 contiguous
+//             bytes of a ring row, a wave instruction = 4 ring rows), up front with everything else, and splits them after the softmax.  No V^T image,
+//             no fourth barrier, 29.5 KiB of LDS instead of 60.
+// Every global load is requested before the first wait: one round trip per workgroup.  Rows past nrows use zero queries, get zero weights and
+// are never written; K rows are clamped into the span and position rows into the table, V past the span is 0.
+// BITS: a context row depends on its own stream and on the step's chunking (T, TS) only -- batch == alone.  At T <= 2 the k steps of P.V start at
+// the span, not at the row's window: a row's bits can depend on which chunks share its workgroup (as in k_attention_mfma, not in k_attention<false>).
+constexpr int SS_SKP = 100, SS_SPP = 116;                 // row pitches (floats) of the score tiles: 96 / 112 + 4 (k_attention_mfma's)
+constexpr int SS_IMG = 16 * 256;                          // one bf16 image [16 rows][128]: 256 B per row, 16-byte chunk c of row i at chunk (c ^ i) & 15
+constexpr int SS_LDS = 4 * SS_IMG + 16 * (SS_SKP + SS_SPP) * 4;       // 16 384 + 13 824 = 30 208 B
+
+__device__ __forceinline__ void ss_split8(const float4 &x0, const float4 &x1, uint4 &hi, uint4 &lo) {
+    as_split2(x0.x, x0.y, hi.x, lo.x);
+    as_split2(x0.z, x0.w, hi.y, lo.y);
+    as_split2(x1.x, x1.y, hi.z, lo.z);
+    as_split2(x1.z, x1.w, hi.w, lo.w);
+}
+
+__global__ __launch_bounds__(256) void k_attention_f32_split(AttnParams p) {
+    __shared__ __attribute__((aligned(16))) char lds[SS_LDS];
+    char *const qu_s = lds, *const qv_s = lds + 2 * SS_IMG;          // hi image, lo image SS_IMG behind it              phases 0-1
+    char *const w_s = lds;                                           // softmax weights, hi and lo                        phases 2-3
+    float *const sk = (float *)(lds + 4 * SS_IMG), *const sp = sk + 16 * SS_SKP;      // score tiles                       phases 1-2
+    const int h = blockIdx.x, b = blockIdx.y, T = p.T, KV = LCTX + T, n_rel = KV + T - 1;
+    const int TS = p.TS > 0 ? p.TS : p.T;
+    const int QB = T <= 2 ? 16 : T;                          // query rows per workgroup
+    const int r0 = blockIdx.z * QB, nrows = TS - r0 < QB ? TS - r0 : QB;
+    const int g0 = r0 / T;                                   // first chunk of the group
+    const int span = LCTX + ((nrows + T - 1) / T) * T;       // ring rows the group can see (<= 86 < 96)
+    const RowDesc rd = p.rows[b];
+    const size_t row0 = (size_t)b * TS + (size_t)r0;
+    int head0 = rd.kv_head + g0 * T;
+    while (head0 >= KVC) head0 -= KVC;
+    const float *kbase = (const float *)p.kv_pool + (size_t)rd.slot * p.kv_slot_stride + h * DH;
+    const float *vbase = kbase + (size_t)KVC * D;
+    const float *pbase = (const float *)p.posproj + h * DH;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
+    // ---- every global read of the workgroup, in the order of use: queries and biases, this wave's K / position tiles, this lane's V elements ----
+    float4 qreg[2], ureg[2], breg[2];
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int e = threadIdx.x + it * 256, i = e >> 5, c4 = (e & 31) * 4;
+        qreg[it] = i < nrows ? *(const float4 *)(p.q + (row0 + i) * D + h * DH + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        ureg[it] = *(const float4 *)(p.bias_u + h * DH + c4);
+        breg[it] = *(const float4 *)(p.bias_v + h * DH + c4);
+    }
+    float4 av[4][8];                                       // tiles wave, wave + 4, wave + 8, wave + 12 of the 6 key + 7 position tiles
+    bool live[4];
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        const int t = wave + 4 * n;
+        live[n] = t < 13 && (t < 6 ? t * 16 < span : (t - 6) * 16 < n_rel);      // wave-uniform
+        if (live[n]) {
+            const float *arow;
+            if (t < 6) {
+                int j = t * 16 + r;
+                if (j >= span) j = span - 1;
+                int ring = head0 + j;
+                if (ring >= KVC) ring -= KVC;
+                arow = kbase + (size_t)ring * D;
+            } else {
+                int rr = (t - 6) * 16 + r;
+                if (rr >= n_rel) rr = n_rel - 1;
+                arow = pbase + (size_t)rr * D;
+            }
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                av[n][2 * ks] = *(const float4 *)(arow + ks * 32 + q * 8);
+                av[n][2 * ks + 1] = *(const float4 *)(arow + ks * 32 + q * 8 + 4);
+            }
+        }
+    }
+    float vreg[2][3][8];                                   // V^T[d = 32 wave + 16 d2 + r][key 32 ks + 8 q + u]
+#pragma unroll
+    for (int ks = 0; ks < 3; ks++)
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int j = ks * 32 + q * 8 + u;
+            int ring = head0 + j;
+            if (ring >= KVC) ring -= KVC;
+            const float *vrow = vbase + (size_t)ring * D + wave * 32 + r;
+            vreg[0][ks][u] = j < span ? vrow[0] : 0.0f;
+            vreg[1][ks][u] = j < span ? vrow[16] : 0.0f;
+        }
+    // ---- phase 0: (q + u), (q + v) -> bf16 hi / lo images ----
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int e = threadIdx.x + it * 256, i = e >> 5, c4 = (e & 31) * 4;
+        const int off = i * 256 + ((((c4 >> 3) ^ i) & 15) << 4) + (c4 & 7) * 2;
+        const float4 x = qreg[it], u = ureg[it], v = breg[it];
+        uint2 hi, lo;
+        as_split2(x.x + u.x, x.y + u.y, hi.x, lo.x);
+        as_split2(x.z + u.z, x.w + u.w, hi.y, lo.y);
+        *(uint2 *)(qu_s + off) = hi;
+        *(uint2 *)(qu_s + SS_IMG + off) = lo;
+        as_split2(x.x + v.x, x.y + v.y, hi.x, lo.x);
+        as_split2(x.z + v.z, x.w + v.w, hi.y, lo.y);
+        *(uint2 *)(qv_s + off) = hi;
+        *(uint2 *)(qv_s + SS_IMG + off) = lo;
+    }
+    __syncthreads();
+    // ---- phase 1: key tiles and relative-position tiles, A split in registers ----
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        const int t = wave + 4 * n;
+        if (live[n]) {
+            const bool isk = t < 6;
+            const char *bq = isk ? qu_s : qv_s;
+            as_f32x4_t acc = (as_f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                uint4 a_hi, a_lo;
+                ss_split8(av[n][2 * ks], av[n][2 * ks + 1], a_hi, a_lo);
+                const char *bp = bq + r * 256 + ((((ks << 2) | q) ^ r) << 4);
+                acc = as_mfma3(a_hi, a_lo, *(const uint4 *)bp, *(const uint4 *)(bp + SS_IMG), acc);
+            }
+            // D[j][i]: lane holds query i = r, rows 4q + reg
+            float *dst = isk ? sk + r * SS_SKP + t * 16 + q * 4 : sp + r * SS_SPP + (t - 6) * 16 + q * 4;
+            *(float4 *)dst = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
+    }
+    __syncthreads();                          // ... and every read of the query images is done: their first half becomes the weight images
+    // ---- phase 2: rel-shift gather + mask + softmax -> hi / lo weights over the span (zero outside the row's window) ----
+    const float scale = 0.08838834764831845f;                    // 1/sqrt(128), applied to the sum of the two terms
+    for (int i = wave; i < 16; i += 4) {
+        const int il = r0 + i, g = il / T, ic = il - g * T;      // (chunk, frame in chunk) of this row
+        const int wo = (g - g0) * T;                             // its window starts wo rows into the span
+        const int valid = rd.valid_len + g * T < LCTX ? rd.valid_len + g * T : LCTX;
+        const int mask_upto = LCTX - valid;
+        const int j0 = lane - wo, j1 = lane + 64 - wo;           // window index of span positions lane, lane + 64
+        const bool in0 = i < nrows && j0 >= 0 && j0 < KV, in1 = i < nrows && j1 >= 0 && j1 < KV;
+        float v0 = -INFINITY, v1 = -INFINITY;
+        if (in0) { v0 = (sk[i * SS_SKP + lane] + sp[i * SS_SPP + j0 + T - 1 - ic]) * scale; if (j0 < mask_upto) v0 += -1e9f; }
+        if (in1) { v1 = (sk[i * SS_SKP + lane + 64] + sp[i * SS_SPP + j1 + T - 1 - ic]) * scale; if (j1 < mask_upto) v1 += -1e9f; }
+        const float mx = wave_max(fmaxf(v0, v1));
+        const float e0 = in0 ? __expf(v0 - mx) : 0.0f;
+        const float e1 = in1 ? __expf(v1 - mx) : 0.0f;
+        const float sum = wave_sum(e0 + e1);
+        const float inv = i < nrows ? 1.0f / sum : 0.0f;
+        uint32_t hi, lo;
+        as_split2(e0 * inv, e1 * inv, hi, lo);
+        const int p0 = lane, p1 = lane + 64;
+        const int o0 = i * 256 + ((((p0 >> 3) ^ i) & 15) << 4) + (p0 & 7) * 2, o1 = i * 256 + ((((p1 >> 3) ^ i) & 15) << 4) + (p1 & 7) * 2;
+        *(bf16_t *)(w_s + o0) = (bf16_t)(hi & 0xffffu);
+        *(bf16_t *)(w_s + SS_IMG + o0) = (bf16_t)(lo & 0xffffu);
+        *(bf16_t *)(w_s + o1) = (bf16_t)(hi >> 16);
+        *(bf16_t *)(w_s + SS_IMG + o1) = (bf16_t)(lo >> 16);
+    }
+    __syncthreads();
+    // ---- phase 3: O^T[d][i] = V^T . w^T, this wave's 2 d tiles x 3 k steps; the V elements are split here ----
+#pragma unroll
+    for (int d2 = 0; d2 < 2; d2++) {
+        as_f32x4_t acc = (as_f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 3; ks++) {
+            const float *v = vreg[d2][ks];
+            uint4 a_hi, a_lo;
+            ss_split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), a_hi, a_lo);
+            const char *bp = w_s + r * 256 + (((((ks << 2) | q) ^ r) & 15) << 4);
+            acc = as_mfma3(a_hi, a_lo, *(const uint4 *)bp, *(const uint4 *)(bp + SS_IMG), acc);
+        }
+        if (r < nrows)     // D[d][i]: lane holds query i = r, d = 32 wave + 16 d2 + 4q + reg
+            store_wt_f4((float *)p.ctx_out + (row0 + r) * D + h * DH + wave * 32 + d2 * 16 + q * 4, make_float4(acc[0], acc[1], acc[2], acc[3]));
+    }
+}
+
+void launch_attention_split(const AttnParams &p, hipStream_t st) {
+    const int TS = p.TS > 0 ? p.TS : p.T, QB = p.T <= 2 ? 16 : p.T;
+    hipLaunchKernelGGL(k_attention_f32_split, dim3(NH, p.B, (TS + QB - 1) / QB), dim3(256), 0, st, p);
 }
 
 }  // namespace nasr

@@ -386,6 +386,10 @@ __global__ __launch_bounds__(256) void k_attention_row1(AttnParams a) {
 
 void launch_attention(const AttnParams &p, hipStream_t st) {
     const int TS = p.TS > 0 ? p.TS : p.T;
+    if (p.act_bf16 == 2 && p.T <= 16) {          // f32 operands on the split-bf16 kernel (kernels_attn_split.hip): launch_off_attention's convention
+        launch_attention_split(p, st);
+        return;
+    }
     if (p.act_bf16 && p.T == 1 && TS == 1) {
         hipLaunchKernelGGL(k_attention_row1, dim3(NH, p.B), dim3(256), 0, st, p);
         return;

@@ -293,6 +293,12 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         if (e->dec_started || e->off) return fail("f32_split_attn must be set before the first step or offline call");
         e->opt_f32_split_attn = value != 0;
     }
+    else if (!strcmp(key, "f32_split_attn_stream")) {
+        // read by every streaming attention launch (and captured into the step graphs): one arithmetic per engine life
+        if (value != 0 && value != 1) return fail("f32_split_attn_stream must be 0 or 1");
+        if (e->dec_started || e->off) return fail("f32_split_attn_stream must be set before the first step or offline call");
+        e->opt_f32_split_attn_stream = value != 0;
+    }
     else if (!strcmp(key, "pipeline")) {
         ApiGuard api_guard;
         HIPCHK(hipSetDevice(e->device));

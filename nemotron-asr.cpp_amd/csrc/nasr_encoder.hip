@@ -269,11 +269,11 @@ int enqueue_encoder(nasr_engine *e, const RowDesc *rows, const RowDesc *vrows, c
             const LayerW &L = e->L[l];
             AttnParams ap;
             memset(&ap, 0, sizeof(ap));
-            ap.q = e->q; ap.kv_pool = e->kv_pool[l]; ap.kv_slot_stride = (int64_t)2 * KVC * D; ap.act_bf16 = act;
+            ap.q = e->q; ap.kv_pool = e->kv_pool[l]; ap.kv_slot_stride = (int64_t)2 * KVC * D; ap.act_bf16 = e->attn_kind();
             ap.posproj = L.posproj[T]; ap.bias_u = L.bias_u; ap.bias_v = L.bias_v; ap.rows = rows; ap.B = B; ap.T = T; ap.TS = TS;
             ap.ctx_out = e->ctx; ap.ablate = (e->opt_ablate >> 6) & 3;
             const int KV = LCTX + T;
-            ProfScope ps(e, "k_attention", (double)B * (2.0 * KV + KV + T - 1) * D * e->esz, 2.0 * B * T * KV * D * 3);
+            ProfScope ps(e, ap.act_bf16 == 2 ? "k_attention_split" : "k_attention", (double)B * (2.0 * KV + KV + T - 1) * D * e->esz, 2.0 * B * T * KV * D * 3);
             if (!(e->opt_ablate & 2)) launch_attention(ap, st);
         };
         // conv module (:646-679): the depthwise conv continues from the stream's conv cache

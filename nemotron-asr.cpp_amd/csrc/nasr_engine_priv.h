@@ -192,6 +192,8 @@ struct nasr_engine {
     bool opt_f32_mfma = true;        // f32 GEMMs above four rows on v_mfma_f32_32x32x2_f32 (bit-identical to the FMA tile kernel)
     bool opt_f32_split = false;      // option "f32_split": an f32 engine's GEMMs above four rows as three bf16 MFMA products of split operands (k_gemm_f32_split; not the f32 kernels' bits)
     bool opt_f32_split_attn = false; // option "f32_split_attn": an f32 engine's OFFLINE attention as three bf16 MFMA products of split operands (k_off_attn_f32_split; not k_off_attn_f32's bits)
+    bool opt_f32_split_attn_stream = false; // option "f32_split_attn_stream": an f32 engine's STREAMING attention as three bf16 MFMA products of split operands (k_attention_f32_split; not k_attention<false>'s bits)
+    int attn_kind() const { return bf16 ? 1 : opt_f32_split_attn_stream ? 2 : 0; }               // AttnParams::act_bf16 of the unfused step's launch_attention
     int off_attn_kind() const { return bf16 ? 1 : opt_f32_split_attn ? 2 : 0; }                  // the integer of off_attn_qb / launch_off_attention
     int f32_gemm_kind() const { return opt_f32_split && !bf16 ? 2 : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
     char *gh = nullptr;                                                               // pinned host block

@@ -196,7 +196,8 @@ void launch_post(const PostParams &p, hipStream_t st);
 
 struct AttnParams {
     const float *q;       // [M][1024]
-    const void *kv_pool; int64_t kv_slot_stride; int act_bf16;
+    const void *kv_pool; int64_t kv_slot_stride;
+    int act_bf16;         // 0 = f32, 1 = bf16, 2 = f32 operands on the split-bf16 MFMA kernel (k_attention_f32_split, engine option "f32_split_attn_stream"; NOT k_attention<false>'s bits)
     const void *posproj;  // [n_rel][1024] act dtype, row r <-> rel = (70+T-1) - r
     const float *bias_u, *bias_v;  // [8][128]
     const RowDesc *rows; int B; int T;
@@ -205,6 +206,7 @@ struct AttnParams {
     int ablate;           // measurement only (engine option "ablate" bits 64 / 128): k_attention_mfma without its V^T LDS writes / without its K and position loads
 };
 void launch_attention(const AttnParams &p, hipStream_t st);
+void launch_attention_split(const AttnParams &p, hipStream_t st);          // kernels_attn_split.hip; the grid of k_attention_mfma
 
 struct ConvParams {
     const float *glu;     // [M][1024] f32

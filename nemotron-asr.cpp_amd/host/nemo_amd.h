@@ -109,6 +109,10 @@ bool nemo_set_f32_split(nemo_context *ctx, bool on);
 // position scores and P.V (nasr_engine_set_option "f32_split_attn"); before the first step or offline call; independent of nemo_set_f32_split; the
 // streaming attention is not touched; no effect on bf16
 bool nemo_set_f32_split_attn(nemo_context *ctx, bool on);
+// MI355X extension: an f32 engine's STREAMING attention on the bf16 MFMA, three products of split operands for the content scores, the position
+// scores and P.V (nasr_engine_set_option "f32_split_attn_stream"); before the first stream processes audio; independent of the two above; the K / V
+// caches, the offline calls and the decode are not touched; no effect on bf16
+bool nemo_set_f32_split_attn_stream(nemo_context *ctx, bool on);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
 // MI355X extension: forced alignment / transcript scoring of one whole utterance (nasr_engine_align): tokens = ids 0 .. 1023 of a KNOWN
