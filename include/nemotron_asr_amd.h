@@ -385,7 +385,11 @@ enum {
  * softmax and context; the K / V rings, the snapshot format, the offline calls, the fused small-M path and the decode are untouched.  Independent of
  * "f32_split" and "f32_split_attn".  Results differ from the default f32 engine's in the last bits; a stream's results depend on its own audio and on the
  * step's chunking only (batch == alone).  Values other than 0 / 1 and calls after the first step or offline call are REJECTED; no effect on a bf16
- * engine), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
+ * engine), "f32_split_planes" (default 0; 1: the GEMMs of "f32_split" read their weights from bf16 hi / lo planes that are made once, when both options are
+ * set -- in either order -- instead of splitting every weight fragment in registers on every pass (k_gemm_f32_split_planes).  A kernel-selection switch
+ * WITHIN "f32_split": every result is "f32_split"'s bit for bit.  Costs one more copy of the encoder's GEMM weights in device memory (counter
+ * "weight_plane_bytes"; about 2.4 GB at 24 layers); if that allocation fails the call fails and the option stays 0.  Inert unless the engine is NASR_DTYPE_F32
+ * and "f32_split" is 1; values other than 0 / 1 and calls after the first step or offline call are REJECTED), "decode_graph_iterations" (decode iterations a pipelined step's decode graph carries before the eager
  * fallback.  N >= 1: max(the synchronous step graph's count, min(10 frames + 1, N)).  Default 0 = auto: as 12, except that a step of ONE
  * frame and up to four rows on a bf16 engine (one to four streams at R = 0) carries 3 -- a frame of two symbols and the closing blank; its
  * decode graph runs behind the fourth encoder piece on a lane the host waits for in every call, so idle iterations there cost step time.
@@ -468,7 +472,7 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
  * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls),
  * "stream_saves" / "stream_restores" (nasr_stream_save calls that wrote a blob / nasr_stream_restore calls that made a stream; refused calls are not counted),
- * "history_calls" / "history_frames" (nasr_engine_history_* calls that succeeded / the frames they gathered out of the streams' rings), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * "history_calls" / "history_frames" (nasr_engine_history_* calls that succeeded / the frames they gathered out of the streams' rings), "weight_plane_bytes" (device bytes of the weight planes of engine option "f32_split_planes"; 0 while it is off or inert), "cut_drains" (pipelined calls that first completed the steps in flight because
  * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);

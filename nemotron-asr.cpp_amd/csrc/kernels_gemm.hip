@@ -1407,6 +1407,7 @@ template <int BM, int BN> __global__ void k_gemm_f32_mfma(GemmParams p, int n_gr
 // the 128 x 128 form (A/B runs only) holds a 96 KiB ring, one workgroup per CU: let it have the registers of one or two waves per SIMD (launch bounds and this on the declaration too: the attribute table below instantiates from it, and without them the kernel is compiled for 1 024 threads, 128 VGPRs)
 #define F32S_WAVES(BM, BN) __attribute__((amdgpu_waves_per_eu(1, (BM) + (BN) >= 256 ? 2 : 8)))
 template <int BM, int BN> __global__ __launch_bounds__(256) F32S_WAVES(BM, BN) void k_gemm_f32_split(GemmParams p, int n_groups, int m_chunks);     // ... and its split-bf16 form (option "f32_split"), below
+template <int BM, int BN> __global__ __launch_bounds__(256) F32S_WAVES(BM, BN) void k_gemm_f32_split_planes(GemmParams p, int n_groups, int m_chunks);     // ... and that with pre-split weight planes (option "f32_split_planes"), below
 
 static int g_num_cus = 256;      // MI355X; refreshed from the device below
 // The ring depths of round 5's loops stay beside the kernels whose counted waits are written for them; the plan's table states the four sizes they give as numbers.
@@ -1426,6 +1427,9 @@ void init_gemm_kernel_attributes() {
     hipFuncSetAttribute((const void *)k_gemm_f32_split<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 256 * 128);
     hipFuncSetAttribute((const void *)k_gemm_f32_split<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 192 * 128);
     hipFuncSetAttribute((const void *)k_gemm_f32_split<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 128 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split_planes<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 256 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split_planes<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 192 * 128);
+    hipFuncSetAttribute((const void *)k_gemm_f32_split_planes<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, F32M_NS * 128 * 128);
 }
 
 // Which instance, grid and LDS size: gemm_plan_bf16() (nasr_gemm_plan.h).  This maps the plan to a launch.
@@ -1773,6 +1777,142 @@ static void launch_gemm_f32_split(const GemmParams &p, hipStream_t st) {
     else launch_f32_split_tile<64, 64>(p, st);
 }
 
+// ------------------------------------------------------------------------------------
+// The split kernel on PRE-SPLIT weights (engine option "f32_split_planes").  Weights never change after upload, so their
+// hi / lo halves are formed once, by k_split_weight_planes with split_bf16x8 itself, into a plane of the weight's size and row pitch 4 K:
+//   row n, 32-deep chunk c = bytes [n 4 K + 128 c, + 128): 64 B hi of k = 32 c .. 32 c + 31 (bf16, k ascending), then 64 B lo of the same k.
+// A row chunk is still 128 B = eight 16-byte columns, so the DMA side is k_gemm_f32_split's to the letter: ring geometry, SLOT and DMA, the
+// hand-counted vmcnt, the glds16 source addressing and its XOR swizzle by (row >> 1) & 7.  What changes is what a weight column MEANS: logical
+// columns 0 .. 3 are hi of k = 8 col .. + 8, columns 4 .. 7 lo of k = 8 (col - 4) .. + 8.  The lane of k step s and half kh (k = 16 s + 8 kh .. + 8)
+// reads its w_hi fragment as column 2 s + kh and its w_lo fragment as column 4 + 2 s + kh: two ds_read_b128 and no VALU, where the split kernel
+// reads columns 4 s + 2 kh and + 1 and splits them.  Activation rows are f32 and are split in registers as there.
+//   BANKS: the 32 lanes of a half wave read ONE logical column col of 32 consecutive rows; lane l31's 16 bytes lie at
+//   row 128 + ((col ^ ((row >> 1) & 7)) << 4).  (row & 1) picks the 128-byte half of the 256-byte bank line and (row >> 1) & 7 runs through all eight
+//   values over 16 consecutive rows, so col ^ that does too -- whatever col is: any 16 consecutive lanes cover the 64 banks once.  The argument of the
+//   split kernel never used which column; it holds for 2 s + kh and 4 + 2 s + kh as for 4 s + 2 kh.  The two halves of a wave read different
+//   columns (kh) in separate passes of the b128 read, as there.
+//   BITS: the plane holds exactly what split_bf16x8 forms in registers, the MFMA operands are therefore the same, and the issue order is the same
+//   (w_hi a_hi, w_lo a_hi, w_hi a_lo per accumulator and k step, k steps ascending from zero, no split-K): every output element has
+//   k_gemm_f32_split's bits in every tile form (tests/test_gpu_gemm_f32_split_planes.py: `==`).
+// Resources: DESIGN section 26.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_split_weight_planes(const float *__restrict__ w, uint4 *__restrict__ plane, size_t n_groups8) {
+    // one thread per 8 consecutive k: group g = (row chunk g / 4, quarter g % 4) since K % 32 == 0 makes chunks contiguous in row-major W
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_groups8; g += (size_t)gridDim.x * blockDim.x) {
+        const float4 x0 = *(const float4 *)(w + g * 8), x1 = *(const float4 *)(w + g * 8 + 4);
+        bf16x8 hi, lo;
+        split_bf16x8(x0, x1, hi, lo);
+        uint4 *chunk = plane + (g >> 2) * 8;                       // 128 B = eight uint4
+        chunk[g & 3] = __builtin_bit_cast(uint4, hi);
+        chunk[4 + (g & 3)] = __builtin_bit_cast(uint4, lo);
+    }
+}
+// plane: N K 4 bytes, 16-byte aligned; K % 32 == 0
+void launch_split_weight_planes(const float *w_f32, void *plane, int N, int K, hipStream_t st) {
+    const size_t groups = (size_t)N * K / 8;
+    const unsigned blocks = (unsigned)std::min<size_t>((groups + 255) / 256, (size_t)g_num_cus * 16);
+    if (groups) hipLaunchKernelGGL(k_split_weight_planes, dim3(blocks), dim3(256), 0, st, w_f32, (uint4 *)plane, groups);
+}
+
+template <int BM, int BN>
+__global__ __launch_bounds__(256) F32S_WAVES(BM, BN)
+void k_gemm_f32_split_planes(GemmParams p, int n_groups, int m_chunks) {
+    constexpr int ROWS = BM + BN, SLOT = ROWS * 128, DMA = ROWS / 32;      // DMA instructions per wave and chunk (8 rows each)
+    constexpr int IM = BM / 64, IN = BN / 64;                              // 32 x 32 blocks per wave along m / n
+    extern __shared__ __attribute__((aligned(16))) char ring[];
+    const int id = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int mc = id % m_chunks, ng = id / m_chunks;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, kh = lane >> 5;
+    const int m0 = mc * BM, n0 = ng * BN, nchunks = p.K / F32M_KC;
+    // this wave fills rows [wave * ROWS / 4, + ROWS / 4) of every slot: activation rows (f32) first, the plane's weight rows (hi | lo) behind them
+    const char *src[DMA];
+#pragma unroll
+    for (int j = 0; j < DMA; j++) {
+        const int row = wave * (ROWS / 4) + j * 8 + (lane >> 3), c4 = lane & 7;
+        const char *base;
+        if (row < BM) { int m = m0 + row; if (m >= p.M) m = p.M - 1; base = a_row_ptr(p, m, 4); }
+        else base = (const char *)p.W_planes + (size_t)(n0 + row - BM) * p.K * 4;
+        src[j] = base + (((c4 ^ (row >> 1)) & 7) << 4);
+    }
+    const unsigned ring_base = (unsigned)(size_t)(__attribute__((address_space(3))) char *)ring;
+    auto issue = [&](int kc, int slot) {
+        const unsigned sb = ring_base + slot * SLOT + wave * (ROWS / 4) * 128;
+#pragma unroll
+        for (int j = 0; j < DMA; j++) glds16(src[j] + (size_t)kc * 128, sb + j * 1024);
+    };
+    f32x16 acc[IN][IM];
+#pragma unroll
+    for (int a = 0; a < IN; a++)
+#pragma unroll
+        for (int b = 0; b < IM; b++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc[a][b][i] = 0.f;
+    issue(0, 0);
+    if (nchunks > 1) issue(1, 1);
+    int slot = 0;
+    for (int i = 0; i < nchunks; i++) {
+        // as in k_gemm_f32_split: chunks i and i + 1 are the only ones outstanding, DMA instructions each, in order -> vmcnt(DMA) = chunk i has landed
+        if (i + 1 < nchunks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();              // ... for every wave; and every wave's MFMAs have consumed the fragments of chunk i - 1
+        if (i + 2 < nchunks) issue(i + 2, slot == 0 ? 2 : slot - 1);     // into the slot chunk i - 1 has just left
+        const char *sp = ring + slot * SLOT;
+        const char *arow = sp + (wm * (BM / 2) + l31) * 128, *wrow = sp + (BM + wn * (BN / 2) + l31) * 128;
+        const int swa = ((wm * (BM / 2) + l31) >> 1) & 7, sww = ((BM + wn * (BN / 2) + l31) >> 1) & 7;     // + 32 rows: the same swizzle
+#pragma unroll
+        for (int s = 0; s < F32M_KC / 16; s++) {
+            const int c = 4 * s + 2 * kh, ch = 2 * s + kh;           // activation: f32 columns c, c + 1; weight: hi column ch, lo column 4 + ch
+            bf16x8 ah[IM], al[IM], wh[IN], wl[IN];
+#pragma unroll
+            for (int a = 0; a < IN; a++) {
+                wh[a] = *(const bf16x8 *)(wrow + a * 32 * 128 + ((ch ^ sww) << 4));
+                wl[a] = *(const bf16x8 *)(wrow + a * 32 * 128 + (((4 + ch) ^ sww) << 4));
+            }
+#pragma unroll
+            for (int b = 0; b < IM; b++)
+                split_bf16x8(*(const float4 *)(arow + b * 32 * 128 + ((c ^ swa) << 4)), *(const float4 *)(arow + b * 32 * 128 + (((c + 1) ^ swa) << 4)), ah[b], al[b]);
+            // the split kernel's order: term by term over the wave's blocks, every accumulator sees w_hi a_hi, w_lo a_hi, w_hi a_lo
+#pragma unroll
+            for (int t = 0; t < 3; t++)
+#pragma unroll
+                for (int a = 0; a < IN; a++)
+#pragma unroll
+                    for (int b = 0; b < IM; b++)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t == 1 ? wl[a] : wh[a], t == 2 ? al[b] : ah[b], acc[a][b], 0, 0, 0);
+        }
+        slot = slot + 1 == F32M_NS ? 0 : slot + 1;
+    }
+#pragma unroll
+    for (int a = 0; a < IN; a++)
+#pragma unroll
+        for (int b = 0; b < IM; b++) {
+            const int m = m0 + wm * (BM / 2) + b * 32 + l31;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int n = n0 + wn * (BN / 2) + a * 32 + g * 8 + kh * 4;
+                epi_quad<false>(p, 0, m, n, acc[a][b][4 * g], acc[a][b][4 * g + 1], acc[a][b][4 * g + 2], acc[a][b][4 * g + 3]);
+            }
+        }
+}
+template <int BM, int BN> static void launch_f32_split_planes_tile(const GemmParams &p, hipStream_t st) {
+    const int n_groups = p.N / BN, m_chunks = (p.M + BM - 1) / BM;
+    hipLaunchKernelGGL((k_gemm_f32_split_planes<BM, BN>), dim3(n_groups * m_chunks), dim3(256), F32M_NS * (BM + BN) * 128, st, p, n_groups, m_chunks);
+}
+// f32_fma_tile kind 3: the tile rule and the forced forms of kind 2 (same bits in every form and in either kernel, so the choice is free).
+// Kind 3 without a plane is a programming error: reported, nothing launched -- never another kernel in silence.
+static void launch_gemm_f32_split_planes(const GemmParams &p, hipStream_t st) {
+    if (!p.W_planes || ((size_t)p.W_planes & 15)) {
+        fprintf(stderr, "nasr: launch_gemm_f32: f32_fma_tile kind 3 (M = %d, N = %d, K = %d) without a 16-byte aligned weight plane: not launched\n", p.M, p.N, p.K);
+        return;
+    }
+    const int force = (p.f32_fma_tile >> 4) & 3;
+    const long t64w = (long)(p.N / 128) * ((p.M + 63) / 64);
+    if (p.N % 128 == 0 && force == 1) launch_f32_split_planes_tile<128, 128>(p, st);
+    else if (p.N % 128 == 0 && (force ? force == 2 : t64w >= F32S_T64W)) launch_f32_split_planes_tile<64, 128>(p, st);
+    else launch_f32_split_planes_tile<64, 64>(p, st);
+}
+
 void launch_gemm_f32(const GemmParams &p0, hipStream_t st) {
     GemmParams p = p0;
     p.splits = 1;
@@ -1783,6 +1923,7 @@ void launch_gemm_f32(const GemmParams &p0, hipStream_t st) {
     const bool mfma_shape = p.M > F32R_MMAX && p.N % 64 == 0 && p.K % F32M_KC == 0 && p.lda % 4 == 0 && ((size_t)p.A & 15) == 0 && ((size_t)p.W & 15) == 0 &&
                             (p.rows_per_batch == 0 || (p.batch_stride % 4 == 0));
     if ((p.f32_fma_tile & 15) == 2 && mfma_shape) { launch_gemm_f32_split(p, st); return; }
+    if ((p.f32_fma_tile & 15) == 3 && mfma_shape) { launch_gemm_f32_split_planes(p, st); return; }
     if (!p.f32_fma_tile && mfma_shape) {
         // 128 x 128 tiles when they fill the chip (or the width allows nothing else to), 64 x 64 otherwise: more, smaller workgroups, three per CU
         const long big = (long)(p.N / 128) * ((p.M + 127) / 128);

@@ -286,6 +286,17 @@ extern "C" int nasr_engine_set_option(nasr_engine *e, const char *key, int value
         if (value != 0 && value != 1) return fail("f32_split must be 0 or 1");
         if (e->dec_started || e->off) return fail("f32_split must be set before the first step or offline call");
         e->opt_f32_split = value != 0;
+        ApiGuard api_guard;
+        if (sync_weight_planes(e)) return -1;          // "f32_split_planes" set before this option: its planes come and go with it
+    }
+    else if (!strcmp(key, "f32_split_planes")) {
+        // the split GEMMs' weights as pre-split bf16 hi / lo planes (f32_split's bits, one more copy of those weights); inert unless the engine is F32 and
+        // "f32_split" is 1.  The planes' addresses are captured into the step graphs: taken like "f32_split"
+        if (value != 0 && value != 1) return fail("f32_split_planes must be 0 or 1");
+        if (e->dec_started || e->off) return fail("f32_split_planes must be set before the first step or offline call");
+        e->opt_f32_split_planes = value != 0;
+        ApiGuard api_guard;
+        if (sync_weight_planes(e)) return -1;
     }
     else if (!strcmp(key, "f32_split_attn")) {
         // read by every offline call's work items (64 query rows per item instead of 16) and attention launches: one arithmetic per engine life
@@ -1102,6 +1113,7 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)
     else if (!strcmp(name, "lm_states")) *value = e->lm ? (int64_t)e->lm->states.size() : 0;
     else if (!strcmp(name, "lm_max_probe")) *value = e->lm ? e->lm->max_probe : 0;
+    else if (!strcmp(name, "weight_plane_bytes")) *value = (int64_t)e->plane_bytes;                   // option "f32_split_planes": bytes of the weight planes in device memory (0: none)
     else if (!strcmp(name, "lanes")) *value = e->pipe_ready ? e->n_lanes : 0;      // HIP streams found to overlap (0: not picked yet)
     else return fail("unknown counter '%s'", name);
     return 0;

@@ -16,7 +16,7 @@ int run_gemm(nasr_engine *e, GemmParams &g, bool f32_weights, const char *tag) {
     const char *name = !use_bf16 ? "k_gemm_f32" : (g.M <= gemm_skinny_max_m() ? "k_gemm_skinny" : "k_gemm_tiled");
     ProfScope ps(e, name, gemm_bytes(e, g.M, g.N, g.K, use_bf16 ? 2 : 4), 2.0 * g.M * g.N * g.K);
     g.coresident = e->opt_gemm_cores == 0 ? 3 : e->opt_gemm_cores == 1 ? 2 : (e->gemm_coresident ? 1 : 0);
-    g.f32_fma_tile = e->f32_gemm_kind();
+    g.f32_fma_tile = e->f32_gemm_kind(); g.W_planes = e->f32_plane(g.W);
     g.no_persist = e->opt_persist_gemm ? 0 : 1;
     g.no_wide = e->opt_wide_tiles ? 0 : 1;
     g.wide_rows = e->opt_wide_tiles == 256 ? 256 : e->opt_wide_tiles == 3 ? 2 : 0;
@@ -406,11 +406,11 @@ int enqueue_encoder_tail(nasr_engine *e, float *x, float *hfuse, float *encproj,
     // ---- a-11 prompt fusion (multilingual only, src/nemo-ggml.cpp:1087-1105) ---------------------
     if (e->hp.num_prompts > 0) {
         GemmParams g = gemm_desc(x, D, e->pk1a, Mg, 2048, D);
-        g.epi = EPI_BIAS_F32; g.out_f32 = hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->f32_gemm_kind();
+        g.epi = EPI_BIAS_F32; g.out_f32 = hfuse; g.ldo = 2048; g.bias = e->pk1_b; g.f32_fma_tile = e->f32_gemm_kind(); g.W_planes = e->f32_plane(g.W);
         { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, 2048, D, 4), 2.0 * M * 2048 * D); launch_gemm_f32(g, st); }
         launch_prompt_add_relu(hfuse, e->pk1p, rows, M, rows_per_prompt, e->hp.num_prompts, st);
         g = gemm_desc(hfuse, 2048, e->pk2_w, Mg, D, 2048);
-        g.epi = EPI_BIAS_F32; g.out_f32 = x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->f32_gemm_kind();
+        g.epi = EPI_BIAS_F32; g.out_f32 = x; g.ldo = D; g.bias = e->pk2_b; g.f32_fma_tile = e->f32_gemm_kind(); g.W_planes = e->f32_plane(g.W);
         { ProfScope ps(e, "k_gemm_f32", gemm_bytes(e, M, D, 2048, 4), 2.0 * M * D * 2048); launch_gemm_f32(g, st); }
     }
     if (tap && tap()) return -1;

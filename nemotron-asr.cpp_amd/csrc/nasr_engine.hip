@@ -397,7 +397,7 @@ int ensure_posproj(nasr_engine *e, int T) {
         memset(&g, 0, sizeof(g));
         g.A = demb; g.W = L.wpos_f32; g.M = n_rel; g.N = D; g.K = D; g.lda = D;
         g.epi = EPI_PART_F32; g.out_f32 = dout; g.ldo = D; g.splits = 1;
-        g.f32_fma_tile = e->f32_gemm_kind();
+        g.f32_fma_tile = e->f32_gemm_kind(); g.W_planes = e->f32_plane(g.W);
         launch_gemm_f32(g, e->st);
         if (e->bf16) {
             bf16_t *pp;
@@ -414,6 +414,47 @@ int ensure_posproj(nasr_engine *e, int T) {
     }
     hipFree(demb);
     hipFree(dout);
+    return 0;
+}
+
+// Option "f32_split_planes": the bf16 hi / lo plane (launch_split_weight_planes) of every f32 weight that a split GEMM of this engine reads -- the subsampling
+// pointwise / out projections, per layer W1, W2 of both feed-forwards, QKV, Wo, pw1, pw2 and the position projection, the prompt-fusion pair -- in ONE
+// allocation of the weights' total size.  Called by the setters of "f32_split" and "f32_split_planes", which are both refused after the first step or offline
+// call: every launch site then finds the planes there (f32_gemm_kind() = 3) or finds none (2), for the engine's life.  The f32 weights stay: the <= 4-row
+// kernel, the fused path and the decode read them.
+int sync_weight_planes(nasr_engine *e) {
+    const bool want = e->opt_f32_split_planes && e->opt_f32_split && !e->bf16;
+    if (want == (e->plane_block != nullptr)) return 0;
+    HIPCHK(hipSetDevice(e->device));
+    if (!want) {
+        HIPCHK(hipStreamSynchronize(e->st));          // a position projection made at stream create may still be reading them
+        hipFree(e->plane_block);
+        e->plane_block = nullptr; e->plane_bytes = 0; e->plane_of.clear();
+        return 0;
+    }
+    struct Wt { const void *w; int N, K; };
+    std::vector<Wt> ws = {{e->w3, SUBC, SUBC}, {e->w6, SUBC, SUBC}, {e->sub_out_w, D, SUBFLAT}};
+    for (const LayerW &L : e->L)
+        for (const Wt &w : {Wt{L.ff1_w1, FF, D}, Wt{L.ff1_w2, D, FF}, Wt{L.wqkv, 3 * D, D}, Wt{L.wo, D, D}, Wt{L.pw1, 2 * D, D}, Wt{L.pw2, D, D},
+                            Wt{L.ff2_w1, FF, D}, Wt{L.ff2_w2, D, FF}, Wt{L.wpos_f32, D, D}})
+            ws.push_back(w);
+    if (e->hp.num_prompts > 0) { ws.push_back({e->pk1a, 2048, D}); ws.push_back({e->pk2_w, D, 2048}); }
+    size_t total = 0;
+    for (const Wt &w : ws) total += (size_t)w.N * w.K * 4;          // every size is a multiple of 128 B: the planes stay 16-byte aligned back to back
+    char *block = nullptr;
+    if (hipMalloc((void **)&block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        e->opt_f32_split_planes = false;
+        return fail("f32_split_planes: no memory for %.2f GB of weight planes (one more copy of the encoder's GEMM weights); the option stays off", total / 1e9);
+    }
+    size_t off = 0;
+    for (const Wt &w : ws) {
+        launch_split_weight_planes((const float *)w.w, block + off, w.N, w.K, e->st);
+        e->plane_of[w.w] = block + off;
+        off += (size_t)w.N * w.K * 4;
+    }
+    e->plane_block = block; e->plane_bytes = total;
+    HIPCHK(hipStreamSynchronize(e->st));
     return 0;
 }
 
@@ -664,6 +705,7 @@ void engine_destroy_impl(nasr_engine *e) {
     if (e->raw_stage) hipFree(e->raw_stage);
     if (e->snap_stage) hipFree(e->snap_stage);
     if (e->hist_ring) hipFree(e->hist_ring);
+    if (e->plane_block) hipFree(e->plane_block);
     if (e->snap_pin.p) hipHostFree(e->snap_pin.p);
     if (e->snap_pin.copied) hipEventDestroy(e->snap_pin.copied);
     for (auto *ring : {e->pcm_pin, e->raw_pin})

@@ -195,7 +195,13 @@ struct nasr_engine {
     bool opt_f32_split_attn_stream = false; // option "f32_split_attn_stream": an f32 engine's STREAMING attention as three bf16 MFMA products of split operands (k_attention_f32_split; not k_attention<false>'s bits)
     int attn_kind() const { return bf16 ? 1 : opt_f32_split_attn_stream ? 2 : 0; }               // AttnParams::act_bf16 of the unfused step's launch_attention
     int off_attn_kind() const { return bf16 ? 1 : opt_f32_split_attn ? 2 : 0; }                  // the integer of off_attn_qb / launch_off_attention
-    int f32_gemm_kind() const { return opt_f32_split && !bf16 ? 2 : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
+    // option "f32_split_planes": the split GEMMs read their weights from pre-split bf16 hi / lo planes (k_gemm_f32_split_planes: f32_split's bits).  Inert unless the
+    // engine is F32 and "f32_split" is 1; then one block holds the plane of every weight a split GEMM reads (sync_weight_planes makes and frees it as the two options are set)
+    bool opt_f32_split_planes = false;
+    char *plane_block = nullptr; size_t plane_bytes = 0;
+    std::map<const void *, const void *> plane_of;   // f32 weight -> its plane inside plane_block
+    int f32_gemm_kind() const { return opt_f32_split && !bf16 ? (plane_block ? 3 : 2) : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
+    const void *f32_plane(const void *W) const { auto it = plane_of.find(W); return it == plane_of.end() ? nullptr : it->second; }   // ... and its GemmParams::W_planes (null: none)
     char *gh = nullptr;                                                               // pinned host block
     int *gh_collect = nullptr;       // pinned landing zone of the token gather: [B][1 + COLLECT_STRIDE] + n_active
     int64_t graph_replays = 0, eager_steps = 0, decode_fallbacks = 0, decode_fallback_rounds = 0;
@@ -366,6 +372,8 @@ void pack_f32_mfma(const std::vector<float> &w, int N, int K, bool lstm_order, s
 void host_pos_emb(int position, float *out);
 int load_weights(nasr_engine *e, const nasr_weight_desc *w, int n_w);
 int ensure_posproj(nasr_engine *e, int T);
+// makes the weight planes when "f32_split_planes" and "f32_split" are both 1 on an F32 engine, frees them otherwise; a failure leaves none and "f32_split_planes" off
+int sync_weight_planes(nasr_engine *e);
 int alloc_ws(nasr_engine *e, nasr_engine::WS &w);
 void use_ws(nasr_engine *e, const nasr_engine::WS &w);
 void engine_destroy_impl(nasr_engine *e);

@@ -101,8 +101,13 @@ struct GemmParams {
     // f32 GEMMs above four rows run on the f32-input MFMA (k_gemm_f32_mfma); 1 = the FMA tile kernel k_gemm_f32 instead (engine
     // option "f32_mfma" = 0: the other side of the bit-identity test); 2 = the split-bf16 kernel k_gemm_f32_split (engine option "f32_split":
     // three bf16 MFMA products of hi / lo operand halves, NOT the bits of the other two) where k_gemm_f32_mfma's shape conditions hold,
-    // else as 1.  With 2, bits 4-5 force one of its tile forms (16: 128 x 128, 32: 64 x 128, 48: 64 x 64; probes and the tile-shape identity test)
+    // else as 1.  With 2, bits 4-5 force one of its tile forms (16: 128 x 128, 32: 64 x 128, 48: 64 x 64; probes and the tile-shape identity test).
+    // 3 = as 2 with the weights read from W_planes (k_gemm_f32_split_planes, engine option "f32_split_planes": kind 2's bits, same forced forms);
+    // 3 with a null W_planes where the split kernel's shape conditions hold is a programming error: reported on stderr, nothing launched
     int f32_fma_tile;
+    // the pre-split image of W that launch_split_weight_planes makes (N K 4 bytes, row pitch 4 K; per 32-deep chunk 64 B of bf16 hi, then 64 B of bf16 lo);
+    // null = no plane.  Read by kind 3 alone; W stays what the <= 4-row kernel and the FMA tile kernel read
+    const void *W_planes;
     // 1 = never the persistent tile loop (k_gemm_persist), whatever the size: engine option "persistent_gemm" = 0, the other side
     // of its bit-identity test
     int no_persist;
@@ -131,6 +136,7 @@ void init_fused_kernel_attributes();
 void launch_gemm_bf16(const GemmParams &p, hipStream_t st);      // the kernel it takes and the rules its callers ask (gemm_chain_ok, gemm_resid_foldable, ...): nasr_gemm_plan.h
 void launch_gemm_f32(const GemmParams &p, hipStream_t st);
 void launch_pack_weight_bf16(const float *w_f32, bf16_t *packed, int N, int K, hipStream_t st);
+void launch_split_weight_planes(const float *w_f32, void *plane, int N, int K, hipStream_t st);   // the hi / lo plane of an f32 weight [N][K], K % 32 == 0 (GemmParams::W_planes)
 void launch_f32_to_bf16(const float *in, bf16_t *out, int64_t n, hipStream_t st);
 
 struct MelParams {

@@ -44,7 +44,7 @@ static int ensure_offline_pos(nasr_engine *e, OfflineState *o) {
         memset(&g, 0, sizeof(g));
         g.A = demb; g.W = L.wpos_f32; g.M = OFFLINE_NREL; g.N = D; g.K = D; g.lda = D;
         g.epi = EPI_PART_F32; g.out_f32 = dout; g.ldo = D; g.splits = 1;
-        g.f32_fma_tile = e->f32_gemm_kind();
+        g.f32_fma_tile = e->f32_gemm_kind(); g.W_planes = e->f32_plane(g.W);
         launch_gemm_f32(g, e->st);
         void *pp;
         if (off_alloc(o, &pp, n * e->esz)) return -1;

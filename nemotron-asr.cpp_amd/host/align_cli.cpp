@@ -13,11 +13,13 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm> <transcript.txt | -> [--f32] [--f32-split-attn] [--device N] [--lang CODE] [--print-tokens]\n"
+            "Usage: %s <model.gguf> <audio.pcm> <transcript.txt | -> [--f32] [--f32-split-planes] [--f32-split-attn] [--device N] [--lang CODE] [--print-tokens]\n"
             "  audio: raw s16le, 16 kHz, mono, one whole utterance (up to 2048 encoder frames = 163.8 s)\n"
             "  transcript: text; every word is cut into vocabulary pieces by greedy longest match, `ids:12,55,9` gives token ids literally\n"
             "  prints one line per word: start_s end_s confidence word   (80 ms frames; confidence = exp(min ln P of the word's tokens)),\n"
             "  then `loglik X` = ln P(transcript | audio) and `best X` = the score of the best alignment\n"
+            "  --f32-split-planes: the f32 engine (as --f32) with its encoder GEMMs as three bf16 matrix products of split operands (engine option f32_split),\n"
+            "  reading weights that were split into bf16 hi / lo planes once at start-up (engine option f32_split_planes)\n"
             "  --f32-split-attn: the f32 engine (as --f32) with its attention as three bf16 matrix products of split operands (engine option f32_split_attn)\n"
             "  --print-tokens: also `tokens ...` and `frames ...`, the ids and the encoder frame each is emitted at\n",
             prog);
@@ -27,13 +29,14 @@ int main(int argc, char **argv) {
     if (argc < 4) { usage(argv[0]); return 1; }
     const char *model_path = argv[1], *audio_path = argv[2], *text_path = argv[3], *lang = nullptr;
     int device = 0, dtype = 1;
-    bool print_tokens = false, f32_split_attn = false;
+    bool print_tokens = false, f32_split_attn = false, f32_split_planes = false;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--lang" && i + 1 < argc) lang = argv[++i];
         else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
         else if (a == "--f32") dtype = 0;
         else if (a == "--f32-split-attn") { dtype = 0; f32_split_attn = true; }
+        else if (a == "--f32-split-planes") { dtype = 0; f32_split_planes = true; }
         else if (a == "--print-tokens") print_tokens = true;
         else { usage(argv[0]); return 1; }
     }
@@ -53,6 +56,7 @@ int main(int argc, char **argv) {
     nemo_context *ctx = nemo_init_with_device(model_path, device, dtype, 1);
     if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
     if (f32_split_attn && !nemo_set_f32_split_attn(ctx, true)) { nemo_free(ctx); return 1; }
+    if (f32_split_planes && (!nemo_set_f32_split(ctx, true) || !nemo_set_f32_split_planes(ctx, true))) { nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     // the transcript, word by word
     const boost_phrases::Vocab vocab(ctx->vocab);

@@ -113,6 +113,10 @@ bool nemo_set_f32_split_attn(nemo_context *ctx, bool on);
 // scores and P.V (nasr_engine_set_option "f32_split_attn_stream"); before the first stream processes audio; independent of the two above; the K / V
 // caches, the offline calls and the decode are not touched; no effect on bf16
 bool nemo_set_f32_split_attn_stream(nemo_context *ctx, bool on);
+// MI355X extension: the GEMMs of nemo_set_f32_split read their weights from bf16 hi / lo planes made once (nasr_engine_set_option "f32_split_planes"):
+// the same results bit for bit, one more copy of the encoder's GEMM weights in GPU memory; before the first step or offline call; no effect unless
+// nemo_set_f32_split is on and the engine is f32
+bool nemo_set_f32_split_planes(nemo_context *ctx, bool on);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
 // MI355X extension: forced alignment / transcript scoring of one whole utterance (nasr_engine_align): tokens = ids 0 .. 1023 of a KNOWN
