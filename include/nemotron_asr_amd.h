@@ -447,6 +447,12 @@ enum {
  * (host/token_confidence.h).  Under "phrase_boost" / "lm_fusion" the value stays the model's.  Tokens, frames, iteration counts, decoder state
  * and the values of the other read-outs are bit-identical to 0.  It selects the decode kernels that are captured into the step graphs and
  * allocates a ring per stream, so it is REJECTED after the first step or offline call.
+ * "joint_split" (default 0; 1: the joint's output layer, 640 -> 1025, of every decode iteration above 64 rows and of the beam search without phrase boosting
+ * runs as three bf16 MFMA products of split operands on bf16 hi / lo planes of the weight made once (k_dec_joint_split) instead of on the
+ * f32 MFMA.  Any engine dtype; independent of the "f32_split*" keys.  A logit differs from the default's by at most 3 * 2^-16 per unit of |x||w| (the order of
+ * the decode's stated 1e-5); a row's logits depend on the row alone.  Iterations of up to 64 rows, the boosted beam evaluation and forced alignment are
+ * untouched.  Costs 2.6 MB of device memory (counter "joint_plane_bytes", 0 while off).  Values other than 0 / 1 and calls after the first step or offline
+ * call are REJECTED.)
  * "frame_history" (0 default; N = 64 .. 2048 in multiples of 64, other values are refused): a capability like "frame_blank_logprobs" -- with
  * N every live stream keeps the joint's encoder-projection rows ([640] f32, prompt fused in) of the last N encoder frames it decoded, in a
  * device ring filled by one more small launch at the head of every step's decode (csrc/nasr_history.h), so that the offline modes can run
@@ -472,7 +478,7 @@ int nasr_engine_set_boost_phrases(nasr_engine *e, int n_phrases, const int32_t *
  * 2 with no phrases; 0 when engine option "phrase_boost" is off), "decode_fallbacks" / "decode_fallback_rounds" (graph steps whose
  * decode needed more iterations than their graph carries and was completed eagerly / the host round trips that took), "stream_forks" / "stream_previews" (nasr_stream_fork launches, a preview's included / nasr_engine_preview calls),
  * "stream_saves" / "stream_restores" (nasr_stream_save calls that wrote a blob / nasr_stream_restore calls that made a stream; refused calls are not counted),
- * "history_calls" / "history_frames" (nasr_engine_history_* calls that succeeded / the frames they gathered out of the streams' rings), "weight_plane_bytes" (device bytes of the weight planes of engine option "f32_split_planes"; 0 while it is off or inert), "cut_drains" (pipelined calls that first completed the steps in flight because
+ * "history_calls" / "history_frames" (nasr_engine_history_* calls that succeeded / the frames they gathered out of the streams' rings), "weight_plane_bytes" (device bytes of the weight planes of engine option "f32_split_planes"; 0 while it is off or inert), "joint_plane_bytes" (device bytes of the joint's weight planes the decode reads under engine option "joint_split"; 0 while it is off), "cut_drains" (pipelined calls that first completed the steps in flight because
  * they are cut into lane pieces differently: another piece count, or the other side of four rows per step on a bf16 engine).  Returns 0, or -1 for an unknown name.  Like every entry point that takes an
  * engine, call it from the thread that steps that engine: it reads the graph caches without a lock. */
 int nasr_engine_get_counter(const nasr_engine *e, const char *name, int64_t *value);

@@ -790,6 +790,7 @@ static void launch_joint_commit(const DecParams &p, hipStream_t st) {
     }
     const int rows = p.B * p.T;
     if (rows <= nasr_lp::SMALL_ROWS) hipLaunchKernelGGL((k_dec_joint<LP, BOOST, ALT, LMF, ENT>), dim3((VOCAB + 15) / 16), dim3(256), 0, st, p);
+    else if (p.out_planes) launch_joint_split<LP, BOOST, ALT, LMF, ENT>(p, st);      // engine option "joint_split": the same form on the bf16 MFMA (kernels_joint_split.hip)
     else hipLaunchKernelGGL((k_dec_joint_tiled<LP, BOOST, ALT, false, LMF, ENT>), dim3((VOCAB + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, p);
     if constexpr (LP) {
         if (p.frame_blank) {                           // "frame_blank_logprobs": the commit variant that also fills the ring
@@ -812,7 +813,8 @@ void launch_decode_candidates(const DecParams &p, hipStream_t st) {
 // always this kernel, so the logits of a row do not depend on how many rows the sub-batch has
 void launch_decode_rows(const DecParams &p, hipStream_t st) {
     launch_decode_candidates(p, st);
-    hipLaunchKernelGGL((k_dec_joint_tiled<true, false, true>), dim3((VOCAB + 63) / 64, (p.B * p.T + 63) / 64), dim3(256), 0, st, p);
+    if (p.out_planes) launch_joint_split<true, false, true, false, false>(p, st);      // engine option "joint_split": a row's logits still depend on the row alone
+    else hipLaunchKernelGGL((k_dec_joint_tiled<true, false, true>), dim3((VOCAB + 63) / 64, (p.B * p.T + 63) / 64), dim3(256), 0, st, p);
 }
 // the boosted beam evaluation: the same with the tiled joint in its BEAMB form (p.boost_bonus, p.boost_state = the beam's own per-slot array,
 // p.raw_logits [B * T][1040])

@@ -169,11 +169,11 @@ extern "C" int nasr_stream_set_boost(nasr_stream *s, int enable) {
 // valid.  A later change would be a silent no-op for the graphs that exist (and the tokens already in the ring would have no value): they are taken
 // until the first decode has been enqueued or the first offline call has run.  "lm_refresh_fold" (0 = the bias rows are refreshed by a launch of
 // their own) and "lm_commit_lookup" (1 = k_dec_commit looks the emitted token up again) are measurement only (profiles/greedy_lm.md)
-static const char *const DECODE_OPTIONS[] = {"token_logprobs", "phrase_boost", "lm_fusion", "lm_refresh_fold", "lm_commit_lookup", "token_alternatives", "frame_blank_logprobs", "token_entropy"};
+static const char *const DECODE_OPTIONS[] = {"token_logprobs", "phrase_boost", "lm_fusion", "lm_refresh_fold", "lm_commit_lookup", "token_alternatives", "frame_blank_logprobs", "token_entropy", "joint_split"};
 static bool is_decode_option(const char *key) { return std::any_of(std::begin(DECODE_OPTIONS), std::end(DECODE_OPTIONS), [key](const char *k) { return !strcmp(key, k); }); }
 static int set_decode_option(nasr_engine *e, const char *key, int value) {      // key is one of DECODE_OPTIONS; the caller holds an ApiGuard
     const auto is = [key](const char *k) { return !strcmp(key, k); };
-    if ((is("token_logprobs") || is("lm_fusion") || is("frame_blank_logprobs")) && value != 0 && value != 1) return fail("%s must be 0 or 1", key);
+    if ((is("token_logprobs") || is("lm_fusion") || is("frame_blank_logprobs") || is("joint_split")) && value != 0 && value != 1) return fail("%s must be 0 or 1", key);
     if (is("phrase_boost") && value != 0 && (value < nasr_boost::MIN_STATES || value > nasr_boost::MAX_STATES))
         return fail("phrase_boost must be 0 or the automaton's state capacity, %d .. %d", nasr_boost::MIN_STATES, nasr_boost::MAX_STATES);
     if (is("token_alternatives") && !nasr_topk::valid_k(value)) return fail("token_alternatives must be 0 .. %d", nasr_topk::KMAX);
@@ -189,6 +189,17 @@ static int set_decode_option(nasr_engine *e, const char *key, int value) {      
     if (is("token_alternatives")) return take(e->opt_token_alt, value);
     if (is("frame_blank_logprobs")) return take(e->opt_frame_blank, value != 0);
     if (is("token_entropy")) return take(e->opt_token_entropy, value);
+    if (is("joint_split")) {                                   // the joint's output layer on the bf16 MFMA: the planes of out_w are made once, when the option is first taken
+        if (value && !e->joint_planes) {
+            uint16_t *planes = nullptr;
+            if (dalloc(e, &planes, JOINT_PLANE_BYTES / sizeof(uint16_t))) return -1;
+            launch_joint_weight_planes(e->out_w, planes, e->st);
+            HIPCHK(hipStreamSynchronize(e->st));
+            e->joint_planes = planes;
+        }
+        e->opt_joint_split = value != 0;
+        return 0;
+    }
     if (is("lm_refresh_fold")) return take(e->opt_lm_fold, value != 0 ? 1 : 0);
     if (is("lm_commit_lookup")) return take(e->opt_lm_relook, value != 0 ? 1 : 0);
     if (is("phrase_boost")) {
@@ -1113,6 +1124,7 @@ extern "C" int nasr_engine_get_counter(const nasr_engine *e, const char *name, i
     else if (!strcmp(name, "lm_ngrams")) *value = e->lm ? e->lm->n_ngrams : 0;                        // the attached language model (0: none)
     else if (!strcmp(name, "lm_states")) *value = e->lm ? (int64_t)e->lm->states.size() : 0;
     else if (!strcmp(name, "lm_max_probe")) *value = e->lm ? e->lm->max_probe : 0;
+    else if (!strcmp(name, "joint_plane_bytes")) *value = e->opt_joint_split ? (int64_t)JOINT_PLANE_BYTES : 0;      // option "joint_split": bytes of the joint's weight planes the decode reads (0: off)
     else if (!strcmp(name, "weight_plane_bytes")) *value = (int64_t)e->plane_bytes;                   // option "f32_split_planes": bytes of the weight planes in device memory (0: none)
     else if (!strcmp(name, "lanes")) *value = e->pipe_ready ? e->n_lanes : 0;      // HIP streams found to overlap (0: not picked yet)
     else return fail("unknown counter '%s'", name);

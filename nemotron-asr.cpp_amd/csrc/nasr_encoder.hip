@@ -447,6 +447,7 @@ void bind_dec_weights(const nasr_engine *e, DecParams &dp) {
     dp.embed = e->embed;
     for (int i = 0; i < 2; i++) { dp.w_ih[i] = e->w_ih[i]; dp.w_hh[i] = e->w_hh[i]; dp.b_ih[i] = e->b_ih[i]; dp.b_hh[i] = e->b_hh[i]; }
     dp.pred_w = e->pred_w; dp.pred_b = e->pred_b; dp.out_w = e->out_w; dp.out_b = e->out_b;
+    dp.out_planes = e->opt_joint_split ? e->joint_planes : nullptr;      // option "joint_split": out_w as bf16 hi / lo planes (k_dec_joint_split)
 }
 
 DecFeatures dec_features(const nasr_engine *e) {

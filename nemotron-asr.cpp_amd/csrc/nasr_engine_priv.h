@@ -202,6 +202,10 @@ struct nasr_engine {
     std::map<const void *, const void *> plane_of;   // f32 weight -> its plane inside plane_block
     int f32_gemm_kind() const { return opt_f32_split && !bf16 ? (plane_block ? 3 : 2) : opt_f32_mfma ? 0 : 1; }      // GemmParams::f32_fma_tile of every launch_gemm_f32 of this engine
     const void *f32_plane(const void *W) const { auto it = plane_of.find(W); return it == plane_of.end() ? nullptr : it->second; }   // ... and its GemmParams::W_planes (null: none)
+    // option "joint_split": the joint's output layer above nasr_lp::SMALL_ROWS rows as three bf16 MFMA products of split operands (k_dec_joint_split, every engine dtype;
+    // not k_dec_joint_tiled's bits).  joint_planes (JOINT_PLANE_BYTES, made when the option is first taken) stays for the engine's life; DecParams::out_planes follows the option
+    bool opt_joint_split = false;
+    uint16_t *joint_planes = nullptr;
     char *gh = nullptr;                                                               // pinned host block
     int *gh_collect = nullptr;       // pinned landing zone of the token gather: [B][1 + COLLECT_STRIDE] + n_active
     int64_t graph_replays = 0, eager_steps = 0, decode_fallbacks = 0, decode_fallback_rounds = 0;

@@ -233,6 +233,11 @@ struct DecParams {
     const float *embed;          // [1025][640]
     const float *w_ih[2], *w_hh[2], *b_ih[2], *b_hh[2];
     const float *pred_w, *pred_b, *out_w, *out_b;
+    // engine option "joint_split" (null when it is off: every launch is then the kernel it was): out_w as bf16 hi / lo planes in the A-fragment order of
+    // v_mfma_f32_16x16x32_bf16 (launch_joint_weight_planes, JOINT_PLANE_BYTES).  A weight, not part of the decode working set.  Read by k_dec_joint_split,
+    // which takes k_dec_joint_tiled's place in launch_decode_iter above nasr_lp::SMALL_ROWS rows and in launch_decode_rows; k_dec_joint and the BEAMB
+    // form (launch_decode_rows_boost) read out_w as before
+    const uint16_t *out_planes;
     float *predg;                // [slot][640]  joint.pred(h1') + b_pred of the current LSTM candidate
     unsigned long long *key;     // [B * T] packed argmax keys, one per (row, frame)
     int *n_active;               // device counters: streams with frames left,
@@ -281,6 +286,11 @@ int decode_blind_iterations(int frames);
 void launch_encproj(const float *x, const float *wpk, const float *bias, float *out, int M, int K, int N, hipStream_t st);
 // the LSTM candidate and g = joint.pred(h1') + b_pred of the rows in p.dlist (*p.n_dirty of them): the first three launches of launch_decode_iter
 void launch_decode_candidates(const DecParams &p, hipStream_t st);
+// engine option "joint_split" (kernels_joint_split.hip): the planes of the packed out_w (65 tiles x 20 k steps x 2 KiB: 1 KiB of bf16 hi,
+// 1 KiB of lo), and k_dec_joint_tiled's forms without BEAMB as three bf16 MFMA products of split operands on them (p.out_planes set; same grid, parts and lists)
+constexpr size_t JOINT_PLANE_BYTES = (size_t)65 * 20 * 2048;
+void launch_joint_weight_planes(const float *out_w_packed, void *planes, hipStream_t st);
+template <bool LP, bool BOOST, bool ALT, bool LMF, bool ENT> void launch_joint_split(const DecParams &p, hipStream_t st);
 
 // ---- engine option "frame_history" (kernels_history.hip, nasr_history.h) ------------------------------------------------------------
 // the append: one launch at the head of a step's decode sequence, right behind launch_decode_begin (DecCtrl::frame0 of the step is in force)

@@ -427,6 +427,15 @@ bool nemo_set_f32_split_planes(nemo_context *ctx, bool on) {
     return true;
 }
 
+bool nemo_set_joint_split(nemo_context *ctx, bool on) {
+    if (!ctx || !ctx->engine) return false;
+    if (nasr_engine_set_option(ctx->engine, "joint_split", on ? 1 : 0) < 0) {
+        fprintf(stderr, "%s: %s\n", __func__, nasr_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool nemo_set_pipeline(nemo_context *ctx, int depth) {
     if (!ctx || !ctx->engine) return false;
     if (nasr_engine_set_option(ctx->engine, "pipeline", depth) < 0) {

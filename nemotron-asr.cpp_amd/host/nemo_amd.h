@@ -117,6 +117,10 @@ bool nemo_set_f32_split_attn_stream(nemo_context *ctx, bool on);
 // the same results bit for bit, one more copy of the encoder's GEMM weights in GPU memory; before the first step or offline call; no effect unless
 // nemo_set_f32_split is on and the engine is f32
 bool nemo_set_f32_split_planes(nemo_context *ctx, bool on);
+// MI355X extension: the RNN-T joint's output layer (640 -> 1025) of decodes above 64 rows per iteration and of the beam search as three bf16 matrix
+// products of split operands (nasr_engine_set_option "joint_split"); any engine precision; before the first step or offline call; logits differ from
+// the default's by at most 3 * 2^-16 per unit of |x||w|; 2.6 MB more GPU memory
+bool nemo_set_joint_split(nemo_context *ctx, bool on);
 bool nemo_set_pipeline(nemo_context *ctx, int depth);   // 0 off, 1 decode beside the next encoder, 2 / 3 / 4: the encoder in that many pieces of consecutive steps side by side
 
 // MI355X extension: forced alignment / transcript scoring of one whole utterance (nasr_engine_align): tokens = ids 0 .. 1023 of a KNOWN

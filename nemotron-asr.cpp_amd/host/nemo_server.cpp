@@ -484,7 +484,7 @@ void on_signal(int) { g_stop = true; if (g_listen_fd >= 0) ::shutdown(g_listen_f
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--cpu | --cuda]\n"
+        fprintf(stderr, "Usage: %s <model.gguf> [--tcp host:port | --unix path] [--right-context R] [--device N | --devices N,M,...] [--f32] [--joint-split] [--max-streams N] [--backlog-chunks K] [--pipeline E] [--prewarm R[,R...] | --no-prewarm] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--cpu | --cuda]\n"
                         "  --lm: greedy shallow fusion of a back-off n-gram model (ARPA over the vocabulary's pieces) for every session, one model per engine, loaded at start;\n"
                         "        --lm-weight X (default 0.5) and --token-bonus Y (default 0), both 0 .. 100\n"
                         "  --boost-file: phrase boosting for every session: one `phrase<TAB>bonus` per line (bonus optional, default --boost-bonus or 4.0), loaded into every engine at start\n"
@@ -493,6 +493,7 @@ int main(int argc, char **argv) {
                         "  --tcp: default 127.0.0.1:8300 (the reference's port, src/nemo-server.cpp:411; the reference binds every interface when no host is given, this server binds loopback unless told otherwise: --tcp 0.0.0.0:8300)\n"
                         "  --pipeline E: consecutive engine calls overlap on the GPU (E = 0..4; 4 pieces on 4 hardware queues is the throughput optimum, 0 the lowest latency); a stream's text arrives\n"
                         "                E calls later while the FIFO is busy and at once when it runs empty\n"
+                        "  --joint-split: the decoder's joint output layer as three bf16 matrix products of split operands in engine calls that decode more than 64 frames (engine option joint_split)\n"
                         "  --devices: one engine + worker per listed GPU; stream s is served by entry s mod count\n"
                         "  --backlog-chunks K: an engine call may carry up to K whole chunks of every stream (default 4; 1 = one chunk per stream and call)\n", argv[0]);
         return 1;
@@ -506,7 +507,7 @@ int main(int argc, char **argv) {
     float boost_bonus = 4.0f;
     const char *lm_path = nullptr;
     float lm_weight = 0.5f, token_bonus = 0.0f;
-    bool lm_opts = false;
+    bool lm_opts = false, joint_split = false;
     for (int i = 2; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--tcp" && i + 1 < argc) tcp = argv[++i];
@@ -525,7 +526,8 @@ int main(int argc, char **argv) {
         else if (a == "--max-streams" && i + 1 < argc) max_streams = atoi(argv[++i]);
         else if (a == "--backlog-chunks" && i + 1 < argc) backlog_chunks = std::max(1, std::min(16, atoi(argv[++i])));
         else if (a == "--f32") dtype = 0;
-        else if (a == "--cpu" || a == "--cuda" || a == "--metal") {
+        else if (a == "--joint-split") joint_split = true;
+        else if (a == "--cpu"|| a == "--cuda" || a == "--metal") {
             // the reference server's backend switches (src/nemo-server.cpp:405-406): accepted so that its invocations run unchanged
             fprintf(stderr, "note: %s has no effect, this build runs on the MI355X engine (HIP)\n", a.c_str());
         }
@@ -555,6 +557,7 @@ int main(int argc, char **argv) {
         if (!ln->model) { fprintf(stderr, "Failed to load ASR model on device %d\n", dev); return 1; }
         if (boost_file && !(nemo_set_phrase_boost(ln->model, 4096) && nemo_load_boost_file(ln->model, boost_file, boost_bonus))) return 1;
         if (lm_path && !(nemo_set_lm_fusion(ln->model, true) && nemo_load_lm_arpa(ln->model, lm_path, 0.0f) && nemo_set_greedy_lm_weights(ln->model, lm_weight, token_bonus))) return 1;
+        if (joint_split && !nemo_set_joint_split(ln->model, true)) return 1;
         if (g_pipeline > 0 && !nemo_set_pipeline(ln->model, g_pipeline)) return 1;
         // one step shape per batch size and right_context in use, and as many again for the multi-chunk shapes of a backlog (chunk counts are
         // powers of two): none is evicted in steady state

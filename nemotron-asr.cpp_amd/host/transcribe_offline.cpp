@@ -13,7 +13,7 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--boost-file FILE] [--boost-bonus X] [--f32] [--f32-split] [--f32-split-planes] [--f32-split-attn] [--device N] [--lang CODE] [--print-tokens] [--confidence] [--confidence-method M] [--confidence-alpha A] [--confidence-norm N] [--confidence-agg G]\n"
+            "Usage: %s <model.gguf> <audio.pcm> [--beam W] [--nbest N] [--max-symbols S] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--boost-file FILE] [--boost-bonus X] [--f32] [--f32-split] [--f32-split-planes] [--f32-split-attn] [--joint-split] [--device N] [--lang CODE] [--print-tokens] [--confidence] [--confidence-method M] [--confidence-alpha A] [--confidence-norm N] [--confidence-agg G]\n"
             "  audio: raw s16le, 16 kHz, mono, one whole utterance (up to 2048 encoder frames = 163.8 s)\n"
             "  without --beam: the greedy transcript, one line\n"
             "  --beam W (1 .. 8): one line per hypothesis, best first: rank score text   (score = ln P of the hypothesis's best path;\n"
@@ -35,6 +35,8 @@ static void usage(const char *prog) {
             "  --f32-split: the f32 engine (as --f32) with its encoder GEMMs as three bf16 matrix products of split operands (engine option f32_split)\n"
             "  --f32-split-planes: as --f32-split, its GEMMs reading weights that were split into bf16 hi / lo planes once at start-up (engine option\n"
             "  f32_split_planes: the same results bit for bit, one more copy of the encoder's GEMM weights in GPU memory)\n"
+            "  --joint-split: the decoder's joint output layer as three bf16 matrix products of split operands, in the greedy decode of utterances above\n"
+            "  64 frames and in the beam search without phrase boosting (engine option joint_split; any precision)\n"
             "  --f32-split-attn: the f32 engine (as --f32) with its attention as three bf16 matrix products of split operands (engine option f32_split_attn);\n"
             "  may be combined with --f32-split\n"
             "  --print-tokens: after each line `tokens ...` and `frames ...`, the ids and the encoder frame each is emitted at\n",
@@ -45,7 +47,7 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     const char *model_path = argv[1], *audio_path = argv[2], *lang = nullptr;
     int device = 0, dtype = 1, beam = 0, nbest = 0, max_symbols = 0;
-    bool f32_split = false, f32_split_planes = false, f32_split_attn = false;
+    bool f32_split = false, f32_split_planes = false, f32_split_attn = false, joint_split = false;
     bool print_tokens = false;
     bool confidence = false, conf_opts = false, conf_entropy_opts = false, conf_max_prob = true;
     token_conf::Method conf_method = token_conf::METHOD_ENTROPY;
@@ -73,6 +75,7 @@ int main(int argc, char **argv) {
         else if (a == "--f32-split") { dtype = 0; f32_split = true; }
         else if (a == "--f32-split-planes") { dtype = 0; f32_split = f32_split_planes = true; }
         else if (a == "--f32-split-attn") { dtype = 0; f32_split_attn = true; }
+        else if (a == "--joint-split") joint_split = true;
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--confidence") confidence = true;
         else if (a == "--confidence-method" && i + 1 < argc) {
@@ -111,6 +114,7 @@ int main(int argc, char **argv) {
     if (!ctx) { fprintf(stderr, "Failed to load model: %s\n", model_path); return 1; }
     if (f32_split && !nemo_set_f32_split(ctx, true)) { nemo_free(ctx); return 1; }
     if (f32_split_planes && !nemo_set_f32_split_planes(ctx, true)) { nemo_free(ctx); return 1; }
+    if (joint_split && !nemo_set_joint_split(ctx, true)) { nemo_free(ctx); return 1; }
     if (f32_split_attn && !nemo_set_f32_split_attn(ctx, true)) { nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
     if (confidence && conf_max_prob && !nemo_set_token_logprobs(ctx, true)) { nemo_free(ctx); return 1; }

@@ -26,11 +26,13 @@
 
 static void usage(const char *prog) {
     fprintf(stderr,
-            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--f32-split] [--f32-split-planes] [--f32-split-attn] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--confidence-method M] [--confidence-alpha A] [--confidence-norm N] [--confidence-agg G] [--alternatives K] [--endpoints] [--preview] [--save-state FILE] [--load-state FILE] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
+            "Usage: %s <model.gguf> <audio.pcm | -> [chunk_ms] [right_context] [--lang CODE] [--f32] [--f32-split] [--f32-split-planes] [--f32-split-attn] [--joint-split] [--device N] [--print-tokens] [--read-chunks N] [--timestamps] [--confidence] [--confidence-method M] [--confidence-alpha A] [--confidence-norm N] [--confidence-agg G] [--alternatives K] [--endpoints] [--preview] [--save-state FILE] [--load-state FILE] [--boost-file FILE] [--boost-bonus X] [--lm FILE.arpa] [--lm-weight X] [--token-bonus Y] [--pipeline [E]] [--input-rate N] [--input-encoding s16|f32|mulaw|alaw] [--input-channels C] [--input-channel I|mix]\n"
             "  audio: raw s16le, 16 kHz, mono, unless the --input-* flags or a WAV header say otherwise.  right_context in {0, 1, 6, 13} (80 ms .. 1.12 s lookahead)\n"
             "  --f32-split: the f32 engine (as --f32) with its encoder GEMMs as three bf16 matrix products of split operands (engine option f32_split)\n"
             "  --f32-split-planes: as --f32-split, its GEMMs reading weights that were split into bf16 hi / lo planes once at start-up (engine option\n"
             "  f32_split_planes: the same results bit for bit, one more copy of the encoder's GEMM weights in GPU memory)\n"
+            "  --joint-split: the decoder's joint output layer as three bf16 matrix products of split operands where a step decodes more than 64 frames\n"
+            "  (engine option joint_split; any precision)\n"
             "  --f32-split-attn: the f32 engine (as --f32) with its streaming attention as three bf16 matrix products of split operands (engine option\n"
             "  f32_split_attn_stream); may be combined with --f32-split\n"
             "  --input-rate N:  sample rate of the audio: 8000, 11025, 16000, 22050, 24000, 32000, 44100 or 48000 (converted to 16 kHz on the GPU)\n"
@@ -94,7 +96,7 @@ int main(int argc, char **argv) {
     if (argc < 3) { usage(argv[0]); return 1; }
     const char *model_path = argv[1], *audio_path = argv[2];
     int chunk_ms = 80, right_context = 0, device = 0, dtype = 1, positional = 0;
-    bool f32_split = false, f32_split_planes = false, f32_split_attn = false;
+    bool f32_split = false, f32_split_planes = false, f32_split_attn = false, joint_split = false;
     const char *lang = nullptr;
     bool print_tokens = false, timestamps = false, confidence = false;
     bool conf_entropy_opts = false;
@@ -126,6 +128,7 @@ int main(int argc, char **argv) {
         else if (a == "--f32-split") { dtype = 0; f32_split = true; }
         else if (a == "--f32-split-planes") { dtype = 0; f32_split = f32_split_planes = true; }
         else if (a == "--f32-split-attn") { dtype = 0; f32_split_attn = true; }
+        else if (a == "--joint-split") joint_split = true;
         else if (a == "--print-tokens") print_tokens = true;
         else if (a == "--timestamps") timestamps = true;
         else if (a == "--confidence") confidence = true;
@@ -218,6 +221,7 @@ int main(int argc, char **argv) {
     }
     if (f32_split && !nemo_set_f32_split(ctx, true)) { nemo_free(ctx); return 1; }
     if (f32_split_planes && !nemo_set_f32_split_planes(ctx, true)) { nemo_free(ctx); return 1; }
+    if (joint_split && !nemo_set_joint_split(ctx, true)) { nemo_free(ctx); return 1; }
     if (f32_split_attn && !nemo_set_f32_split_attn_stream(ctx, true)) { nemo_free(ctx); return 1; }
     if (pipeline && !nemo_set_pipeline(ctx, pipeline)) { fprintf(stderr, "Failed to enable pipelined steps\n"); nemo_free(ctx); return 1; }
     if (lang && !nemo_set_language(ctx, lang)) { fprintf(stderr, "Failed to set language '%s'\n", lang); nemo_free(ctx); return 1; }
